@@ -41,6 +41,7 @@ C4_ROWS, C4_Q, C4_DIM, C4_K = 50_000_000, 10_000, 1024, 1000    # BASELINE.json 
 MFMA_PEAK_TFLOPS = 2500.0   # dense bf16, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "r06_locality.json")   # tools/exp_locality.py: separate rocprofv3 --pmc passes per workload
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
 
 
 def parse():
@@ -61,9 +62,15 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (single-GPU rehearsal of N > 1)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--dump-ids", default=None, help="rank 0 saves the final [queries, k] id tensor here (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned (scores.npy float32, ids.npy float64) under DIR, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB in all (a seeded sample of query rows beyond that, named by rows.npy)")
     ap.add_argument("--rehearse-secondary", type=int, default=0, metavar="D",
                     help="tests: run the N > 1 side runs on a custom shape too, the configs[2] one on 1/D of its rows and queries")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def log(*a):
@@ -181,6 +188,29 @@ def completeness_all_queries(corpus_bf16, queries_bf16, scores, chunk=65536):
     bad = int(((above_hi > in_list) | (in_list > above_lo)).sum())
     return {"queries_checked": int(Qf.shape[0]), "queries_with_a_missing_row_above_the_cut": bad,
             "rule": "fp32 torch.matmul sweep of the whole corpus on the device: rows scoring above the list's k-th score + 1e-4 must all be in the list"}
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> numpy array, all with one row per query) as <out_dir>/<name>.npy, float32 kept,
+    anything else as float64 (ids below 2^53 are exact).  Past `limit` bytes in all, the same seeded sample of query rows (ascending) is kept
+    of every array and rows.npy names them: the sample depends on the shape alone, so two builds dump the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = {n: np.ascontiguousarray(a if a.dtype == np.float32 else a.astype(np.float64)) for n, a in arrays.items()}
+    n_rows = {a.shape[0] for a in out.values()}
+    assert len(n_rows) == 1, {n: a.shape for n, a in out.items()}
+    n_rows = n_rows.pop()
+    header = 128                  # bytes of one .npy header (numpy pads it to 64-byte multiples; 128 holds these shapes)
+    if sum(a.nbytes + header for a in out.values()) > limit:
+        per_row = sum(a.nbytes for a in out.values()) // max(1, n_rows) + 8      # + the row's entry in rows.npy
+        keep = (limit - header * (len(out) + 1)) // per_row
+        assert keep >= 1, "one query row alone passes the dump limit"
+        rows = np.sort(np.random.RandomState(0).choice(n_rows, keep, replace=False))
+        out = {n: np.ascontiguousarray(a[rows]) for n, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    for n, a in out.items():
+        np.save(os.path.join(out_dir, f"{n}.npy"), a)
+    return sorted(out)
 
 
 class Workload:
@@ -726,6 +756,9 @@ def main():
     log(f"rank {rank}: inputs resident, rows [{w.lo},{w.hi}), data={args.data}")
     r = w.run(args.steps, args.warmup, "main")
     st = r["stats"]
+    if args.dump_outputs and rank == 0:     # the last timed step's lists (merged over the ranks at N > 1), before any untimed extra runs
+        names = dump_outputs(args.dump_outputs, {"scores": w.scores.cpu().numpy(), "ids": w.ids.cpu().numpy()})
+        log(f"outputs of the last timed step: {', '.join(names)} under {args.dump_outputs}")
 
     # untimed extras: pack-kernel HBM rate
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -638,6 +638,31 @@ def test_committed_bench_line_has_the_contract_fields():
     assert abs(line["value"] - line["config"]["queries"] / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
 
 
+def test_bench_dump_outputs_keeps_values_exact_and_samples_past_the_limit(tmp_path):
+    """bench.py --dump-outputs (its file writer, no GPU): fp32 scores stay fp32 and int64 ids become exact fp64; past the byte limit every
+    array keeps the SAME seeded sample of query rows (rows.npy names them, ascending), whatever the values -- two builds dump alike."""
+    import bench
+    rs = np.random.RandomState(5)
+    scores = rs.standard_normal((1000, 100)).astype(np.float32)
+    ids = rs.randint(0, 2 ** 40, (1000, 100)).astype(np.int64)
+    assert bench.dump_outputs(str(tmp_path / "all"), {"scores": scores, "ids": ids}) == ["ids", "scores"]
+    s, i = np.load(tmp_path / "all" / "scores.npy"), np.load(tmp_path / "all" / "ids.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64
+    assert np.array_equal(s.view(np.uint32), scores.view(np.uint32)) and np.array_equal(i.astype(np.int64), ids)
+    limit, picked = 300_000, []
+    for tag in ("a", "b"):
+        sc = np.random.RandomState(len(picked)).standard_normal((1000, 100)).astype(np.float32)
+        assert bench.dump_outputs(str(tmp_path / tag), {"scores": sc, "ids": ids}, limit=limit) == ["ids", "rows", "scores"]
+        files = [tmp_path / tag / f"{n}.npy" for n in ("ids", "rows", "scores")]
+        assert sum(os.path.getsize(f) for f in files) <= limit
+        rows = np.load(files[1])
+        assert rows.dtype == np.float64 and 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+        r = rows.astype(np.int64)
+        assert np.array_equal(np.load(files[2]), sc[r]) and np.array_equal(np.load(files[0]).astype(np.int64), ids[r])
+        picked.append(rows)
+    assert np.array_equal(picked[0], picked[1])
+
+
 
 def test_replica_cache_replicate_returns_cached_copies_for_a_device_subset(monkeypatch):
     """src/ccrec/util/data_parallel.py:8-20: after cache_replicas(), torch's DataParallel.forward asks replicate() for the

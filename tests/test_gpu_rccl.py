@@ -131,6 +131,38 @@ def test_bench_ranks_rehearsal_in_fresh_processes(tmp_path, world, rows, launche
     assert a.shape == (300, 100) and torch.equal(a, b)
 
 
+def test_bench_dump_outputs_are_the_last_timed_steps_lists(tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments dump the same bits; they are the lists --dump-ids saves and a plain
+    search of the same generated corpus and queries returns; the 2-rank rehearsal (merged lists on rank 0) dumps the same."""
+    import bench as bench_mod
+    from ccrec_amd import ops
+    bench = os.path.join(ROOT, "bench.py")
+    rows, nq, k = 200000, 300, 100
+    common = ["--steps", "3", "--warmup", "1", "--rows", str(rows), "--queries", str(nq), "--cpu-queries", "0", "--no-secondary"]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CCR_BENCH_WATCHDOG="150")
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    runs = {"a": ["--gpus", "1"], "b": ["--gpus", "1"], "two": ["--gpus", "2", "--dist-backend", "gloo", "--same-device"]}
+    dumps = {}
+    for tag, head in runs.items():
+        out, _ = _run_child([sys.executable, bench] + head + common + ["--dump-outputs", str(tmp_path / tag), "--dump-ids", str(tmp_path / f"{tag}.pt")],
+                            env, tmp_path, tag)
+        assert json.loads([ln for ln in out.splitlines() if ln.startswith("{")][0])["steps"] == 3
+        assert sorted(os.listdir(tmp_path / tag)) == ["ids.npy", "scores.npy"]
+        s, i = np.load(tmp_path / tag / "scores.npy"), np.load(tmp_path / tag / "ids.npy")
+        assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (nq, k)
+        assert np.array_equal(i.astype(np.int64), torch.load(tmp_path / f"{tag}.pt").numpy())
+        dumps[tag] = (s.view(np.uint32), i)
+    for tag in ("b", "two"):
+        assert np.array_equal(dumps[tag][0], dumps["a"][0]) and np.array_equal(dumps[tag][1], dumps["a"][1]), tag
+    dev = torch.device("cuda", 0)
+    D = ops.pack_bf16(bench_mod.gen_rows(rows, 768, 1234, dev))
+    Q = ops.pack_bf16(bench_mod.gen_rows(nq, 768, 4321, dev))
+    s, i = ops.CorpusIndex(D).search(Q, k)
+    assert np.array_equal(i.cpu().numpy(), dumps["a"][1].astype(np.int64))
+    assert np.array_equal(s.cpu().numpy().view(np.uint32), dumps["a"][0])
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_ranks_rehearsal_records_the_multi_gpu_side_runs(tmp_path, world):
     """One N > 1 invocation also measures the shapes the multi-GPU target is quoted on -- ranking()'s k = 1001 on the same corpus (the
