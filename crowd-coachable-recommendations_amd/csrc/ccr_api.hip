@@ -24,9 +24,6 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-#ifndef CCR_QDIRECT_DEFAULT
-#define CCR_QDIRECT_DEFAULT 0   // 16x16x32 main pass: query fragments through the LDS ring (0) or straight from global memory (1 / 3 / 4 / 5)
-#endif
 // ------------------------------------------------------------------ planner
 // Query-block groups per XCD set: the smallest divisor of qblocks among {1,2,4,8} that keeps one XCD's
 // query rows (qblocks / groups blocks of 256 rows) within ~3 MiB of its 4-MiB L2.
@@ -42,9 +39,7 @@ Knobs read_knobs() {
     kn.max_phases = env_int("CCR_PHASES", 3);
     kn.mfma16 = env_int("CCR_MFMA16", -1);
     kn.sample_div = env_int("CCR_SAMPLE_DIV", 0);
-    kn.gemm_dbg = env_int("CCR_GEMM_DBG", 0);
     kn.stagger = env_int("CCR_GEMM_STAGGER", 1);
-    kn.qdirect = env_int("CCR_QDIRECT", CCR_QDIRECT_DEFAULT);
     kn.max_lists = env_int("CCR_MAX_LISTS", 0);
     kn.ranges = env_int("CCR_RANGES", 0);
     kn.item_swap = env_int("CCR_ITEM_SWAP", 0);
@@ -727,7 +722,6 @@ static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float 
         g.store = scratch;
         g.store_pitch = pitch;
         g.stagger = 1;
-        g.qdirect = ix->knobs.qdirect;
         int rc = (ix->knobs.mfma16 >= 0 ? ix->knobs.mfma16 : CCR_MFMA16_DEFAULT) ? launch_gemm16_store(g, grid, s) : launch_gemm_store(g, grid, s);
         if (rc != CCR_OK) return rc;
         rc = launch_margin_select(scratch, pitch, ix->n_rows, k, ix->dim, g.Q, ix->D, ix->tile_norm, ix->row_norm, ix->dmax_bits,
@@ -934,7 +928,6 @@ static int search_complete(ccr_index *ix) {
                 g.qblocks = pad2 / TILE_Q;
                 g.qgroups = pick_qgroups(g.qblocks, ix->dim, ix->knobs);
                 g.stagger = ix->knobs.stagger;
-                g.qdirect = ix->knobs.qdirect;
                 g.n_vt = p.tiles;
                 g.tile_stride = 1;
                 g.ranges = p.ranges;
@@ -1124,14 +1117,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     g.nq_pad = p.nq_pad;
     g.qblocks = p.qblocks;
     g.qgroups = p.qgroups;
-#ifdef CCR_DIAGNOSTICS
-    g.dbg = ix->knobs.gemm_dbg;
-    g.dbg_pitch = env_int("CCR_DBG_PITCH", ix->dim);
-    g.dbg_alloc_rows = getenv("CCR_DBG_ALLOC_ROWS") ? atoll(getenv("CCR_DBG_ALLOC_ROWS")) : 0;
-    g.dbg_alloc_q = env_int("CCR_DBG_ALLOC_Q", 0);
-#endif
     g.stagger = ix->knobs.stagger;
-    g.qdirect = ix->knobs.qdirect;
 
     // sample pass -> group maxima -> thresholds
     GemmArgs gs = g;
@@ -1160,17 +1146,6 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     gm.qblocks = p.main_qblocks;   // (blocks of p.tile_q queries; the sample pass above walks blocks of TILE_Q)
     gm.qgroups = p.main_qgroups;
     gm.item_swap = (ix->knobs.item_swap && !p.item_a) ? 1 : 0;   // the phases' "ranges completed so far" needs the default order
-    unsigned long long *stamps = nullptr;   // CCR_GEMM_DBG=16: in-kernel cycle stamps of the main pass (diagnostic build only)
-#ifdef CCR_DIAGNOSTICS
-    const bool want_stamps = ix->knobs.gemm_dbg == 16 || ix->knobs.gemm_dbg == 144;
-#else
-    const bool want_stamps = false;
-#endif
-    if (want_stamps) {
-        CCR_HIP_CHECK(hipMalloc((void **)&stamps, (size_t)p.grid * 64 * 8));
-        CCR_HIP_CHECK(hipMemsetAsync(stamps, 0, (size_t)p.grid * 64 * 8, s));
-        gm.store = reinterpret_cast<float *>(stamps);
-    }
     CCR_HIP_CHECK(hipEventRecord(ix->ev[3], s));
     if (p.narrow) {
         // small batch: the corpus is STREAMED past query rows resident in LDS (ccr_narrow.hip); two atomically filled sub-lists per query
@@ -1203,39 +1178,6 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     if (rc != CCR_OK) return rc;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[4], s));
     ix->main_pass_recorded = true;
-    if (want_stamps) {
-        std::vector<unsigned long long> h((size_t)p.grid * 64);
-        CCR_HIP_CHECK(hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, s));
-        CCR_HIP_CHECK(hipStreamSynchronize(s));
-        static const char *names[8] = {"barrierB+loop", "epi_hits", "dma_wait", "lds_reads+dma_issue", "barrierA", "mfma", "epi_trees|lgkm_before_A", "mfma_drain"};
-        for (int grp = 0; grp < 2; ++grp) {
-            double sum[8] = {0};
-            int n = 0;
-            for (int b = 0; b < p.grid; ++b)
-                for (int w = grp * 4; w < grp * 4 + 4; ++w, ++n)
-                    for (int i = 0; i < 8; ++i) sum[i] += (double)h[((size_t)b * 8 + w) * 8 + i];
-            double tot = 0;
-            for (int i = 0; i < 8; ++i) tot += sum[i];
-            fprintf(stderr, "[ccr stamps] waves %d-%d: total %.0f cycles/wave;", grp * 4, grp * 4 + 3, tot / n);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.1f%%", names[i], 100.0 * sum[i] / tot);
-            fprintf(stderr, "\n");
-        }
-        (void)hipFree(stamps);
-    }
-
-#ifdef CCR_DIAGNOSTICS
-    if (ix->knobs.gemm_dbg != 0 && ix->knobs.gemm_dbg != 16) {
-        // timing-only ablation of the main pass: its candidates are meaningless, so nothing is selected or re-done -- the outputs are
-        // zeroed and the main pass's time by the library's own events goes to stderr (diagnostic library only)
-        CCR_HIP_CHECK(hipMemsetAsync(out_scores, 0, (size_t)n_q * k * 4, s));
-        CCR_HIP_CHECK(hipStreamSynchronize(s));
-        float ms = 0.f;
-        CCR_HIP_CHECK(hipEventElapsedTime(&ms, ix->ev[3], ix->ev[4]));
-        fprintf(stderr, "[ccr diag] CCR_GEMM_DBG=%d main pass %.4f ms (%d launches)\n", ix->knobs.gemm_dbg, ms, p.item_a ? 3 : 1);
-        ix->pending.active = false;
-        return CCR_OK;
-    }
-#endif
     rc = launch_select_rescore(cand, cnt, p.first_nsub, p.first_sp, n_q, p.nq_pad, p.first_lay, k, p.rescore_cap, p.select_compact, ix->n_rows, thr, delta,
                                ix->tile_norm, ix->row_norm, ix->dmax_bits, Q_bf16, ix->D, ix->dim,
                                ix->id_out, out_scores, out_ids, flag_count, flag_list, stat_cand, nullptr, s);
@@ -1326,7 +1268,6 @@ extern "C" int ccr_scores(const ccr_index *ix, const uint16_t *Q_bf16, int n_q, 
     g.item_end = INT32_MAX;
     g.store = out;
     g.stagger = 1;
-    g.qdirect = ix->knobs.qdirect;
     const int grid = std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD);
     if (ix->knobs.mfma16 >= 0 ? ix->knobs.mfma16 : CCR_MFMA16_DEFAULT) return launch_gemm16_store(g, grid, (hipStream_t)stream);
     return launch_gemm_store(g, grid, (hipStream_t)stream);

@@ -62,23 +62,7 @@ __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-__device__ __forceinline__ unsigned long long stamp() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-#define CCR_STAMP(idx)                                   \
-    if constexpr ((DBG & 16) != 0) {                     \
-        __builtin_amdgcn_sched_barrier(0);               \
-        const unsigned long long _t = stamp();           \
-        __builtin_amdgcn_sched_barrier(0);               \
-        seg[idx] += _t - tprev;                          \
-        tprev = _t;                                      \
-    }
-
-// DBG (compile-time, diagnostic instantiations only; results are WRONG when non-zero):
-//   1 corpus rows always tile 0, 2 query slice always 0, 4 no DMA, 8 no MFMA, 16 cycle stamps
-template <int EPI, bool STAGGER, int DBG, bool TAIL = false>
+template <int EPI, bool STAGGER, bool TAIL = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -91,13 +75,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
     const int h = lane >> 5;
     const bool g1 = STAGGER && (wv >= 4);  // the trailing half of the ping-pong (wave-uniform)
     const int KS2 = TAIL ? (a.dim + SUB_K - 1) / SUB_K : a.dim / SUB_K;   // TAIL: the last sub-stage is partly zero-filled
-    unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // DBG 16: cycles per segment of the inner loop
-    unsigned long long tprev = 0;
-    if constexpr ((DBG & 16) != 0) tprev = stamp();
-    if constexpr ((DBG & 4) != 0) {  // no-DMA ablation: zero operands (scores 0 stay below the thresholds)
-        for (int i = tid; i < RING * SUB_BYTES / 16; i += GEMM_THREADS) reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0, 0, 0, 0);
-        __syncthreads();
-    }
 
     // DMA role: 4 x 1-KiB pieces per sub-stage (16 rows x 64 B each); LDS image is lane-linear, the
     // 16-byte chunk swizzle (chunk ^ (row>>2)&3) is applied on the SOURCE address and on the read
@@ -172,7 +149,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
         int iks = 0;
         const uint16_t *dsrc[2];
         auto tile_ptrs = [&]() {
-            const int64_t row0 = (DBG & 1) ? 0 : (r + it * a.ranges) * a.tile_stride * TILE_DOCS;
+            const int64_t row0 = (r + it * a.ranges) * a.tile_stride * TILE_DOCS;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 int64_t drow = row0 + i * 128 + srow;
@@ -184,22 +161,19 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
         auto issue = [&]() {
             char *buf = smem + (int)(iu & (RING - 1)) * SUB_BYTES;
             const int k0 = iks * SUB_K;
-            if constexpr (!(DBG & 4)) {
-                if (TAIL && iks == KS2 - 1) {   // wave-uniform: chunks beyond the row end come from the zero chunk
-                    const bool in = k0 + schunk * 8 < a.dim;
+            if (TAIL && iks == KS2 - 1) {   // wave-uniform: chunks beyond the row end come from the zero chunk
+                const bool in = k0 + schunk * 8 < a.dim;
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        glds16(in ? (const void *)(dsrc[i] + k0) : (const void *)g_zero_chunk, buf + (i * 512 + wv * 64) * 16);
+                for (int i = 0; i < 2; ++i)
+                    glds16(in ? (const void *)(dsrc[i] + k0) : (const void *)g_zero_chunk, buf + (i * 512 + wv * 64) * 16);
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        glds16(in ? (const void *)(qsrc[i] + k0) : (const void *)g_zero_chunk, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
-                } else {
+                for (int i = 0; i < 2; ++i)
+                    glds16(in ? (const void *)(qsrc[i] + k0) : (const void *)g_zero_chunk, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
+            } else {
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) glds16(dsrc[i] + k0, buf + (i * 512 + wv * 64) * 16);
+                for (int i = 0; i < 2; ++i) glds16(dsrc[i] + k0, buf + (i * 512 + wv * 64) * 16);
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        glds16(qsrc[i] + ((DBG & 2) ? 0 : k0), buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
-                }
+                for (int i = 0; i < 2; ++i) glds16(qsrc[i] + k0, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
             }
             ++iu;
             if (++iks == KS2) {
@@ -227,11 +201,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
                         sub[dt][g] = fmaxf(fmaxf(acc[dt][qt][4 * g], acc[dt][qt][4 * g + 1]),
                                            fmaxf(acc[dt][qt][4 * g + 2], acc[dt][qt][4 * g + 3]));
                     mdt[dt] = fmaxf(fmaxf(sub[dt][0], sub[dt][1]), fmaxf(sub[dt][2], sub[dt][3]));
-                }
-                if constexpr ((DBG & 16) != 0) {
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) asm volatile("" : "+v"(mdt[dt]));
-                    CCR_STAMP(6)  // max trees (the hit path is charged to segment 1)
                 }
                 if (EPI == EPI_GMAX) {
                     const int ql = wq * 64 + qt * 32 + l31;
@@ -306,22 +275,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
         bool pending = false;
         int64_t pending_vt = 0;
         float pending_nt = 0.f;
-        if constexpr ((DBG & 16) != 0) tprev = stamp();
         for (int64_t u = 0; u < U; ++u) {
             // ================= mem phase
-            CCR_STAMP(0)  // barrier B wait (+ loop overhead)
             if (pending) {
                 epilogue(pending_vt, pending_nt);
                 pending = false;
             }
-            CCR_STAMP(1)  // tile epilogue
             if (u + 1 < U) {  // confirm OWN DMA of sub-stage u+1 (published by the barrier below)
                 if (u + 2 < U)
                     CCR_WAIT_VM(4);
                 else
                     CCR_WAIT_VM(0);
             }
-            CCR_STAMP(2)  // DMA wait
             const char *buf = smem + (int)(u & (RING - 1)) * SUB_BYTES;
             bf16x8 af[2][4], bfr[2][2];
 #pragma unroll
@@ -335,50 +300,29 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
             }
             if (u + 3 < U) issue();  // into the buffer of sub-stage u-1 (see the WAR note above)
             CCR_WAIT_LGKM0();        // operands in registers BEFORE the barrier; free behind the DMA issue
-            CCR_STAMP(3)  // LDS reads + DMA issue
             CCR_BARRIER();
-            CCR_STAMP(4)  // barrier A wait
             // ================= mfma phase
-            if constexpr ((DBG & 8) != 0) {  // no matrix work: keep the operands alive, skip the MFMAs
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) asm volatile("" ::"v"(af[ks][dt]));
-#pragma unroll
-                    for (int qt = 0; qt < 2; ++qt) asm volatile("" ::"v"(bfr[ks][qt]));
-                }
-                if (cks == 0) {
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                        for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-                            for (int e = 0; e < 16; ++e) acc[dt][qt][e] = -1e30f;
-                }
-            } else {
-                // no s_setprio(1) here: the partner wave's mem phase carries VALU work (filter, addresses) that a
-                // raised MFMA wave would starve (MI355X_MICROARCH 'Two waves per SIMD', item 2)
-                if (cks == 0) {  // first sub-stage of a tile: C = 0 (no accumulator clearing pass)
-                    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                        for (int qt = 0; qt < 2; ++qt)
-                            acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][dt], bfr[0][qt], z, 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                        for (int qt = 0; qt < 2; ++qt)
-                            acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][dt], bfr[0][qt], acc[dt][qt], 0, 0, 0);
-                }
+            // no s_setprio(1) here: the partner wave's mem phase carries VALU work (filter, addresses) that a
+            // raised MFMA wave would starve (MI355X_MICROARCH 'Two waves per SIMD', item 2)
+            if (cks == 0) {  // first sub-stage of a tile: C = 0 (no accumulator clearing pass)
+                const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
                     for (int qt = 0; qt < 2; ++qt)
-                        acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][dt], bfr[1][qt], acc[dt][qt], 0, 0, 0);
+                        acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][dt], bfr[0][qt], z, 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                    for (int qt = 0; qt < 2; ++qt)
+                        acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][dt], bfr[0][qt], acc[dt][qt], 0, 0, 0);
             }
-            CCR_STAMP(5)  // MFMA phase
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int qt = 0; qt < 2; ++qt)
+                    acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][dt], bfr[1][qt], acc[dt][qt], 0, 0, 0);
             if (++cks == KS2) {
                 cks = 0;
                 // Tile finished.  The leading group filters it at the start of its next mem phase; the trailing
@@ -409,13 +353,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
         }
         __syncthreads();  // LDS ring free for the next item
     }
-    if constexpr ((DBG & 16) != 0) {
-        if (lane == 0 && a.store) {
-            unsigned long long *o = reinterpret_cast<unsigned long long *>(a.store) + ((size_t)blockIdx.x * 8 + wv) * 8;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = seg[i];
-        }
-    }
 }
 
 
@@ -444,7 +381,7 @@ __device__ __forceinline__ float max3_asm(float a, float b, float c) {
     return m;
 }
 
-template <int EPI, int DBG, bool TAIL = false>
+template <int EPI, bool TAIL = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -456,17 +393,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
     const int lq = lane >> 4;  // 0..3: K chunk of the operand fragments, row quad of the accumulator
     const bool g1 = (wv >= 4);
     const int KS2 = TAIL ? (a.dim + SUB_K - 1) / SUB_K : a.dim / SUB_K;
-    // DBG (diagnostic instantiations only, WRONG results): 4 no DMA at all, 8 no MFMA, 32 corpus-only DMA (the query region of the ring stays
-    // zero), 64 query-only DMA (the corpus region stays zero), 128 thresholds +inf (the complete kernel without a single hit: the baseline
-    // of the others, whose zero scores never pass), 256 every DMA piece reads whole 128-byte lines (8 rows x 128 B; garbage operands: use 384 = 256 + 128);
-    // the counted waits follow the pieces a wave issues per sub-stage
-    constexpr bool DMA_D = !(DBG & 4) && !(DBG & 64);
-    constexpr bool DMA_Q = !(DBG & 4) && !(DBG & 32);
-    constexpr int PIECES = (DMA_D ? 2 : 0) + (DMA_Q ? 2 : 0);
-    if constexpr ((DBG & (4 | 32 | 64)) != 0) {
-        for (int i = tid; i < RING * SUB_BYTES / 16; i += GEMM_THREADS) reinterpret_cast<uint4 *>(smem)[i] = make_uint4(0, 0, 0, 0);
-        __syncthreads();
-    }
 
     const int srow = wv * 16 + (lane >> 2);  // + piece*128
     const int schunk = (lane & 3) ^ (((srow >> 2) & 1) << 1);
@@ -510,23 +436,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
                 cqv[qt] = (q < a.n_q) ? a.cq[q] : 0.f;
                 clist[qt] = a.cand + seg_base + ((int64_t)(r - seg_r0) * a.nq_pad + q) * 8 * cap + (wd * 4 + lq);   // slot-major cell
             }
-            if constexpr ((DBG & 128) != 0) {   // everything runs, nothing passes the filter: the baseline of the ablations
-#pragma unroll
-                for (int qt = 0; qt < 4; ++qt) thr[qt] = INFINITY;
-            }
             asm volatile("" : "+v"(thr[0]), "+v"(thr[1]), "+v"(thr[2]), "+v"(thr[3]), "+v"(cqv[0]), "+v"(cqv[1]), "+v"(cqv[2]), "+v"(cqv[3]));
         }
-        const uint16_t *qsrc[(DBG & 256) ? 4 : 2];
+        const uint16_t *qsrc[2];
 #pragma unroll
-        for (int i = 0; i < ((DBG & 256) ? 4 : 2); ++i) {
-            int qrow = q0 + ((DBG & 256) ? i * 64 + wv * 8 + (lane >> 3) : i * 128 + srow);
+        for (int i = 0; i < 2; ++i) {
+            int qrow = q0 + (i * 128 + srow);
             if (qrow > a.n_q - 1) qrow = a.n_q - 1;
-            if constexpr ((DBG & 1024) != 0) {
-                const int last = (int)(((int64_t)(a.dbg_alloc_q > a.n_q ? a.dbg_alloc_q : a.n_q) * a.dim - a.dim) / a.dbg_pitch);
-                if (qrow > last) qrow = last;
-                qsrc[i] = a.Q + (int64_t)qrow * a.dbg_pitch + schunk * 8;
-            } else
-            qsrc[i] = a.Q + (int64_t)qrow * a.dim + ((DBG & 256) ? (lane & 7) : schunk) * 8;
+            qsrc[i] = a.Q + (int64_t)qrow * a.dim + schunk * 8;
         }
 
         f32x4v acc[8][4];
@@ -534,22 +451,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
 
         int64_t iu = 0, it = 0;
         int iks = 0;
-        const uint16_t *dsrc[(DBG & 256) ? 4 : 2];
+        const uint16_t *dsrc[2];
         auto tile_ptrs = [&]() {
             const int64_t row0 = (r + it * a.ranges) * a.tile_stride * TILE_DOCS;
 #pragma unroll
-            for (int i = 0; i < ((DBG & 256) ? 4 : 2); ++i) {
-                // DBG 256 (timing only): a piece reads 8 rows x 128 B (whole cache lines) instead of 16 rows x 64 B; the LDS image is garbage
-                int64_t drow = row0 + ((DBG & 256) ? i * 64 + wv * 8 + (lane >> 3) : i * 128 + srow);
+            for (int i = 0; i < 2; ++i) {
+                int64_t drow = row0 + (i * 128 + srow);
                 if (drow > a.n_rows - 1) drow = a.n_rows - 1;
-                if constexpr ((DBG & 1024) != 0) {   // timing only: the traffic of rows at another PITCH (a.dbg_pitch elements), kept inside the array
-                    // (a.dbg_alloc_rows: rows of `dim` elements the array behind D really holds -- the experiment hands the index the first
-                    // n_rows = alloc * dim / pitch rows of a larger array, so that no address is clamped)
-                    const int64_t last = ((a.dbg_alloc_rows > a.n_rows ? a.dbg_alloc_rows : a.n_rows) * a.dim - a.dim) / a.dbg_pitch;
-                    if (drow > last) drow = last;
-                    dsrc[i] = a.D + drow * a.dbg_pitch + schunk * 8;
-                } else
-                dsrc[i] = a.D + drow * a.dim + ((DBG & 256) ? (lane & 7) : schunk) * 8;
+                dsrc[i] = a.D + drow * a.dim + schunk * 8;
             }
         };
         tile_ptrs();
@@ -564,44 +473,11 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
                     glds16(in ? (const void *)(qsrc[i] + k0) : (const void *)g_zero_chunk, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
-            } else if constexpr ((DBG & 512) != 0) {
-                // DBG 512 (timing only): the traffic of a K-TILED layout -- the 16 KiB a sub-stage takes from the corpus tile (and from the
-                // query block) are ONE contiguous block, every piece one contiguous KiB: piece (iks * 16 + i * 8 + wv) of the tile's /
-                // block's 384 contiguous KiB in the row-major arrays.  Every byte is still requested exactly once; operands are garbage.
-                const int64_t row0 = (r + it * a.ranges) * a.tile_stride * TILE_DOCS;
-                const int64_t dtile = (int64_t)(a.n_rows - row0 < TILE_DOCS ? a.n_rows - row0 : TILE_DOCS) * a.dim * 2;   // bytes of this tile
-                const int64_t qblk = (int64_t)(a.n_q - q0 < TILE_Q ? a.n_q - q0 : TILE_Q) * a.dim * 2;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    int64_t o = (int64_t)(iks * 16 + i * 8 + wv) * 1024;
-                    if (o > dtile - 1024) o = dtile - 1024;
-                    glds16(reinterpret_cast<const char *>(a.D + row0 * a.dim) + o + lane * 16, buf + (i * 512 + wv * 64) * 16);
-                }
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    int64_t o = (int64_t)(iks * 16 + i * 8 + wv) * 1024;
-                    if (o > qblk - 1024) o = qblk - 1024;
-                    glds16(reinterpret_cast<const char *>(a.Q + (int64_t)q0 * a.dim) + o + lane * 16, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
-                }
-            } else if constexpr ((DBG & 256) != 0) {
-                // even sub-stage: rows 0 .. 127 of the tile, K [k0, k0 + 64); odd: rows 128 .. 255, the same K range: every byte of the tile
-                // is still requested exactly once, now as whole 128-byte lines
-                const int ofs = (iks & ~1) * SUB_K, hf = (iks & 1) * 2;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) glds16((hf ? dsrc[(i + 2) & 3] : dsrc[i]) + ofs, buf + (i * 512 + wv * 64) * 16);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) glds16((hf ? qsrc[(i + 2) & 3] : qsrc[i]) + ofs, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
             } else {
-                // DBG 2048 / 4096 / 8192 (timing AND results stay right): cache policy sc1 / sc0 / sc0 sc1 on every piece
-                constexpr int AUX = ((DBG & 2048) ? 16 : 0) | ((DBG & 4096) ? 1 : 0) | ((DBG & 8192) ? 17 : 0);
-                if constexpr (DMA_D) {
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) glds16_aux<AUX>(dsrc[i] + k0, buf + (i * 512 + wv * 64) * 16);
-                }
-                if constexpr (DMA_Q) {
+                for (int i = 0; i < 2; ++i) glds16(dsrc[i] + k0, buf + (i * 512 + wv * 64) * 16);
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) glds16_aux<AUX>(qsrc[i] + k0, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
-                }
+                for (int i = 0; i < 2; ++i) glds16(qsrc[i] + k0, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
             }
             ++iu;
             if (++iks == KS2) {
@@ -666,9 +542,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
         const int npro = U < 3 ? (int)U : 3;
         for (int i = 0; i < npro; ++i) issue();
         if (npro == 3)
-            wait_vm<2 * PIECES>();
+            CCR_WAIT_VM(8);
         else if (npro == 2)
-            wait_vm<PIECES>();
+            CCR_WAIT_VM(4);
         else
             CCR_WAIT_VM(0);
         CCR_BARRIER();
@@ -686,7 +562,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
             }
             if (u + 1 < U) {
                 if (u + 2 < U)
-                    wait_vm<PIECES>();
+                    CCR_WAIT_VM(4);
                 else
                     CCR_WAIT_VM(0);
             }
@@ -699,24 +575,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
             if (u + 3 < U) issue();
             CCR_WAIT_LGKM0();
             CCR_BARRIER();
-            if constexpr ((DBG & 8) != 0) {   // no matrix work: keep the operands alive, skip the MFMAs
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt) asm volatile("" ::"v"(af[dt]));
-#pragma unroll
-                for (int qt = 0; qt < 4; ++qt) asm volatile("" ::"v"(bfr[qt]));
-                if (cks == 0) {
-#pragma unroll
-                    for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                        for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[dt][qt][e] = -1e30f;
-                }
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                    for (int qt = 0; qt < 4; ++qt) asm volatile("" : "+v"(acc[dt][qt]));   // opaque: the filter trees stay
-            } else if (cks == 0) {
+            if (cks == 0) {
                 const f32x4v z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int dt = 0; dt < 8; ++dt)
@@ -786,7 +645,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
 //          so GROUP 0 FETCHES NO REFILL ROW -- its waves take the 16 corpus pieces and rows 0-15 of each query group, group 1 (whose
 //          mem(u) starts behind its own B_{u-1} and behind g0's) the query rows 16-95.  (The assignment is kept with six resident
 //          fragments: it costs nothing.)
-// dim % 32 == 0 only (the planner keeps the 256 x 256 kernel elsewhere).  DBG 128 (diagnostic library): thresholds +inf.
+// dim % 32 == 0 only (the planner keeps the 256 x 256 kernel elsewhere).
 
 // The lane id, computed where it is needed (two VALU instructions) instead of living in a register across the K loop: the wide kernel
 // has no register to spare for lane coordinates and the addresses derived from them.
@@ -823,7 +682,6 @@ constexpr int WIDE_QT = 6;                                         // query tile
 constexpr int WIDE_RING_BYTES = WIDE_RING * WIDE_SUB_BYTES;        // 122880
 constexpr size_t WIDE_LDS = (size_t)WIDE_RING_BYTES + WIDE_Q * 8 + (size_t)(GEMM_THREADS / 64) * WIDE_QT * 64 * 4;   // 138240
 
-template <int DBG>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *s_tc = reinterpret_cast<float2 *>(smem + WIDE_RING_BYTES);                     // [384] {tau_q, cq} of the item's query block
@@ -834,8 +692,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
     const bool g1 = (wv >= 4);
     const int KS2 = a.dim / SUB_K;
     const uint32_t pitch = (uint32_t)a.dim * 2u;    // bytes per row
-    unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // DBG 16 (diagnostic library): cycles per segment of the K loop
-    unsigned long long tprev = 0;
     // TWO lane-dependent registers live across the K loop -- the DMA source offset of a lane inside a piece and its operand-read offset
     // inside a slot --; everything else that depends on the lane is rebuilt from fresh_lane() where it is needed.  (VALU instructions of
     // the memory phase are issued beside the partner wave's MFMAs and wait for a slot: 34 of them per K step for addresses were 30 % of
@@ -878,9 +734,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             const int tid = wv * 64 + ln;
             if (tid < WIDE_Q) {
                 const int q = q0 + tid;
-                float t = (q < a.n_q) ? a.thr[q] : __builtin_nanf("");
-                if constexpr ((DBG & 128) != 0) t = INFINITY;
-                s_tc[tid] = make_float2(t, (q < a.n_q) ? a.cq[q] : 0.f);
+                s_tc[tid] = make_float2((q < a.n_q) ? a.thr[q] : __builtin_nanf(""), (q < a.n_q) ? a.cq[q] : 0.f);
             }
 #pragma unroll
             for (int qt = 0; qt < WIDE_QT; ++qt) s_cnt[(wv * WIDE_QT + qt) * 64 + ln] = 0u;
@@ -917,20 +771,16 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             if (q_whole && (g1 || dlimit == TILE_DOCS - 1)) {
                 // every row of every piece exists: wave-uniform bases (scalar arithmetic) + ONE per-lane offset for all the pieces
                 const uint32_t voff = lane_src + kb;
-                if constexpr ((DBG & 4) == 0) {
-                    if (!g1) {
-                        if constexpr (!(DBG & 64)) {
-                            const char *rows = dtile + (size_t)(wv * 64) * pitch;
+                if (!g1) {
+                    const char *rows = dtile + (size_t)(wv * 64) * pitch;
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) glds16(rows + (size_t)(i * 16) * pitch + voff, buf + (wv * 4 + i) * 1024);
-                        }
-                        if constexpr (!(DBG & 32)) glds16(qblk + (size_t)(wv * 96) * pitch + voff, buf + WIDE_Q_REGION + wv * 96 * 64);
-                    } else if constexpr (!(DBG & 32)) {
-                        const char *rows = qblk + (size_t)((wv - 4) * 96 + 16) * pitch;
-                        char *dst = buf + WIDE_Q_REGION + ((wv - 4) * 96 + 16) * 64;
+                    for (int i = 0; i < 4; ++i) glds16(rows + (size_t)(i * 16) * pitch + voff, buf + (wv * 4 + i) * 1024);
+                    glds16(qblk + (size_t)(wv * 96) * pitch + voff, buf + WIDE_Q_REGION + wv * 96 * 64);
+                } else {
+                    const char *rows = qblk + (size_t)((wv - 4) * 96 + 16) * pitch;
+                    char *dst = buf + WIDE_Q_REGION + ((wv - 4) * 96 + 16) * 64;
 #pragma unroll
-                        for (int i = 0; i < WIDE_PIECES; ++i) glds16(rows + (size_t)(i * 16) * pitch + voff, dst + i * 1024);
-                    }
+                    for (int i = 0; i < WIDE_PIECES; ++i) glds16(rows + (size_t)(i * 16) * pitch + voff, dst + i * 1024);
                 }
             } else {
                 // the last tile of the shard / the last block of the batch: rows beyond the end re-read the last row (never recorded)
@@ -942,18 +792,14 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
                     row = row < limit ? row : limit;
                     glds16(rows + ((uint32_t)row * pitch + co), dst);
                 };
-                if constexpr ((DBG & 4) == 0) {
-                    if (!g1) {
-                        if constexpr (!(DBG & 64)) {
+                if (!g1) {
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) piece(dtile, (wv * 4 + i) * 16, dlimit, buf + (wv * 4 + i) * 1024);
-                        }
-                        if constexpr (!(DBG & 32)) piece(qblk, wv * 96, qlimit, buf + WIDE_Q_REGION + wv * 96 * 64);
-                    } else if constexpr (!(DBG & 32)) {
+                    for (int i = 0; i < 4; ++i) piece(dtile, (wv * 4 + i) * 16, dlimit, buf + (wv * 4 + i) * 1024);
+                    piece(qblk, wv * 96, qlimit, buf + WIDE_Q_REGION + wv * 96 * 64);
+                } else {
 #pragma unroll
-                        for (int i = 0; i < WIDE_PIECES; ++i)
-                            piece(qblk, (wv - 4) * 96 + 16 * (1 + i), qlimit, buf + WIDE_Q_REGION + ((wv - 4) * 96 + 16 * (1 + i)) * 64);
-                    }
+                    for (int i = 0; i < WIDE_PIECES; ++i)
+                        piece(qblk, (wv - 4) * 96 + 16 * (1 + i), qlimit, buf + WIDE_Q_REGION + ((wv - 4) * 96 + 16 * (1 + i)) * 64);
                 }
             }
             islot = islot == WIDE_RING - 1 ? 0 : islot + 1;
@@ -1010,24 +856,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             }
         };
 
-        // pieces in flight per wave and K step: 5 (production); the DMA ablations issue 0 / 4 or 0 / 1 or 5 per group
-        auto wait_all_but_one_step = [&]() __attribute__((always_inline)) {
-            if constexpr ((DBG & 4) != 0) {
-            } else if constexpr ((DBG & 32) != 0) {
-                if (!g1) wait_vm<4>();
-            } else if constexpr ((DBG & 64) != 0) {
-                if (!g1)
-                    wait_vm<1>();
-                else
-                    wait_vm<WIDE_PIECES>();
-            } else {
-                wait_vm<WIDE_PIECES>();
-            }
-        };
         const int npro = U < 2 ? U : 2;
         for (int i = 0; i < npro; ++i) issue();
         if (npro == 2)
-            wait_all_but_one_step();
+            wait_vm<WIDE_PIECES>();   // all but the last K step's pieces
         else
             CCR_WAIT_VM(0);
         CCR_BARRIER();
@@ -1039,20 +871,16 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
         int64_t pending_vt = 0;
         float pending_nt = 0.f;
         int uslot = 0;
-        if constexpr ((DBG & 16) != 0) tprev = stamp();
         for (int u = 0; u < U; ++u) {
-            CCR_STAMP(0)  // barrier B wait (+ loop overhead)
             // the pieces of u + 2 go out FIRST (into the slot of u - 1, free since the barrier just passed): the L1 miss path, which bounds
             // the pass, gets its work at the start of the phase instead of behind the filter and the operand reads (-1 %; two pieces in
             // front of the operand reads and three behind them: +3 %)
             if (u + 2 < U) issue();
             __builtin_amdgcn_sched_barrier(0);
-            CCR_STAMP(3)  // DMA issue
             if (pending) {
                 epilogue(pending_vt, pending_nt);
                 pending = false;
             }
-            CCR_STAMP(1)  // tile epilogue (group 0)
             const char *abuf = smem + uslot * WIDE_SUB_BYTES;
             const char *bbuf = abuf + WIDE_Q_REGION;
             uslot = uslot == WIDE_RING - 1 ? 0 : uslot + 1;
@@ -1064,38 +892,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
 #pragma unroll
             for (int qt = 0; qt < WIDE_BFR; ++qt) bfr[qt] = *reinterpret_cast<const bf16x8 *>(bbuf + b_base + qt * 1024);
             if (u + 2 < U)
-                wait_all_but_one_step();           // own pieces of u + 1 have landed
+                wait_vm<WIDE_PIECES>();           // own pieces of u + 1 have landed
             else
                 CCR_WAIT_VM(0);
-            CCR_STAMP(2)  // DMA wait
             // (group 0 could confirm its pieces as late as its B_u -- the barrier instance of g1's A_u --: measured 3 % slower)
             CCR_WAIT_LGKM0();
-            CCR_STAMP(6)  // operand reads landed
             CCR_BARRIER();
-            CCR_STAMP(4)  // barrier A wait
-            if constexpr ((DBG & 8) != 0) {   // no matrix work: the operand reads (refills included) stay, the accumulators are opaque
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt) asm volatile("" ::"v"(af[dt]));
-#pragma unroll
-                for (int qt = 0; qt < WIDE_QT; ++qt) {
-                    asm volatile("" ::"v"(bfr[qt % WIDE_BFR]));
-                    if (WIDE_BFR == 3 && qt < 3) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        bfr[qt] = *reinterpret_cast<const bf16x8 *>(bbuf + b_base + (qt + 3) * 1024);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-                if (cks == 0) {
-#pragma unroll
-                    for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                        for (int qt = 0; qt < WIDE_QT; ++qt) acc[dt][qt] = f32x4v{-1e30f, -1e30f, -1e30f, -1e30f};
-                }
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                    for (int qt = 0; qt < WIDE_QT; ++qt) asm volatile("" : "+v"(acc[dt][qt]));
-            } else if (cks == 0) {
+            if (cks == 0) {
                 const f32x4v z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int qt = 0; qt < WIDE_QT; ++qt) {
@@ -1120,7 +923,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
                     }
                 }
             }
-            CCR_STAMP(5)  // MFMA phase (issue of the 48 MFMAs and the refills)
             if (++cks == KS2) {
                 cks = 0;
                 // (the tile's norm bound: a SCALAR load + wait right here, behind the MFMAs just issued)
@@ -1135,9 +937,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
                 }
                 ++ct;
             }
-            CCR_STAMP(1)  // tile epilogue (group 1)
             CCR_WAIT_LGKM0();   // the refills of this K step are retired before the barrier behind which group 1 rewrites their rows
-            CCR_STAMP(7)  // MFMA drain: the step's last refills / MFMAs
             CCR_BARRIER();
         }
         if (pending) epilogue(pending_vt, pending_nt);
@@ -1151,316 +951,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
         }
         __syncthreads();
     }
-    if constexpr ((DBG & 16) != 0) {
-        if (fresh_lane() == 0 && a.store) {
-            unsigned long long *o = reinterpret_cast<unsigned long long *>(a.store) + ((size_t)blockIdx.x * 8 + wv) * 8;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) o[i] = seg[i];
-        }
-    }
 }
-
-// =============================================================================================
-// QUERY-DIRECT form of the 16x16x32 main pass (round 6) -- an EXPERIMENT kept for the record, compiled only into the diagnostic library
-// (make DIAG=1 / tools/build_diag.sh, CCR_QDIRECT = 1 / 3 / 4 / 5).  Exact (every form returns the production kernel's ids and score bits)
-// and 38-48 % SLOWER: NQ main pass 16.8-18.2 ms against 12.1 (profiles/r06_qdirect_ab.txt).  Why: what bounds the main pass is the CU's
-// vector-memory pipeline (L1 / TCP miss handling: ~0.3 64-byte requests per clock, profiles/r06_main_pass_memory_pipeline_pmc.txt), not the
-// LDS-DMA issue; fragments fetched straight into registers are requested by BOTH waves that share a query quarter, so the CU moves
-// 16 + 32 KiB per sub-stage through that pipeline instead of 16 + 16.
-#ifdef CCR_DIAGNOSTICS
-// (The reasoning it was built on, before the measurement.)  The ablation of the kernel above (profiles/r06_main_pass_ablation.txt:
-// full 11.35 ms, corpus-only DMA 8.0, no DMA 7.75) says that the LDS-DMA *issue* -- four 1-KiB pieces per wave and sub-stage, two of
-// them the query slice that is re-streamed for every corpus tile -- is what keeps the mem phase longer than the partner's MFMA phase.
-// Here the ring carries the CORPUS alone (two pieces per wave and sub-stage) and a lane fetches its four B-operand fragments -- 16 bytes
-// of query row (q0 + wq*64 + qt*16 + l15) at K chunk lq: exactly what v_mfma_f32_16x16x32_bf16 wants in SrcB -- straight from global
-// memory (the item's query block stays in the XCD's L2) one sub-stage ahead: no LDS round trip for the queries, no ds_read for them.
-//   QD = 1  fragments of u + 1 requested at the TAIL of the MFMA phase of u (behind the 32 MFMAs), ONE register set
-//   QD = 3  requested BETWEEN the MFMAs of u: query tile qt's eight MFMAs, then qt's next fragment, ONE register set
-//   QD = 4 / 5  the same two placements with TWO register sets: the fragments of u + 2 are requested during u
-// vmcnt order per wave, one set: ... DMA(u+2)[2] | Q(u)[4] | DMA(u+3)[2] | Q(u+1)[4] ...: `vmcnt(2)` before barrier A_u confirms Q(u) and, being
-// older, this wave's DMA of u + 1 AND u + 2 (a sub-stage of corpus has one period to land).  Two sets: ... Q(u)[4] | DMA(u+2)[2] Q(u+1)[4] DMA(u+3)[2]:
-// `vmcnt(8)` confirms Q(u) and the DMA of u + 1 -- the prefetch distance of the kernel above.
-// Same ring protocol, same ping-pong, same epilogues and candidate layout as gemm_topk16_kernel; dim % 32 == 0 only.
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-
-template <int EPI, int QD>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16q_kernel(const GemmArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wd = wv >> 2;
-    const int wq = wv & 3;
-    const int l15 = lane & 15;
-    const int lq = lane >> 4;
-    const bool g1 = (wv >= 4);
-    const int KS2 = a.dim / SUB_K;
-
-    const int srow = wv * 16 + (lane >> 2);  // + piece*128
-    const int schunk = (lane & 3) ^ (((srow >> 2) & 1) << 1);
-    const int cofs = ((lq ^ (((lane >> 2) & 1) << 1)) << 4);
-    const int a_base = (wd * 128 + l15) * 64 + cofs;                // + dt*1024
-
-    const int xcd = blockIdx.x & (NUM_XCD - 1);
-    const int jx = blockIdx.x >> 3;
-    const int per_x = gridDim.x >> 3;
-    const int qg = xcd % a.qgroups;
-    const int rc = xcd / a.qgroups;
-    const int nrc = NUM_XCD / a.qgroups;
-    const int qb_per = a.qblocks / a.qgroups;
-    const int count_x = (a.ranges / nrc) * qb_per;
-    const int item_end = a.item_end < count_x ? a.item_end : count_x;
-
-    for (int item = a.item_begin + jx; item < item_end; item += per_x) {
-        const int n_rl = a.ranges / nrc;
-        const int rl = a.item_swap ? item % n_rl : item / qb_per;
-        const int qb = qg * qb_per + (a.item_swap ? item / n_rl : item % qb_per);
-        const int r = rc + nrc * rl;
-        const int64_t ntile = (a.n_vt - r + a.ranges - 1) / a.ranges;
-        if (ntile <= 0) continue;
-        const int q0 = qb * TILE_Q;
-
-        float thr[4] = {0.f, 0.f, 0.f, 0.f}, cqv[4] = {0.f, 0.f, 0.f, 0.f};
-        uint32_t ncand[4] = {0u, 0u, 0u, 0u};
-        uint2 *clist[4] = {nullptr, nullptr, nullptr, nullptr};
-        int cap = 0;
-        if (EPI == EPI_FILTER) {
-            int seg_r0;
-            long long seg_base;
-            cand_segment(a.lay, r, cap, seg_r0, seg_base);
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) {
-                const int q = q0 + wq * 64 + qt * 16 + l15;
-                thr[qt] = (q < a.n_q) ? a.thr[q] : __builtin_nanf("");
-                cqv[qt] = (q < a.n_q) ? a.cq[q] : 0.f;
-                clist[qt] = a.cand + seg_base + ((int64_t)(r - seg_r0) * a.nq_pad + q) * 8 * cap + (wd * 4 + lq);
-            }
-            asm volatile("" : "+v"(thr[0]), "+v"(thr[1]), "+v"(thr[2]), "+v"(thr[3]), "+v"(cqv[0]), "+v"(cqv[1]), "+v"(cqv[2]), "+v"(cqv[3]));
-        }
-        // this lane's four query rows (B fragments): byte offsets from a.Q, K chunk lq folded in (n_q * dim * 2 < 2^31: checked by the launcher)
-        uint32_t qoff[4];
-#pragma unroll
-        for (int qt = 0; qt < 4; ++qt) {
-            int q = q0 + wq * 64 + qt * 16 + l15;
-            if (q > a.n_q - 1) q = a.n_q - 1;
-            qoff[qt] = (uint32_t)q * (uint32_t)(a.dim * 2) + (uint32_t)(lq * 16);
-        }
-        // The fragment loads and their waits are inline asm on purpose: hipcc's own wait for a C++ load is `vmcnt(0)` in front of the
-        // first MFMA (it cannot bound the conditional DMA issue in between), which drains the ring every sub-stage.  The asm load
-        // updates its destination in place ("+v": one physical register set across the loop), the counted wait names the same
-        // registers, so nothing reads them in between.
-        const char *qbase = reinterpret_cast<const char *>(a.Q);
-        auto ldq = [&](u32x4v &dst, int qt, int ks) {   // ks: K sub-stage inside the tile (wave-uniform)
-            const char *sb = qbase + ks * (SUB_K * 2);
-            asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(dst) : "v"(qoff[qt]), "s"(sb));
-        };
-#define CCR_WAIT_VM_Q(n, b) asm volatile("s_waitcnt vmcnt(" #n ")" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])::"memory")
-
-        f32x4v acc[8][4];
-        const int64_t U = ntile * KS2;
-
-        int64_t iu = 0, it = 0;
-        int iks = 0;
-        const uint16_t *dsrc[2];
-        auto tile_ptrs = [&]() {
-            const int64_t row0 = (r + it * a.ranges) * a.tile_stride * TILE_DOCS;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                int64_t drow = row0 + i * 128 + srow;
-                if (drow > a.n_rows - 1) drow = a.n_rows - 1;
-                dsrc[i] = a.D + drow * a.dim + schunk * 8;
-            }
-        };
-        tile_ptrs();
-        auto issue = [&]() {   // the corpus slice of one sub-stage: two 1-KiB pieces per wave
-            char *buf = smem + (int)(iu & (RING - 1)) * SUB_BYTES;
-            const int k0 = iks * SUB_K;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) glds16(dsrc[i] + k0, buf + (i * 512 + wv * 64) * 16);
-            ++iu;
-            if (++iks == KS2) {
-                iks = 0;
-                ++it;
-                tile_ptrs();
-            }
-        };
-
-        auto epilogue = [&](int64_t vt, float nt) __attribute__((always_inline)) {
-            const int64_t row_base = vt * a.tile_stride * TILE_DOCS + wd * 128 + 4 * lq;  // + dt*16 + e
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) {
-                if (EPI == EPI_FILTER) {
-                    float sub[8];
-#pragma unroll
-                    for (int dt = 0; dt < 8; ++dt)
-                        sub[dt] = fmaxf(fmaxf(acc[dt][qt][0], acc[dt][qt][1]), fmaxf(acc[dt][qt][2], acc[dt][qt][3]));
-                    const float t = fmaf(-cqv[qt], nt, thr[qt]);
-                    const float mall = fmaxf(fmaxf(fmaxf(sub[0], sub[1]), fmaxf(sub[2], sub[3])),
-                                             fmaxf(fmaxf(sub[4], sub[5]), fmaxf(sub[6], sub[7])));
-                    if (__ballot(mall >= t) != 0ull) {
-#pragma unroll
-                        for (int dt = 0; dt < 8; ++dt) {
-                            if (sub[dt] >= t) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) {
-                                    const float v = acc[dt][qt][e];
-                                    const int64_t doc = row_base + dt * 16 + e;
-                                    if (v >= t && doc < a.n_rows) {
-                                        if (ncand[qt] < (uint32_t)cap)
-                                            clist[qt][ncand[qt] * 8] = make_uint2(__float_as_uint(v), (uint32_t)doc);
-                                        ++ncand[qt];
-                                    }
-                                }
-                            }
-                        }
-                    }
-                } else {  // EPI_STORE
-                    const int q = q0 + wq * 64 + qt * 16 + l15;
-                    const int64_t pitch = a.store_pitch ? a.store_pitch : a.n_rows;
-                    if (q < a.n_q) {
-                        float *dst = a.store + (int64_t)q * pitch;
-#pragma unroll
-                        for (int dt = 0; dt < 8; ++dt) {
-                            const int64_t doc = row_base + dt * 16;
-                            if ((pitch & 3) == 0 && doc + 3 < a.n_rows) {
-                                *reinterpret_cast<float4 *>(dst + doc) =
-                                    make_float4(acc[dt][qt][0], acc[dt][qt][1], acc[dt][qt][2], acc[dt][qt][3]);
-                            } else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e)
-                                    if (doc + e < a.n_rows) dst[doc + e] = acc[dt][qt][e];
-                            }
-                        }
-                    }
-                }
-            }
-        };
-
-        // ---- prologue: the fragments of sub-stage 0 (and 1) first -- oldest in vmcnt -- then up to three sub-stages of corpus DMA
-        constexpr bool TWO = (QD >= 4);          // two register sets: fragments requested TWO sub-stages ahead
-        constexpr bool INTER = (QD == 3 || QD == 5);   // requested between the MFMAs (query tile by query tile) instead of behind them
-        u32x4v bq[4] = {}, bq2[4] = {};
-#pragma unroll
-        for (int qt = 0; qt < 4; ++qt) ldq(bq[qt], qt, 0);
-        if constexpr (TWO) {
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) ldq(bq2[qt], qt, KS2 > 1 ? 1 : 0);
-        }
-        // The DMA issue is UNCONDITIONAL (three sub-stages here, one per sub-stage in the loop -- the last three of an item fetch clamped
-        // rows into ring buffers nobody reads again): every counted wait below is then ONE straight-line statement.  A wait inside a branch
-        // makes hipcc merge the fragment registers of the two paths with copies, and it places such copies IN FRONT of the wait.
-        for (int i = 0; i < 3; ++i) issue();
-        if constexpr (TWO)
-            CCR_WAIT_VM_Q(2, bq);   // Q(0) Q(1) DMA(0) DMA(1) | DMA(2): sub-stage 1 has landed too, so that vmcnt(8) is enough at u = 0
-        else
-            CCR_WAIT_VM_Q(4, bq);   // Q(0) DMA(0) | DMA(1) DMA(2)
-        CCR_BARRIER();
-        if (g1) CCR_BARRIER();
-
-        int cks = 0;
-        int64_t ct = 0;
-        bool pending = false;
-        int64_t pending_vt = 0;
-        float pending_nt = 0.f;
-        // one sub-stage; cur = the fragments of u (requested one -- TWO: two -- sub-stages ago), nxt = where this sub-stage's requests go
-        // (ONE set: cur itself, for u + 1; TWO: cur as well -- it is free once the MFMAs of u are issued -- for u + 2, while the other
-        // set holds u + 1 in flight)
-        auto substage = [&](int64_t u, u32x4v (&cur)[4]) __attribute__((always_inline)) {
-            if (pending) {
-                epilogue(pending_vt, pending_nt);
-                pending = false;
-            }
-            int nks = cks + (TWO ? 2 : 1);   // K sub-stage (inside its tile) of the fragments requested during u
-            if (nks >= KS2) nks -= KS2;
-            if (nks >= KS2) nks = 0;        // (KS2 == 1)
-            const char *buf = smem + (int)(u & (RING - 1)) * SUB_BYTES;
-            bf16x8 af[8];
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) af[dt] = *reinterpret_cast<const bf16x8 *>(buf + a_base + dt * 1024);
-            issue();   // sub-stage u + 3 (past the item's end: see the prologue)
-            // confirm, before this wave's barrier A_u: the fragments of u and -- older in vmcnt -- this wave's corpus DMA of u + 1
-            if constexpr (TWO)
-                CCR_WAIT_VM_Q(8, cur);   // ... Q(u) | DMA(u+2)[2] Q(u+1)[4] DMA(u+3)[2]
-            else
-                CCR_WAIT_VM_Q(2, cur);   // ... DMA(u+2)[2] Q(u) | DMA(u+3)[2]
-            CCR_WAIT_LGKM0();
-            CCR_BARRIER();
-            if constexpr (INTER) {   // query tile by query tile; a tile's next fragment is requested as soon as its MFMAs are issued
-#pragma unroll
-                for (int qt = 0; qt < 4; ++qt) {
-                    if (cks == 0) {
-                        const f32x4v z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int dt = 0; dt < 8; ++dt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], __builtin_bit_cast(bf16x8, cur[qt]), z, 0, 0, 0);
-                    } else {
-#pragma unroll
-                        for (int dt = 0; dt < 8; ++dt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], __builtin_bit_cast(bf16x8, cur[qt]), acc[dt][qt], 0, 0, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    ldq(cur[qt], qt, nks);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            } else {
-                if (cks == 0) {
-                    const f32x4v z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                        for (int qt = 0; qt < 4; ++qt)
-                            acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], __builtin_bit_cast(bf16x8, cur[qt]), z, 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                        for (int qt = 0; qt < 4; ++qt)
-                            acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], __builtin_bit_cast(bf16x8, cur[qt]), acc[dt][qt], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int qt = 0; qt < 4; ++qt) ldq(cur[qt], qt, nks);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (++cks == KS2) {
-                cks = 0;
-                const int64_t vt_done = r + ct * a.ranges;
-                const float nt_done = EPI == EPI_FILTER ? load_uniform_f32(a.tile_norm + vt_done * a.tile_stride) : 0.f;
-                if (g1) {
-                    epilogue(vt_done, nt_done);
-                } else {
-                    pending = true;
-                    pending_vt = vt_done;
-                    pending_nt = nt_done;
-                }
-                ++ct;
-            }
-            CCR_BARRIER();
-        };
-        if constexpr (TWO) {
-            int64_t u = 0;
-            for (; u + 1 < U; u += 2) {
-                substage(u, bq);
-                substage(u + 1, bq2);
-            }
-            if (u < U) substage(u, bq);
-        } else {
-            for (int64_t u = 0; u < U; ++u) substage(u, bq);
-        }
-        // The DMA and the fragments requested past the item's end land here, unused.  The wait NAMES the fragment registers: they stay
-        // allocated until nothing is in flight into them (hipcc would otherwise hand them to the epilogue below as temporaries).
-        if constexpr (TWO) CCR_WAIT_VM_Q(0, bq2);
-        CCR_WAIT_VM_Q(0, bq);
-        if (pending) epilogue(pending_vt, pending_nt);
-        if (!g1) CCR_BARRIER();
-
-        if (EPI == EPI_FILTER) {
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt)
-                a.cnt[((int64_t)r * a.nq_pad + q0 + wq * 64 + qt * 16 + l15) * 8 + wd * 4 + lq] = ncand[qt];
-        }
-        __syncthreads();
-    }
-}
-#endif   // CCR_DIAGNOSTICS
 
 // ---------------------------------------------------------------------------------------------
 // bf16 row norms (fp32 accumulate; used only for error margins, inflated by the caller).  With tile_bits (the index's own
@@ -2237,70 +1728,16 @@ static int launch_kernel(K kernel, size_t lds, const GemmArgs &a, int grid, hipS
 template <int EPI>
 static int launch_gemm(const GemmArgs &a, int grid, hipStream_t s) {
     const size_t lds = RING * (size_t)SUB_BYTES;
-#ifdef CCR_DIAGNOSTICS
-    // Timing-only ablations of the main pass (CCR_GEMM_DBG, read once at index creation): they return WRONG results, so they exist
-    // only in a library built with -DCCR_DIAGNOSTICS (make DIAG=1); the shipped library has no such mode.
-    if (EPI == EPI_FILTER && a.dbg != 0) {
-        switch (a.dbg) {
-            case 1: return launch_kernel(&gemm_topk_kernel<EPI, true, 1>, lds, a, grid, s);
-            case 2: return launch_kernel(&gemm_topk_kernel<EPI, true, 2>, lds, a, grid, s);
-            case 3: return launch_kernel(&gemm_topk_kernel<EPI, true, 3>, lds, a, grid, s);
-            case 4: return launch_kernel(&gemm_topk_kernel<EPI, true, 4>, lds, a, grid, s);
-            case 8: return launch_kernel(&gemm_topk_kernel<EPI, true, 8>, lds, a, grid, s);
-            case 11: return launch_kernel(&gemm_topk_kernel<EPI, true, 11>, lds, a, grid, s);
-            case 16: return launch_kernel(&gemm_topk_kernel<EPI, true, 16>, lds, a, grid, s);
-            default: break;   // unknown value: the production kernel
-        }
-    }
-#endif
-    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk_kernel<EPI, true, 0, true>, lds, a, grid, s);   // zero-filled last K sub-stage
-    if (!a.stagger) return launch_kernel(&gemm_topk_kernel<EPI, false, 0>, lds, a, grid, s);   // CCR_GEMM_STAGGER=0 (A/B of the ping-pong)
-    return launch_kernel(&gemm_topk_kernel<EPI, true, 0>, lds, a, grid, s);
+    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk_kernel<EPI, true, true>, lds, a, grid, s);   // zero-filled last K sub-stage
+    if (!a.stagger) return launch_kernel(&gemm_topk_kernel<EPI, false>, lds, a, grid, s);   // CCR_GEMM_STAGGER=0 (A/B of the ping-pong)
+    return launch_kernel(&gemm_topk_kernel<EPI, true>, lds, a, grid, s);
 }
 
 int launch_gemm_filter(const GemmArgs &a, int grid, hipStream_t s) { return launch_gemm<EPI_FILTER>(a, grid, s); }
-#ifdef CCR_DIAGNOSTICS
-// query-direct forms (a.qdirect = 1 / 3 / 4 / 5: gemm_topk16q_kernel; diagnostic library only); dim % 32 == 0 and a query block of less than 2^31 bytes
-template <int EPI>
-static int launch_gemm16q(const GemmArgs &a, int grid, hipStream_t s) {
-    const size_t lds = RING * (size_t)SUB_BYTES;
-    switch (a.qdirect) {
-        case 1: return launch_kernel(&gemm_topk16q_kernel<EPI, 1>, lds, a, grid, s);
-        case 3: return launch_kernel(&gemm_topk16q_kernel<EPI, 3>, lds, a, grid, s);
-        case 4: return launch_kernel(&gemm_topk16q_kernel<EPI, 4>, lds, a, grid, s);
-        default: return launch_kernel(&gemm_topk16q_kernel<EPI, 5>, lds, a, grid, s);
-    }
-}
-static bool qdirect_ok(const GemmArgs &a) {
-    return a.qdirect > 0 && a.dim % SUB_K == 0 && (int64_t)a.n_q * a.dim * 2 < (int64_t)1 << 31;
-}
-#endif
 
 int launch_gemm16_filter(const GemmArgs &a, int grid, hipStream_t s) {
-#ifdef CCR_DIAGNOSTICS
-    // timing-only ablations of the 16x16x32 main pass (CCR_GEMM_DBG; WRONG results): diagnostic library only (make DIAG=1)
-    switch (a.dbg) {
-        case 4: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 4>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 8: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 8>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 12: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 12>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 32: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 32>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 40: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 40>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 64: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 64>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 128: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 128>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 384: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 384>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 640: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 640>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 1152: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 1152>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 2176: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 2176>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 4224: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 4224>, RING * (size_t)SUB_BYTES, a, grid, s);
-        case 8320: return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 8320>, RING * (size_t)SUB_BYTES, a, grid, s);
-        default: break;   // 0 or unknown: the production kernel
-    }
-#endif
-#ifdef CCR_DIAGNOSTICS
-    if (qdirect_ok(a)) return launch_gemm16q<EPI_FILTER>(a, grid, s);
-#endif
-    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 0, true>, RING * (size_t)SUB_BYTES, a, grid, s);
-    return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, 0>, RING * (size_t)SUB_BYTES, a, grid, s);
+    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, true>, RING * (size_t)SUB_BYTES, a, grid, s);
+    return launch_kernel(&gemm_topk16_kernel<EPI_FILTER>, RING * (size_t)SUB_BYTES, a, grid, s);
 }
 // the 256 x 384 form (a.qblocks counts blocks of WIDE_Q queries; dim % 32 == 0)
 int launch_gemm16w_filter(const GemmArgs &a, int grid, hipStream_t s) {
@@ -2308,28 +1745,11 @@ int launch_gemm16w_filter(const GemmArgs &a, int grid, hipStream_t s) {
         set_error("launch_gemm16w_filter: dim %d is not a multiple of %d", a.dim, SUB_K);
         return CCR_ERR_INVALID;
     }
-#ifdef CCR_DIAGNOSTICS
-    switch (a.dbg) {   // timing-only ablations (thresholds +inf in all of them)
-        case 16: return launch_kernel(&gemm_topk16w_kernel<16>, WIDE_LDS, a, grid, s);     // cycle stamps (results stay right)
-        case 144: return launch_kernel(&gemm_topk16w_kernel<144>, WIDE_LDS, a, grid, s);   // cycle stamps, thresholds +inf
-        case 128: return launch_kernel(&gemm_topk16w_kernel<128>, WIDE_LDS, a, grid, s);
-        case 132: return launch_kernel(&gemm_topk16w_kernel<132>, WIDE_LDS, a, grid, s);   // no DMA
-        case 136: return launch_kernel(&gemm_topk16w_kernel<136>, WIDE_LDS, a, grid, s);   // no MFMA
-        case 140: return launch_kernel(&gemm_topk16w_kernel<140>, WIDE_LDS, a, grid, s);   // neither: LDS reads + barriers + filter trees
-        case 160: return launch_kernel(&gemm_topk16w_kernel<160>, WIDE_LDS, a, grid, s);   // corpus pieces only
-        case 192: return launch_kernel(&gemm_topk16w_kernel<192>, WIDE_LDS, a, grid, s);   // query pieces only
-        case 168: return launch_kernel(&gemm_topk16w_kernel<168>, WIDE_LDS, a, grid, s);   // corpus pieces only, no MFMA
-        default: break;
-    }
-#endif
-    return launch_kernel(&gemm_topk16w_kernel<0>, WIDE_LDS, a, grid, s);
+    return launch_kernel(&gemm_topk16w_kernel, WIDE_LDS, a, grid, s);
 }
 int launch_gemm16_store(const GemmArgs &a, int grid, hipStream_t s) {
-#ifdef CCR_DIAGNOSTICS
-    if (qdirect_ok(a)) return launch_gemm16q<EPI_STORE>(a, grid, s);
-#endif
-    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk16_kernel<EPI_STORE, 0, true>, RING * (size_t)SUB_BYTES, a, grid, s);
-    return launch_kernel(&gemm_topk16_kernel<EPI_STORE, 0>, RING * (size_t)SUB_BYTES, a, grid, s);
+    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk16_kernel<EPI_STORE, true>, RING * (size_t)SUB_BYTES, a, grid, s);
+    return launch_kernel(&gemm_topk16_kernel<EPI_STORE>, RING * (size_t)SUB_BYTES, a, grid, s);
 }
 int launch_gemm_gmax(const GemmArgs &a, int grid, hipStream_t s) { return launch_gemm<EPI_GMAX>(a, grid, s); }
 int launch_gemm_store(const GemmArgs &a, int grid, hipStream_t s) { return launch_gemm<EPI_STORE>(a, grid, s); }

@@ -5,16 +5,14 @@
 
 namespace ccr {
 
-// Tuning / diagnostic knobs from the environment, read ONCE when an index is created (never inside a search).
+// Tuning knobs from the environment, read ONCE when an index is created (never inside a search).
 struct Knobs {
     int qgroups;       // CCR_QGROUPS      0 = planner's choice, else 1/2/4/8
     int progressive;   // CCR_PROGRESSIVE  0 = single main-pass launch
     int max_phases;    // CCR_PHASES       2 = at most one re-tightening (default 3)
     int mfma16;        // CCR_MFMA16       -1 = planner's choice, 0 = 32x32x16 kernel, 1 = 16x16x32 kernel
     int sample_div;    // CCR_SAMPLE_DIV   0 = planner's choice, else the pinned sample fraction 1/div
-    int gemm_dbg;      // CCR_GEMM_DBG     timing-only ablations of the main pass (WRONG results when non-zero)
     int stagger;       // CCR_GEMM_STAGGER 0 = both wave groups of the 32x32x16 kernel in phase
-    int qdirect;       // CCR_QDIRECT      16x16x32 main pass: 0 = queries through the LDS ring, 1 / 3 / 4 / 5 = query fragments straight from global memory
     int ranges;        // CCR_RANGES       0 = planner's choice, else the pinned range count (rounded to a multiple of 8)
     int item_swap;     // CCR_ITEM_SWAP    1 = co-resident workgroups share the query block instead of the corpus range (honoured with CCR_PROGRESSIVE=0)
     int optimistic;    // CCR_OPTIMISTIC   -1 = planner's choice, 0 = conservative thresholds only, 1 = estimated thresholds wherever the sample allows

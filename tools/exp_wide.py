@@ -1,8 +1,6 @@
 #!/usr/bin/env python3
 """Same-box A/B of the main pass on 256 x 384 tiles (CCR_WIDE, csrc/ccr_fused.hip gemm_topk16w_kernel) against the 256 x 256 kernel, at the
-NQ shape.  Runs ON THE GPU BOX, one process per variant.  Variants with CCR_GEMM_DBG=128 (thresholds +inf: the complete kernel without a
-single hit) need the DIAGNOSTIC library (tools/build_diag.sh) and return no results; every other variant must return the ids and score
-bits of the first one.
+NQ shape.  Runs ON THE GPU BOX, one process per variant.  Every variant must return the ids and score bits of the first one.
 
   python3 tools/exp_wide.py [outfile] [--rows N --queries Q --k K] [--set NAME]"""
 import os
@@ -21,10 +19,6 @@ def arg(name, dflt, conv=int):
 def one():
     sys.path[:0] = [ROOT, PKG]
     import torch
-    from ccrec_amd import _lib
-    diag = os.environ.get("CCR_GEMM_DBG", "0") != "0"
-    if diag:
-        _lib.LIB_PATH = os.path.join(PKG, "lib_diag", "libccr_hip.so")
     from ccrec_amd import ops
     n, nq, d, k = arg("--rows", 2681468), arg("--queries", 3452), arg("--dim", 768), arg("--k", 100)
     g = torch.Generator(device="cuda").manual_seed(1234)
@@ -41,9 +35,6 @@ def one():
         st = ix.last_stats()
         ms.append(st["ms_main"])
         tot.append(st["ms_total"])
-    if diag:
-        print("RESULT diag")
-        return
     ref = os.environ["QD_REF"]
     same = "ref"
     if os.path.exists(ref):
@@ -55,18 +46,12 @@ def one():
           f"rank {st['opt_rank']} sample {st['sample_tiles']} cand {st['n_candidates']} fallback {st['n_fallback']} {same}")
 
 
-_NH = {"CCR_PROGRESSIVE": "0", "CCR_OPTIMISTIC": "0"}
 SETS = {
-    "ablate": [dict(_NH, CCR_GEMM_DBG=str(v)) for v in (128, 132, 136, 140, 160, 192, 168, 128)],
     "narrow": [{"CCR_WIDE": "0"}, {"CCR_WIDE": "0", "CCR_PROGRESSIVE": "0"}, {"CCR_WIDE": "0"}],
     "ab": [{"CCR_WIDE": "0"}, {}, {"CCR_WIDE": "0"}, {}],
     "order": [{}, {"CCR_ITEM_SWAP": "1"}, {"CCR_QGROUPS": "1", "CCR_WIDE": "0", "CCR_PROGRESSIVE": "0"}, {}],
     "plans": [{"CCR_WIDE": "0"}, {}, {"CCR_OPTIMISTIC": "0"}, {"CCR_PROGRESSIVE": "0", "CCR_OPTIMISTIC": "0"}, {"CCR_WIDE": "0", "CCR_PROGRESSIVE": "0"},
               {"CCR_RANGES": "128"}, {"CCR_RANGES": "256"}, {"CCR_RANGES": "128", "CCR_OPTIMISTIC": "0"}, {"CCR_WIDE": "0"}],
-    "nohit": [{"CCR_WIDE": "0", "CCR_GEMM_DBG": "128", "CCR_PROGRESSIVE": "0"}, {"CCR_GEMM_DBG": "128", "CCR_PROGRESSIVE": "0", "CCR_OPTIMISTIC": "0"},
-              {"CCR_GEMM_DBG": "128", "CCR_PROGRESSIVE": "0", "CCR_OPTIMISTIC": "0", "CCR_RANGES": "256"},
-              {"CCR_GEMM_DBG": "128", "CCR_PROGRESSIVE": "0", "CCR_OPTIMISTIC": "0", "CCR_RANGES": "64"},
-              {"CCR_WIDE": "0", "CCR_GEMM_DBG": "128", "CCR_PROGRESSIVE": "0"}],
 }
 
 
@@ -84,11 +69,7 @@ def main():
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one"] + extra, env=env, capture_output=True, text=True, timeout=900)
         m = re.search(r"RESULT (.*)", r.stdout)
         name = " ".join(f"{k}={v}" for k, v in env_v.items()) or "(defaults)"
-        if m and m.group(1) == "diag":
-            t = sorted(float(x) for x in re.findall(r"\[ccr diag\] CCR_GEMM_DBG=\d+ main pass ([0-9.]+) ms", r.stderr)[-5:])
-            lines.append(f"{name:70s} no-hit main pass {t[len(t) // 2]:.4f} ms")
-        else:
-            lines.append(f"{name:70s} " + (m.group(1) if m else f"FAILED rc={r.returncode} {r.stderr[-400:]!r}"))
+        lines.append(f"{name:70s} " + (m.group(1) if m else f"FAILED rc={r.returncode} {r.stderr[-400:]!r}"))
         print(lines[-1], flush=True)
     open(out, "w").write("\n".join(lines) + "\n")
     if os.path.exists(ref):
