@@ -39,15 +39,12 @@ Knobs read_knobs() {
     kn.max_phases = env_int("CCR_PHASES", 3);
     kn.mfma16 = env_int("CCR_MFMA16", -1);
     kn.sample_div = env_int("CCR_SAMPLE_DIV", 0);
-    kn.stagger = env_int("CCR_GEMM_STAGGER", 1);
     kn.max_lists = env_int("CCR_MAX_LISTS", 0);
     kn.ranges = env_int("CCR_RANGES", 0);
-    kn.item_swap = env_int("CCR_ITEM_SWAP", 0);
     kn.optimistic = env_int("CCR_OPTIMISTIC", -1);
     kn.opt_rank = env_int("CCR_OPT_RANK", 0);
     kn.narrow = env_int("CCR_NARROW", -1);
     kn.wide = env_int("CCR_WIDE", -1);
-    kn.narrow_nt = env_int("CCR_NARROW_NT", 0);
     kn.narrow_grid = env_int("CCR_NARROW_GRID", 0);
     kn.narrow_groups = env_int("CCR_NARROW_GROUPS", NARROW_MAX_GROUPS);
     return kn;
@@ -101,9 +98,6 @@ static int best_sample_ranges(int64_t n_vt, int qblocks, int qgroups, int grid) 
 }
 
 constexpr size_t DENSE_SCRATCH_TARGET = (size_t)1 << 30;  // ~1 GiB of score rows per dense chunk
-#ifndef CCR_MFMA16_DEFAULT
-#define CCR_MFMA16_DEFAULT 1
-#endif
 
 // ------------------------------------------------------------------ main-pass planner
 // Work items of the main pass are (range, query block); range r owns the tiles r, r + R, ...  An XCD set of per_x
@@ -298,8 +292,7 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
         int nqt = n_q <= 16 ? 1 : (n_q <= 32 ? 2 : 4);
         int ngroups = n_q <= NARROW_MAX_Q ? 1 : 2;
         // 65 .. 96 queries: ONE group of six query tiles where their rows fit the LDS (dim <= 768) -- every corpus row is pulled once
-        if (n_q > NARROW_MAX_Q && n_q <= 96 && kn.narrow_groups >= 2 && dim % TILE_K == 0 && narrow_lds_bytes(6, dim) <= (size_t)160 * 1024 &&
-            env_int("CCR_NARROW_WIDE", 1) != 0)
+        if (n_q > NARROW_MAX_Q && n_q <= 96 && kn.narrow_groups >= 2 && dim % TILE_K == 0 && narrow_lds_bytes(6, dim) <= (size_t)160 * 1024)
             nqt = 6, ngroups = 1;
         const bool narrow = kn.narrow != 0 && n_q <= NARROW_MAX_Q * std::min(std::max(kn.narrow_groups, 1), NARROW_MAX_GROUPS) && dim % TILE_K == 0 &&
                             narrow_lds_bytes(nqt, dim) <= (size_t)160 * 1024 && (ngroups == 1 || num_cu >= 16);
@@ -455,7 +448,6 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
 // sub-lists (config-4 shard, k = 1000, 62 ranges: main pass 111 vs 120 ms, select 8.9 vs 9.4 ms).
 Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn) {
     if (kn.mfma16 >= 0) return make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, kn.mfma16 ? 1 : 0);
-    if (!CCR_MFMA16_DEFAULT) return make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, 0);
     if (k <= 512) return make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, 1);
     const Plan p32 = make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, 0);
     if (p32.fused && p32.ranges * 8 <= 2048) return make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, 1);
@@ -694,6 +686,22 @@ static int dense_for_list(const ccr_index *ix, const uint16_t *Q, const uint32_t
 // out_rows[i] (or q_begin + i).  Queries the margin select cannot finish are appended to flag_list (flag_count is NOT reset here).
 static bool margin_path_ok(const ccr_index *ix, int k) { return ix->dim % 8 == 0 && k <= MAX_K; }
 
+// kernel arguments of n_q query rows at Q (nq_pad / TILE_Q blocks) against the index's corpus, all work items
+static GemmArgs gemm_args(const ccr_index *ix, const uint16_t *Q, int n_q, int nq_pad) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.D = ix->D;
+    g.n_rows = ix->n_rows;
+    g.dim = ix->dim;
+    g.Q = Q;
+    g.n_q = n_q;
+    g.nq_pad = nq_pad;
+    g.qblocks = nq_pad / TILE_Q;
+    g.item_begin = 0;
+    g.item_end = INT32_MAX;
+    return g;
+}
+
 static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float *hint, const uint32_t *out_rows, int q_begin, int n, int k, float *scratch,
                            size_t scratch_bytes, float *out_scores, int64_t *out_ids, uint32_t *flag_count, uint32_t *flag_list,
                            hipStream_t s) {
@@ -704,25 +712,14 @@ static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float 
     const int grid = std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD);
     for (int lo = 0; lo < n; lo += (int)chunk) {
         const int m = std::min<int64_t>(chunk, n - lo);
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.D = ix->D;
-        g.n_rows = ix->n_rows;
-        g.dim = ix->dim;
-        g.Q = Qc + (int64_t)lo * ix->dim;
-        g.n_q = m;
-        g.nq_pad = (int)round_up(m, TILE_Q);
-        g.qblocks = g.nq_pad / TILE_Q;
+        GemmArgs g = gemm_args(ix, Qc + (int64_t)lo * ix->dim, m, (int)round_up(m, TILE_Q));
         g.n_vt = (ix->n_rows + TILE_DOCS - 1) / TILE_DOCS;
         g.tile_stride = 1;
         g.ranges = (int)round_up(std::min<int64_t>(std::max<int64_t>(1, g.n_vt / 4), 1024), NUM_XCD);   // ~4 tiles per work item
         g.qgroups = 1;
-        g.item_begin = 0;
-        g.item_end = INT32_MAX;
         g.store = scratch;
         g.store_pitch = pitch;
-        g.stagger = 1;
-        int rc = (ix->knobs.mfma16 >= 0 ? ix->knobs.mfma16 : CCR_MFMA16_DEFAULT) ? launch_gemm16_store(g, grid, s) : launch_gemm_store(g, grid, s);
+        int rc = ix->knobs.mfma16 != 0 ? launch_gemm16_store(g, grid, s) : launch_gemm_store(g, grid, s);
         if (rc != CCR_OK) return rc;
         rc = launch_margin_select(scratch, pitch, ix->n_rows, k, ix->dim, g.Q, ix->D, ix->tile_norm, ix->row_norm, ix->dmax_bits,
                                   hint ? hint + lo : nullptr, out_rows ? out_rows + lo : nullptr, q_begin + lo, m, ix->id_out, out_scores, out_ids, flag_count, flag_list, s);
@@ -917,17 +914,8 @@ static int search_complete(ccr_index *ix) {
                 lay2.cap[0] = lay2.cap[1] = lay2.cap[2] = (int)cap2;
                 CCR_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nsub_all * pad2 * 4, s));
                 CCR_HIP_CHECK(hipMemsetAsync(flag2, 0, 64, s));
-                GemmArgs g;
-                memset(&g, 0, sizeof(g));
-                g.D = ix->D;
-                g.n_rows = ix->n_rows;
-                g.dim = ix->dim;
-                g.Q = Q2;
-                g.n_q = n_cur;
-                g.nq_pad = pad2;
-                g.qblocks = pad2 / TILE_Q;
+                GemmArgs g = gemm_args(ix, Q2, n_cur, pad2);
                 g.qgroups = pick_qgroups(g.qblocks, ix->dim, ix->knobs);
-                g.stagger = ix->knobs.stagger;
                 g.n_vt = p.tiles;
                 g.tile_stride = 1;
                 g.ranges = p.ranges;
@@ -937,8 +925,6 @@ static int search_complete(ccr_index *ix) {
                 g.cnt = cnt;
                 g.cand = cand;
                 g.lay = lay2;
-                g.item_begin = 0;
-                g.item_end = INT32_MAX;
                 rc = p.mfma16 ? launch_gemm16_filter(g, p.grid, s) : launch_gemm_filter(g, p.grid, s);
                 if (rc != CCR_OK) return rc;
                 rc = launch_select_rescore(cand, cnt, nsub_all, p.sublists, n_cur, pad2, lay2, k, p.rescore_cap, p.select_compact, ix->n_rows,
@@ -1101,23 +1087,15 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     uint32_t *flag_list = (uint32_t *)(ws + p.off_flag + 64);
 
     CCR_HIP_CHECK(hipMemsetAsync(flag_count, 0, 64, s));
-    // every (range, query block) item with at least one tile writes its counters at its end (padded query columns included);
+    // every (range, query block) item with at least one tile writes its counters at its end, for the columns below
+    // main_qblocks * tile_q (the 256 x 384 kernel leaves [main_qblocks * 384, nq_pad) unwritten: no reader goes past n_q);
     // only a plan with more ranges than tiles (forced fused searches of tiny corpora) leaves counters unwritten
     if ((int64_t)p.ranges > p.tiles) CCR_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)p.ranges * p.nq_pad * p.sublists * 4, s));
     int rc = launch_row_norms_bf16(Q_bf16, n_q, ix->dim, qnorm, nullptr, nullptr, s);
     if (rc != CCR_OK) return rc;
 
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.D = ix->D;
-    g.n_rows = ix->n_rows;
-    g.dim = ix->dim;
-    g.Q = Q_bf16;
-    g.n_q = n_q;
-    g.nq_pad = p.nq_pad;
-    g.qblocks = p.qblocks;
+    GemmArgs g = gemm_args(ix, Q_bf16, n_q, p.nq_pad);
     g.qgroups = p.qgroups;
-    g.stagger = ix->knobs.stagger;
 
     // sample pass -> group maxima -> thresholds
     GemmArgs gs = g;
@@ -1125,8 +1103,6 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     gs.tile_stride = p.sample_stride;
     gs.ranges = p.sample_ranges;
     gs.gmax = gmax;
-    gs.item_begin = 0;
-    gs.item_end = INT32_MAX;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[1], s));
     rc = launch_gemm_gmax(gs, p.grid, s);
     if (rc != CCR_OK) return rc;
@@ -1145,7 +1121,6 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     gm.cnt = cnt;
     gm.qblocks = p.main_qblocks;   // (blocks of p.tile_q queries; the sample pass above walks blocks of TILE_Q)
     gm.qgroups = p.main_qgroups;
-    gm.item_swap = (ix->knobs.item_swap && !p.item_a) ? 1 : 0;   // the phases' "ranges completed so far" needs the default order
     CCR_HIP_CHECK(hipEventRecord(ix->ev[3], s));
     if (p.narrow) {
         // small batch: the corpus is STREAMED past query rows resident in LDS (ccr_narrow.hip); two atomically filled sub-lists per query
@@ -1171,7 +1146,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
         const int64_t blocks = (ix->n_rows + 16 * NARROW_WAVES - 1) / (16 * NARROW_WAVES);
         if ((int64_t)ngrid > blocks) ngrid = (int)std::max<int64_t>(1, blocks);
         if (p.narrow_groups == 2) ngrid = std::max(16, ngrid / 16 * 16);   // whole sets of eight (b, b + 8) pairs; a pair shares its row stream
-        rc = launch_narrow_filter(na, p.narrow, ngrid, ix->knobs.narrow_nt != 0, s);
+        rc = launch_narrow_filter(na, p.narrow, ngrid, s);
     } else {
         rc = run_main_pass(ix, p, gm, cand, cnt, thr, delta, p.item_b ? (uint32_t *)(ws + p.off_top) : nullptr, n_q, k, true, s);
     }
@@ -1251,24 +1226,13 @@ extern "C" int ccr_scores(const ccr_index *ix, const uint16_t *Q_bf16, int n_q, 
         return launch_dense_scores(ix->D, ix->n_rows, ix->dim, Q_bf16, nullptr, 0, n_q, nullptr, out, (hipStream_t)stream);
     CCR_REQUIRE(mode == CCR_SCORES_MFMA, "ccr_scores: unknown mode %d", mode);
     CCR_REQUIRE(ix->dim % 8 == 0, "ccr_scores: CCR_SCORES_MFMA needs dim %% 8 == 0 (dim=%d)", ix->dim);
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.D = ix->D;
-    g.n_rows = ix->n_rows;
-    g.dim = ix->dim;
-    g.Q = Q_bf16;
-    g.n_q = n_q;
-    g.nq_pad = (int)round_up(n_q, TILE_Q);
-    g.qblocks = g.nq_pad / TILE_Q;
+    GemmArgs g = gemm_args(ix, Q_bf16, n_q, (int)round_up(n_q, TILE_Q));
     g.n_vt = (ix->n_rows + TILE_DOCS - 1) / TILE_DOCS;
     g.tile_stride = 1;
     g.ranges = (int)round_up(std::min<int64_t>(64, g.n_vt), NUM_XCD);
     g.qgroups = 1;
-    g.item_begin = 0;
-    g.item_end = INT32_MAX;
     g.store = out;
-    g.stagger = 1;
     const int grid = std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD);
-    if (ix->knobs.mfma16 >= 0 ? ix->knobs.mfma16 : CCR_MFMA16_DEFAULT) return launch_gemm16_store(g, grid, (hipStream_t)stream);
+    if (ix->knobs.mfma16 != 0) return launch_gemm16_store(g, grid, (hipStream_t)stream);
     return launch_gemm_store(g, grid, (hipStream_t)stream);
 }

@@ -138,8 +138,6 @@ struct GemmArgs {
     // EPI_STORE (debug)
     float *store;         // [n_q][store_pitch]
     int64_t store_pitch;  // floats per stored query row (0: n_rows); a multiple of 4 lets a lane store its 4 consecutive rows as 16 bytes
-    int item_swap;        // experiment (CCR_ITEM_SWAP, single-launch plans only): co-resident workgroups share the query block, not the range
-    int stagger;          // 32x32x16 kernel: 1 = the two wave groups run one barrier interval apart (production), 0 = in phase
 };
 
 

@@ -62,7 +62,7 @@ __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int EPI, bool STAGGER, bool TAIL = false>
+template <int EPI, bool TAIL = false>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
     const int wq = wv & 3;    // query quarter of the tile
     const int l31 = lane & 31;
     const int h = lane >> 5;
-    const bool g1 = STAGGER && (wv >= 4);  // the trailing half of the ping-pong (wave-uniform)
+    const bool g1 = (wv >= 4);  // the trailing half of the ping-pong (wave-uniform)
     const int KS2 = TAIL ? (a.dim + SUB_K - 1) / SUB_K : a.dim / SUB_K;   // TAIL: the last sub-stage is partly zero-filled
 
     // DMA role: 4 x 1-KiB pieces per sub-stage (16 rows x 64 B each); LDS image is lane-linear, the
@@ -102,10 +102,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
 
     for (int item = a.item_begin + jx; item < item_end; item += per_x) {
         // item order: consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for
-        // different query blocks; item_swap (experiment, single-launch plans): they share the QUERY BLOCK instead
-        const int n_rl = a.ranges / nrc;
-        const int rl = a.item_swap ? item % n_rl : item / qb_per;
-        const int qb = qg * qb_per + (a.item_swap ? item / n_rl : item % qb_per);
+        // different query blocks
+        const int rl = item / qb_per;
+        const int qb = qg * qb_per + item % qb_per;
         const int r = rc + nrc * rl;
         const int64_t ntile = (a.n_vt - r + a.ranges - 1) / a.ranges;
         if (ntile <= 0) continue;
@@ -344,7 +343,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmAr
             CCR_BARRIER();
         }
         if (pending) epilogue(pending_vt, pending_nt);
-        if (STAGGER && !g1) CCR_BARRIER();  // every wave executes the same number of barriers
+        if (!g1) CCR_BARRIER();  // every wave executes the same number of barriers
 
         if (EPI == EPI_FILTER) {
 #pragma unroll
@@ -412,10 +411,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
 
     for (int item = a.item_begin + jx; item < item_end; item += per_x) {
         // item order: consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for
-        // different query blocks; item_swap (experiment, single-launch plans): they share the QUERY BLOCK instead
-        const int n_rl = a.ranges / nrc;
-        const int rl = a.item_swap ? item % n_rl : item / qb_per;
-        const int qb = qg * qb_per + (a.item_swap ? item / n_rl : item % qb_per);
+        // different query blocks
+        const int rl = item / qb_per;
+        const int qb = qg * qb_per + item % qb_per;
         const int r = rc + nrc * rl;
         const int64_t ntile = (a.n_vt - r + a.ranges - 1) / a.ranges;
         if (ntile <= 0) continue;
@@ -715,12 +713,11 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
     const int item_end = a.item_end < count_x ? a.item_end : count_x;
 
     for (int item = a.item_begin + jx; item < item_end; item += per_x) {
-        const int n_rl = a.ranges / nrc;
         // item order: consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for different
-        // query blocks.  (Measured at NQ, nine blocks = 5 MiB of query rows per XCD against 4 MiB of L2: sharing the query block instead
-        // -- CCR_ITEM_SWAP -- main pass 12.05 ms against 11.49; blocks in two halves, all ranges x first half then x second: 11.75.)
-        const int rl = a.item_swap ? item % n_rl : item / qb_per;
-        const int qb = qg * qb_per + (a.item_swap ? item / n_rl : item % qb_per);
+        // query blocks.  (Measured at NQ, nine blocks = 5 MiB of query rows per XCD against 4 MiB of L2: sharing the query block instead,
+        // main pass 12.05 ms against 11.49; blocks in two halves, all ranges x first half then x second: 11.75.)
+        const int rl = item / qb_per;
+        const int qb = qg * qb_per + item % qb_per;
         const int r = rc + nrc * rl;
         const int64_t ntile = (a.n_vt - r + a.ranges - 1) / a.ranges;
         if (ntile <= 0) continue;
@@ -1728,9 +1725,8 @@ static int launch_kernel(K kernel, size_t lds, const GemmArgs &a, int grid, hipS
 template <int EPI>
 static int launch_gemm(const GemmArgs &a, int grid, hipStream_t s) {
     const size_t lds = RING * (size_t)SUB_BYTES;
-    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk_kernel<EPI, true, true>, lds, a, grid, s);   // zero-filled last K sub-stage
-    if (!a.stagger) return launch_kernel(&gemm_topk_kernel<EPI, false>, lds, a, grid, s);   // CCR_GEMM_STAGGER=0 (A/B of the ping-pong)
-    return launch_kernel(&gemm_topk_kernel<EPI, true>, lds, a, grid, s);
+    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk_kernel<EPI, true>, lds, a, grid, s);   // zero-filled last K sub-stage
+    return launch_kernel(&gemm_topk_kernel<EPI>, lds, a, grid, s);
 }
 
 int launch_gemm_filter(const GemmArgs &a, int grid, hipStream_t s) { return launch_gemm<EPI_FILTER>(a, grid, s); }

@@ -21,8 +21,6 @@
 // r5: 65 .. 128 queries run as TWO groups of <= 64 (NarrowArgs::groups): workgroups b and b + 8 -- the same XCD -- hold the two groups'
 // query rows and walk the SAME corpus rows, so HBM still delivers the corpus once (the partner finds the rows in the XCD's L2 or in the
 // Infinity Cache) instead of the tile kernels' full 256-query tile per corpus tile.
-#include <stdlib.h>
-
 #include "ccr_gemm_common.h"
 #include "ccr_index.h"
 #include "ccr_narrow.h"
@@ -37,17 +35,11 @@ __device__ __forceinline__ float narrow_uniform_f32(const float *p) {
     return v;
 }
 
-template <bool NT>
-__device__ __forceinline__ bf16x8 stream_load(const char *p) {
-    if constexpr (NT)
-        return __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(p));
-    else
-        return *reinterpret_cast<const bf16x8 *>(p);
-}
+__device__ __forceinline__ bf16x8 stream_load(const char *p) { return *reinterpret_cast<const bf16x8 *>(p); }
 
 // NQT: query tiles of 16 (1, 2, 4; 6 = 65 .. 96 queries in one group, with a short staging list per query); P: loads in flight per wave =
 // K-steps per chunk (divides dim / 32)
-template <int NQT, int P, bool NT>
+template <int NQT, int P>
 __global__ __launch_bounds__(NARROW_THREADS) void narrow_filter_kernel(const NarrowArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -109,7 +101,7 @@ __global__ __launch_bounds__(NARROW_THREADS) void narrow_filter_kernel(const Nar
     const char *lp = my_groups > 0 ? row_ptr(lgroup) : Dbytes;
     if (n_chunks > 0) {
 #pragma unroll
-        for (int j = 0; j < P; ++j) buf[j] = stream_load<NT>(lp + j * 64);
+        for (int j = 0; j < P; ++j) buf[j] = stream_load(lp + j * 64);
         if (++lc == cpg) {
             lc = 0;
             lgroup += g_step;
@@ -152,7 +144,7 @@ __global__ __launch_bounds__(NARROW_THREADS) void narrow_filter_kernel(const Nar
             // wave): a branch around the load makes hipcc count vmcnt for the path without it, which drains the window at the end of
             // every chunk.  The scheduling barrier keeps hipcc from collecting the P refills at the end of the chunk (a burst: the
             // window would run empty while the chunk is consumed).
-            buf[j] = stream_load<NT>(lp + j * 64);
+            buf[j] = stream_load(lp + j * 64);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int qt = 0; qt < NQT; ++qt) bcur[qt] = bnext[qt];
@@ -224,43 +216,38 @@ size_t narrow_lds_bytes(int nqt, int dim) {
 }
 
 template <int NQT, int P>
-static int launch_narrow_np(const NarrowArgs &a, int grid, bool nt, hipStream_t s) {
-    const size_t lds = narrow_lds_bytes(NQT, a.dim);
-    if (nt) {
-        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&narrow_filter_kernel<NQT, P, true>), 160 * 1024);
-        if (rc != CCR_OK) return rc;
-        hipLaunchKernelGGL((narrow_filter_kernel<NQT, P, true>), dim3(grid), dim3(NARROW_THREADS), lds, s, a);
-    } else {
-        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&narrow_filter_kernel<NQT, P, false>), 160 * 1024);
-        if (rc != CCR_OK) return rc;
-        hipLaunchKernelGGL((narrow_filter_kernel<NQT, P, false>), dim3(grid), dim3(NARROW_THREADS), lds, s, a);
-    }
+static int launch_narrow_np(const NarrowArgs &a, int grid, hipStream_t s) {
+    const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&narrow_filter_kernel<NQT, P>), 160 * 1024);
+    if (rc != CCR_OK) return rc;
+    hipLaunchKernelGGL((narrow_filter_kernel<NQT, P>), dim3(grid), dim3(NARROW_THREADS), narrow_lds_bytes(NQT, a.dim), s, a);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
 
 template <int NQT>
-static int launch_narrow_n(const NarrowArgs &a, int grid, bool nt, hipStream_t s) {
+static int launch_narrow_n(const NarrowArgs &a, int grid, hipStream_t s) {
     const int KS = a.dim / SUB_K;
     // two query groups: every corpus row is pulled by two CUs (one of them from the L2 / the Infinity Cache), i.e. a CU moves twice the
     // bytes of the one-group launch -- twice the window (24 KiB per wave in flight) keeps the pull rate per CU from binding
-    if (NQT == 4 && a.groups == 2 && KS % 24 == 0 && getenv("CCR_NARROW_P12") == nullptr) return launch_narrow_np<NQT, 24>(a, grid, nt, s);
-    if (KS % 12 == 0) return launch_narrow_np<NQT, 12>(a, grid, nt, s);
-    if (KS % 8 == 0) return launch_narrow_np<NQT, 8>(a, grid, nt, s);
-    if (KS % 4 == 0) return launch_narrow_np<NQT, 4>(a, grid, nt, s);
-    if (KS % 2 == 0) return launch_narrow_np<NQT, 2>(a, grid, nt, s);
-    return launch_narrow_np<NQT, 1>(a, grid, nt, s);
+    if constexpr (NQT == 4) {
+        if (a.groups == 2 && KS % 24 == 0) return launch_narrow_np<NQT, 24>(a, grid, s);
+    }
+    if (KS % 12 == 0) return launch_narrow_np<NQT, 12>(a, grid, s);
+    if (KS % 8 == 0) return launch_narrow_np<NQT, 8>(a, grid, s);
+    if (KS % 4 == 0) return launch_narrow_np<NQT, 4>(a, grid, s);
+    if (KS % 2 == 0) return launch_narrow_np<NQT, 2>(a, grid, s);
+    return launch_narrow_np<NQT, 1>(a, grid, s);
 }
 
-int launch_narrow_filter(const NarrowArgs &a, int nqt, int grid, bool nt, hipStream_t s) {
+int launch_narrow_filter(const NarrowArgs &a, int nqt, int grid, hipStream_t s) {
     CCR_REQUIRE(a.dim % SUB_K == 0 && a.n_q >= 1 && (nqt == 1 || nqt == 2 || nqt == 4 || nqt == 6) && (a.groups == 1 || a.groups == 2) &&
                     (a.groups == 1 ? a.n_q <= nqt * 16 : (nqt == 4 && a.n_q > NARROW_MAX_Q && a.n_q <= 2 * NARROW_MAX_Q && grid % 16 == 0)),
                 "narrow main pass: bad shape (internal)");
     CCR_REQUIRE(narrow_lds_bytes(nqt, a.dim) <= 160 * 1024, "narrow main pass: %zu bytes of LDS (internal)", narrow_lds_bytes(nqt, a.dim));
-    if (nqt == 1) return launch_narrow_n<1>(a, grid, nt, s);
-    if (nqt == 2) return launch_narrow_n<2>(a, grid, nt, s);
-    if (nqt == 6) return launch_narrow_n<6>(a, grid, nt, s);
-    return launch_narrow_n<4>(a, grid, nt, s);
+    if (nqt == 1) return launch_narrow_n<1>(a, grid, s);
+    if (nqt == 2) return launch_narrow_n<2>(a, grid, s);
+    if (nqt == 6) return launch_narrow_n<6>(a, grid, s);
+    return launch_narrow_n<4>(a, grid, s);
 }
 
 }  // namespace ccr

@@ -19,7 +19,6 @@ int main() {
     kn.progressive = 1;
     kn.max_phases = 3;
     kn.mfma16 = -1;
-    kn.stagger = 1;
     kn.optimistic = -1;   // the planner's choice, as in production
     kn.wide = -1;         // 256 x 384 main-pass tiles where the planner prices them in
     const long long rows[] = {300, 9862, 70000, 335184, 1105228, 2681468, 8841823, 6250000};
@@ -96,7 +95,6 @@ int main() {
     // small batches: the first main pass is the streaming kernel (ccr_narrow.hip) -- one launch, two sub-lists per query inside the
     // candidate area, chosen exactly when the query rows fit its LDS image; the retry layout stays the tile kernels'
     kn.narrow = -1;
-    kn.narrow_nt = 1;
     int narrow = 0;
     for (long long n : rows)
         for (int d : dims)

@@ -7,9 +7,8 @@ For every variant of the work mapping (environment knobs read by the library at 
   * three separate `rocprofv3 --kernel-trace --pmc` passes  -> FETCH_SIZE (x2 on gfx950, KiB), WRITE_SIZE + TCC_HIT/MISS,
                                                               GRBM_GUI_ACTIVE (/ 8 XCDs / kernel duration = effective clock)
 Counters are never combined with sys/hip traces; the profiled program is `python3 bench.py` itself.  This driver makes no
-GPU call.  Variants: query-group width (CCR_QGROUPS: how many XCDs share a set of query blocks), single launch
-(CCR_PROGRESSIVE=0, so that the mappings are comparable) and the swapped item order (CCR_ITEM_SWAP=1: the co-resident
-workgroups of an XCD share the QUERY BLOCK instead of the corpus range)."""
+GPU call.  Variants: query-group width (CCR_QGROUPS: how many XCDs share a set of query blocks) and single launch
+(CCR_PROGRESSIVE=0, so that the mappings are comparable)."""
 import csv
 import glob
 import json
@@ -83,14 +82,11 @@ def main():
         ("nq_tile256", {"CCR_WIDE": "0"}, nq),            # round 6: the 256 x 256 kernel beside the planner's 256 x 384 choice
         ("nq_single_qg2", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "2"}, nq),
         ("nq_single_qg1", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "1"}, nq),
-        ("nq_single_qg2_swap", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "2", "CCR_ITEM_SWAP": "1"}, nq),
-        ("nq_single_qg1_swap", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "1", "CCR_ITEM_SWAP": "1"}, nq),
         ("q4096_default", {}, q16),
         ("q4096_single_qg1", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "1"}, q16),
         ("q4096_single_qg2", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "2"}, q16),
         ("q4096_single_qg4", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "4"}, q16),
         ("q4096_single_qg8", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "8"}, q16),
-        ("q4096_single_qg8_swap", {"CCR_PROGRESSIVE": "0", "CCR_QGROUPS": "8", "CCR_ITEM_SWAP": "1"}, q16),
         # the secondaries of the bench line (their `traffic` was null in round 2)
         ("msmarco_scale", {}, ["--rows", "8841823", "--queries", "6980"]),
         ("nq_k1001", {}, ["--k", "1001"]),
