@@ -719,7 +719,7 @@ static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float 
         g.qgroups = 1;
         g.store = scratch;
         g.store_pitch = pitch;
-        int rc = ix->knobs.mfma16 != 0 ? launch_gemm16_store(g, grid, s) : launch_gemm_store(g, grid, s);
+        int rc = launch_gemm(g, ix->knobs.mfma16 != 0 ? MAIN_16X16 : MAIN_32X32, EPI_STORE, grid, s);
         if (rc != CCR_OK) return rc;
         rc = launch_margin_select(scratch, pitch, ix->n_rows, k, ix->dim, g.Q, ix->D, ix->tile_norm, ix->row_norm, ix->dmax_bits,
                                   hint ? hint + lo : nullptr, out_rows ? out_rows + lo : nullptr, q_begin + lo, m, ix->id_out, out_scores, out_ids, flag_count, flag_list, s);
@@ -757,8 +757,8 @@ static int run_main_pass(const ccr_index *ix, const Plan &p, GemmArgs gm, uint2 
         }
         gm.item_begin = done;
         gm.item_end = bounds[ph];
-        const int rc = p.tile_q == WIDE_Q ? launch_gemm16w_filter(gm, p.grid, s)
-                                          : (p.mfma16 ? launch_gemm16_filter(gm, p.grid, s) : launch_gemm_filter(gm, p.grid, s));
+        const MainKernel kind = p.tile_q == WIDE_Q ? MAIN_WIDE : p.mfma16 ? MAIN_16X16 : MAIN_32X32;
+        const int rc = launch_gemm(gm, kind, EPI_FILTER, p.grid, s);
         if (rc != CCR_OK) return rc;
         done = bounds[ph];
     }
@@ -925,7 +925,7 @@ static int search_complete(ccr_index *ix) {
                 g.cnt = cnt;
                 g.cand = cand;
                 g.lay = lay2;
-                rc = p.mfma16 ? launch_gemm16_filter(g, p.grid, s) : launch_gemm_filter(g, p.grid, s);
+                rc = launch_gemm(g, p.mfma16 ? MAIN_16X16 : MAIN_32X32, EPI_FILTER, p.grid, s);   // TILE_Q blocks: never the wide kernel
                 if (rc != CCR_OK) return rc;
                 rc = launch_select_rescore(cand, cnt, nsub_all, p.sublists, n_cur, pad2, lay2, k, p.rescore_cap, p.select_compact, ix->n_rows,
                                            thr2, delta2, ix->tile_norm, ix->row_norm, ix->dmax_bits, Q2, ix->D, ix->dim, ix->id_out, pd.out_scores, pd.out_ids, flag2,
@@ -1104,7 +1104,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     gs.ranges = p.sample_ranges;
     gs.gmax = gmax;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[1], s));
-    rc = launch_gemm_gmax(gs, p.grid, s);
+    rc = launch_gemm(gs, MAIN_32X32, EPI_GMAX, p.grid, s);
     if (rc != CCR_OK) return rc;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[2], s));
     // (small batches: the streaming pass's sub-list counters are cleared by the threshold launch)
@@ -1233,6 +1233,5 @@ extern "C" int ccr_scores(const ccr_index *ix, const uint16_t *Q_bf16, int n_q, 
     g.qgroups = 1;
     g.store = out;
     const int grid = std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD);
-    if (ix->knobs.mfma16 != 0) return launch_gemm16_store(g, grid, (hipStream_t)stream);
-    return launch_gemm_store(g, grid, (hipStream_t)stream);
+    return launch_gemm(g, ix->knobs.mfma16 != 0 ? MAIN_16X16 : MAIN_32X32, EPI_STORE, grid, (hipStream_t)stream);
 }

@@ -110,6 +110,9 @@ struct Plan {
     int64_t dense_rows_per_chunk;  // queries per dense chunk
 };
 
+// epilogues of the fused GEMM kernel; EPI_FILTER's candidate record = one corpus row {MFMA score, row}
+enum { EPI_FILTER = 0, EPI_GMAX = 1, EPI_STORE = 2 };
+
 // arguments of the fused GEMM kernel (ccr_fused.hip)
 struct GemmArgs {
     const uint16_t *D;

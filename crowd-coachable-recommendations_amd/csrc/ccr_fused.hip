@@ -13,18 +13,24 @@
 //                              canonically (fp64 ordered) and sort by (score desc, id asc).
 //
 // GEMM geometry (gfx950): 256 docs x 256 queries per workgroup tile, 512 threads = 8 waves as
-// 2 (doc halves) x 4 (query quarters); each wave owns 128 docs x 64 queries = 4 x 2 tiles of
-// v_mfma_f32_32x32x16_bf16 (docs on the accumulator rows/registers, queries on the lanes, so a lane
-// compares its 16 registers against ONE per-lane threshold).  Staging: global_load_lds_dwordx4 into a
-// ring of four 32-KiB sub-stages (32 K elements = 64-B rows), 16-byte chunk index XOR-swizzled with
-// (row>>2)&3 on the SOURCE address and on the fragment read (conflict-free ds_read_b128).
+// 2 (doc halves) x 4 (query quarters); each wave owns 128 docs x 64 queries (docs on the accumulator
+// rows/registers, queries on the lanes, so a lane compares its registers against ONE threshold per
+// query column).  Staging: global_load_lds_dwordx4 into a ring of four 32-KiB sub-stages (32 K
+// elements = 64-B rows), the 16-byte chunk index XOR-swizzled on the SOURCE address and on the
+// fragment read (conflict-free ds_read_b128).  One body, main_pass_256, serves two MFMA shapes:
+//   gemm_topk_kernel     v_mfma_f32_32x32x16_bf16 (Mfma32): the sample pass (EPI_GMAX), and EPI_FILTER / EPI_STORE where
+//                        the plan or CCR_MFMA16=0 picks it
+//   gemm_topk16_kernel   v_mfma_f32_16x16x32_bf16 (Mfma16): the default 256 x 256 main pass (EPI_FILTER) and EPI_STORE
+// gemm_topk16w_kernel is the 256 x 384 form of the 16x16 main pass (EPI_FILTER, dim % 32 == 0) on a body of its own.
 #include <stdlib.h>
 
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 
 #include "ccr_gemm_common.h"
+#include "ccr_index.h"
 #include "ccr_topk_device.h"
 
 namespace ccr {
@@ -40,330 +46,12 @@ __device__ __forceinline__ float load_uniform_f32(const float *p) {
     return v;
 }
 
-// =============================================================================================
-// GEMM + top-k filter kernel.  Ping-pong schedule: K is walked in 32-element sub-stages through a
-// ring of four 32-KiB LDS buffers (up to 3 sub-stages of LDS-DMA in flight, counted vmcnt, raw
-// s_barrier).  The two waves that share a SIMD (wave w and w+4) run one barrier interval apart:
-// while one executes its 16 MFMAs, the other reads its next operands from LDS, issues the next
-// sub-stage's DMA and runs the top-k filter of a finished tile (VALU beside the partner's MFMAs).
-//   per wave and sub-stage u:
-//     mem(u):  [filter of a finished tile] wait OWN DMA of u+1 | 12 ds_read_b128 of u | DMA of u+3 | lgkmcnt(0)
-//     barrier A_u | 16 x v_mfma_f32_32x32x16_bf16 | barrier B_u
-// LDS ring protocol (why this is race free):
-//   RAW  a wave confirms (vmcnt) its own DMA of sub-stage u in mem(u-1), i.e. before its barrier
-//        A_{u-1}; every reader of u starts mem(u) after a later barrier instance.
-//   WAR  DMA of u+3 overwrites the buffer of u-1.  It is issued in mem(u); every wave's reads of
-//        u-1 were retired (lgkmcnt(0)) before its barrier A_{u-1}, and for both groups that
-//        barrier instance precedes every mem(u).
-
 // s_waitcnt vmcnt(N) with a compile-time N
 template <int N>
 __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int EPI, bool TAIL = false>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wd = wv >> 2;   // doc half of the tile
-    const int wq = wv & 3;    // query quarter of the tile
-    const int l31 = lane & 31;
-    const int h = lane >> 5;
-    const bool g1 = (wv >= 4);  // the trailing half of the ping-pong (wave-uniform)
-    const int KS2 = TAIL ? (a.dim + SUB_K - 1) / SUB_K : a.dim / SUB_K;   // TAIL: the last sub-stage is partly zero-filled
-
-    // DMA role: 4 x 1-KiB pieces per sub-stage (16 rows x 64 B each); LDS image is lane-linear, the
-    // 16-byte chunk swizzle (chunk ^ (row>>2)&3) is applied on the SOURCE address and on the read
-    const int srow = wv * 16 + (lane >> 2);  // + piece*128
-    const int schunk = (lane & 3) ^ ((srow >> 2) & 3);
-    const int swz = (lane >> 2) & 3;
-    int cofs[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) cofs[ks] = (((2 * ks + h) ^ swz) << 4);
-    const int a_base = (wd * 128 + l31) * 64;                // + dt*2048
-    const int b_base = SUB_Q_REGION + (wq * 64 + l31) * 64;  // + qt*2048
-
-    // Work items (range r, query block qb).  Blocks b and b+8 share an XCD (its 4-MiB L2), so XCD x takes
-    // query-block group x % qgroups (its query rows stay L2-resident) and the ranges r = x / qgroups
-    // (mod 8 / qgroups); co-resident workgroups walk the same corpus tiles for different query blocks.
-    const int xcd = blockIdx.x & (NUM_XCD - 1);
-    const int jx = blockIdx.x >> 3;
-    const int per_x = gridDim.x >> 3;
-    const int qg = xcd % a.qgroups;
-    const int rc = xcd / a.qgroups;
-    const int nrc = NUM_XCD / a.qgroups;           // range classes
-    const int qb_per = a.qblocks / a.qgroups;      // query blocks of this XCD (qgroups divides qblocks)
-    const int count_x = (a.ranges / nrc) * qb_per;   // items of this XCD set over the whole pass
-    const int item_end = a.item_end < count_x ? a.item_end : count_x;
-
-    for (int item = a.item_begin + jx; item < item_end; item += per_x) {
-        // item order: consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for
-        // different query blocks
-        const int rl = item / qb_per;
-        const int qb = qg * qb_per + item % qb_per;
-        const int r = rc + nrc * rl;
-        const int64_t ntile = (a.n_vt - r + a.ranges - 1) / a.ranges;
-        if (ntile <= 0) continue;
-        const int q0 = qb * TILE_Q;
-
-        // Each lane owns ONE (query, lane-half, wave-row) candidate sub-list per query column, so the
-        // append counter is a plain register: no atomics anywhere in the filter.
-        float thr[2] = {0.f, 0.f}, cqv[2] = {0.f, 0.f};
-        uint32_t ncand[2] = {0u, 0u};
-        uint2 *clist[2] = {nullptr, nullptr};
-        int cap = 0;
-        if (EPI == EPI_FILTER) {
-            int seg_r0;
-            long long seg_base;
-            cand_segment(a.lay, r, cap, seg_r0, seg_base);   // this range's segment of the candidate area (wave-uniform)
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt) {
-                const int q = q0 + wq * 64 + qt * 32 + l31;
-                thr[qt] = (q < a.n_q) ? a.thr[q] : __builtin_nanf("");
-                cqv[qt] = (q < a.n_q) ? a.cq[q] : 0.f;
-                clist[qt] = a.cand + seg_base + ((int64_t)(r - seg_r0) * a.nq_pad + q) * 4 * cap + (wd * 2 + h);   // slot-major cell
-            }
-            // make hipcc wait for the threshold loads HERE, before any LDS-DMA is in flight: its own
-            // wait at the first use inside the tile epilogue would be vmcnt(0) and drain the DMA ring
-            asm volatile("" : "+v"(thr[0]), "+v"(thr[1]), "+v"(cqv[0]), "+v"(cqv[1]));
-        }
-        const uint16_t *qsrc[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int qrow = q0 + i * 128 + srow;
-            if (qrow > a.n_q - 1) qrow = a.n_q - 1;
-            qsrc[i] = a.Q + (int64_t)qrow * a.dim + schunk * 8;
-        }
-
-        f32x16 acc[4][2];
-        const int64_t U = ntile * KS2;
-
-        // ---- DMA issue stream (runs up to 3 sub-stages ahead of the consumer).  Per-thread source pointers
-        // are recomputed once per tile; a sub-stage adds only the K offset.
-        int64_t iu = 0, it = 0;
-        int iks = 0;
-        const uint16_t *dsrc[2];
-        auto tile_ptrs = [&]() {
-            const int64_t row0 = (r + it * a.ranges) * a.tile_stride * TILE_DOCS;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                int64_t drow = row0 + i * 128 + srow;
-                if (drow > a.n_rows - 1) drow = a.n_rows - 1;
-                dsrc[i] = a.D + drow * a.dim + schunk * 8;
-            }
-        };
-        tile_ptrs();
-        auto issue = [&]() {
-            char *buf = smem + (int)(iu & (RING - 1)) * SUB_BYTES;
-            const int k0 = iks * SUB_K;
-            if (TAIL && iks == KS2 - 1) {   // wave-uniform: chunks beyond the row end come from the zero chunk
-                const bool in = k0 + schunk * 8 < a.dim;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-                    glds16(in ? (const void *)(dsrc[i] + k0) : (const void *)g_zero_chunk, buf + (i * 512 + wv * 64) * 16);
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-                    glds16(in ? (const void *)(qsrc[i] + k0) : (const void *)g_zero_chunk, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) glds16(dsrc[i] + k0, buf + (i * 512 + wv * 64) * 16);
-#pragma unroll
-                for (int i = 0; i < 2; ++i) glds16(qsrc[i] + k0, buf + SUB_Q_REGION + (i * 512 + wv * 64) * 16);
-            }
-            ++iu;
-            if (++iks == KS2) {
-                iks = 0;
-                ++it;
-                tile_ptrs();
-            }
-        };
-
-        // ---- epilogue of a finished 256x256 tile (accumulators still live)
-        // C layout of v_mfma_f32_32x32x16: lane -> query column (lane & 31); register e -> corpus row
-        // (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5) of the 32-row MFMA tile.
-        auto epilogue = [&](int64_t vt, float nt) {   // nt: norm bound of the tile's rows (wave-uniform)
-            const int64_t row_base = vt * a.tile_stride * TILE_DOCS + wd * 128 + 4 * h;
-            const uint32_t row32 = (uint32_t)row_base;
-            const int64_t left = a.n_rows - row_base;
-            const uint32_t rows_left = left <= 0 ? 0u : (left > 128 ? 128u : (uint32_t)left);   // rows of this block inside the shard
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt) {
-                float sub[4][4], mdt[4];
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        sub[dt][g] = fmaxf(fmaxf(acc[dt][qt][4 * g], acc[dt][qt][4 * g + 1]),
-                                           fmaxf(acc[dt][qt][4 * g + 2], acc[dt][qt][4 * g + 3]));
-                    mdt[dt] = fmaxf(fmaxf(sub[dt][0], sub[dt][1]), fmaxf(sub[dt][2], sub[dt][3]));
-                }
-                if (EPI == EPI_GMAX) {
-                    const int ql = wq * 64 + qt * 32 + l31;
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt)
-                        a.gmax[(vt * GROUPS_PER_TILE + wd * 8 + dt * 2 + h) * a.nq_pad + q0 + ql] = mdt[dt];
-                } else if (EPI == EPI_FILTER) {
-                    // a row of this tile can reach tau_q only if mfma + cq * ||d|| >= tau_q, and ||d|| <= nt
-                    const float t = fmaf(-cqv[qt], nt, thr[qt]);
-                    const float mall = fmaxf(fmaxf(mdt[0], mdt[1]), fmaxf(mdt[2], mdt[3]));
-                    if (__ballot(mall >= t) != 0ull) {
-#pragma unroll
-                        for (int dt = 0; dt < 4; ++dt) {
-                            if (__ballot(mdt[dt] >= t) == 0ull) continue;
-#pragma unroll
-                            for (int g = 0; g < 4; ++g) {
-                                if (sub[dt][g] >= t) {  // rare, divergent: <= 4 rows to test
-#pragma unroll
-                                    for (int e2 = 0; e2 < 4; ++e2) {
-                                        const float v = acc[dt][qt][4 * g + e2];
-                                        // 32-bit row arithmetic (local rows < 2^32; rows_left = n_rows - first row of this
-                                        // lane's block, clamped): the hit path is instruction-bound beside the partner's MFMAs
-                                        const uint32_t off = (uint32_t)(dt * 32 + 8 * g + e2);
-                                        if (v >= t && off < rows_left) {
-                                            if (ncand[qt] < (uint32_t)cap)
-                                                clist[qt][ncand[qt] * 4] = make_uint2(__float_as_uint(v), row32 + off);
-                                            ++ncand[qt];
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                    }
-                } else {  // EPI_STORE
-                    const int q = q0 + wq * 64 + qt * 32 + l31;
-                    const int64_t pitch = a.store_pitch ? a.store_pitch : a.n_rows;
-                    if (q < a.n_q) {
-                        float *dst = a.store + (int64_t)q * pitch;
-#pragma unroll
-                        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                            for (int g = 0; g < 4; ++g) {   // registers 4g .. 4g+3 are four consecutive corpus rows
-                                const int64_t doc = row_base + dt * 32 + 8 * g;
-                                if ((pitch & 3) == 0 && doc + 3 < a.n_rows) {
-                                    *reinterpret_cast<float4 *>(dst + doc) = make_float4(acc[dt][qt][4 * g], acc[dt][qt][4 * g + 1],
-                                                                                         acc[dt][qt][4 * g + 2], acc[dt][qt][4 * g + 3]);
-                                } else {
-#pragma unroll
-                                    for (int e2 = 0; e2 < 4; ++e2)
-                                        if (doc + e2 < a.n_rows) dst[doc + e2] = acc[dt][qt][4 * g + e2];
-                                }
-                            }
-                    }
-                }
-            }
-        };
-
-        // ---- prologue: up to 3 sub-stages in flight, sub-stage 0 confirmed and published
-        const int npro = U < 3 ? (int)U : 3;
-        for (int i = 0; i < npro; ++i) issue();
-        if (npro == 3)
-            CCR_WAIT_VM(8);
-        else if (npro == 2)
-            CCR_WAIT_VM(4);
-        else
-            CCR_WAIT_VM(0);
-        CCR_BARRIER();
-        if (g1) CCR_BARRIER();
-
-        int cks = 0;
-        int64_t ct = 0;
-        bool pending = false;
-        int64_t pending_vt = 0;
-        float pending_nt = 0.f;
-        for (int64_t u = 0; u < U; ++u) {
-            // ================= mem phase
-            if (pending) {
-                epilogue(pending_vt, pending_nt);
-                pending = false;
-            }
-            if (u + 1 < U) {  // confirm OWN DMA of sub-stage u+1 (published by the barrier below)
-                if (u + 2 < U)
-                    CCR_WAIT_VM(4);
-                else
-                    CCR_WAIT_VM(0);
-            }
-            const char *buf = smem + (int)(u & (RING - 1)) * SUB_BYTES;
-            bf16x8 af[2][4], bfr[2][2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt)
-                    af[ks][dt] = *reinterpret_cast<const bf16x8 *>(buf + a_base + dt * 2048 + cofs[ks]);
-#pragma unroll
-                for (int qt = 0; qt < 2; ++qt)
-                    bfr[ks][qt] = *reinterpret_cast<const bf16x8 *>(buf + b_base + qt * 2048 + cofs[ks]);
-            }
-            if (u + 3 < U) issue();  // into the buffer of sub-stage u-1 (see the WAR note above)
-            CCR_WAIT_LGKM0();        // operands in registers BEFORE the barrier; free behind the DMA issue
-            CCR_BARRIER();
-            // ================= mfma phase
-            // no s_setprio(1) here: the partner wave's mem phase carries VALU work (filter, addresses) that a
-            // raised MFMA wave would starve (MI355X_MICROARCH 'Two waves per SIMD', item 2)
-            if (cks == 0) {  // first sub-stage of a tile: C = 0 (no accumulator clearing pass)
-                const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                    for (int qt = 0; qt < 2; ++qt)
-                        acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][dt], bfr[0][qt], z, 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                    for (int qt = 0; qt < 2; ++qt)
-                        acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][dt], bfr[0][qt], acc[dt][qt], 0, 0, 0);
-            }
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int qt = 0; qt < 2; ++qt)
-                    acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][dt], bfr[1][qt], acc[dt][qt], 0, 0, 0);
-            if (++cks == KS2) {
-                cks = 0;
-                // Tile finished.  The leading group filters it at the start of its next mem phase; the trailing
-                // group (one barrier interval behind) filters it right here, so that BOTH filters fall into the
-                // same interval instead of stalling the partner twice per tile.
-                // (the tile's norm bound: a SCALAR load + wait right here, behind the MFMAs just issued -- a vector load would
-                // sit in vmcnt among the LDS-DMA pieces and hipcc's own wait for it would drain the ring)
-                const int64_t vt_done = r + ct * a.ranges;
-                const float nt_done = EPI == EPI_FILTER ? load_uniform_f32(a.tile_norm + vt_done * a.tile_stride) : 0.f;
-                if (g1) {
-                    epilogue(vt_done, nt_done);
-                } else {
-                    pending = true;
-                    pending_vt = vt_done;
-                    pending_nt = nt_done;
-                }
-                ++ct;
-            }
-            CCR_BARRIER();
-        }
-        if (pending) epilogue(pending_vt, pending_nt);
-        if (!g1) CCR_BARRIER();  // every wave executes the same number of barriers
-
-        if (EPI == EPI_FILTER) {
-#pragma unroll
-            for (int qt = 0; qt < 2; ++qt)
-                a.cnt[((int64_t)r * a.nq_pad + q0 + wq * 64 + qt * 32 + l31) * 4 + wd * 2 + h] = ncand[qt];
-        }
-        __syncthreads();  // LDS ring free for the next item
-    }
-}
-
-
-// =============================================================================================
-// Variant of the main-pass kernel on v_mfma_f32_16x16x32_bf16 (same tile, same ring, same ping-pong).
-// The chip holds a higher clock on this MFMA shape in power-limited loops (MI355X_MICROARCH 'DVFS
-// give-back' item 7), so it is A/B-ed against the 32x32x16 kernel by wall time (CCR_MFMA16).
-//   wave tile 128 x 64 = 8 x 4 MFMA tiles, one K step (32) per sub-stage: 32 MFMAs, 8 + 4 ds_read_b128
-//   C layout: lane -> query column (lane & 15), register e -> corpus row 4 * (lane >> 4) + e of the 16-row tile
-//   -> a lane owns 4 query columns x 32 rows; 8 candidate sub-lists per (range, query): (wave row, lane >> 4)
-//   LDS image: 64-B rows, 16-byte chunk c of row r stored at chunk c ^ (((r >> 2) & 1) << 1) (conflict-free for
-//   the 16x16 fragment read pattern; brute-forced over all xor tables).
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // Maximum of a 16x16 MFMA tile's four registers in two VALU instructions (fmaxf() costs four: hipcc canonicalises the operands first).
@@ -380,73 +68,317 @@ __device__ __forceinline__ float max3_asm(float a, float b, float c) {
     return m;
 }
 
-template <int EPI, bool TAIL = false>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const GemmArgs a) {
+// Work items (range r, query block qb) of a main-pass launch.  Blocks b and b+8 share an XCD (its 4-MiB L2), so XCD x takes
+// query-block group x % qgroups (its query rows stay L2-resident) and the ranges r = x / qgroups (mod 8 / qgroups).  Item order:
+// consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for different query blocks.
+//   for (int item = walk.first(a); item < walk.end; item += walk.step) { ntile = walk.item(a, item, r, qb); ... }
+struct ItemWalk {
+    int jx, step, qg, rc, nrc, qb_per, end;   // end: one past this XCD set's last item of the launch
+    __device__ __forceinline__ explicit ItemWalk(const GemmArgs &a) {
+        const int xcd = blockIdx.x & (NUM_XCD - 1);
+        jx = blockIdx.x >> 3;
+        step = gridDim.x >> 3;
+        qg = xcd % a.qgroups;
+        rc = xcd / a.qgroups;
+        nrc = NUM_XCD / a.qgroups;           // range classes
+        qb_per = a.qblocks / a.qgroups;      // query blocks of this XCD (qgroups divides qblocks)
+        const int count_x = (a.ranges / nrc) * qb_per;   // items of this XCD set over the whole pass
+        end = a.item_end < count_x ? a.item_end : count_x;
+    }
+    __device__ __forceinline__ int first(const GemmArgs &a) const { return a.item_begin + jx; }
+    // range r and query block qb of item i; returns the range's tile count (nothing to do when <= 0)
+    __device__ __forceinline__ int64_t item(const GemmArgs &a, int i, int &r, int &qb) const {
+        const int rl = i / qb_per;
+        const int b = qg * qb_per + i % qb_per;
+        const int ri = rc + nrc * rl;
+        const int64_t ntile = (a.n_vt - ri + a.ranges - 1) / a.ranges;
+        r = ri;   // (outputs written last: storing r before the division changes hipcc's code for the division)
+        qb = b;
+        return ntile;
+    }
+};
+
+// =============================================================================================
+// The two MFMA shapes of the 256 x 256 tile.  Each wave tile is 128 corpus rows x 64 queries of DT x QT square MFMA tiles of
+// edge TILE; a lane holds query column lane % TILE and, per MFMA tile, REGS registers = REGS / 4 groups of four consecutive
+// corpus rows, the first at row 4 * (lane / TILE) + 8 * group.  A lane's candidates of one query go to its own sub-list
+// wd * SUBLISTS / 2 + lane / TILE of the (range, query) cell.
+
+// v_mfma_f32_32x32x16_bf16: 4 x 2 MFMA tiles, two K steps of 16 per sub-stage: 16 MFMAs, 12 ds_read_b128.
+//   C layout: lane -> query column (lane & 31); register e -> corpus row (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5) of the 32-row
+//   MFMA tile -> 4 candidate sub-lists per (range, query): (wave row, lane >> 5).
+//   LDS image: 16-byte chunk c of row r stored at chunk c ^ ((r >> 2) & 3).
+struct Mfma32 {
+    typedef f32x16 Acc;
+    static constexpr int TILE = 32, REGS = 16, DT = 4, QT = 2, SUBLISTS = 4;
+    struct Frags { bf16x8 a[2][4], b[2][2]; };
+
+    static __device__ __forceinline__ int src_swizzle(int row) { return (row >> 2) & 3; }
+
+    int a_base, b_base, cofs[2];   // this lane's fragment offsets in a sub-stage
+    __device__ __forceinline__ Mfma32(int lane, int wd, int wq) {
+        const int swz = (lane >> 2) & 3;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) cofs[ks] = (((2 * ks + (lane >> 5)) ^ swz) << 4);
+        a_base = (wd * 128 + (lane & 31)) * 64;                 // + dt*2048
+        b_base = SUB_Q_REGION + (wq * 64 + (lane & 31)) * 64;   // + qt*2048
+    }
+    __device__ __forceinline__ void read(const char *buf, Frags &f) const {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) f.a[ks][dt] = *reinterpret_cast<const bf16x8 *>(buf + a_base + dt * 2048 + cofs[ks]);
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt) f.b[ks][qt] = *reinterpret_cast<const bf16x8 *>(buf + b_base + qt * 2048 + cofs[ks]);
+        }
+    }
+    // the MFMAs of one sub-stage; the first sub-stage of a tile starts from C = 0 (no accumulator clearing pass)
+    static __device__ __forceinline__ void mma(Acc (&acc)[4][2], const Frags &f, bool first) {
+        if (first) {
+            const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][dt], f.b[0][qt], z, 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+                for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][dt], f.b[0][qt], acc[dt][qt], 0, 0, 0);
+        }
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1][dt], f.b[1][qt], acc[dt][qt], 0, 0, 0);
+    }
+
+    // maxima of query tile qt: per group of four registers, and per MFMA tile (two 16-row groups, one per lane half)
+    static __device__ __forceinline__ void tile_max(const Acc (&acc)[4][2], int qt, float (&sub)[4][4], float (&mdt)[4]) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                sub[dt][g] = fmaxf(fmaxf(acc[dt][qt][4 * g], acc[dt][qt][4 * g + 1]), fmaxf(acc[dt][qt][4 * g + 2], acc[dt][qt][4 * g + 3]));
+            mdt[dt] = fmaxf(fmaxf(sub[dt][0], sub[dt][1]), fmaxf(sub[dt][2], sub[dt][3]));
+        }
+    }
+    // The epilogues of a finished wave tile.  row_base: corpus row of this lane's first register; this lane's column of query tile
+    // qt is q0 + wq * 64 + qt * 32 + (lane & 31).  Each epilogue walks the query tiles itself: handed one query tile at a time,
+    // the filter costs hipcc more registers.
+    // EPI_GMAX: the maximum of each 16-row group -> gmax[group][query]
+    static __device__ __forceinline__ void gmax(const Acc (&acc)[4][2], const GemmArgs &a, int64_t vt, int q0, int wd, int wq, int lane) {
+        const int h = lane >> 5;
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+            float sub[4][4], mdt[4];
+            tile_max(acc, qt, sub, mdt);
+            const int ql = wq * 64 + qt * 32 + (lane & 31);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) a.gmax[(vt * GROUPS_PER_TILE + wd * 8 + dt * 2 + h) * a.nq_pad + q0 + ql] = mdt[dt];
+        }
+    }
+    // EPI_FILTER: append every row that may reach its query's threshold to the lane's sub-list
+    static __device__ __forceinline__ void filter(const Acc (&acc)[4][2], const float (&thr)[2], const float (&cqv)[2], float nt,
+                                                  int64_t row_base, const GemmArgs &a, uint2 *const (&clist)[2], uint32_t (&ncand)[2],
+                                                  int cap) {
+        const uint32_t row32 = (uint32_t)row_base;
+        const int64_t left = a.n_rows - row_base;
+        const uint32_t rows_left = left <= 0 ? 0u : (left > 128 ? 128u : (uint32_t)left);   // rows of this block inside the shard
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+            float sub[4][4], mdt[4];
+            tile_max(acc, qt, sub, mdt);
+            // a row of this tile can reach tau_q only if mfma + cq * ||d|| >= tau_q, and ||d|| <= nt
+            const float t = fmaf(-cqv[qt], nt, thr[qt]);
+            const float mall = fmaxf(fmaxf(mdt[0], mdt[1]), fmaxf(mdt[2], mdt[3]));
+            if (__ballot(mall >= t) == 0ull) continue;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                if (__ballot(mdt[dt] >= t) == 0ull) continue;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    if (sub[dt][g] >= t) {  // rare, divergent: <= 4 rows to test
+#pragma unroll
+                        for (int e2 = 0; e2 < 4; ++e2) {
+                            const float v = acc[dt][qt][4 * g + e2];
+                            // 32-bit row arithmetic (local rows < 2^32; rows_left = n_rows - first row of this lane's block,
+                            // clamped): the hit path is instruction-bound beside the partner's MFMAs
+                            const uint32_t off = (uint32_t)(dt * 32 + 8 * g + e2);
+                            if (v >= t && off < rows_left) {
+                                if (ncand[qt] < (uint32_t)cap) clist[qt][ncand[qt] * 4] = make_uint2(__float_as_uint(v), row32 + off);
+                                ++ncand[qt];
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+// v_mfma_f32_16x16x32_bf16: 8 x 4 MFMA tiles, one K step of 32 per sub-stage: 32 MFMAs, 8 + 4 ds_read_b128.  The chip holds a higher
+// clock on this shape in power-limited loops (MI355X_MICROARCH 'DVFS give-back' item 7).
+//   C layout: lane -> query column (lane & 15), register e -> corpus row 4 * (lane >> 4) + e of the 16-row tile
+//   -> a lane owns 4 query columns x 32 rows; 8 candidate sub-lists per (range, query): (wave row, lane >> 4).
+//   LDS image: 16-byte chunk c of row r stored at chunk c ^ (((r >> 2) & 1) << 1) (conflict-free for the 16x16 fragment read
+//   pattern; brute-forced over all xor tables).
+struct Mfma16 {
+    typedef f32x4v Acc;
+    static constexpr int TILE = 16, REGS = 4, DT = 8, QT = 4, SUBLISTS = 8;
+    struct Frags { bf16x8 a[8], b[4]; };
+
+    static __device__ __forceinline__ int src_swizzle(int row) { return ((row >> 2) & 1) << 1; }
+
+    int a_base, b_base;   // this lane's fragment offsets in a sub-stage
+    __device__ __forceinline__ Mfma16(int lane, int wd, int wq) {
+        const int cofs = (((lane >> 4) ^ (((lane >> 2) & 1) << 1)) << 4);   // lane >> 4: K chunk of the operand fragments
+        a_base = (wd * 128 + (lane & 15)) * 64 + cofs;                      // + dt*1024
+        b_base = SUB_Q_REGION + (wq * 64 + (lane & 15)) * 64 + cofs;        // + qt*1024
+    }
+    __device__ __forceinline__ void read(const char *buf, Frags &f) const {
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) f.a[dt] = *reinterpret_cast<const bf16x8 *>(buf + a_base + dt * 1024);
+#pragma unroll
+        for (int qt = 0; qt < 4; ++qt) f.b[qt] = *reinterpret_cast<const bf16x8 *>(buf + b_base + qt * 1024);
+    }
+    static __device__ __forceinline__ void mma(Acc (&acc)[8][4], const Frags &f, bool first) {
+        if (first) {
+            const f32x4v z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+                for (int qt = 0; qt < 4; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[dt], f.b[qt], z, 0, 0, 0);
+            return;
+        }
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+            for (int qt = 0; qt < 4; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[dt], f.b[qt], acc[dt][qt], 0, 0, 0);
+    }
+
+    // EPI_FILTER of a finished wave tile (see Mfma32::filter; a query tile's column of this lane is q0 + wq * 64 + qt * 16 + (lane & 15))
+    static __device__ __forceinline__ void filter(const Acc (&acc)[8][4], const float (&thr)[4], const float (&cqv)[4], float nt,
+                                                  int64_t row_base, const GemmArgs &a, uint2 *const (&clist)[4], uint32_t (&ncand)[4],
+                                                  int cap) {
+#pragma unroll
+        for (int qt = 0; qt < 4; ++qt) {
+            float sub[8];
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt) sub[dt] = max4_asm(acc[dt][qt]);   // (two VALU instructions per tile instead of fmaxf's four)
+            const float t = fmaf(-cqv[qt], nt, thr[qt]);   // per-tile margin: mfma + cq * ||d|| >= tau_q with ||d|| <= nt
+            float mall = max3_asm(sub[0], sub[1], sub[2]);
+            mall = max3_asm(mall, sub[3], sub[4]);
+            mall = max3_asm(mall, sub[5], sub[6]);
+            mall = fmaxf(mall, sub[7]);
+            if (__ballot(mall >= t) == 0ull) continue;
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt) {
+                if (sub[dt] >= t) {  // rare, divergent: 4 rows to test
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float v = acc[dt][qt][e];
+                        const int64_t doc = row_base + dt * 16 + e;
+                        if (v >= t && doc < a.n_rows) {
+                            if (ncand[qt] < (uint32_t)cap) clist[qt][ncand[qt] * 8] = make_uint2(__float_as_uint(v), (uint32_t)doc);
+                            ++ncand[qt];
+                        }
+                    }
+                }
+            }
+        }
+    }
+};
+
+// =============================================================================================
+// The 256 x 256 main-pass body on MFMA shape S.  Ping-pong schedule: K is walked in 32-element sub-stages through a ring of four
+// 32-KiB LDS buffers (up to 3 sub-stages of LDS-DMA in flight, counted vmcnt, raw s_barrier).  The two waves that share a SIMD
+// (wave w and w+4) run one barrier interval apart: while one executes its MFMAs, the other reads its next operands from LDS,
+// issues the next sub-stage's DMA and runs the top-k filter of a finished tile (VALU beside the partner's MFMAs).
+//   per wave and sub-stage u:
+//     mem(u):  [filter of a finished tile] wait OWN DMA of u+1 | 12 ds_read_b128 of u | DMA of u+3 | lgkmcnt(0)
+//     barrier A_u | MFMAs of u | barrier B_u
+// LDS ring protocol (why this is race free):
+//   RAW  a wave confirms (vmcnt) its own DMA of sub-stage u in mem(u-1), i.e. before its barrier
+//        A_{u-1}; every reader of u starts mem(u) after a later barrier instance.
+//   WAR  DMA of u+3 overwrites the buffer of u-1.  It is issued in mem(u); every wave's reads of
+//        u-1 were retired (lgkmcnt(0)) before its barrier A_{u-1}, and for both groups that
+//        barrier instance precedes every mem(u).
+template <class S, int EPI, bool TAIL>
+__device__ __forceinline__ void main_pass_256(const GemmArgs &a) {
+    static_assert(EPI != EPI_GMAX || std::is_same<S, Mfma32>::value, "EPI_GMAX exists on the 32x32 shape only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
+
+    // (the mask costs nothing once inlined into a kernel with GEMM_THREADS threads, but tells hipcc the range of the thread id while it
+    // optimises this body on its own: without it the lane and wave roles are treated as wider and the kernels need more registers)
+    const int tid = threadIdx.x & (GEMM_THREADS - 1);
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wd = wv >> 2;
-    const int wq = wv & 3;
-    const int l15 = lane & 15;
-    const int lq = lane >> 4;  // 0..3: K chunk of the operand fragments, row quad of the accumulator
-    const bool g1 = (wv >= 4);
-    const int KS2 = TAIL ? (a.dim + SUB_K - 1) / SUB_K : a.dim / SUB_K;
+    const int wd = wv >> 2;   // doc half of the tile
+    const int wq = wv & 3;    // query quarter of the tile
+    const int lc = lane & (S::TILE - 1);   // query column of the MFMA tiles
+    const int lh = lane / S::TILE;         // row group of the accumulators
+    const int cell = wd * (S::SUBLISTS / 2) + lh;   // this lane's sub-list of a (range, query)
+    const bool g1 = (wv >= 4);  // the trailing half of the ping-pong (wave-uniform)
+    const int KS2 = TAIL ? (a.dim + SUB_K - 1) / SUB_K : a.dim / SUB_K;   // TAIL: the last sub-stage is partly zero-filled
 
+    // DMA role: 4 x 1-KiB pieces per sub-stage (16 rows x 64 B each); LDS image is lane-linear, the
+    // 16-byte chunk swizzle is applied on the SOURCE address and on the read
     const int srow = wv * 16 + (lane >> 2);  // + piece*128
-    const int schunk = (lane & 3) ^ (((srow >> 2) & 1) << 1);
-    const int cofs = ((lq ^ (((lane >> 2) & 1) << 1)) << 4);
-    const int a_base = (wd * 128 + l15) * 64 + cofs;                // + dt*1024
-    const int b_base = SUB_Q_REGION + (wq * 64 + l15) * 64 + cofs;  // + qt*1024
+    const int schunk = (lane & 3) ^ S::src_swizzle(srow);
+    const S mfma(lane, wd, wq);
 
-    const int xcd = blockIdx.x & (NUM_XCD - 1);
-    const int jx = blockIdx.x >> 3;
-    const int per_x = gridDim.x >> 3;
-    const int qg = xcd % a.qgroups;
-    const int rc = xcd / a.qgroups;
-    const int nrc = NUM_XCD / a.qgroups;
-    const int qb_per = a.qblocks / a.qgroups;
-    const int count_x = (a.ranges / nrc) * qb_per;   // items of this XCD set over the whole pass
-    const int item_end = a.item_end < count_x ? a.item_end : count_x;
-
-    for (int item = a.item_begin + jx; item < item_end; item += per_x) {
-        // item order: consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for
-        // different query blocks
-        const int rl = item / qb_per;
-        const int qb = qg * qb_per + item % qb_per;
-        const int r = rc + nrc * rl;
-        const int64_t ntile = (a.n_vt - r + a.ranges - 1) / a.ranges;
+    const ItemWalk walk(a);
+    for (int item = walk.first(a); item < walk.end; item += walk.step) {
+        int r, qb;
+        const int64_t ntile = walk.item(a, item, r, qb);
         if (ntile <= 0) continue;
         const int q0 = qb * TILE_Q;
 
-        float thr[4] = {0.f, 0.f, 0.f, 0.f}, cqv[4] = {0.f, 0.f, 0.f, 0.f};
-        uint32_t ncand[4] = {0u, 0u, 0u, 0u};
-        uint2 *clist[4] = {nullptr, nullptr, nullptr, nullptr};
+        // Each lane owns ONE candidate sub-list per query column, so the append counter is a plain
+        // register: no atomics anywhere in the filter.
+        float thr[S::QT] = {}, cqv[S::QT] = {};
+        uint32_t ncand[S::QT] = {};
+        uint2 *clist[S::QT] = {};
         int cap = 0;
         if (EPI == EPI_FILTER) {
             int seg_r0;
             long long seg_base;
             cand_segment(a.lay, r, cap, seg_r0, seg_base);   // this range's segment of the candidate area (wave-uniform)
 #pragma unroll
-            for (int qt = 0; qt < 4; ++qt) {
-                const int q = q0 + wq * 64 + qt * 16 + l15;
+            for (int qt = 0; qt < S::QT; ++qt) {
+                const int q = q0 + wq * 64 + qt * S::TILE + lc;
                 thr[qt] = (q < a.n_q) ? a.thr[q] : __builtin_nanf("");
                 cqv[qt] = (q < a.n_q) ? a.cq[q] : 0.f;
-                clist[qt] = a.cand + seg_base + ((int64_t)(r - seg_r0) * a.nq_pad + q) * 8 * cap + (wd * 4 + lq);   // slot-major cell
+                clist[qt] = a.cand + seg_base + ((int64_t)(r - seg_r0) * a.nq_pad + q) * S::SUBLISTS * cap + cell;   // slot-major cell
             }
-            asm volatile("" : "+v"(thr[0]), "+v"(thr[1]), "+v"(thr[2]), "+v"(thr[3]), "+v"(cqv[0]), "+v"(cqv[1]), "+v"(cqv[2]), "+v"(cqv[3]));
+            // make hipcc wait for the threshold loads HERE, before any LDS-DMA is in flight: its own
+            // wait at the first use inside the tile epilogue would be vmcnt(0) and drain the DMA ring
+#pragma unroll
+            for (int qt = 0; qt < S::QT; ++qt) asm volatile("" : "+v"(thr[qt]), "+v"(cqv[qt]));
+        }
+        // EPI_STORE: this lane's score row of each query tile, null past the last query (set once per item, like the filter's lists)
+        float *dst[S::QT] = {};
+        if (EPI == EPI_STORE) {
+            const int64_t pitch = a.store_pitch ? a.store_pitch : a.n_rows;
+#pragma unroll
+            for (int qt = 0; qt < S::QT; ++qt) {
+                const int q = q0 + wq * 64 + qt * S::TILE + lc;
+                if (q < a.n_q) dst[qt] = a.store + (int64_t)q * pitch;
+            }
         }
         const uint16_t *qsrc[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            int qrow = q0 + (i * 128 + srow);
+            int qrow = q0 + i * 128 + srow;
             if (qrow > a.n_q - 1) qrow = a.n_q - 1;
             qsrc[i] = a.Q + (int64_t)qrow * a.dim + schunk * 8;
         }
 
-        f32x4v acc[8][4];
+        typename S::Acc acc[S::DT][S::QT];
         const int64_t U = ntile * KS2;
 
+        // ---- DMA issue stream (runs up to 3 sub-stages ahead of the consumer).  Per-thread source pointers
+        // are recomputed once per tile; a sub-stage adds only the K offset.
         int64_t iu = 0, it = 0;
         int iks = 0;
         const uint16_t *dsrc[2];
@@ -485,58 +417,37 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
             }
         };
 
+        // ---- epilogue of a finished 256x256 tile (accumulators still live)
         auto epilogue = [&](int64_t vt, float nt) {   // nt: norm bound of the tile's rows (wave-uniform)
-            const int64_t row_base = vt * a.tile_stride * TILE_DOCS + wd * 128 + 4 * lq;  // + dt*16 + e
+            const int64_t row_base = vt * a.tile_stride * TILE_DOCS + wd * 128 + 4 * lh;   // + dt * TILE + 8 * group + register
+            if constexpr (EPI == EPI_GMAX) {
+                S::gmax(acc, a, vt, q0, wd, wq, lane);
+            } else if constexpr (EPI == EPI_FILTER) {
+                S::filter(acc, thr, cqv, nt, row_base, a, clist, ncand, cap);
+            } else {
+                const int64_t pitch = a.store_pitch ? a.store_pitch : a.n_rows;
 #pragma unroll
-            for (int qt = 0; qt < 4; ++qt) {
-                if (EPI == EPI_FILTER) {
-                    float sub[8];
+                for (int qt = 0; qt < S::QT; ++qt) {
+                    if (!dst[qt]) continue;
 #pragma unroll
-                    for (int dt = 0; dt < 8; ++dt) sub[dt] = max4_asm(acc[dt][qt]);   // (two VALU instructions per tile instead of fmaxf's four)
-                    const float t = fmaf(-cqv[qt], nt, thr[qt]);   // per-tile margin: mfma + cq * ||d|| >= tau_q with ||d|| <= nt
-                    float mall = max3_asm(sub[0], sub[1], sub[2]);
-                    mall = max3_asm(mall, sub[3], sub[4]);
-                    mall = max3_asm(mall, sub[5], sub[6]);
-                    mall = fmaxf(mall, sub[7]);
-                    if (__ballot(mall >= t) != 0ull) {
+                    for (int dt = 0; dt < S::DT; ++dt)
 #pragma unroll
-                        for (int dt = 0; dt < 8; ++dt) {
-                            if (sub[dt] >= t) {  // rare, divergent: 4 rows to test
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) {
-                                    const float v = acc[dt][qt][e];
-                                    const int64_t doc = row_base + dt * 16 + e;
-                                    if (v >= t && doc < a.n_rows) {
-                                        if (ncand[qt] < (uint32_t)cap)
-                                            clist[qt][ncand[qt] * 8] = make_uint2(__float_as_uint(v), (uint32_t)doc);
-                                        ++ncand[qt];
-                                    }
-                                }
-                            }
-                        }
-                    }
-                } else {  // EPI_STORE
-                    const int q = q0 + wq * 64 + qt * 16 + l15;
-                    const int64_t pitch = a.store_pitch ? a.store_pitch : a.n_rows;
-                    if (q < a.n_q) {
-                        float *dst = a.store + (int64_t)q * pitch;
-#pragma unroll
-                        for (int dt = 0; dt < 8; ++dt) {   // the four registers of a tile are four consecutive corpus rows
-                            const int64_t doc = row_base + dt * 16;
+                        for (int g = 0; g < S::REGS / 4; ++g) {   // registers 4g .. 4g+3 are four consecutive corpus rows
+                            const int64_t doc = row_base + dt * S::TILE + 8 * g;
                             if ((pitch & 3) == 0 && doc + 3 < a.n_rows) {
-                                *reinterpret_cast<float4 *>(dst + doc) =
-                                    make_float4(acc[dt][qt][0], acc[dt][qt][1], acc[dt][qt][2], acc[dt][qt][3]);
+                                *reinterpret_cast<float4 *>(dst[qt] + doc) = make_float4(acc[dt][qt][4 * g], acc[dt][qt][4 * g + 1],
+                                                                                             acc[dt][qt][4 * g + 2], acc[dt][qt][4 * g + 3]);
                             } else {
 #pragma unroll
-                                for (int e = 0; e < 4; ++e)
-                                    if (doc + e < a.n_rows) dst[doc + e] = acc[dt][qt][e];
+                                for (int e2 = 0; e2 < 4; ++e2)
+                                    if (doc + e2 < a.n_rows) dst[qt][doc + e2] = acc[dt][qt][4 * g + e2];
                             }
                         }
-                    }
                 }
             }
         };
 
+        // ---- prologue: up to 3 sub-stages in flight, sub-stage 0 confirmed and published
         const int npro = U < 3 ? (int)U : 3;
         for (int i = 0; i < npro; ++i) issue();
         if (npro == 3)
@@ -554,41 +465,31 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
         int64_t pending_vt = 0;
         float pending_nt = 0.f;
         for (int64_t u = 0; u < U; ++u) {
+            // ================= mem phase
             if (pending) {
                 epilogue(pending_vt, pending_nt);
                 pending = false;
             }
-            if (u + 1 < U) {
+            if (u + 1 < U) {  // confirm OWN DMA of sub-stage u+1 (published by the barrier below)
                 if (u + 2 < U)
                     CCR_WAIT_VM(4);
                 else
                     CCR_WAIT_VM(0);
             }
-            const char *buf = smem + (int)(u & (RING - 1)) * SUB_BYTES;
-            bf16x8 af[8], bfr[4];
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) af[dt] = *reinterpret_cast<const bf16x8 *>(buf + a_base + dt * 1024);
-#pragma unroll
-            for (int qt = 0; qt < 4; ++qt) bfr[qt] = *reinterpret_cast<const bf16x8 *>(buf + b_base + qt * 1024);
-            if (u + 3 < U) issue();
-            CCR_WAIT_LGKM0();
+            typename S::Frags f;
+            mfma.read(smem + (int)(u & (RING - 1)) * SUB_BYTES, f);
+            if (u + 3 < U) issue();  // into the buffer of sub-stage u-1 (see the WAR note above)
+            CCR_WAIT_LGKM0();        // operands in registers BEFORE the barrier; free behind the DMA issue
             CCR_BARRIER();
-            if (cks == 0) {
-                const f32x4v z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                    for (int qt = 0; qt < 4; ++qt)
-                        acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], bfr[qt], z, 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                    for (int qt = 0; qt < 4; ++qt)
-                        acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], bfr[qt], acc[dt][qt], 0, 0, 0);
-            }
+            // ================= mfma phase
+            // no s_setprio(1) here: the partner wave's mem phase carries VALU work (filter, addresses) that a
+            // raised MFMA wave would starve (MI355X_MICROARCH 'Two waves per SIMD', item 2)
+            S::mma(acc, f, cks == 0);   // first sub-stage of a tile: C = 0 (no accumulator clearing pass)
             if (++cks == KS2) {
                 cks = 0;
+                // Tile finished.  The leading group filters it at the start of its next mem phase; the trailing
+                // group (one barrier interval behind) filters it right here, so that BOTH filters fall into the
+                // same interval instead of stalling the partner twice per tile.
                 // (the tile's norm bound: a SCALAR load + wait right here, behind the MFMAs just issued -- a vector load would
                 // sit in vmcnt among the LDS-DMA pieces and hipcc's own wait for it would drain the ring)
                 const int64_t vt_done = r + ct * a.ranges;
@@ -605,16 +506,21 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const Gemm
             CCR_BARRIER();
         }
         if (pending) epilogue(pending_vt, pending_nt);
-        if (!g1) CCR_BARRIER();
+        if (!g1) CCR_BARRIER();  // every wave executes the same number of barriers
 
         if (EPI == EPI_FILTER) {
 #pragma unroll
-            for (int qt = 0; qt < 4; ++qt)
-                a.cnt[((int64_t)r * a.nq_pad + q0 + wq * 64 + qt * 16 + l15) * 8 + wd * 4 + lq] = ncand[qt];
+            for (int qt = 0; qt < S::QT; ++qt)
+                a.cnt[((int64_t)r * a.nq_pad + q0 + wq * 64 + qt * S::TILE + lc) * S::SUBLISTS + cell] = ncand[qt];
         }
-        __syncthreads();
+        __syncthreads();  // LDS ring free for the next item
     }
 }
+
+template <int EPI, bool TAIL = false>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmArgs a) { main_pass_256<Mfma32, EPI, TAIL>(a); }
+template <int EPI, bool TAIL = false>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const GemmArgs a) { main_pass_256<Mfma16, EPI, TAIL>(a); }
 
 // =============================================================================================
 // WIDE form of the 16x16x32 main pass (round 6): a 256 x 384 tile on the same eight waves.
@@ -702,25 +608,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
         lane_lds = (uint32_t)((ln & 15) * 64 + (((ln >> 4) ^ (((ln >> 2) & 1) << 1)) << 4));
     }
 
-    const int xcd = blockIdx.x & (NUM_XCD - 1);
-    const int jx = blockIdx.x >> 3;
-    const int per_x = gridDim.x >> 3;
-    const int qg = xcd % a.qgroups;
-    const int rc = xcd / a.qgroups;
-    const int nrc = NUM_XCD / a.qgroups;
-    const int qb_per = a.qblocks / a.qgroups;
-    const int count_x = (a.ranges / nrc) * qb_per;
-    const int item_end = a.item_end < count_x ? a.item_end : count_x;
-
-    for (int item = a.item_begin + jx; item < item_end; item += per_x) {
-        // item order: consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for different
-        // query blocks.  (Measured at NQ, nine blocks = 5 MiB of query rows per XCD against 4 MiB of L2: sharing the query block instead,
-        // main pass 12.05 ms against 11.49; blocks in two halves, all ranges x first half then x second: 11.75.)
-        const int rl = item / qb_per;
-        const int qb = qg * qb_per + item % qb_per;
-        const int r = rc + nrc * rl;
-        const int64_t ntile = (a.n_vt - r + a.ranges - 1) / a.ranges;
+    const ItemWalk walk(a);
+    for (int item = walk.first(a); item < walk.end; item += walk.step) {
+        int r, qb;
+        const int64_t ntile = walk.item(a, item, r, qb);
         if (ntile <= 0) continue;
+        // (Measured at NQ, nine blocks = 5 MiB of query rows per XCD against 4 MiB of L2: sharing the query block instead of the
+        // range, main pass 12.05 ms against 11.49; blocks in two halves, all ranges x first half then x second: 11.75.)
         const int q0 = qb * WIDE_Q;
 
         int cap, seg_r0;
@@ -1722,33 +1616,34 @@ static int launch_kernel(K kernel, size_t lds, const GemmArgs &a, int grid, hipS
     return CCR_OK;
 }
 
-template <int EPI>
-static int launch_gemm(const GemmArgs &a, int grid, hipStream_t s) {
-    const size_t lds = RING * (size_t)SUB_BYTES;
-    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk_kernel<EPI, true>, lds, a, grid, s);   // zero-filled last K sub-stage
-    return launch_kernel(&gemm_topk_kernel<EPI>, lds, a, grid, s);
-}
-
-int launch_gemm_filter(const GemmArgs &a, int grid, hipStream_t s) { return launch_gemm<EPI_FILTER>(a, grid, s); }
-
-int launch_gemm16_filter(const GemmArgs &a, int grid, hipStream_t s) {
-    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk16_kernel<EPI_FILTER, true>, RING * (size_t)SUB_BYTES, a, grid, s);
-    return launch_kernel(&gemm_topk16_kernel<EPI_FILTER>, RING * (size_t)SUB_BYTES, a, grid, s);
-}
-// the 256 x 384 form (a.qblocks counts blocks of WIDE_Q queries; dim % 32 == 0)
-int launch_gemm16w_filter(const GemmArgs &a, int grid, hipStream_t s) {
-    if (a.dim % SUB_K != 0 || a.dim < SUB_K) {
-        set_error("launch_gemm16w_filter: dim %d is not a multiple of %d", a.dim, SUB_K);
+int launch_gemm(const GemmArgs &a, MainKernel kind, int epi, int grid, hipStream_t s) {
+    if (epi != EPI_FILTER && epi != EPI_GMAX && epi != EPI_STORE) {
+        set_error("launch_gemm: unknown epilogue %d", epi);
         return CCR_ERR_INVALID;
     }
-    return launch_kernel(&gemm_topk16w_kernel, WIDE_LDS, a, grid, s);
+    if (kind == MAIN_WIDE) {   // the 256 x 384 form: a.qblocks counts blocks of WIDE_Q queries
+        if (epi != EPI_FILTER || a.dim % SUB_K != 0 || a.dim < SUB_K) {
+            set_error("launch_gemm: the 256 x 384 kernel takes EPI_FILTER and dim %% %d == 0 only (epi %d, dim %d)", SUB_K, epi, a.dim);
+            return CCR_ERR_INVALID;
+        }
+        return launch_kernel(&gemm_topk16w_kernel, WIDE_LDS, a, grid, s);
+    }
+    typedef void (*Kernel)(const GemmArgs);
+    static const Kernel k256[2][3][2] = {   // [kind][epi][TAIL: dim % 32 != 0, the last K sub-stage zero-filled]
+        {{gemm_topk_kernel<EPI_FILTER>, gemm_topk_kernel<EPI_FILTER, true>},
+         {gemm_topk_kernel<EPI_GMAX>, gemm_topk_kernel<EPI_GMAX, true>},
+         {gemm_topk_kernel<EPI_STORE>, gemm_topk_kernel<EPI_STORE, true>}},
+        {{gemm_topk16_kernel<EPI_FILTER>, gemm_topk16_kernel<EPI_FILTER, true>},
+         {nullptr, nullptr},
+         {gemm_topk16_kernel<EPI_STORE>, gemm_topk16_kernel<EPI_STORE, true>}},
+    };
+    const Kernel k = k256[kind == MAIN_16X16][epi][a.dim % SUB_K != 0];
+    if (!k) {
+        set_error("launch_gemm: the 16x16x32 kernel has no EPI_GMAX");
+        return CCR_ERR_INVALID;
+    }
+    return launch_kernel(k, RING * (size_t)SUB_BYTES, a, grid, s);
 }
-int launch_gemm16_store(const GemmArgs &a, int grid, hipStream_t s) {
-    if (a.dim % SUB_K != 0) return launch_kernel(&gemm_topk16_kernel<EPI_STORE, true>, RING * (size_t)SUB_BYTES, a, grid, s);
-    return launch_kernel(&gemm_topk16_kernel<EPI_STORE>, RING * (size_t)SUB_BYTES, a, grid, s);
-}
-int launch_gemm_gmax(const GemmArgs &a, int grid, hipStream_t s) { return launch_gemm<EPI_GMAX>(a, grid, s); }
-int launch_gemm_store(const GemmArgs &a, int grid, hipStream_t s) { return launch_gemm<EPI_STORE>(a, grid, s); }
 
 int launch_row_norms_bf16(const uint16_t *X, int64_t rows, int dim, float *norms, uint32_t *max_bits, uint32_t *tile_bits,
                           hipStream_t s) {

@@ -28,12 +28,10 @@ constexpr int FALLBACK_ROWS = 16;   // dense score rows reserved for flagged que
 Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn);
 
 // kernels implemented in the other translation units
-int launch_gemm_filter(const GemmArgs &a, int grid, hipStream_t s);
-int launch_gemm_gmax(const GemmArgs &a, int grid, hipStream_t s);
-int launch_gemm_store(const GemmArgs &a, int grid, hipStream_t s);
-int launch_gemm16_filter(const GemmArgs &a, int grid, hipStream_t s);
-int launch_gemm16_store(const GemmArgs &a, int grid, hipStream_t s);
-int launch_gemm16w_filter(const GemmArgs &a, int grid, hipStream_t s);   // 256 x 384 tiles (a.qblocks = blocks of 384 queries), dim % 32 == 0
+// the fused GEMM + top-k kernels: 256 x 256 tiles on the 32x32x16 MFMA (every epi) or the 16x16x32 MFMA (no EPI_GMAX), or
+// 256 x 384 tiles on the 16x16x32 MFMA (MAIN_WIDE: a.qblocks = blocks of 384 queries, EPI_FILTER and dim % 32 == 0 only)
+enum MainKernel { MAIN_32X32, MAIN_16X16, MAIN_WIDE };
+int launch_gemm(const GemmArgs &a, MainKernel kind, int epi, int grid, hipStream_t s);
 int launch_shard_header(const ccr_shard_header &h, void *message, hipStream_t s);   // ccr_merge.hip: the 32-byte header, by value
 int ensure_dynamic_lds(const void *kernel, size_t lds);   // per (kernel, device) opt-in to > 64 KiB of dynamic LDS
 // tile_bits (optional): bit patterns of the largest row norm of every 256-row tile, max-accumulated (zeroed by the caller)

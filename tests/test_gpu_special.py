@@ -207,14 +207,18 @@ def test_assign_topk_accepts_rime_lite_expression_objects():
 
 
 # ----------------------------------------------------------------------------------------- ccr_scores, async search
-def test_scores_public_entry_modes():
+def test_scores_public_entry_modes(monkeypatch):
+    """"mfma" scores come from the 16x16x32 kernel's EPI_STORE; CCR_MFMA16=0 takes the 32x32x16 kernel's (d = 200: its TAIL form)."""
     from ccrec_amd import ops
-    Db, Qb = _rand_bits(1500, 128, 11), _rand_bits(70, 128, 12)
-    index = ops.CorpusIndex(_bf16(Db))
-    can = index.scores(_bf16(Qb), "canonical").cpu().numpy()
-    assert np.array_equal(can.view(np.uint32), orc.canonical_scores(Qb, Db).view(np.uint32))
-    mf = index.scores(_bf16(Qb), "mfma").cpu().numpy()
-    assert np.abs(mf - can).max() < 1e-6
+    for d, mfma16 in ((128, None), (128, "0"), (200, "0")):
+        if mfma16 is not None:
+            monkeypatch.setenv("CCR_MFMA16", mfma16)   # read when an index is created
+        Db, Qb = _rand_bits(1500, d, 11), _rand_bits(70, d, 12)
+        index = ops.CorpusIndex(_bf16(Db))
+        can = index.scores(_bf16(Qb), "canonical").cpu().numpy()
+        assert np.array_equal(can.view(np.uint32), orc.canonical_scores(Qb, Db).view(np.uint32)), (d, mfma16)
+        mf = index.scores(_bf16(Qb), "mfma").cpu().numpy()
+        assert np.abs(mf - can).max() < 1e-6, (d, mfma16)
     with pytest.raises(KeyError):
         index.scores(_bf16(Qb), "fp8")
 
