@@ -234,6 +234,16 @@ static MainPassChoice choose_main_pass(const Plan &p, int k, int64_t sample_a, i
     return best_choice;
 }
 
+// candidate layout of one segment over every range
+static CandLayout one_segment(int cap) {
+    CandLayout L;
+    memset(&L, 0, sizeof(L));
+    L.nseg = 1;
+    L.seg_end[0] = L.seg_end[1] = L.seg_end[2] = INT32_MAX;
+    L.cap[0] = L.cap[1] = L.cap[2] = cap;
+    return L;
+}
+
 static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn, int mfma16) {
     Plan p;
     memset(&p, 0, sizeof(p));
@@ -273,12 +283,6 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
     if (flags & CCR_SEARCH_FORCE_DENSE) fused = false;
     p.fused = fused ? 1 : 0;
 
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = (size_t)round_up((int64_t)(off + bytes), 256);
-        return o;
-    };
     if (p.fused) {
         p.qgroups = pick_qgroups(p.qblocks, dim, kn);
         // the planner prices three sample sizes: 1/32 of the tiles, 1/64 (cheaper pass, twice the survivors of phase A) and 1/16
@@ -332,7 +336,6 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
         p.opt_rank = choice.opt_rank;
         // ranges that hold items of a phase: the candidate segments (a range started in phase A keeps phase A's capacity)
         const int nrc_p = NUM_XCD / p.main_qgroups, qb_per_p = p.main_qblocks / p.main_qgroups;
-        const int64_t items_p = R / nrc_p * qb_per_p;
         const int64_t RA = p.item_a ? std::min<int64_t>(R, (int64_t)nrc_p * ((p.item_a + qb_per_p - 1) / qb_per_p)) : 0;
         const int64_t RB = p.item_b ? std::min<int64_t>(R, (int64_t)nrc_p * ((p.item_b + qb_per_p - 1) / qb_per_p)) : 0;
         const double ratio = (double)p.tiles / (double)sample;
@@ -359,7 +362,6 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
         // corpus fractions the re-tightenings have SEEN: the ranges completed by then
         const double fa = p.item_a ? (double)(p.item_a / qb_per_p) * nrc_p / (double)R : 0.0;
         const double fb = p.item_b ? std::max(0.0, (double)(p.item_b / qb_per_p) * nrc_p / (double)R - fa) : 0.0;
-        (void)items_p;
         // the re-tightening selects among at most `compact` of the candidates found so far (launch_threshold_update): when
         // phase A is expected to leave more than that, the bound is the k-th of a subset and passes proportionally more
         const double upd_compact = std::min(32768.0, std::max(4096.0, 8.0 * pow2_ceil(k)));
@@ -408,38 +410,69 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
             int64_t capn = std::max<int64_t>(recs / ((int64_t)NARROW_SUBLISTS * std::max(1, n_q)), (int64_t)(8.0 * pass) + 4096);
             capn = std::min<int64_t>(capn, (int64_t)1 << 22) / 4 * 4;
             recs = std::max<int64_t>(recs, capn * NARROW_SUBLISTS * n_q);
-            CandLayout &N = p.first_lay;
-            memset(&N, 0, sizeof(N));
-            N.nseg = 1;
-            N.seg_end[0] = N.seg_end[1] = N.seg_end[2] = INT32_MAX;
-            N.cap[0] = N.cap[1] = N.cap[2] = (int)capn;
+            p.first_lay = one_segment((int)capn);
             p.first_nsub = NARROW_SUBLISTS;
             p.first_sp = NARROW_SUBLISTS;
         }
-        p.off_qnorm = take((size_t)p.nq_pad * 4);
-        p.off_thr = take((size_t)p.nq_pad * 4 * 2);  // thr then delta
-        p.off_gmax = take((size_t)p.sample_tiles * GROUPS_PER_TILE * p.nq_pad * 4);
-        p.off_cnt = take((size_t)p.ranges * p.nq_pad * p.sublists * 4);
-        p.off_cand = take((size_t)recs * 8);
-        p.off_flag = take(64 + (size_t)n_q * 4);
-        // the k best lower bounds per query between two re-tightenings (three-phase plans only)
-        p.off_top = take(p.item_b ? ((size_t)p.nq_pad + (size_t)n_q * k) * 4 : 0);
-        // estimated thresholds: room for the conservative bounds (+ margin coefficients) a failing search computes after the fact
-        p.off_safe = take(p.opt_rank ? (size_t)p.nq_pad * 8 : 0);
+        p.cand_recs = recs;
         p.dense_rows_per_chunk = FALLBACK_ROWS;
-        p.off_dense = take((size_t)FALLBACK_ROWS * n_rows * 4);
-        // retry pass of flagged queries: compact query rows, thresholds + margins, the two lists, counts, second flag area
-        p.off_retry = take((size_t)p.nq_pad * dim * 2 + (size_t)p.nq_pad * 8 + (size_t)n_q * 16 + 64 + 64 + (size_t)n_q * 4 + 256 * 10);
     } else {
         int64_t rows = (int64_t)(DENSE_SCRATCH_TARGET / ((size_t)n_rows * 4));
         rows = std::min<int64_t>(std::max<int64_t>(rows, 1), n_q);
         if (rows >= 64) rows = rows / 64 * 64;
         p.dense_rows_per_chunk = rows;
-        p.off_flag = take(64 + (size_t)n_q * 4);   // queries the margin select hands to the fp64 path
-        p.off_dense = take((size_t)rows * (n_rows + 3) * 4);
     }
-    p.total = off;
+    const SearchWs w = search_ws(p, n_rows, dim, n_q, k, nullptr);   // no base: the pointers are the byte offsets
+    p.off_qnorm = (size_t)w.qnorm, p.off_thr = (size_t)w.thr, p.off_gmax = (size_t)w.gmax, p.off_cnt = (size_t)w.cnt, p.off_cand = (size_t)w.cand;
+    p.off_flag = (size_t)w.flag_count, p.off_dense = (size_t)w.dense, p.off_retry = (size_t)w.Q2, p.off_top = (size_t)w.top, p.off_safe = (size_t)w.thr_safe;
+    p.total = w.total;
     return p;
+}
+
+SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char *base) {
+    SearchWs w;
+    memset(&w, 0, sizeof(w));
+    Bump b = {0};
+    auto at = [&](size_t off) { return (char *)((uintptr_t)base + off); };
+    auto take = [&](size_t bytes) { return at(b.take(bytes)); };
+    if (!p.fused) {
+        w.flag_count = (uint32_t *)take(64 + (size_t)n_q * 4);   // queries the margin select hands to the fp64 path
+        w.flag_list = w.flag_count + 16;
+        w.dense_bytes = (size_t)p.dense_rows_per_chunk * (n_rows + 3) * 4;
+        w.dense = (float *)take(w.dense_bytes);
+        w.total = b.off;
+        return w;
+    }
+    const size_t nq_pad = p.nq_pad;
+    w.qnorm = (float *)take(nq_pad * 4);
+    w.thr = (float *)take(nq_pad * 8);
+    w.cq = w.thr + nq_pad;
+    w.gmax = (float *)take((size_t)p.sample_tiles * GROUPS_PER_TILE * nq_pad * 4);
+    w.cnt = (uint32_t *)take((size_t)p.ranges * nq_pad * p.sublists * 4);
+    w.cand = (uint2 *)take((size_t)p.cand_recs * 8);
+    w.flag_count = (uint32_t *)take(64 + (size_t)n_q * 4);
+    w.stat_cand = (unsigned long long *)(w.flag_count + 2);
+    w.flag_list = w.flag_count + 16;
+    w.cand_bytes = (char *)w.flag_count - (char *)w.cand;
+    w.top = (uint32_t *)take(p.item_b ? (nq_pad + (size_t)n_q * k) * 4 : 0);
+    w.thr_safe = (float *)take(p.opt_rank ? nq_pad * 8 : 0);
+    w.cq_safe = w.thr_safe + nq_pad;
+    w.dense_bytes = (size_t)p.dense_rows_per_chunk * n_rows * 4;
+    w.dense = (float *)take(w.dense_bytes);
+    // the retry area keeps its reserved size: its nine sub-buffers plus up to 255 bytes of rounding each
+    w.retry_bytes = nq_pad * dim * 2 + nq_pad * 8 + (size_t)n_q * 16 + 64 + 64 + (size_t)n_q * 4 + 256 * 10;
+    Bump r = {b.take(w.retry_bytes)};
+    w.Q2 = (uint16_t *)at(r.take(nq_pad * dim * 2));
+    w.thr2 = (float *)at(r.take(nq_pad * 4));
+    w.cq2 = (float *)at(r.take(nq_pad * 4));
+    w.retry_list = (uint32_t *)at(r.take((size_t)n_q * 4));
+    w.dense_list = (uint32_t *)at(r.take((size_t)n_q * 4));
+    w.counts = (uint32_t *)at(r.take(64));
+    w.flag2 = (uint32_t *)at(r.take(64 + (size_t)n_q * 4));
+    w.list_b = (uint32_t *)at(r.take((size_t)n_q * 4));
+    w.list_c = (uint32_t *)at(r.take((size_t)n_q * 4));
+    w.total = b.off;
+    return w;
 }
 
 // Which main-pass kernel: CCR_MFMA16 pins it.  Otherwise the 16x16x32 kernel (the chip holds a higher clock on that MFMA shape)
@@ -625,7 +658,7 @@ extern "C" int ccr_index_destroy(ccr_index *ix) {
     if (!ix) return CCR_OK;
     // an asynchronous search the caller never finished: its kernels still read the index's arrays -- wait for THAT search (not
     // for the stream) before the blocks go back to the cache; queries it flagged beyond the on-stream chunk stay un-redone
-    if (ix->pending.active && ix->have_events) (void)hipEventSynchronize(ix->ev[7]);
+    if (ix->pending.active && ix->have_events) (void)hipEventSynchronize(ix->ev[EV_ASYNC_END]);
     ix->pending.active = false;
     // a slot / block handed back may be rewritten by the next index's create on ITS stream; the caller destroys an index only
     // after the work that uses it has completed (the same contract as for the borrowed corpus)
@@ -633,7 +666,7 @@ extern "C" int ccr_index_destroy(ccr_index *ix) {
     block_give(ix->device, ix->tile_norm, ix->tile_bytes);
     block_give(ix->device, ix->row_norm_own, ix->row_bytes);
     if (ix->have_events)
-        for (int i = 0; i < 8; ++i)
+        for (int i = 0; i < EV_COUNT; ++i)
             if (ix->ev[i]) (void)hipEventDestroy(ix->ev[i]);
     delete ix;
     return CCR_OK;
@@ -654,7 +687,7 @@ extern "C" size_t ccr_search_workspace_bytes(const ccr_index *ix, int n_q, int k
 extern "C" int ccr_search_stream_wait_main_pass(const ccr_index *ix, void *stream) {
     CCR_REQUIRE(ix, "ccr_search_stream_wait_main_pass: null index");
     if (!ix->main_pass_recorded) return CCR_OK;   // dense path / no search yet: nothing to order against
-    CCR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ix->ev[4], 0));
+    CCR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ix->ev[EV_MAIN_END], 0));
     return CCR_OK;
 }
 
@@ -665,26 +698,21 @@ extern "C" int ccr_search_last_stats(const ccr_index *ix, ccr_search_stats *stat
     return CCR_OK;
 }
 
-// Exact dense path for n queries: the rows d_qlist[lo .. lo + n) (or q_begin + lo ... when d_qlist is null), results to the
-// same rows of the outputs.
-static int dense_for_list(const ccr_index *ix, const uint16_t *Q, const uint32_t *d_qlist, int q_begin, int n, int k,
-                          float *scratch, int64_t rows_per_chunk, float *out_scores, int64_t *out_ids, hipStream_t s) {
+// Exact dense path for n queries: the rows d_qlist[0 .. n) (or 0 .. n when d_qlist is null), results to the same rows of the outputs.
+static int dense_for_list(const ccr_index *ix, const uint16_t *Q, const uint32_t *d_qlist, int n, int k, float *scratch, int64_t rows_per_chunk,
+                          float *out_scores, int64_t *out_ids, hipStream_t s) {
     for (int lo = 0; lo < n; lo += (int)rows_per_chunk) {
         const int m = std::min<int64_t>(rows_per_chunk, n - lo);
-        int rc = launch_dense_scores(ix->D, ix->n_rows, ix->dim, Q, d_qlist ? d_qlist + lo : nullptr, q_begin + lo, m, nullptr,
-                                     scratch, s);
+        int rc = launch_dense_scores(ix->D, ix->n_rows, ix->dim, Q, d_qlist ? d_qlist + lo : nullptr, lo, m, nullptr, scratch, s);
         if (rc != CCR_OK) return rc;
-        rc = launch_dense_select(scratch, ix->n_rows, k, d_qlist ? d_qlist + lo : nullptr, q_begin + lo, m, nullptr, ix->id_out,
-                                 out_scores, out_ids, s);
+        rc = launch_dense_select(scratch, ix->n_rows, k, d_qlist ? d_qlist + lo : nullptr, lo, m, nullptr, ix->id_out, out_scores, out_ids, s);
         if (rc != CCR_OK) return rc;
     }
     return CCR_OK;
 }
 
-// The same for inner-product scores the fast way: MFMA score rows of the chunk (EPI_STORE of the fused kernel) + margin select
-// (ccr_dense.hip).  Queries are the rows Qc[0 .. n) -- contiguous: the caller gathers a list first -- results go to rows
-// out_rows[i] (or q_begin + i).  Queries the margin select cannot finish are appended to flag_list (flag_count is NOT reset here).
 static bool margin_path_ok(const ccr_index *ix, int k) { return ix->dim % 8 == 0 && k <= MAX_K; }
+static int64_t tiles_of(const ccr_index *ix) { return (ix->n_rows + TILE_DOCS - 1) / TILE_DOCS; }
 
 // kernel arguments of n_q query rows at Q (nq_pad / TILE_Q blocks) against the index's corpus, all work items
 static GemmArgs gemm_args(const ccr_index *ix, const uint16_t *Q, int n_q, int nq_pad) {
@@ -697,58 +725,78 @@ static GemmArgs gemm_args(const ccr_index *ix, const uint16_t *Q, int n_q, int n
     g.n_q = n_q;
     g.nq_pad = nq_pad;
     g.qblocks = nq_pad / TILE_Q;
-    g.item_begin = 0;
     g.item_end = INT32_MAX;
     return g;
 }
 
-static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float *hint, const uint32_t *out_rows, int q_begin, int n, int k, float *scratch,
-                           size_t scratch_bytes, float *out_scores, int64_t *out_ids, uint32_t *flag_count, uint32_t *flag_list,
-                           hipStream_t s) {
+// EPI_FILTER arguments: every corpus tile in the plan's ranges, candidates to the workspace's lists as `lay` places them
+static GemmArgs filter_args(const ccr_index *ix, const Plan &p, const SearchWs &w, const uint16_t *Q, int n_q, int nq_pad, int qblocks,
+                            int qgroups, const float *thr, const float *cq, const CandLayout &lay) {
+    GemmArgs g = gemm_args(ix, Q, n_q, nq_pad);
+    g.qblocks = qblocks;
+    g.qgroups = qgroups;
+    g.n_vt = p.tiles;
+    g.tile_stride = 1;
+    g.ranges = p.ranges;
+    g.thr = thr;
+    g.cq = cq;
+    g.tile_norm = ix->tile_norm;
+    g.cnt = w.cnt;
+    g.cand = w.cand;
+    g.lay = lay;
+    return g;
+}
+
+// EPI_STORE: MFMA score rows of the n_q queries at Q against every corpus row, in `ranges` ranges, to out [n_q][pitch] (0: n_rows)
+static int store_scores(const ccr_index *ix, const uint16_t *Q, int n_q, int ranges, float *out, int64_t pitch, hipStream_t s) {
+    GemmArgs g = gemm_args(ix, Q, n_q, (int)round_up(n_q, TILE_Q));
+    g.n_vt = tiles_of(ix);
+    g.tile_stride = 1;
+    g.ranges = ranges;
+    g.qgroups = 1;
+    g.store = out;
+    g.store_pitch = pitch;
+    return launch_gemm(g, ix->knobs.mfma16 != 0 ? MAIN_16X16 : MAIN_32X32, EPI_STORE, std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD), s);
+}
+
+// The same for inner-product scores the fast way: MFMA score rows of the chunk (EPI_STORE of the fused kernel) + margin select
+// (ccr_dense.hip).  Queries are the rows Qc[0 .. n) -- contiguous: the caller gathers a list first -- results go to rows
+// out_rows[i] (or i).  Queries the margin select cannot finish are appended to flag_list (flag_count is NOT reset here).
+static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float *hint, const uint32_t *out_rows, int n, int k, float *scratch,
+                           size_t scratch_bytes, float *out_scores, int64_t *out_ids, uint32_t *flag_count, uint32_t *flag_list, hipStream_t s) {
     const int64_t pitch = round_up(ix->n_rows, 4);
     int64_t chunk = (int64_t)(scratch_bytes / ((size_t)pitch * 4));   // score rows the scratch holds: any number of query blocks per launch
     CCR_REQUIRE(chunk >= 1, "margin path: no room for one score row");
     if (chunk > TILE_Q) chunk = chunk / TILE_Q * TILE_Q;
-    const int grid = std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD);
+    const int ranges = (int)round_up(std::min<int64_t>(std::max<int64_t>(1, tiles_of(ix) / 4), 1024), NUM_XCD);   // ~4 tiles per work item
     for (int lo = 0; lo < n; lo += (int)chunk) {
         const int m = std::min<int64_t>(chunk, n - lo);
-        GemmArgs g = gemm_args(ix, Qc + (int64_t)lo * ix->dim, m, (int)round_up(m, TILE_Q));
-        g.n_vt = (ix->n_rows + TILE_DOCS - 1) / TILE_DOCS;
-        g.tile_stride = 1;
-        g.ranges = (int)round_up(std::min<int64_t>(std::max<int64_t>(1, g.n_vt / 4), 1024), NUM_XCD);   // ~4 tiles per work item
-        g.qgroups = 1;
-        g.store = scratch;
-        g.store_pitch = pitch;
-        int rc = launch_gemm(g, ix->knobs.mfma16 != 0 ? MAIN_16X16 : MAIN_32X32, EPI_STORE, grid, s);
+        const uint16_t *Q = Qc + (int64_t)lo * ix->dim;
+        int rc = store_scores(ix, Q, m, ranges, scratch, pitch, s);
         if (rc != CCR_OK) return rc;
-        rc = launch_margin_select(scratch, pitch, ix->n_rows, k, ix->dim, g.Q, ix->D, ix->tile_norm, ix->row_norm, ix->dmax_bits,
-                                  hint ? hint + lo : nullptr, out_rows ? out_rows + lo : nullptr, q_begin + lo, m, ix->id_out, out_scores, out_ids, flag_count, flag_list, s);
+        rc = launch_margin_select(scratch, pitch, ix->n_rows, k, ix->dim, Q, ix->D, ix->tile_norm, ix->row_norm, ix->dmax_bits,
+                                  hint ? hint + lo : nullptr, out_rows ? out_rows + lo : nullptr, lo, m, ix->id_out, out_scores, out_ids, flag_count, flag_list, s);
         if (rc != CCR_OK) return rc;
     }
     return CCR_OK;
 }
 
 // The main pass: one launch per phase (work items [begin, end) of every XCD set), the thresholds re-tightened from the candidates
-// of the ranges completed so far between two launches when `retighten` is set.
-static int run_main_pass(const ccr_index *ix, const Plan &p, GemmArgs gm, uint2 *cand, uint32_t *cnt, float *thr, const float *cq,
-                         uint32_t *top, int n_q, int k, bool retighten, hipStream_t s) {
-    const int nrc = NUM_XCD / gm.qgroups, qb_per = gm.qblocks / gm.qgroups;
-    const int items = p.ranges / nrc * qb_per;
-    const int bounds[4] = {0, retighten ? p.item_a : 0, retighten ? p.item_b : 0, items};
-    gm.cand = cand;
-    gm.lay = p.cand;
-    gm.cq = cq;
-    gm.tile_norm = ix->tile_norm;
-    int done = 0, updates = 0;
-    int prev_full = 0, prev_part = 0, prev_blocks = 0;
+// of the ranges completed so far between two launches.
+static int run_main_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, const uint16_t *Q, int n_q, int k, hipStream_t s) {
+    // (blocks of p.tile_q queries; the sample pass walks blocks of TILE_Q)
+    GemmArgs gm = filter_args(ix, p, w, Q, n_q, p.nq_pad, p.main_qblocks, p.main_qgroups, w.thr, w.cq, p.cand);
+    const int nrc = NUM_XCD / gm.qgroups, qb_per = gm.qblocks / gm.qgroups, items = p.ranges / nrc * qb_per;
+    const int bounds[4] = {0, p.item_a, p.item_b, items};
+    int done = 0, updates = 0, prev_full = 0, prev_part = 0, prev_blocks = 0;
     for (int ph = 1; ph < 4; ++ph) {
         if (bounds[ph] <= done) continue;
         if (done > 0) {
             const int rl_full = done / qb_per, part = done % qb_per;   // complete range rows; blocks done of the started one
             const int full = rl_full * nrc * p.sublists, partial = part ? (rl_full + 1) * nrc * p.sublists : 0;
             const bool more = bounds[ph] < items && ph < 3;   // another re-tightening follows this phase
-            const int rc = launch_threshold_update(cand, cnt, full, partial, part, prev_full, prev_part, prev_blocks, qb_per, p.sublists, n_q,
-                                                   p.nq_pad, p.cand, k, cq, ix->tile_norm, top, updates > 0, more, thr, s, p.tile_q);
+            const int rc = launch_threshold_update(w.cand, w.cnt, full, partial, part, prev_full, prev_part, prev_blocks, qb_per, p.sublists, n_q,
+                                                   p.nq_pad, p.cand, k, w.cq, ix->tile_norm, p.item_b ? w.top : nullptr, updates > 0, more, w.thr, s, p.tile_q);
             if (rc != CCR_OK) return rc;
             prev_full = full;
             prev_part = partial;
@@ -765,6 +813,190 @@ static int run_main_pass(const ccr_index *ix, const Plan &p, GemmArgs gm, uint2 
     return CCR_OK;
 }
 
+// Small batch: the corpus is STREAMED past query rows resident in LDS (ccr_narrow.hip); two atomically filled sub-lists per query
+// (their counters were cleared by launch_threshold)
+static int run_narrow_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, const uint16_t *Q, int n_q, hipStream_t s) {
+    NarrowArgs na;
+    memset(&na, 0, sizeof(na));
+    na.D = ix->D;
+    na.n_rows = ix->n_rows;
+    na.dim = ix->dim;
+    na.Q = Q;
+    na.n_q = n_q;
+    na.q_stride = narrow_query_stride(ix->dim);
+    na.thr = w.thr;
+    na.cq = w.cq;
+    na.tile_norm = ix->tile_norm;
+    na.cand = w.cand;
+    na.cnt = w.cnt;
+    na.cap = p.first_lay.cap[0];
+    na.groups = p.narrow_groups;
+    // one workgroup (8 waves x 12 KiB of loads in flight) per CU: measured at NQ 6.2 / 6.2 / 6.0 TB/s of corpus bytes at n_q = 1 / 16 / 64;
+    // two or four per CU -- the 16- and 32-query images would fit -- stream no faster (6.2 / 5.9 TB/s at 1 / 16)
+    int ngrid = ix->knobs.narrow_grid > 0 ? ix->knobs.narrow_grid : ix->num_cu;
+    const int64_t blocks = (ix->n_rows + 16 * NARROW_WAVES - 1) / (16 * NARROW_WAVES);
+    if ((int64_t)ngrid > blocks) ngrid = (int)std::max<int64_t>(1, blocks);
+    if (p.narrow_groups == 2) ngrid = std::max(16, ngrid / 16 * 16);   // whole sets of eight (b, b + 8) pairs; a pair shares its row stream
+    return launch_narrow_filter(na, p.narrow, ngrid, s);
+}
+
+// n 32-bit words from the device to the host; synchronises the stream
+static int read_words(void *host, const void *dev, int n, hipStream_t s) {
+    CCR_HIP_CHECK(hipMemcpyAsync(host, dev, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    CCR_HIP_CHECK(hipStreamSynchronize(s));
+    return CCR_OK;
+}
+
+// The stages of the completion of a fused search (search_complete) read the search from ix->plan and ix->pending.
+
+// Statistics of the search from its events (all of them complete) and its flag line.
+static int fused_stats(ccr_index *ix, uint32_t nflag, unsigned long long ncand) {
+    const Plan &p = ix->plan;
+    ccr_search_stats &st = ix->stats;
+    float a = 0, b = 0;
+    CCR_HIP_CHECK(hipEventElapsedTime(&st.ms_sample, ix->ev[EV_SAMPLE_BEGIN], ix->ev[EV_SAMPLE_END]));
+    CCR_HIP_CHECK(hipEventElapsedTime(&a, ix->ev[EV_BEGIN], ix->ev[EV_SAMPLE_BEGIN]));
+    CCR_HIP_CHECK(hipEventElapsedTime(&b, ix->ev[EV_SAMPLE_END], ix->ev[EV_MAIN_BEGIN]));
+    st.ms_threshold = a + b;
+    CCR_HIP_CHECK(hipEventElapsedTime(&st.ms_main, ix->ev[EV_MAIN_BEGIN], ix->ev[EV_MAIN_END]));
+    CCR_HIP_CHECK(hipEventElapsedTime(&st.ms_select, ix->ev[EV_MAIN_END], ix->ev[EV_SELECT_END]));
+    CCR_HIP_CHECK(hipEventElapsedTime(&st.ms_total, ix->ev[EV_BEGIN], ix->ev[EV_SELECT_END]));
+    st.path = 1;
+    st.n_fallback = (int32_t)nflag;
+    st.sample_tiles = p.sample_tiles;
+    st.ranges = p.narrow ? 1 : p.ranges;                      // (streaming main pass of a small batch: one range, two sub-lists per query)
+    st.cap = p.narrow ? p.first_lay.cap[0] : p.cap;
+    st.sublists = p.narrow ? p.first_sp : p.sublists;
+    st.main_launches = 1 + (p.item_a ? 1 : 0) + (p.item_b ? 1 : 0);
+    st.opt_rank = p.opt_rank;
+    st.main_tile_queries = p.narrow ? 0 : p.tile_q;
+    st.n_candidates = (int64_t)ncand;
+    return CCR_OK;
+}
+
+// Estimated thresholds: a query for which fewer than k rows passed has no list to take a bound from (the select left thr = -inf
+// and FLAG_DENSE).  The sample's group maxima are still in the workspace: the CONSERVATIVE threshold (the k-th largest, a valid
+// bound) is computed now -- only on this path -- and those of the nflag flagged queries join the retry under it.
+static int recover_thresholds(const ccr_index *ix, const SearchWs &w, int nflag) {
+    const auto &pd = ix->pending;
+    const int rc = launch_threshold(w.gmax, (int64_t)ix->plan.sample_tiles * GROUPS_PER_TILE, pd.n_q, ix->plan.nq_pad, pd.k, w.qnorm, ix->dmax_bits,
+                                    ix->dim, ix->tile_norm, ix->plan.sample_stride, w.thr_safe, w.cq_safe, pd.stream);
+    if (rc != CCR_OK) return rc;
+    return launch_underfilled_to_retry(w.flag_list, 0, nflag, w.thr_safe, w.thr, pd.stream);
+}
+
+// appends the n queries of a device list to the dense list (n_dense entries so far)
+static int to_dense(const SearchWs &w, const uint32_t *list, int n, int &n_dense, hipStream_t s) {
+    CCR_HIP_CHECK(hipMemcpyAsync(w.dense_list + n_dense, list, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    n_dense += n;
+    return CCR_OK;
+}
+
+// One group of flagged queries in up to three rounds: a round retries what the previous one flagged again, under thresholds
+// re-tightened from the previous round's (truncated) lists.  What is left joins the dense list.
+static int retry_group(ccr_index *ix, const SearchWs &w, const uint32_t *cur, int n_cur, int &n_dense) {
+    const Plan &p = ix->plan;
+    const auto &pd = ix->pending;
+    hipStream_t s = pd.stream;
+    const int nsub_all = p.ranges * p.sublists;
+    for (int round = 0;; ++round) {
+        int rc = launch_gather_queries(pd.Q, ix->dim, cur, n_cur, w.thr, w.cq, w.Q2, w.thr2, w.cq2, s);
+        if (rc != CCR_OK) return rc;
+        const int pad2 = (int)round_up(n_cur, TILE_Q);
+        const int64_t cap2 = std::min<int64_t>(8192, (int64_t)(w.cand_bytes / 8) / ((int64_t)nsub_all * pad2) / 4 * 4);
+        if (cap2 < 16) break;
+        const CandLayout lay2 = one_segment((int)cap2);
+        CCR_HIP_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)nsub_all * pad2 * 4, s));
+        CCR_HIP_CHECK(hipMemsetAsync(w.flag2, 0, 64, s));
+        const GemmArgs g = filter_args(ix, p, w, w.Q2, n_cur, pad2, pad2 / TILE_Q, pick_qgroups(pad2 / TILE_Q, ix->dim, ix->knobs), w.thr2, w.cq2, lay2);
+        rc = launch_gemm(g, p.mfma16 ? MAIN_16X16 : MAIN_32X32, EPI_FILTER, p.grid, s);   // TILE_Q blocks: never the wide kernel
+        if (rc != CCR_OK) return rc;
+        rc = launch_select_rescore(w.cand, w.cnt, nsub_all, p.sublists, n_cur, pad2, lay2, pd.k, p.rescore_cap, p.select_compact, ix->n_rows,
+                                   w.thr2, w.cq2, ix->tile_norm, ix->row_norm, ix->dmax_bits, w.Q2, ix->D, ix->dim, ix->id_out, pd.out_scores, pd.out_ids,
+                                   w.flag2, w.flag2 + 16, nullptr, cur, s);
+        if (rc != CCR_OK) return rc;
+        ix->stats.n_retried += n_cur;
+        uint32_t again = 0;
+        rc = read_words(&again, w.flag2, 1, s);
+        if (rc != CCR_OK || again == 0) return rc;
+        uint32_t *next = (cur == w.list_b) ? w.list_c : w.list_b;
+        rc = launch_partition_flags(w.flag2 + 16, 0, (int)again, next, w.dense_list + n_dense, w.counts, s);
+        if (rc != CCR_OK) return rc;
+        uint32_t hc[2] = {0, 0};
+        rc = read_words(hc, w.counts, 2, s);
+        if (rc != CCR_OK) return rc;
+        n_dense += (int)hc[1];
+        const uint32_t *list = cur;
+        const int n = n_cur;
+        cur = next;
+        n_cur = (int)hc[0];
+        // none left, three rounds done, or no progress (every retried query overflowed again): the dense path takes them
+        if (n_cur == 0 || round == 2 || n_cur >= n) break;
+        rc = launch_threshold_update(w.cand, w.cnt, nsub_all, 0, 0, 0, 0, 0, 1, p.sublists, n, pad2, lay2, pd.k, w.cq2, ix->tile_norm, nullptr,
+                                     false, false, w.thr2, s);
+        if (rc != CCR_OK) return rc;
+        rc = launch_scatter_thresholds(list, n, w.thr2, w.thr, s);
+        if (rc != CCR_OK) return rc;
+    }
+    return n_cur > 0 ? to_dense(w, cur, n_cur, n_dense, s) : CCR_OK;
+}
+
+// Retry of the n_retry queries of the retry list on the fused path; what it cannot finish joins the dense list.
+static int retry_flagged(ccr_index *ix, const SearchWs &w, int n_retry, int &n_dense) {
+    const Plan &p = ix->plan;
+    const auto &pd = ix->pending;
+    const int nsub_all = p.ranges * p.sublists;
+    if (nsub_all > 2048) return to_dense(w, w.retry_list, n_retry, n_dense, pd.stream);
+    // thresholds re-tightened from everything the first attempt recorded (truncated lists included) -- for every flagged
+    // query at once, before the candidate area is reused
+    int rc = launch_threshold_update(w.cand, w.cnt, p.first_nsub, 0, 0, 0, 0, 0, 1, p.first_sp, pd.n_q, p.nq_pad, p.first_lay, pd.k, w.cq,
+                                     ix->tile_norm, nullptr, false, false, w.thr, pd.stream);
+    if (rc != CCR_OK) return rc;
+    // The flagged queries are retried in GROUPS that get the whole candidate area to themselves: the fewer queries share
+    // it, the larger every sub-list.  A group is as large as still leaves four times the first attempt's capacity (when
+    // most of a batch is flagged -- the lists were flooded, not unlucky -- one group per query block: about one corpus
+    // pass of ONE block per 256 queries instead of 0.65 ms of fp64 scoring per query).
+    const int64_t want_cap = std::min<int64_t>(8192, 4 * (int64_t)p.cap);
+    int64_t group = (int64_t)(w.cand_bytes / 8) / ((int64_t)nsub_all * want_cap) / TILE_Q * TILE_Q;
+    group = std::max<int64_t>(TILE_Q, std::min<int64_t>(group, round_up(n_retry, TILE_Q)));
+    for (int g0 = 0; g0 < n_retry && rc == CCR_OK; g0 += (int)group)
+        rc = retry_group(ix, w, w.retry_list + g0, std::min<int>((int)group, n_retry - g0), n_dense);
+    return rc;
+}
+
+// The exact dense path for the n_dense queries of the dense list: MFMA score rows + margin select first (0.9 ms of GEMM per 256
+// queries + one row scan each, against 0.65 ms of fp64 scoring per query); only what that cannot finish -- more than 8 192 rows
+// inside the margin, non-finite embeddings -- is left to the fp64 path.
+static int complete_dense(ccr_index *ix, const SearchWs &w, int n_dense) {
+    const Plan &p = ix->plan;
+    const auto &pd = ix->pending;
+    hipStream_t s = pd.stream;
+    // The candidate area is free by now.  The margin path scores in it when it is larger than the reserved rows.  The fp64 path
+    // moves there when it holds 64 rows or more and more than one chunk of queries waits: its 64 x 64 score tiles are a quarter
+    // full with the 16 reserved rows (2.2 instead of 0.65 ms per NQ query) -- 64 (or more) queries per chunk in there.
+    const bool margin_in_cand = w.cand_bytes > w.dense_bytes;
+    const int64_t fit = (int64_t)(w.cand_bytes / ((size_t)ix->n_rows * 4)) / 64 * 64;
+    const bool fp64_in_cand = n_dense > p.dense_rows_per_chunk && fit >= 64;
+    const int64_t chunk = fp64_in_cand ? std::min<int64_t>(fit, 256) : p.dense_rows_per_chunk;
+    float *fp64_scr = fp64_in_cand ? (float *)w.cand : w.dense;
+    if (!margin_path_ok(ix, pd.k))
+        return dense_for_list(ix, pd.Q, w.dense_list, n_dense, pd.k, fp64_scr, chunk, pd.out_scores, pd.out_ids, s);
+    CCR_HIP_CHECK(hipMemsetAsync(w.flag2, 0, 64, s));
+    for (int lo = 0; lo < n_dense; lo += p.nq_pad) {   // Q2 holds nq_pad gathered query rows
+        const int m = std::min(p.nq_pad, n_dense - lo);
+        int rc = launch_gather_queries(pd.Q, ix->dim, w.dense_list + lo, m, w.thr, w.cq, w.Q2, w.thr2, w.cq2, s);
+        if (rc != CCR_OK) return rc;
+        // (thr2: the gathered thresholds of these queries -- valid lower bounds of their k-th largest scores)
+        rc = margin_for_rows(ix, w.Q2, w.thr2, w.dense_list + lo, m, pd.k, margin_in_cand ? (float *)w.cand : w.dense,
+                             margin_in_cand ? w.cand_bytes : w.dense_bytes, pd.out_scores, pd.out_ids, w.flag2, w.flag2 + 16, s);
+        if (rc != CCR_OK) return rc;
+    }
+    uint32_t left = 0;
+    const int rc = read_words(&left, w.flag2, 1, s);
+    if (rc != CCR_OK || left == 0) return rc;
+    return dense_for_list(ix, pd.Q, w.flag2 + 16, (int)left, pd.k, fp64_scr, chunk, pd.out_scores, pd.out_ids, s);
+}
+
 // Completion of a fused search: read how many queries the select stage flagged and re-do them.
 //   * a query whose candidates were dropped (sub-list overflow: a corpus in topical order floods the lists of the query's
 //     own cluster) is RETRIED on the fused path: its truncated lists still hold real rows, so the k-th largest of them is a
@@ -775,242 +1007,74 @@ static int run_main_pass(const ccr_index *ix, const Plan &p, GemmArgs gm, uint2 
 // Synchronises the stream.
 static int search_complete(ccr_index *ix) {
     auto &pd = ix->pending;
-    const Plan &p = ix->plan;
     hipStream_t s = pd.stream;
-    char *ws = pd.ws;
     const bool was_async = pd.active;
     pd.active = false;
-    struct {
-        uint32_t nflag, pad;
-        unsigned long long ncand;
-    } host;
+    const SearchWs w = search_ws(ix->plan, ix->n_rows, ix->dim, pd.n_q, pd.k, pd.ws);
+    struct { uint32_t nflag, pad; unsigned long long ncand; } host;   // the flag line
+    int rc = CCR_OK;
     if (was_async) {
-        // the search itself copied its flag line to pinned host memory and recorded ev[7] behind it: wait for THAT event, not for
-        // the stream -- work enqueued after the search (the next step's pack and search, the exchange) is not waited for
-        CCR_HIP_CHECK(hipEventSynchronize(ix->ev[7]));
+        // the search itself copied its flag line to pinned host memory and recorded EV_ASYNC_END behind it: wait for THAT event,
+        // not for the stream -- work enqueued after the search (the next step's pack and search, the exchange) is not waited for
+        CCR_HIP_CHECK(hipEventSynchronize(ix->ev[EV_ASYNC_END]));
         host.nflag = ix->host_flags[0];
         host.ncand = *reinterpret_cast<volatile unsigned long long *>(ix->host_flags + 2);
     } else {
-        CCR_HIP_CHECK(hipMemcpyAsync(&host, ws + p.off_flag, sizeof(host), hipMemcpyDeviceToHost, s));
-        CCR_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    {
-        float a = 0, b = 0;
-        CCR_HIP_CHECK(hipEventElapsedTime(&ix->stats.ms_sample, ix->ev[1], ix->ev[2]));
-        CCR_HIP_CHECK(hipEventElapsedTime(&a, ix->ev[0], ix->ev[1]));
-        CCR_HIP_CHECK(hipEventElapsedTime(&b, ix->ev[2], ix->ev[3]));
-        ix->stats.ms_threshold = a + b;
-        CCR_HIP_CHECK(hipEventElapsedTime(&ix->stats.ms_main, ix->ev[3], ix->ev[4]));
-        CCR_HIP_CHECK(hipEventElapsedTime(&ix->stats.ms_select, ix->ev[4], ix->ev[5]));
-        CCR_HIP_CHECK(hipEventElapsedTime(&ix->stats.ms_total, ix->ev[0], ix->ev[5]));
-    }
-    ix->stats.path = 1;
-    ix->stats.n_fallback = (int32_t)host.nflag;
-    ix->stats.sample_tiles = p.sample_tiles;
-    ix->stats.ranges = p.narrow ? 1 : p.ranges;                      // (streaming main pass of a small batch: one range, two sub-lists per query)
-    ix->stats.cap = p.narrow ? p.first_lay.cap[0] : p.cap;
-    ix->stats.sublists = p.narrow ? p.first_sp : p.sublists;
-    ix->stats.main_launches = 1 + (p.item_a ? 1 : 0) + (p.item_b ? 1 : 0);
-    ix->stats.opt_rank = p.opt_rank;
-    ix->stats.main_tile_queries = p.narrow ? 0 : p.tile_q;
-    ix->stats.n_candidates = (int64_t)host.ncand;
-    const int begin = 0;
-    ix->stats.n_dense = 0;
-    if (host.nflag == 0) return CCR_OK;
-
-    const int n_q = pd.n_q, k = pd.k;
-    uint32_t *flag_list = (uint32_t *)(ws + p.off_flag + 64);
-    float *thr = (float *)(ws + p.off_thr);
-    float *delta = thr + p.nq_pad;   // cq: margin coefficients gamma ||q|| (the per-tile margin is cq * tile norm)
-    uint32_t *cnt = (uint32_t *)(ws + p.off_cnt);
-    uint2 *cand = (uint2 *)(ws + p.off_cand);
-    float *dense_scratch = (float *)(ws + p.off_dense);
-    // retry area: [Q2 nq_pad x dim bf16][thr2 nq_pad][delta2 nq_pad][retry_list n_q][dense_list n_q][counts 64 B][flag2 64 B + n_q]
-    char *ra = ws + p.off_retry;
-    auto carve = [&](size_t bytes) {
-        char *o = ra;
-        ra += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    uint16_t *Q2 = (uint16_t *)carve((size_t)p.nq_pad * ix->dim * 2);
-    float *thr2 = (float *)carve((size_t)p.nq_pad * 4);
-    float *delta2 = (float *)carve((size_t)p.nq_pad * 4);
-    uint32_t *retry_list = (uint32_t *)carve((size_t)n_q * 4);
-    uint32_t *dense_list = (uint32_t *)carve((size_t)n_q * 4);
-    uint32_t *counts = (uint32_t *)carve(64);
-    uint32_t *flag2 = (uint32_t *)carve(64 + (size_t)n_q * 4);
-
-    uint32_t *list_b = (uint32_t *)carve((size_t)n_q * 4);   // the rounds of a group ping-pong between these two lists
-    uint32_t *list_c = (uint32_t *)carve((size_t)n_q * 4);
-    int rc = CCR_OK;
-    if (p.opt_rank) {
-        // Estimated thresholds: a query for which fewer than k rows passed has no list to take a bound from (the select left
-        // thr = -inf and FLAG_DENSE).  The sample's group maxima are still in the workspace: the CONSERVATIVE threshold (the k-th
-        // largest, a valid bound) is computed now -- only on this path -- and those queries join the retry under it.
-        float *thr_safe = (float *)(ws + p.off_safe);
-        rc = launch_threshold((const float *)(ws + p.off_gmax), (int64_t)p.sample_tiles * GROUPS_PER_TILE, n_q, p.nq_pad, k,
-                              (const float *)(ws + p.off_qnorm), ix->dmax_bits, ix->dim, ix->tile_norm, p.sample_stride, thr_safe,
-                              thr_safe + p.nq_pad, s);
-        if (rc != CCR_OK) return rc;
-        rc = launch_underfilled_to_retry(flag_list, begin, (int)host.nflag, thr_safe, thr, s);
+        rc = read_words(&host, w.flag_count, 4, s);
         if (rc != CCR_OK) return rc;
     }
-    rc = launch_partition_flags(flag_list, begin, (int)host.nflag, retry_list, dense_list, counts, s);
+    rc = fused_stats(ix, host.nflag, host.ncand);
+    if (rc != CCR_OK || host.nflag == 0) return rc;
+    rc = ix->plan.opt_rank ? recover_thresholds(ix, w, (int)host.nflag) : CCR_OK;
     if (rc != CCR_OK) return rc;
-    uint32_t hc[2] = {0, 0};
-    CCR_HIP_CHECK(hipMemcpyAsync(hc, counts, 8, hipMemcpyDeviceToHost, s));
-    CCR_HIP_CHECK(hipStreamSynchronize(s));
-    const int n_retry = (int)hc[0];
+    rc = launch_partition_flags(w.flag_list, 0, (int)host.nflag, w.retry_list, w.dense_list, w.counts, s);
+    if (rc != CCR_OK) return rc;
+    uint32_t hc[2] = {0, 0};   // queries to retry, queries for the dense path
+    rc = read_words(hc, w.counts, 2, s);
+    if (rc != CCR_OK) return rc;
     int n_dense = (int)hc[1];
-    int n_again = 0;   // queries the retry could not finish (they join the dense list)
-    const int64_t area_recs = (int64_t)((p.off_flag - p.off_cand) / 8);   // records the candidate area holds
-    const int nsub_all = p.ranges * p.sublists;
-    auto to_dense = [&](const uint32_t *list, int n) -> int {
-        CCR_HIP_CHECK(hipMemcpyAsync(dense_list + n_dense, list, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-        n_dense += n;
-        n_again += n;
-        return CCR_OK;
-    };
-    if (n_retry > 0 && nsub_all > 2048) {
-        rc = to_dense(retry_list, n_retry);
-        if (rc != CCR_OK) return rc;
-    } else if (n_retry > 0) {
-        // thresholds re-tightened from everything the first attempt recorded (truncated lists included) -- for every flagged
-        // query at once, before the candidate area is reused
-        rc = launch_threshold_update(cand, cnt, p.first_nsub, 0, 0, 0, 0, 0, 1, p.first_sp, n_q, p.nq_pad, p.first_lay, k, delta, ix->tile_norm, nullptr, false,
-                                     false, thr, s);
-        if (rc != CCR_OK) return rc;
-        // The flagged queries are retried in GROUPS that get the whole candidate area to themselves: the fewer queries share
-        // it, the larger every sub-list.  A group is as large as still leaves four times the first attempt's capacity (when
-        // most of a batch is flagged -- the lists were flooded, not unlucky -- one group per query block: about one corpus
-        // pass of ONE block per 256 queries instead of 0.65 ms of fp64 scoring per query).
-        const int64_t want_cap = std::min<int64_t>(8192, 4 * (int64_t)p.cap);
-        int64_t group = area_recs / ((int64_t)nsub_all * want_cap) / TILE_Q * TILE_Q;
-        group = std::max<int64_t>(TILE_Q, std::min<int64_t>(group, round_up(n_retry, TILE_Q)));
-        for (int g0 = 0; g0 < n_retry; g0 += (int)group) {
-            const uint32_t *cur = retry_list + g0;
-            int n_cur = std::min<int>((int)group, n_retry - g0);
-            const uint32_t *prev_list = nullptr;
-            CandLayout prev_lay = p.cand;
-            int prev_n = 0, prev_pad = 0;
-            for (int round = 0; round < 3 && n_cur > 0; ++round) {
-                if (round > 0) {   // re-tighten from the previous round's (truncated) lists of this group
-                    rc = launch_threshold_update(cand, cnt, nsub_all, 0, 0, 0, 0, 0, 1, p.sublists, prev_n, prev_pad, prev_lay, k, delta2, ix->tile_norm,
-                                                 nullptr, false, false, thr2, s);
-                    if (rc != CCR_OK) return rc;
-                    rc = launch_scatter_thresholds(prev_list, prev_n, thr2, thr, s);
-                    if (rc != CCR_OK) return rc;
-                }
-                rc = launch_gather_queries(pd.Q, ix->dim, cur, n_cur, thr, delta, Q2, thr2, delta2, s);
-                if (rc != CCR_OK) return rc;
-                const int pad2 = (int)round_up(n_cur, TILE_Q);
-                int64_t cap2 = area_recs / ((int64_t)nsub_all * pad2);
-                cap2 = std::min<int64_t>(8192, cap2 / 4 * 4);
-                if (cap2 < 16) break;
-                CandLayout lay2;
-                memset(&lay2, 0, sizeof(lay2));
-                lay2.nseg = 1;
-                lay2.seg_end[0] = lay2.seg_end[1] = lay2.seg_end[2] = INT32_MAX;
-                lay2.cap[0] = lay2.cap[1] = lay2.cap[2] = (int)cap2;
-                CCR_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nsub_all * pad2 * 4, s));
-                CCR_HIP_CHECK(hipMemsetAsync(flag2, 0, 64, s));
-                GemmArgs g = gemm_args(ix, Q2, n_cur, pad2);
-                g.qgroups = pick_qgroups(g.qblocks, ix->dim, ix->knobs);
-                g.n_vt = p.tiles;
-                g.tile_stride = 1;
-                g.ranges = p.ranges;
-                g.thr = thr2;
-                g.cq = delta2;
-                g.tile_norm = ix->tile_norm;
-                g.cnt = cnt;
-                g.cand = cand;
-                g.lay = lay2;
-                rc = launch_gemm(g, p.mfma16 ? MAIN_16X16 : MAIN_32X32, EPI_FILTER, p.grid, s);   // TILE_Q blocks: never the wide kernel
-                if (rc != CCR_OK) return rc;
-                rc = launch_select_rescore(cand, cnt, nsub_all, p.sublists, n_cur, pad2, lay2, k, p.rescore_cap, p.select_compact, ix->n_rows,
-                                           thr2, delta2, ix->tile_norm, ix->row_norm, ix->dmax_bits, Q2, ix->D, ix->dim, ix->id_out, pd.out_scores, pd.out_ids, flag2,
-                                           flag2 + 16, nullptr, cur, s);
-                if (rc != CCR_OK) return rc;
-                ix->stats.n_retried += n_cur;
-                uint32_t again = 0;
-                CCR_HIP_CHECK(hipMemcpyAsync(&again, flag2, 4, hipMemcpyDeviceToHost, s));
-                CCR_HIP_CHECK(hipStreamSynchronize(s));
-                prev_list = cur;
-                prev_lay = lay2;
-                prev_n = n_cur;
-                prev_pad = pad2;
-                if (again == 0) {
-                    n_cur = 0;
-                    break;
-                }
-                uint32_t *next = (cur == list_b) ? list_c : list_b;
-                rc = launch_partition_flags(flag2 + 16, 0, (int)again, next, dense_list + n_dense, counts, s);
-                if (rc != CCR_OK) return rc;
-                CCR_HIP_CHECK(hipMemcpyAsync(hc, counts, 8, hipMemcpyDeviceToHost, s));
-                CCR_HIP_CHECK(hipStreamSynchronize(s));
-                n_dense += (int)hc[1];
-                cur = next;
-                n_cur = (int)hc[0];
-                if (n_cur >= prev_n) break;   // no progress (every retried query overflowed again): the dense path takes them
-            }
-            if (n_cur > 0) {   // still flagged after the rounds of this group
-                rc = to_dense(cur, n_cur);
-                if (rc != CCR_OK) return rc;
-            }
-        }
-    }
-    // Many queries for the dense path: its 64 x 64 score tiles are a quarter full with the 16 reserved rows (2.2 instead of
-    // 0.65 ms per NQ query), and the candidate area is free by now -- score 64 (or more) queries per chunk in there.
-    int64_t chunk = p.dense_rows_per_chunk;
-    {
-        const int64_t fit = (int64_t)((p.off_flag - p.off_cand) / ((size_t)ix->n_rows * 4)) / 64 * 64;
-        if (n_dense > chunk && fit >= 64) {
-            chunk = std::min<int64_t>(fit, 256);
-            dense_scratch = (float *)cand;
-        }
-    }
-    if (n_dense > 0 && margin_path_ok(ix, k)) {
-        // MFMA score rows + margin select first (0.9 ms of GEMM per 256 queries + one row scan each, against 0.65 ms of fp64 scoring
-        // per query); only what that cannot finish -- more than 8 192 rows inside the margin, non-finite embeddings -- is left
-        size_t room = (size_t)p.dense_rows_per_chunk * ix->n_rows * 4;
-        float *scr = (float *)(ws + p.off_dense);
-        if ((size_t)(p.off_flag - p.off_cand) > room) {   // the candidate area is free by now
-            room = (size_t)(p.off_flag - p.off_cand);
-            scr = (float *)cand;
-        }
-        CCR_HIP_CHECK(hipMemsetAsync(flag2, 0, 64, s));
-        for (int lo = 0; lo < n_dense; lo += p.nq_pad) {   // Q2 holds nq_pad gathered query rows
-            const int m = std::min(p.nq_pad, n_dense - lo);
-            rc = launch_gather_queries(pd.Q, ix->dim, dense_list + lo, m, thr, delta, Q2, thr2, delta2, s);
-            if (rc != CCR_OK) return rc;
-            // (thr2: the gathered thresholds of these queries -- valid lower bounds of their k-th largest scores)
-            rc = margin_for_rows(ix, Q2, thr2, dense_list + lo, 0, m, k, scr, room, pd.out_scores, pd.out_ids, flag2, flag2 + 16, s);
-            if (rc != CCR_OK) return rc;
-        }
-        uint32_t left = 0;
-        CCR_HIP_CHECK(hipMemcpyAsync(&left, flag2, 4, hipMemcpyDeviceToHost, s));
-        CCR_HIP_CHECK(hipStreamSynchronize(s));
-        if (left > 0) {
-            rc = dense_for_list(ix, pd.Q, flag2 + 16, 0, (int)left, k, dense_scratch, chunk, pd.out_scores, pd.out_ids, s);
-            if (rc != CCR_OK) return rc;
-        }
-    } else if (n_dense > 0) {
-        rc = dense_for_list(ix, pd.Q, dense_list, 0, n_dense, k, dense_scratch, chunk, pd.out_scores, pd.out_ids, s);
-        if (rc != CCR_OK) return rc;
-    }
-    ix->stats.n_dense += n_dense;   // (n_again of them after a retry)
-    (void)n_again;
-    CCR_HIP_CHECK(hipEventRecord(ix->ev[6], s));
+    if (hc[0] > 0) rc = retry_flagged(ix, w, (int)hc[0], n_dense);
+    if (rc == CCR_OK && n_dense > 0) rc = complete_dense(ix, w, n_dense);
+    if (rc != CCR_OK) return rc;
+    ix->stats.n_dense += n_dense;
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_DONE], s));
     CCR_HIP_CHECK(hipStreamSynchronize(s));
-    CCR_HIP_CHECK(hipEventElapsedTime(&ix->stats.ms_fallback, ix->ev[5], ix->ev[6]));
+    CCR_HIP_CHECK(hipEventElapsedTime(&ix->stats.ms_fallback, ix->ev[EV_SELECT_END], ix->ev[EV_DONE]));
     ix->stats.ms_total += ix->stats.ms_fallback;
     return CCR_OK;
 }
 
 extern "C" int ccr_search_finish(ccr_index *ix) {
     CCR_REQUIRE(ix, "ccr_search_finish: null index");
-    if (!ix->pending.active) return CCR_OK;
-    return search_complete(ix);
+    return ix->pending.active ? search_complete(ix) : CCR_OK;
+}
+
+// A search on a plan without the fused path: MFMA score rows + margin select where they apply; what that cannot finish (mass
+// ties, non-finite embeddings) and every query of a forced-dense or asynchronous search take the fp64 path.
+static int search_dense(ccr_index *ix, const SearchWs &w, const uint16_t *Q, int n_q, int k, float *out_scores, int64_t *out_ids,
+                        int flags, hipStream_t s) {
+    const bool async = (flags & CCR_SEARCH_ASYNC) != 0;
+    const int64_t chunk = ix->plan.dense_rows_per_chunk;
+    int rc;
+    if (!async && !(flags & CCR_SEARCH_FORCE_DENSE) && margin_path_ok(ix, k)) {
+        CCR_HIP_CHECK(hipMemsetAsync(w.flag_count, 0, 64, s));
+        rc = margin_for_rows(ix, Q, nullptr, nullptr, n_q, k, w.dense, w.dense_bytes, out_scores, out_ids, w.flag_count, w.flag_list, s);
+        if (rc != CCR_OK) return rc;
+        uint32_t nf = 0;
+        rc = read_words(&nf, w.flag_count, 1, s);
+        if (rc != CCR_OK) return rc;
+        ix->stats.n_fallback = ix->stats.n_dense = (int32_t)nf;
+        if (nf > 0) rc = dense_for_list(ix, Q, w.flag_list, (int)nf, k, w.dense, chunk, out_scores, out_ids, s);
+    } else {
+        rc = dense_for_list(ix, Q, nullptr, n_q, k, w.dense, chunk, out_scores, out_ids, s);
+    }
+    if (rc != CCR_OK) return rc;
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_DONE], s));
+    if (async) return CCR_OK;   // nothing to complete: the dense path has no flagged queries (no timing statistics either)
+    CCR_HIP_CHECK(hipStreamSynchronize(s));
+    CCR_HIP_CHECK(hipEventElapsedTime(&ix->stats.ms_total, ix->ev[EV_BEGIN], ix->ev[EV_DONE]));
+    ix->stats.ms_fallback = ix->stats.ms_total;
+    return CCR_OK;
 }
 
 // id_out: what the result ids are (ix->offset: int64 global ids; ID_LOCAL_U32: u32 local rows of a shard message).
@@ -1041,145 +1105,63 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
         set_error("ccr_search: workspace %zu bytes (256-byte aligned) required, got %zu at %p", p.total, ws_bytes, workspace);
         return CCR_ERR_WORKSPACE;
     }
-    char *ws = (char *)workspace;
-    float *dense_scratch = (float *)(ws + p.off_dense);
+    const SearchWs w = search_ws(p, ix->n_rows, ix->dim, n_q, k, (char *)workspace);
 
     if (!ix->have_events) {   // phase-boundary events of the statistics, created on first use
-        for (int i = 0; i < 8; ++i) CCR_HIP_CHECK(hipEventCreate(&ix->ev[i]));
+        for (int i = 0; i < EV_COUNT; ++i) CCR_HIP_CHECK(hipEventCreate(&ix->ev[i]));
         ix->have_events = true;
     }
-    CCR_HIP_CHECK(hipEventRecord(ix->ev[0], s));
-    if (!p.fused) {
-        ix->stats.path = 0;
-        int rc0 = CCR_OK;
-        if (!async && !(flags & CCR_SEARCH_FORCE_DENSE) && margin_path_ok(ix, k)) {
-            // MFMA score rows + margin select; what it cannot finish (mass ties, non-finite embeddings) takes the fp64 path
-            uint32_t *fc = (uint32_t *)(ws + p.off_flag), *fl = (uint32_t *)(ws + p.off_flag + 64);
-            CCR_HIP_CHECK(hipMemsetAsync(fc, 0, 64, s));
-            rc0 = margin_for_rows(ix, Q_bf16, nullptr, nullptr, 0, n_q, k, dense_scratch, (size_t)p.dense_rows_per_chunk * (ix->n_rows + 3) * 4,
-                                  out_scores, out_ids, fc, fl, s);
-            if (rc0 != CCR_OK) return rc0;
-            uint32_t nf = 0;
-            CCR_HIP_CHECK(hipMemcpyAsync(&nf, fc, 4, hipMemcpyDeviceToHost, s));
-            CCR_HIP_CHECK(hipStreamSynchronize(s));
-            ix->stats.n_fallback = ix->stats.n_dense = (int32_t)nf;
-            if (nf > 0) rc0 = dense_for_list(ix, Q_bf16, fl, 0, (int)nf, k, dense_scratch, p.dense_rows_per_chunk, out_scores, out_ids, s);
-        } else {
-            rc0 = dense_for_list(ix, Q_bf16, nullptr, 0, n_q, k, dense_scratch, p.dense_rows_per_chunk, out_scores, out_ids, s);
-        }
-        if (rc0 != CCR_OK) return rc0;
-        CCR_HIP_CHECK(hipEventRecord(ix->ev[6], s));
-        if (async) return CCR_OK;   // nothing to complete: the dense path has no flagged queries (no timing statistics either)
-        CCR_HIP_CHECK(hipStreamSynchronize(s));
-        CCR_HIP_CHECK(hipEventElapsedTime(&ix->stats.ms_total, ix->ev[0], ix->ev[6]));
-        ix->stats.ms_fallback = ix->stats.ms_total;
-        return CCR_OK;
-    }
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_BEGIN], s));
+    if (!p.fused) return search_dense(ix, w, Q_bf16, n_q, k, out_scores, out_ids, flags, s);
 
-    float *qnorm = (float *)(ws + p.off_qnorm);
-    float *thr = (float *)(ws + p.off_thr);
-    float *delta = thr + p.nq_pad;
-    float *gmax = (float *)(ws + p.off_gmax);
-    uint32_t *cnt = (uint32_t *)(ws + p.off_cnt);
-    uint2 *cand = (uint2 *)(ws + p.off_cand);
-    uint32_t *flag_count = (uint32_t *)(ws + p.off_flag);
-    unsigned long long *stat_cand = (unsigned long long *)(ws + p.off_flag + 8);
-    uint32_t *flag_list = (uint32_t *)(ws + p.off_flag + 64);
-
-    CCR_HIP_CHECK(hipMemsetAsync(flag_count, 0, 64, s));
+    CCR_HIP_CHECK(hipMemsetAsync(w.flag_count, 0, 64, s));
     // every (range, query block) item with at least one tile writes its counters at its end, for the columns below
     // main_qblocks * tile_q (the 256 x 384 kernel leaves [main_qblocks * 384, nq_pad) unwritten: no reader goes past n_q);
     // only a plan with more ranges than tiles (forced fused searches of tiny corpora) leaves counters unwritten
-    if ((int64_t)p.ranges > p.tiles) CCR_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)p.ranges * p.nq_pad * p.sublists * 4, s));
-    int rc = launch_row_norms_bf16(Q_bf16, n_q, ix->dim, qnorm, nullptr, nullptr, s);
+    if ((int64_t)p.ranges > p.tiles) CCR_HIP_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)p.ranges * p.nq_pad * p.sublists * 4, s));
+    int rc = launch_row_norms_bf16(Q_bf16, n_q, ix->dim, w.qnorm, nullptr, nullptr, s);
     if (rc != CCR_OK) return rc;
 
-    GemmArgs g = gemm_args(ix, Q_bf16, n_q, p.nq_pad);
-    g.qgroups = p.qgroups;
-
     // sample pass -> group maxima -> thresholds
-    GemmArgs gs = g;
+    GemmArgs gs = gemm_args(ix, Q_bf16, n_q, p.nq_pad);
+    gs.qgroups = p.qgroups;
     gs.n_vt = p.sample_tiles;
     gs.tile_stride = p.sample_stride;
     gs.ranges = p.sample_ranges;
-    gs.gmax = gmax;
-    CCR_HIP_CHECK(hipEventRecord(ix->ev[1], s));
+    gs.gmax = w.gmax;
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SAMPLE_BEGIN], s));
     rc = launch_gemm(gs, MAIN_32X32, EPI_GMAX, p.grid, s);
     if (rc != CCR_OK) return rc;
-    CCR_HIP_CHECK(hipEventRecord(ix->ev[2], s));
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SAMPLE_END], s));
     // (small batches: the streaming pass's sub-list counters are cleared by the threshold launch)
-    rc = launch_threshold(gmax, (int64_t)p.sample_tiles * GROUPS_PER_TILE, n_q, p.nq_pad, p.opt_rank ? p.opt_rank : k, qnorm, ix->dmax_bits,
-                          ix->dim, ix->tile_norm, p.sample_stride, thr, delta, s, p.narrow ? cnt : nullptr, p.narrow ? NARROW_SUBLISTS : 0);
+    rc = launch_threshold(w.gmax, (int64_t)p.sample_tiles * GROUPS_PER_TILE, n_q, p.nq_pad, p.opt_rank ? p.opt_rank : k, w.qnorm, ix->dmax_bits,
+                          ix->dim, ix->tile_norm, p.sample_stride, w.thr, w.cq, s, p.narrow ? w.cnt : nullptr, p.narrow ? NARROW_SUBLISTS : 0);
     if (rc != CCR_OK) return rc;
 
-    // main pass -> candidates
-    GemmArgs gm = g;
-    gm.n_vt = p.tiles;
-    gm.tile_stride = 1;
-    gm.ranges = p.ranges;
-    gm.thr = thr;
-    gm.cnt = cnt;
-    gm.qblocks = p.main_qblocks;   // (blocks of p.tile_q queries; the sample pass above walks blocks of TILE_Q)
-    gm.qgroups = p.main_qgroups;
-    CCR_HIP_CHECK(hipEventRecord(ix->ev[3], s));
-    if (p.narrow) {
-        // small batch: the corpus is STREAMED past query rows resident in LDS (ccr_narrow.hip); two atomically filled sub-lists per query
-        // (their counters were cleared by launch_threshold)
-        NarrowArgs na;
-        memset(&na, 0, sizeof(na));
-        na.D = ix->D;
-        na.n_rows = ix->n_rows;
-        na.dim = ix->dim;
-        na.Q = Q_bf16;
-        na.n_q = n_q;
-        na.q_stride = narrow_query_stride(ix->dim);
-        na.thr = thr;
-        na.cq = delta;
-        na.tile_norm = ix->tile_norm;
-        na.cand = cand;
-        na.cnt = cnt;
-        na.cap = p.first_lay.cap[0];
-        na.groups = p.narrow_groups;
-        // one workgroup (8 waves x 12 KiB of loads in flight) per CU: measured at NQ 6.2 / 6.2 / 6.0 TB/s of corpus bytes at n_q = 1 / 16 / 64;
-        // two or four per CU -- the 16- and 32-query images would fit -- stream no faster (6.2 / 5.9 TB/s at 1 / 16)
-        int ngrid = ix->knobs.narrow_grid > 0 ? ix->knobs.narrow_grid : ix->num_cu;
-        const int64_t blocks = (ix->n_rows + 16 * NARROW_WAVES - 1) / (16 * NARROW_WAVES);
-        if ((int64_t)ngrid > blocks) ngrid = (int)std::max<int64_t>(1, blocks);
-        if (p.narrow_groups == 2) ngrid = std::max(16, ngrid / 16 * 16);   // whole sets of eight (b, b + 8) pairs; a pair shares its row stream
-        rc = launch_narrow_filter(na, p.narrow, ngrid, s);
-    } else {
-        rc = run_main_pass(ix, p, gm, cand, cnt, thr, delta, p.item_b ? (uint32_t *)(ws + p.off_top) : nullptr, n_q, k, true, s);
-    }
+    // main pass -> candidates -> select
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_MAIN_BEGIN], s));
+    rc = p.narrow ? run_narrow_pass(ix, p, w, Q_bf16, n_q, s) : run_main_pass(ix, p, w, Q_bf16, n_q, k, s);
     if (rc != CCR_OK) return rc;
-    CCR_HIP_CHECK(hipEventRecord(ix->ev[4], s));
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_MAIN_END], s));
     ix->main_pass_recorded = true;
-    rc = launch_select_rescore(cand, cnt, p.first_nsub, p.first_sp, n_q, p.nq_pad, p.first_lay, k, p.rescore_cap, p.select_compact, ix->n_rows, thr, delta,
-                               ix->tile_norm, ix->row_norm, ix->dmax_bits, Q_bf16, ix->D, ix->dim,
-                               ix->id_out, out_scores, out_ids, flag_count, flag_list, stat_cand, nullptr, s);
+    rc = launch_select_rescore(w.cand, w.cnt, p.first_nsub, p.first_sp, n_q, p.nq_pad, p.first_lay, k, p.rescore_cap, p.select_compact, ix->n_rows, w.thr,
+                               w.cq, ix->tile_norm, ix->row_norm, ix->dmax_bits, Q_bf16, ix->D, ix->dim, ix->id_out, out_scores, out_ids,
+                               w.flag_count, w.flag_list, w.stat_cand, nullptr, s);
     if (rc != CCR_OK) return rc;
-    CCR_HIP_CHECK(hipEventRecord(ix->ev[5], s));
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SELECT_END], s));
 
-    ix->pending.Q = Q_bf16;
-    ix->pending.n_q = n_q;
-    ix->pending.k = k;
-    ix->pending.out_scores = out_scores;
-    ix->pending.out_ids = out_ids;
-    ix->pending.ws = ws;
-    ix->pending.stream = s;
-    if (async) {
-        // The host does not learn the flag count here, and nothing is re-done on the stream: flagged queries (rare: a sub-list
-        // overflow, mass ties, an estimated threshold that failed its check) are completed by ccr_search_finish(), which has the
-        // retry pass and the margin path at its disposal (2-3 ms for a handful of NQ queries; an unconditional on-stream chunk of
-        // the fp64 path cost 35 ms as soon as ONE query was flagged, and two no-op launches per search when none was).
-        // the shard message's header learns the count on the stream: the exchange can be enqueued without the host knowing it
-        if (flagged_out) CCR_HIP_CHECK(hipMemcpyAsync(flagged_out, flag_count, 4, hipMemcpyDeviceToDevice, s));
-        CCR_HIP_CHECK(hipMemcpyAsync((void *)ix->host_flags, flag_count, 16, hipMemcpyDeviceToHost, s));   // pinned: stays asynchronous
-        CCR_HIP_CHECK(hipEventRecord(ix->ev[7], s));
-        ix->pending.active = true;
-        return CCR_OK;
-    }
-    ix->pending.active = false;
-    return search_complete(ix);   // (synchronous form: every flagged query has been re-done, the header's zero stands)
+    ix->pending = {false, Q_bf16, n_q, k, out_scores, out_ids, (char *)workspace, s};
+    if (!async) return search_complete(ix);   // (synchronous form: every flagged query has been re-done, the header's zero stands)
+    // The host does not learn the flag count here, and nothing is re-done on the stream: flagged queries (rare: a sub-list
+    // overflow, mass ties, an estimated threshold that failed its check) are completed by ccr_search_finish(), which has the
+    // retry pass and the margin path at its disposal (2-3 ms for a handful of NQ queries; an unconditional on-stream chunk of
+    // the fp64 path cost 35 ms as soon as ONE query was flagged, and two no-op launches per search when none was).
+    // the shard message's header learns the count on the stream: the exchange can be enqueued without the host knowing it
+    if (flagged_out) CCR_HIP_CHECK(hipMemcpyAsync(flagged_out, w.flag_count, 4, hipMemcpyDeviceToDevice, s));
+    CCR_HIP_CHECK(hipMemcpyAsync((void *)ix->host_flags, w.flag_count, 16, hipMemcpyDeviceToHost, s));   // pinned: stays asynchronous
+    CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_ASYNC_END], s));
+    ix->pending.active = true;
+    return CCR_OK;
 }
 
 extern "C" int ccr_search(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, float *out_scores, int64_t *out_ids,
@@ -1226,12 +1208,5 @@ extern "C" int ccr_scores(const ccr_index *ix, const uint16_t *Q_bf16, int n_q, 
         return launch_dense_scores(ix->D, ix->n_rows, ix->dim, Q_bf16, nullptr, 0, n_q, nullptr, out, (hipStream_t)stream);
     CCR_REQUIRE(mode == CCR_SCORES_MFMA, "ccr_scores: unknown mode %d", mode);
     CCR_REQUIRE(ix->dim % 8 == 0, "ccr_scores: CCR_SCORES_MFMA needs dim %% 8 == 0 (dim=%d)", ix->dim);
-    GemmArgs g = gemm_args(ix, Q_bf16, n_q, (int)round_up(n_q, TILE_Q));
-    g.n_vt = (ix->n_rows + TILE_DOCS - 1) / TILE_DOCS;
-    g.tile_stride = 1;
-    g.ranges = (int)round_up(std::min<int64_t>(64, g.n_vt), NUM_XCD);
-    g.qgroups = 1;
-    g.store = out;
-    const int grid = std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD);
-    return launch_gemm(g, ix->knobs.mfma16 != 0 ? MAIN_16X16 : MAIN_32X32, EPI_STORE, grid, (hipStream_t)stream);
+    return store_scores(ix, Q_bf16, n_q, (int)round_up(std::min<int64_t>(64, tiles_of(ix)), NUM_XCD), out, 0, (hipStream_t)stream);
 }

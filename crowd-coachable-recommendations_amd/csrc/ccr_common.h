@@ -105,7 +105,8 @@ struct Plan {
     int first_nsub;       // sub-lists per query the first main pass fills (ranges * sublists, or 2) ...
     int first_sp;         // ... per cell (sublists, or 2) ...
     CandLayout first_lay; // ... and where they are (cand, or one segment of narrow capacity)
-    // workspace layout (byte offsets)
+    int64_t cand_recs;    // 8-byte records of the candidate area
+    // workspace layout (byte offsets, as search_ws lays it out)
     size_t off_qnorm, off_thr, off_gmax, off_cnt, off_cand, off_flag, off_dense, off_retry, off_top, off_safe, total;
     int64_t dense_rows_per_chunk;  // queries per dense chunk
 };

@@ -27,6 +27,31 @@ constexpr int FALLBACK_ROWS = 16;   // dense score rows reserved for flagged que
 
 Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn);
 
+// Workspace layouts: take() places a buffer at the current offset and moves on to the next 256-byte boundary.
+struct Bump {
+    size_t off;
+    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) / 256 * 256; return o; }
+};
+
+// The workspace of one search, typed: search_ws() is the one description of its layout (with a null base the pointers are byte
+// offsets; the planner takes `total` from there).  A dense plan has the flag area and the dense scratch only.
+struct SearchWs {
+    float *qnorm, *thr, *cq, *gmax;     // thr, cq (margin coefficients gamma ||q||): [nq_pad] each, cq right after thr
+    uint32_t *cnt;                      // sub-list counters
+    uint2 *cand;                        // candidate area (cand_bytes): free once the select stage has run
+    uint32_t *flag_count, *flag_list;   // flag area: flag count at +0, candidate count (stat_cand) at +8, flagged queries at +64
+    unsigned long long *stat_cand;
+    uint32_t *top;                      // the k best lower bounds per query between two re-tightenings (three-phase plans)
+    float *thr_safe, *cq_safe, *dense;  // estimated thresholds: the conservative bounds of a failing search; dense scratch (dense_bytes)
+    // retry area (retry_bytes from Q2 on): compact query rows, their thresholds and margin coefficients, the retry and dense
+    // lists, two partition counts, a second flag area, and the two lists the rounds of a group alternate on
+    uint16_t *Q2;
+    float *thr2, *cq2;
+    uint32_t *retry_list, *dense_list, *counts, *flag2, *list_b, *list_c;
+    size_t cand_bytes, dense_bytes, retry_bytes, total;
+};
+SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char *base);
+
 // kernels implemented in the other translation units
 // the fused GEMM + top-k kernels: 256 x 256 tiles on the 32x32x16 MFMA (every epi) or the 16x16x32 MFMA (no EPI_GMAX), or
 // 256 x 384 tiles on the 16x16x32 MFMA (MAIN_WIDE: a.qblocks = blocks of 384 queries, EPI_FILTER and dim % 32 == 0 only)
@@ -83,6 +108,10 @@ int launch_margin_select(const float *scores, int64_t pitch, int64_t n_rows, int
                          int q_begin, int nq_chunk, int64_t id_offset, float *out_scores, int64_t *out_ids, uint32_t *flag_count, uint32_t *flag_list,
                          hipStream_t s);
 
+// Events of a search at its phase boundaries.  EV_MAIN_END: what ccr_search_stream_wait_main_pass orders against; EV_DONE: the
+// flagged queries re-done (or the dense path finished); EV_ASYNC_END: an asynchronous search's flag line copied to the host.
+enum SearchEvent { EV_BEGIN, EV_SAMPLE_BEGIN, EV_SAMPLE_END, EV_MAIN_BEGIN, EV_MAIN_END, EV_SELECT_END, EV_DONE, EV_ASYNC_END, EV_COUNT };
+
 }  // namespace ccr
 
 struct ccr_index {
@@ -98,11 +127,11 @@ struct ccr_index {
     float *row_norm_own;     // the latter (per-device block cache), else null
     size_t row_bytes;
     bool have_events;
-    bool main_pass_recorded;   // ev[4] was recorded by the last search (fused path): ccr_search_stream_wait_main_pass has something to wait for
+    bool main_pass_recorded;   // EV_MAIN_END was recorded by the last search (fused path): ccr_search_stream_wait_main_pass has something to wait for
     int num_cu;
     int device;
     ccr::Knobs knobs;
-    hipEvent_t ev[8];     // phase boundaries of the last search; ev[7]: end of an asynchronous search's stream work (flag line copied)
+    hipEvent_t ev[ccr::EV_COUNT];
     volatile uint32_t *host_flags;   // pinned host line {flag count, -, candidate count (8 B)} of the per-device slab
     ccr::Plan plan;       // plan of the last search and its key (the planner simulates item assignments: ~25 us)
     int plan_nq, plan_k, plan_flags;

@@ -336,23 +336,18 @@ static int plan_special(const ccr_index *ix, int n_q, int k, const int64_t *ptr_
     }
     const int n_long = (int)sp.long_list.size();
     sp.k_in = n_long < n_q ? k + max_short : 0;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = (off + bytes + 255) / 256 * 256;
-        return o;
-    };
     sp.search_bytes = sp.k_in ? ccr_search_workspace_bytes(ix, n_q, sp.k_in) : 0;
-    take(sp.search_bytes);
-    sp.off_ls = take((size_t)n_q * sp.k_in * 4);
-    sp.off_li = take((size_t)n_q * sp.k_in * 8);
-    sp.off_ptr = take((size_t)(n_q + 1) * 8);
-    sp.off_qlist = take((size_t)std::max(1, n_long) * 4);
-    sp.off_dense = take(n_long ? (size_t)FALLBACK_ROWS * ix->n_rows * 4 : 0);
-    sp.off_lp = take(prior ? (size_t)std::max<int64_t>(1, ptr_host[n_q]) * 4 : 0);
-    sp.off_ts = take(prior ? (size_t)n_long * k * 4 : 0);
-    sp.off_ti = take(prior ? (size_t)n_long * k * 8 : 0);
-    sp.total = off + 256;
+    Bump b = {0};
+    b.take(sp.search_bytes);
+    sp.off_ls = b.take((size_t)n_q * sp.k_in * 4);
+    sp.off_li = b.take((size_t)n_q * sp.k_in * 8);
+    sp.off_ptr = b.take((size_t)(n_q + 1) * 8);
+    sp.off_qlist = b.take((size_t)std::max(1, n_long) * 4);
+    sp.off_dense = b.take(n_long ? (size_t)FALLBACK_ROWS * ix->n_rows * 4 : 0);
+    sp.off_lp = b.take(prior ? (size_t)std::max<int64_t>(1, ptr_host[n_q]) * 4 : 0);
+    sp.off_ts = b.take(prior ? (size_t)n_long * k * 4 : 0);
+    sp.off_ti = b.take(prior ? (size_t)n_long * k * 8 : 0);
+    sp.total = b.off + 256;
     return CCR_OK;
 }
 

@@ -3,6 +3,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "ccr_index.h"
 #include "ccr_narrow.h"
 
@@ -11,6 +13,39 @@ using namespace ccr;
 static int fail(const char *what, long long n, int d, int nq, int k) {
     printf("FAIL %s at n=%lld dim=%d nq=%d k=%d\n", what, n, d, nq, k);
     return 1;
+}
+
+static size_t at(const void *p) { return (size_t)(uintptr_t)p; }   // search_ws without a base: the pointers are byte offsets
+
+// the plan's offsets are search_ws's; every buffer of the search workspace ends at or before `total`, every sub-buffer of the
+// retry area inside that area
+static int check_layout(const Plan &p, long long n, int d, int nq, int k) {
+    const SearchWs w = search_ws(p, n, d, nq, k, nullptr);
+    int bad = 0;
+    if (p.off_qnorm != at(w.qnorm) || p.off_thr != at(w.thr) || p.off_gmax != at(w.gmax) || p.off_cnt != at(w.cnt) || p.off_cand != at(w.cand) ||
+        p.off_flag != at(w.flag_count) || p.off_dense != at(w.dense) || p.off_retry != at(w.Q2) || p.off_top != at(w.top) ||
+        p.off_safe != at(w.thr_safe) || p.total != w.total)
+        bad += fail("plan offsets differ from search_ws", n, d, nq, k);
+    const size_t pad = p.nq_pad, q4 = (size_t)nq * 4;
+    struct Buf {
+        const void *p;
+        size_t bytes;
+    };
+    std::vector<Buf> bufs = {{w.flag_count, 64 + q4}, {w.dense, w.dense_bytes}};
+    if (p.fused) {
+        const Buf fused[] = {{w.qnorm, pad * 4}, {w.thr, pad * 4}, {w.cq, pad * 4}, {w.gmax, (size_t)p.sample_tiles * GROUPS_PER_TILE * pad * 4},
+                             {w.cnt, (size_t)p.ranges * pad * p.sublists * 4}, {w.cand, w.cand_bytes}, {w.cand, (size_t)p.cand_recs * 8},
+                             {w.top, p.item_b ? (pad + (size_t)nq * k) * 4 : 0}, {w.thr_safe, p.opt_rank ? pad * 4 : 0},
+                             {w.cq_safe, p.opt_rank ? pad * 4 : 0}, {w.Q2, w.retry_bytes}};
+        bufs.insert(bufs.end(), fused, fused + sizeof(fused) / sizeof(fused[0]));
+        const Buf retry[] = {{w.Q2, pad * d * 2}, {w.thr2, pad * 4}, {w.cq2, pad * 4}, {w.retry_list, q4}, {w.dense_list, q4},
+                             {w.counts, 64}, {w.flag2, 64 + q4}, {w.list_b, q4}, {w.list_c, q4}};
+        for (const Buf &b : retry)
+            if (at(b.p) < at(w.Q2) || at(b.p) + b.bytes > at(w.Q2) + w.retry_bytes) bad += fail("retry sub-buffer outside the retry area", n, d, nq, k);
+    }
+    for (const Buf &b : bufs)
+        if (at(b.p) + b.bytes > p.total) bad += fail("buffer ends past the workspace total", n, d, nq, k);
+    return bad;
 }
 
 int main() {
@@ -34,6 +69,7 @@ int main() {
                     const Plan p = make_plan(n, d, nq, k, CCR_SEARCH_DEFAULT, 256, kn);
                     ++total;
                     if (p.total == 0) bad += fail("empty workspace", n, d, nq, k);
+                    bad += check_layout(p, n, d, nq, k);
                     if (!p.fused) continue;
                     ++fused;
                     // work items of the MAIN pass: blocks of p.tile_q queries (256, or 384 with the wide tile) in p.main_qgroups groups
@@ -102,6 +138,7 @@ int main() {
                 for (int k : ks) {
                     if (k > n) continue;
                     const Plan p = make_plan(n, d, nq, k, CCR_SEARCH_DEFAULT, 256, kn);
+                    bad += check_layout(p, n, d, nq, k);
                     if (!p.fused) {
                         if (p.narrow) bad += fail("narrow without the fused path", n, d, nq, k);
                         continue;
