@@ -11,12 +11,14 @@ outputs resident in HBM:  pack corpus shard fp32->bf16, build the index (row nor
 fused MFMA score + top-k, [N > 1: RCCL all-gather of the per-shard top-k + merge].
 N > 1 row-shards the SAME corpus over the ranks (strong scaling); value = queries / step time.
 
-Extra objects on the JSON line: `roofline` for the dominant kernel (main-pass GEMM + filter; HIP
-events recorded by the library on the search stream), `cpu_baseline` (the oracle's
-reference-faithful CPU path timed on this host's cores on a bounded query sample, rank 0, N = 1) and, in the default
-N = 1 run, `secondary`: the same step at the north-star target shape (MS-MARCO scale 8,841,823 x 768, 6,980 queries,
-top-100, with its own CPU leg), at k = 1001 (what ranking() asks for) and the configs[4] in-batch-negative loss step -- short runs,
-never part of `value`.
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  Beside the headline it carries only
+what the timed steps themselves recorded: `roofline` for the dominant kernel (main-pass GEMM + filter; HIP events recorded by the
+library on the search stream), `phases_ms`, `search_stats` and, at N > 1, `exchange`; `cpu_baseline` is null.
+--full adds, untimed and after the headline: `pack_kernel` (one more corpus pack, its HBM rate), `all_queries_check`, `cpu_baseline`
+(the oracle's reference-faithful CPU path timed on this host's cores on a bounded query sample, rank 0, N = 1) and, at the default
+shape, `secondary`: at N = 1 the same step at the north-star target shape (MS-MARCO scale 8,841,823 x 768, 6,980 queries, top-100,
+with its own CPU leg), at k = 1001 (what ranking() asks for), small query batches, the configs[4] in-batch-negative loss step, the
+encoder and BM25; at N > 1 k = 1001, configs[2] and configs[3] sharded over the ranks -- short runs, never part of `value`.
 --data clustered: a non-iid corpus (1,024 Gaussian clusters, log-normal row norms, 3 % duplicate rows).
 """
 import argparse
@@ -44,7 +46,7 @@ PMC_SUMMARY = os.path.join(ROOT, "profiles", "r06_locality.json")   # tools/exp_
 DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -57,8 +59,11 @@ def parse():
                     help="gaussian: iid N(0, 1/dim) rows (BASELINE.md); clustered: 1,024 clusters, log-normal norms, 3 %% duplicates; "
                          "sorted: the same with every cluster's rows CONTIGUOUS (a corpus in topical order)")
     ap.add_argument("--sim", default="dot", choices=["dot", "cos"], help="cos: rows are L2-normalised by the pack kernel (CCREC_SIM_TYPE=cos)")
-    ap.add_argument("--cpu-queries", type=int, default=64, help="query sample of the CPU baseline (0 = skip)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the MS-MARCO-scale and k = 1001 side runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check what it does not need: the pack kernel's HBM rate, every query against "
+                         "an independent sweep, the CPU baseline and the side runs (a plain run does none of them)")
+    ap.add_argument("--cpu-queries", type=int, default=64, help="--full: query sample of the CPU baseline (0 = skip)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the MS-MARCO-scale and k = 1001 side runs")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (single-GPU rehearsal of N > 1)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--dump-ids", default=None, help="rank 0 saves the final [queries, k] id tensor here (tests)")
@@ -66,10 +71,12 @@ def parse():
                     help="rank 0 writes what the last timed step returned (scores.npy float32, ids.npy float64) under DIR, "
                          f"at most {DUMP_LIMIT_BYTES >> 20} MB in all (a seeded sample of query rows beyond that, named by rows.npy)")
     ap.add_argument("--rehearse-secondary", type=int, default=0, metavar="D",
-                    help="tests: run the N > 1 side runs on a custom shape too, the configs[2] one on 1/D of its rows and queries")
-    args = ap.parse_args()
+                    help="tests: run the N > 1 side runs on a custom shape too, the configs[2] one on 1/D of its rows and queries (implies --full)")
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.rehearse_secondary > 0:
+        args.full = True        # it asks for side runs, which only --full runs
     return args
 
 
@@ -684,83 +691,23 @@ def exchange_obj(w, r):
             "host_wait_for_exchange_ms_max": round(r["exchange_wait_ms_max"], 3)}
 
 
-def launch_ranks(n):
-    """`python bench.py --gpus N` without a launcher: start the N ranks as a CHILD `python -m torch.distributed.run` (one
-    process per GPU, RCCL rendezvous on 127.0.0.1), relay rank 0's JSON line and the ranks' stderr, return the child's exit
-    code.  Called before this process has made any GPU call (importing torch makes none), and the child is a child process,
-    not an exec."""
-    import socket
-    import subprocess
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    log("launching", " ".join(cmd))
-    proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, env=env)
-    for line in proc.stdout:   # rank 0 prints ONE JSON line; anything else on stdout goes to stderr
-        if line.startswith("{"):
-            sys.stdout.write(line)
-            sys.stdout.flush()
-        else:
-            sys.stderr.write(line)
-    return proc.wait()
+# HBM traffic of the dominant kernel cannot be read from inside the process (it needs rocprofv3 --pmc passes): the line
+# carries the offline PMC measurement of the same workload committed under profiles/, labelled as such
+def offline_traffic(tag):
+    """(bytes per step, label) of the main pass from the committed PMC measurement of the same workload, or (None, None)."""
+    try:
+        rec = json.load(open(PMC_SUMMARY))[tag]
+        return rec["traffic_bytes"], (f"offline rocprofv3 --pmc passes of this workload (profiles/r06_locality.json[{tag}]: FETCH_SIZE x 2 + "
+                                      f"WRITE_SIZE of the main-pass launches of one step); not measured in this run")
+    except Exception:
+        return None, None
 
 
-def install_watchdog():
-    """Tests (CCR_BENCH_WATCHDOG = seconds): a rank that is still running then dumps every thread's Python stack and exits;
-    SIGUSR1 dumps the stacks at any time (the parent test sends it before it kills a child that overran its time limit).
-    CCR_BENCH_WATCHDOG_DIR: the dumps go to <dir>/stacks.rank<R>.txt instead of stderr, so they survive a killed pipe."""
-    secs = int(os.environ.get("CCR_BENCH_WATCHDOG", "0"))
-    if secs <= 0:
-        return
-    import faulthandler
-    import signal
-    out = sys.stderr
-    d = os.environ.get("CCR_BENCH_WATCHDOG_DIR")
-    if d:
-        out = open(os.path.join(d, f"stacks.rank{os.environ.get('RANK', '0')}.txt"), "w")
-    faulthandler.enable(file=out, all_threads=True)
-    faulthandler.register(signal.SIGUSR1, file=out, all_threads=True)
-    faulthandler.dump_traceback_later(secs, exit=True, file=out)
-
-
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(launch_ranks(args.gpus))   # plain `python bench.py --gpus N`: this process never touches a GPU
-    install_watchdog()
-    rank = int(os.environ.get("RANK", 0))
-    world = int(os.environ.get("WORLD_SIZE", 1))
-    local = int(os.environ.get("LOCAL_RANK", 0))
-    if world != args.gpus:
-        log(f"--gpus {args.gpus} but WORLD_SIZE={world}: start it as `python bench.py --gpus {args.gpus}` (it launches its own ranks) "
-            f"or through `python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus}`")
-        sys.exit(2)
-    if args.same_device:
-        local = 0
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    if world > 1:
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        if args.dist_backend == "nccl":
-            dist.init_process_group("nccl", device_id=dev)
-        else:
-            dist.init_process_group(args.dist_backend)
-
+def full_extras(args, w, out, dev, rank, world, default_shape):
+    """--full, after the headline and untimed: the pack kernel's HBM rate, every query of the last timed step against an independent sweep,
+    the CPU baseline and the side runs, recorded into `out` (rank 0's line)."""
     from ccrec_amd import ops
-
-    w = Workload(args.rows, args.queries, args.dim, args.k, args.data, dev, rank, world, args.dist_backend, normalize=args.sim == "cos")
-    log(f"rank {rank}: inputs resident, rows [{w.lo},{w.hi}), data={args.data}")
-    r = w.run(args.steps, args.warmup, "main")
-    st = r["stats"]
-    if args.dump_outputs and rank == 0:     # the last timed step's lists (merged over the ranks at N > 1), before any untimed extra runs
-        names = dump_outputs(args.dump_outputs, {"scores": w.scores.cpu().numpy(), "ids": w.ids.cpu().numpy()})
-        log(f"outputs of the last timed step: {', '.join(names)} under {args.dump_outputs}")
-
-    # untimed extras: pack-kernel HBM rate
+    # the pack kernel's HBM rate: one more corpus pack (the same bits again, every step has completed)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     ops.pack_bf16(w.corpus_f32, out=w.slots[0]["shard"], norm_bounds=w.slots[0]["bounds"], normalize=w.normalize)
@@ -768,50 +715,8 @@ def main():
     torch.cuda.synchronize()
     pack_ms = e0.elapsed_time(e1)
     pack_gbs = (w.hi - w.lo) * args.dim * 6 / (pack_ms * 1e-3) / 1e9
-
-    default_shape = (args.rows, args.queries, args.dim, args.k, args.data, args.sim) == (N_ROWS, N_Q, DIM, TOP_K, "gaussian", "dot")
-    # HBM traffic of the dominant kernel cannot be read from inside the process (it needs rocprofv3 --pmc passes): the
-    # figure below is the offline PMC measurement of THIS command committed under profiles/, labelled as such
-    def offline_traffic(tag):
-        """(bytes per step, label) of the main pass from the committed PMC measurement of the same workload, or (None, None)."""
-        try:
-            rec = json.load(open(PMC_SUMMARY))[tag]
-            return rec["traffic_bytes"], (f"offline rocprofv3 --pmc passes of this workload (profiles/r06_locality.json[{tag}]: FETCH_SIZE x 2 + "
-                                          f"WRITE_SIZE of the main-pass launches of one step); not measured in this run")
-        except Exception:
-            return None, None
-
-    traffic, traffic_source = offline_traffic("nq_default") if (default_shape and world == 1) else (None, None)
-
-    workload = ("configs[1]: NQ corpus top-100, corpus row-sharded over n_gpus" if default_shape else
-                f"custom shape (not the headline config): {args.rows:,} x {args.dim} corpus ({args.data}, {args.sim}), {args.queries:,} queries, "
-                f"top-{args.k}, corpus row-sharded over n_gpus")
-    out = {
-        "metric": ("queries/sec, exhaustive inner-product top-100 retrieval (NQ-shaped 2,681,468 x 768 bf16 corpus)" if default_shape
-                   else f"queries/sec, exhaustive inner-product top-{args.k} retrieval ({args.rows:,} x {args.dim} bf16 corpus)"),
-        "value": round(r["qps"], 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(r["ms_per_step"], 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "bf16", "data": {"gaussian": "synthetic", "clustered": "synthetic (clustered, log-normal norms, 3% duplicates)",
-                                   "sorted": "synthetic (clustered in topical row order, log-normal norms, 3% duplicates)",
-                                   "outlier": "synthetic (gaussian, every 500,000th corpus row scaled by CCR_BENCH_OUTLIER)"}[args.data],
-        "config": {"workload": workload, "corpus_rows": args.rows,
-                   "dim": args.dim, "queries": args.queries, "k": args.k,
-                   "step": "pack corpus shard fp32->bf16 + index build + pack queries + fused MFMA score/top-k (asynchronous: the host enqueues "
-                           "step i + 1 before it completes step i; the corpus pack of step i + 1 runs on a side stream from the end of step i's main "
-                           "pass, beside its select stage)"
-                           + (" + RCCL all-gather of the packed shard message + merge (the exchange of step i overlaps the pack and search of step i + 1)" if world > 1 else ""),
-                   "parallelism": f"row-shard x{world}"},
-        "roofline": roofline_obj(r, traffic, traffic_source),
-        "phases_ms": dict(phases_obj(st), corpus_pack=round(pack_ms, 3)),
-        "pack_kernel": {"bound": "hbm", "achieved": round(pack_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(pack_gbs / HBM_PEAK_GBS, 4)},
-        "search_stats": dict({k_: st[k_] for k_ in ("path", "n_fallback", "sample_tiles", "ranges", "sublists", "cap", "n_candidates", "opt_rank", "n_retried", "n_dense", "main_tile_queries")},
-                             candidates_per_query=round(st["n_candidates"] / max(1, args.queries), 1), n_fallback_max=r["n_fallback_max"]),
-    }
-    if world > 1:
-        out["exchange"] = exchange_obj(w, r)
-    if args.dump_ids and rank == 0:
-        torch.save(w.ids.cpu(), args.dump_ids)
+    out["phases_ms"]["corpus_pack"] = round(pack_ms, 3)
+    out["pack_kernel"] = {"bound": "hbm", "achieved": round(pack_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(pack_gbs / HBM_PEAK_GBS, 4)}
     if rank == 0 and world == 1:
         try:     # every query of the last timed step against an independent sweep (beside the CPU leg's bounded sample)
             out["all_queries_check"] = completeness_all_queries(w.shard, w.qpack, w.scores)
@@ -819,10 +724,8 @@ def main():
             out["all_queries_check"] = {"skipped": f"{type(e).__name__}: {e}"}
     if rank == 0 and world == 1 and args.cpu_queries > 0:
         out["cpu_baseline"] = cpu_baseline(w.shard, w.qpack, min(args.cpu_queries, args.queries), args.k, w.ids)
-    elif rank == 0:
-        out["cpu_baseline"] = None
 
-    # ---- side runs of the default invocation (short; never part of `value`)
+    # ---- side runs of the default shape (short; never part of `value`)
     if world == 1 and default_shape and not args.no_secondary:
         sec = {}
         side_steps, side_warm = min(args.steps, 5), min(args.warmup, 2)
@@ -896,6 +799,116 @@ def main():
                               "exchange": exchange_obj(c, r4)}
             c.release()
         out["secondary"] = sec
+
+
+def launch_ranks(n):
+    """`python bench.py --gpus N` without a launcher: start the N ranks as a CHILD `python -m torch.distributed.run` (one
+    process per GPU, RCCL rendezvous on 127.0.0.1), relay rank 0's JSON line and the ranks' stderr, return the child's exit
+    code.  Called before this process has made any GPU call (importing torch makes none), and the child is a child process,
+    not an exec."""
+    import socket
+    import subprocess
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    log("launching", " ".join(cmd))
+    proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, env=env)
+    for line in proc.stdout:   # rank 0 prints ONE JSON line; anything else on stdout goes to stderr
+        if line.startswith("{"):
+            sys.stdout.write(line)
+            sys.stdout.flush()
+        else:
+            sys.stderr.write(line)
+    return proc.wait()
+
+
+def install_watchdog():
+    """Tests (CCR_BENCH_WATCHDOG = seconds): a rank that is still running then dumps every thread's Python stack and exits;
+    SIGUSR1 dumps the stacks at any time (the parent test sends it before it kills a child that overran its time limit).
+    CCR_BENCH_WATCHDOG_DIR: the dumps go to <dir>/stacks.rank<R>.txt instead of stderr, so they survive a killed pipe."""
+    secs = int(os.environ.get("CCR_BENCH_WATCHDOG", "0"))
+    if secs <= 0:
+        return
+    import faulthandler
+    import signal
+    out = sys.stderr
+    d = os.environ.get("CCR_BENCH_WATCHDOG_DIR")
+    if d:
+        out = open(os.path.join(d, f"stacks.rank{os.environ.get('RANK', '0')}.txt"), "w")
+    faulthandler.enable(file=out, all_threads=True)
+    faulthandler.register(signal.SIGUSR1, file=out, all_threads=True)
+    faulthandler.dump_traceback_later(secs, exit=True, file=out)
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(launch_ranks(args.gpus))   # plain `python bench.py --gpus N`: this process never touches a GPU
+    install_watchdog()
+    rank = int(os.environ.get("RANK", 0))
+    world = int(os.environ.get("WORLD_SIZE", 1))
+    local = int(os.environ.get("LOCAL_RANK", 0))
+    if world != args.gpus:
+        log(f"--gpus {args.gpus} but WORLD_SIZE={world}: start it as `python bench.py --gpus {args.gpus}` (it launches its own ranks) "
+            f"or through `python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus}`")
+        sys.exit(2)
+    if args.same_device:
+        local = 0
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    if world > 1:
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        if args.dist_backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev)
+        else:
+            dist.init_process_group(args.dist_backend)
+
+    w = Workload(args.rows, args.queries, args.dim, args.k, args.data, dev, rank, world, args.dist_backend, normalize=args.sim == "cos")
+    log(f"rank {rank}: inputs resident, rows [{w.lo},{w.hi}), data={args.data}")
+    r = w.run(args.steps, args.warmup, "main")
+    st = r["stats"]
+    if args.dump_outputs and rank == 0:     # the last timed step's lists (merged over the ranks at N > 1), before any untimed extra runs
+        names = dump_outputs(args.dump_outputs, {"scores": w.scores.cpu().numpy(), "ids": w.ids.cpu().numpy()})
+        log(f"outputs of the last timed step: {', '.join(names)} under {args.dump_outputs}")
+
+    default_shape = (args.rows, args.queries, args.dim, args.k, args.data, args.sim) == (N_ROWS, N_Q, DIM, TOP_K, "gaussian", "dot")
+    traffic, traffic_source = offline_traffic("nq_default") if (default_shape and world == 1) else (None, None)
+
+    workload = ("configs[1]: NQ corpus top-100, corpus row-sharded over n_gpus" if default_shape else
+                f"custom shape (not the headline config): {args.rows:,} x {args.dim} corpus ({args.data}, {args.sim}), {args.queries:,} queries, "
+                f"top-{args.k}, corpus row-sharded over n_gpus")
+    out = {
+        "metric": ("queries/sec, exhaustive inner-product top-100 retrieval (NQ-shaped 2,681,468 x 768 bf16 corpus)" if default_shape
+                   else f"queries/sec, exhaustive inner-product top-{args.k} retrieval ({args.rows:,} x {args.dim} bf16 corpus)"),
+        "value": round(r["qps"], 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(r["ms_per_step"], 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "bf16", "data": {"gaussian": "synthetic", "clustered": "synthetic (clustered, log-normal norms, 3% duplicates)",
+                                   "sorted": "synthetic (clustered in topical row order, log-normal norms, 3% duplicates)",
+                                   "outlier": "synthetic (gaussian, every 500,000th corpus row scaled by CCR_BENCH_OUTLIER)"}[args.data],
+        "config": {"workload": workload, "corpus_rows": args.rows,
+                   "dim": args.dim, "queries": args.queries, "k": args.k,
+                   "step": "pack corpus shard fp32->bf16 + index build + pack queries + fused MFMA score/top-k (asynchronous: the host enqueues "
+                           "step i + 1 before it completes step i; the corpus pack of step i + 1 runs on a side stream from the end of step i's main "
+                           "pass, beside its select stage)"
+                           + (" + RCCL all-gather of the packed shard message + merge (the exchange of step i overlaps the pack and search of step i + 1)" if world > 1 else ""),
+                   "parallelism": f"row-shard x{world}"},
+        "roofline": roofline_obj(r, traffic, traffic_source),
+        "phases_ms": phases_obj(st),
+        "search_stats": dict({k_: st[k_] for k_ in ("path", "n_fallback", "sample_tiles", "ranges", "sublists", "cap", "n_candidates", "opt_rank", "n_retried", "n_dense", "main_tile_queries")},
+                             candidates_per_query=round(st["n_candidates"] / max(1, args.queries), 1), n_fallback_max=r["n_fallback_max"]),
+    }
+    if world > 1:
+        out["exchange"] = exchange_obj(w, r)
+    if args.dump_ids and rank == 0:
+        torch.save(w.ids.cpu(), args.dump_ids)
+    if rank == 0:
+        out["cpu_baseline"] = None     # --full measures it
+    if args.full:
+        full_extras(args, w, out, dev, rank, world, default_shape)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -615,8 +615,8 @@ def test_bench_step_loop_rehearsal_world8_gloo(tmp_path, data):
 
 
 def test_committed_bench_line_has_the_contract_fields():
-    """The NEWEST default bench line committed under profiles/ (a real MI355X run of `python bench.py`: profiles/rNN_bench<i>.json)
-    carries every field the driver reads."""
+    """The NEWEST default bench line committed under profiles/ (a real MI355X run of `python bench.py` when it measured everything that
+    `--full` measures now: profiles/rNN_bench<i>.json) carries every field the driver reads."""
     import glob
     import json
     import re
@@ -661,6 +661,14 @@ def test_bench_dump_outputs_keeps_values_exact_and_samples_past_the_limit(tmp_pa
         assert np.array_equal(np.load(files[2]), sc[r]) and np.array_equal(np.load(files[0]).astype(np.int64), ids[r])
         picked.append(rows)
     assert np.array_equal(picked[0], picked[1])
+
+
+def test_bench_full_is_off_by_default_and_side_run_rehearsals_imply_it():
+    """bench.py's extra measurements and checks run only with --full; --rehearse-secondary, which only sizes side runs, turns it on."""
+    import bench
+    assert bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    assert bench.parse(["--full"]).full is True
+    assert bench.parse(["--rehearse-secondary", "40"]).full is True
 
 
 

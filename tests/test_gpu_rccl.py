@@ -163,9 +163,38 @@ def test_bench_dump_outputs_are_the_last_timed_steps_lists(tmp_path):
     assert np.array_equal(s.cpu().numpy().view(np.uint32), dumps["a"][0])
 
 
+def test_bench_plain_run_records_the_headline_and_full_adds_the_extras(tmp_path):
+    """A plain bench.py run times its steps and prints the headline with what those steps recorded (roofline, phases, search stats)
+    and nothing it would have to measure or check on its own; --full adds the pack kernel's rate, the all-queries sweep and the CPU
+    baseline, computed on the same lists (both runs dump the same bits)."""
+    bench = os.path.join(ROOT, "bench.py")
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--rows", "200000", "--queries", "300"]
+    env = dict(os.environ, CCR_BENCH_WATCHDOG="150")
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    recs = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--cpu-queries", "8"])):
+        out, _ = _run_child([sys.executable, bench] + common + extra + ["--dump-outputs", str(tmp_path / tag)], env, tmp_path, tag)
+        lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out[-2000:]
+        recs[tag] = json.loads(lines[0])
+    plain, full = recs["plain"], recs["full"]
+    headline = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                "data", "config", "roofline", "phases_ms", "search_stats", "cpu_baseline"}
+    assert set(plain) == headline and plain["cpu_baseline"] is None and "corpus_pack" not in plain["phases_ms"]
+    assert plain["value"] > 0 and plain["steps"] == 2 and plain["warmup"] == 1 and plain["roofline"]["bound"] == "mfma"
+    assert set(full) == headline | {"pack_kernel", "all_queries_check"}
+    assert full["metric"] == plain["metric"] and full["config"] == plain["config"] and full["phases_ms"]["corpus_pack"] > 0
+    assert full["pack_kernel"]["achieved"] > 0 and full["all_queries_check"]["queries_checked"] == 300
+    assert full["all_queries_check"]["queries_with_a_missing_row_above_the_cut"] == 0
+    assert full["cpu_baseline"]["kind"] == "port" and full["cpu_baseline"]["recall_at_k_of_gpu_vs_cpu"] >= 0.99
+    for name in ("scores.npy", "ids.npy"):
+        assert np.array_equal(np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)), name
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_ranks_rehearsal_records_the_multi_gpu_side_runs(tmp_path, world):
-    """One N > 1 invocation also measures the shapes the multi-GPU target is quoted on -- ranking()'s k = 1001 on the same corpus (the
+    """One N > 1 invocation with --full also measures the shapes the multi-GPU target is quoted on -- ranking()'s k = 1001 on the same corpus (the
     short-list exchange), configs[2] and configs[3] (here 1/40 of their rows and queries; configs[3] runs from 4 ranks up outside a
     rehearsal) -- each with its own `exchange` record: entries per query
     and rank, message bytes, repeats, per-rank min / max step, and the host-observed wait for the collective split from the search time."""
@@ -174,7 +203,7 @@ def test_bench_ranks_rehearsal_records_the_multi_gpu_side_runs(tmp_path, world):
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     cmd = [sys.executable, bench, "--gpus", str(world), "--dist-backend", "gloo", "--same-device", "--steps", "2", "--warmup", "1", "--rows", "150000",
-           "--queries", "200", "--cpu-queries", "0", "--rehearse-secondary", "40"]
+           "--queries", "200", "--cpu-queries", "0", "--full", "--rehearse-secondary", "40"]
     out, err = _run_child(cmd, env, tmp_path, "ranks")
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out[-2000:]

@@ -1,11 +1,14 @@
 #!/bin/bash
-# the round's closing run on the GPU box: the whole -m gpu suite, smoke(), the default bench line.  bash tools/final_check.sh
-mkdir -p gpurun_out/final
-timeout -k 10 1100 python -m pytest tests -x -q -m gpu > gpurun_out/final/tests.log 2>&1; tail -3 gpurun_out/final/tests.log
-timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout -k 10 400 python bench.py > gpurun_out/final/bench.json 2> gpurun_out/final/bench.err; tail -2 gpurun_out/final/bench.err | cut -c1-200; python - <<'PY'
-import json
-r=json.load(open('gpurun_out/final/bench.json'))
+# a closing run on a GPU box: the whole -m gpu suite, smoke(), the full bench line.  bash tools/final_check.sh OUT_DIR
+OUT=${1:?usage: bash tools/final_check.sh OUT_DIR}
+mkdir -p "$OUT"
+# each GPU step must succeed before the next one starts
+timeout -k 10 1100 python -m pytest tests -x -q -m gpu > "$OUT/tests.log" 2>&1; rc=$?; tail -3 "$OUT/tests.log"; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; rc=$?; tail -1 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?; tail -2 "$OUT/bench.err" | cut -c1-200; [ $rc -eq 0 ] || exit $rc
+python - "$OUT/bench.json" <<'PY'
+import json, sys
+r=json.load(open(sys.argv[1]))
 print(r['value'], r['ms_per_step'], r['roofline']['frac'], r['roofline']['traffic'])
 s=r['secondary']
 for k,v in s['small_batches']['batches'].items(): print('nq',k,v['ms_per_search'],v['phases_ms']['search_total'],v['roofline']['achieved'])
