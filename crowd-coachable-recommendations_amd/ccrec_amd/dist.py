@@ -421,3 +421,100 @@ def sharded_search(index, queries_bf16, k, group=None, merge_fn=None, search_fn=
     message.fill(scores, ids, lo, index.n_rows)
     return ShardExchange(message, index, group, merge_fn, k_out=k, queries=queries_bf16, search_fn=search_fn,
                          short_merge_fn=short_merge_fn).submit().result()
+
+
+# ---------------------------------------------------------------------------------------------- training: the loss over every rank's candidates
+def _collective_device(group, like):
+    """Where a collective's tensors live: a cuda device when the backend string contains "nccl" (RCCL moves device memory; the
+    string may name several backends, "cpu:gloo,cuda:nccl"), the host otherwise (gloo)."""
+    if "nccl" in str(dist.get_backend(group)):
+        return like.device if like.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return torch.device("cpu")
+
+
+def _device_pool_ce(q, pool, labels, weights, inv_temperature):
+    """The local_fn of gathered_pool_ce on the GPU: ccr_pool_ce_fwd now, ccr_pool_ce_bwd_dev when the graph runs backward."""
+    out3, state = ops.pool_ce_forward(q, pool, labels, inv_temperature, weights)
+    return out3[1], out3[2], lambda grad_out, W: ops.pool_ce_backward(state, grad_out, W)
+
+
+class _GatheredPoolCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, c, labels, weights, inv_temperature, group, local_fn):
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+        cdev = _collective_device(group, q)
+        # every rank sees every rank's shapes before any payload moves: all raise together, or none does.  The rank-local checks
+        # (2-d operands, one width, one label and one weight per query) travel in the same row as a flag, so a rank that fails
+        # one of them does not leave the others waiting in the next collective.
+        n_q, dim = (int(q.shape[0]), int(q.shape[1])) if q.dim() == 2 else (-1, -1)
+        n_c, dim_c = (int(c.shape[0]), int(c.shape[1])) if c.dim() == 2 else (-1, -1)
+        local_ok = (n_q >= 1 and n_c >= 1 and dim >= 1 and dim == dim_c and labels.dim() == 1 and labels.numel() == n_q
+                    and (weights is None or (weights.dim() == 1 and weights.numel() == n_q)))
+        mine = torch.tensor([n_q, n_c, dim, dim_c, int(weights is not None), int(local_ok)], dtype=torch.int64, device=cdev)
+        table = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(table, mine, group=group)
+        table = torch.stack(table).cpu().tolist()
+        if any(row != table[0] for row in table) or not all(row[5] for row in table):
+            raise ValueError(f"gathered_pool_ce needs the same shapes on every rank: q [n_q, dim], c [n_c, dim], one label (and weight) "
+                             f"per query; per rank [n_q, n_c, dim of q, dim of c, has weights, locally consistent] = {table}")
+        # the wire carries 2 bytes per element: this rank's candidates rounded to bf16 (torch's .to(bfloat16) bits either way)
+        if c.is_cuda and dim % 8 == 0:
+            c16 = ops.pack_bf16(c.detach())
+        else:
+            c16 = c.detach().to(torch.bfloat16).contiguous()
+        wire = c16.view(torch.uint8).to(cdev)   # (bytes: gloo moves no 16-bit integers)
+        parts = [torch.empty_like(wire) for _ in range(world)]
+        dist.all_gather(parts, wire, group=group)
+        pool = torch.cat(parts).to(q.device).view(torch.bfloat16)
+        shifted = labels.detach().to(q.device) + rank * n_c
+        w = weights.detach().to(q.device) if weights is not None else None
+        num, den, backward = local_fn(q.detach(), pool, shifted, w, float(inv_temperature))
+        sums = torch.stack([num.detach().double().reshape(()), den.detach().double().reshape(())]).to(cdev)
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+        sums = sums.to(device=q.device, dtype=num.dtype)
+        # a label outside the pool on ANY rank makes the global numerator NaN; num - num (0, or NaN) carries that into the divisor
+        # every rank's backward uses, so every rank's dq and dc are NaN too, as ops.pool_ce promises -- on the device, no read-back
+        den = (sums[1:2] + (sums[0:1] - sums[0:1])).contiguous()
+        ctx.local_backward, ctx.den, ctx.group, ctx.cdev = backward, den, group, cdev
+        ctx.rows, ctx.dtypes, ctx.c_device = (rank * n_c, (rank + 1) * n_c), (q.dtype, c.dtype), c.device
+        return sums[0] / sums[1]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dq, dpool = ctx.local_backward(grad_out, ctx.den)
+        # every rank's queries pull on every rank's candidates: sum the pool gradients, keep the rows this rank owns
+        total = dpool.contiguous().to(ctx.cdev)
+        dist.all_reduce(total, op=dist.ReduceOp.SUM, group=ctx.group)
+        lo, hi = ctx.rows
+        tq, tc = ctx.dtypes
+        return dq.to(tq), total[lo:hi].to(device=ctx.c_device, dtype=tc), None, None, None, None, None
+
+
+def gathered_pool_ce(q, c, labels, inv_temperature, weights=None, group=None, local_fn=None):
+    """ops.pool_ce with the candidates of EVERY rank as the pool (one process per GPU, a per-rank batch of queries q [n_q, dim],
+    candidates c [n_c, dim] and labels [n_q] that index this rank's own candidates; the same shapes on every rank, or every rank
+    raises ValueError before any payload moves).
+
+    forward: the local candidates are rounded to bf16 and all-gathered (2 bytes per element on the wire), the labels shifted by
+    the rank's offset in the pool, the local queries scored against the whole pool, and numerator and denominator all-reduced:
+    every rank returns the same GLOBAL sum_i w_i ce_i / sum_i w_i over all ranks' queries.
+    backward: the exact gradient of that global loss -- with respect to this rank's q from the local kernel (scaled by the
+    global denominator), and with respect to this rank's c from every rank's queries: the pool gradients of all ranks are
+    summed (all-reduce) and each rank keeps its own rows.
+
+    Under a DistributedDataParallel wrapper: the wrapper AVERAGES parameter gradients over the ranks.  Every rank here already
+    backpropagates its share of the gradient of the one global loss, so the average is 1 / world of the true gradient:
+    multiply the loss by the world size (loss * dist.get_world_size()) before backward() when the encoder is wrapped in DDP.
+
+    A label outside the pool on any rank gives a NaN loss and NaN gradients on every rank.  An exception that local_fn raises on
+    one rank only is not covered: it must fail on all ranks or on none.
+
+    Collective tensors live on the device when the backend string contains "nccl", on the host otherwise.
+    local_fn(q, pool_bf16, labels, weights, inv_temperature) -> (numerator, denominator, backward), with
+    backward(grad_out, W) -> (dq, dpool) = grad_out / W times the gradient of the numerator, replaces the device loss
+    (default: the HIP kernels; it is called inside an autograd node, with recording off), so the protocol can be rehearsed over gloo on a machine without a GPU."""
+    if local_fn is None:
+        local_fn = _device_pool_ce
+    if not (dist.is_available() and dist.is_initialized()):
+        raise RuntimeError("gathered_pool_ce needs an initialised process group (a single process uses ops.pool_ce)")
+    return _GatheredPoolCE.apply(q, c, labels, weights, inv_temperature, group, local_fn)

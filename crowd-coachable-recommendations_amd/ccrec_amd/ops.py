@@ -642,3 +642,99 @@ class _InBatchCE(torch.autograd.Function):
 
 def inbatch_ce(q, p, n, inv_temperature):
     return _InBatchCE.apply(q, p, n, inv_temperature)
+
+
+def pool_ce_forward(q, c, labels, inv_temperature, weights=None):
+    """The forward half of pool_ce without autograd (dist.gathered_pool_ce builds its own graph node on it):
+    -> (out3, state).  out3 = [loss, numerator sum w ce, denominator sum w] fp32 on the device; state goes to pool_ce_backward.
+    ONE allocation holds the packed bf16 operands, the library's workspace (the scaled logits stay there for the backward) and lse.
+    fp32 contiguous operands of a width that is a multiple of 8 are rounded by the library in the same call (torch's
+    .to(bfloat16) bits); anything else (other dtypes, strides, widths zero-padded to a multiple of 8 as pack_bf16 does) goes
+    through torch copies into the packed block first."""
+    lib = require_gpu()
+    assert q.is_cuda and q.dim() == 2 and c.dim() == 2 and q.shape[1] == c.shape[1] and c.device == q.device, "q [n_q, dim], c [n_c, dim] on one device"
+    n_q, dim = q.shape
+    n_c = c.shape[0]
+    assert n_q >= 1 and n_c >= 1 and dim >= 1, "pool_ce needs at least one query, one candidate and one column"
+    dev = q.device
+    labels = labels.detach().to(device=dev, dtype=torch.int32).contiguous()
+    assert labels.shape == (n_q,), "one label per query"
+    if weights is not None:
+        weights = weights.detach().to(device=dev, dtype=torch.float32).contiguous()
+        assert weights.shape == (n_q,), "one weight per query"
+    pdim = padded_dim(dim)
+    ws_bytes = int(lib.ccr_pool_ce_workspace_bytes(n_q, n_c, pdim))   # (host arithmetic only)
+    if ws_bytes == 0:
+        raise _lib.CcrError("ccr_pool_ce_workspace_bytes: " + lib.ccr_last_error().decode("utf-8", "replace"))
+    head = ((n_q + n_c) * pdim * 2 + 255) // 256 * 256
+    total = head + (ws_bytes + 255) // 256 * 256 + n_q * 4
+    buf = torch.empty(total, dtype=torch.uint8, device=dev)
+    out3 = torch.empty(3, dtype=torch.float32, device=dev)
+    base = buf.data_ptr()
+    lse_ptr = base + total - n_q * 4
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    fast = (q.dtype == c.dtype == torch.float32 and q.is_contiguous() and c.is_contiguous() and pdim == dim
+            and (q.data_ptr() | c.data_ptr()) % 16 == 0)
+    wp = weights.data_ptr() if weights is not None else None
+    with _on(q):
+        if fast:
+            _lib.check(lib.ccr_pool_ce_fwd_f32(q.data_ptr(), c.data_ptr(), labels.data_ptr(), wp, n_q, n_c, dim, float(inv_temperature), base,
+                                               out3.data_ptr(), lse_ptr, base + head, ws_bytes, stream), "ccr_pool_ce_fwd_f32")
+        else:
+            packed = buf[:(n_q + n_c) * pdim * 2].view(torch.bfloat16).view(n_q + n_c, pdim)
+            if pdim != dim:
+                packed[:, dim:].zero_()
+            packed[:n_q, :dim].copy_(q.detach())
+            packed[n_q:, :dim].copy_(c.detach())
+            _lib.check(lib.ccr_pool_ce_fwd(base, base + n_q * pdim * 2, labels.data_ptr(), wp, n_q, n_c, pdim, float(inv_temperature),
+                                           out3.data_ptr(), lse_ptr, base + head, ws_bytes, stream), "ccr_pool_ce_fwd")
+    return out3, (buf, labels, weights, (n_q, n_c, dim, pdim, head, ws_bytes, total, float(inv_temperature)))
+
+
+def pool_ce_backward(state, grad_out, W=None):
+    """-> (dq [n_q, dim], dc [n_c, dim]) fp32: grad_out times the gradient of numerator / W.  W: None = the forward's own
+    denominator, or a 1-element fp32 device tensor (the denominator summed over all ranks).  One allocation, one library call;
+    grad_out and W are read on the device."""
+    lib = require_gpu()
+    buf, labels, weights, (n_q, n_c, dim, pdim, head, ws_bytes, total, inv_t) = state
+    dev = buf.device
+    grads = torch.empty(n_q + n_c, pdim, dtype=torch.float32, device=dev)
+    g = grad_out
+    if g.dtype != torch.float32 or g.device != dev or not g.is_contiguous():
+        g = g.detach().to(device=dev, dtype=torch.float32).contiguous()   # stays on the device either way
+    if W is not None and (W.dtype != torch.float32 or W.device != dev or not W.is_contiguous()):
+        W = W.detach().to(device=dev, dtype=torch.float32).contiguous()
+    base, gp = buf.data_ptr(), grads.data_ptr()
+    with _on(buf):
+        _lib.check(lib.ccr_pool_ce_bwd_dev(base, base + n_q * pdim * 2, labels.data_ptr(), weights.data_ptr() if weights is not None else None,
+                                           base + total - n_q * 4, n_q, n_c, pdim, inv_t, g.data_ptr(), W.data_ptr() if W is not None else None,
+                                           gp, gp + n_q * pdim * 4, base + head, ws_bytes, torch.cuda.current_stream(dev).cuda_stream),
+                   "ccr_pool_ce_bwd_dev")
+    return grads[:n_q, :dim], grads[n_q:, :dim]
+
+
+class _PoolCE(torch.autograd.Function):
+    """loss = sum_i w_i (logsumexp_j s_ij - s_{i,label_i}) / sum_i w_i,  s = inv_T q c^T: bf16 operands, fp32 accumulate.
+    The buffer belongs to THIS forward until its backward has run (the backward reads the forward's logits there; the library
+    checks the workspace's stamp on the device)."""
+
+    @staticmethod
+    def forward(ctx, q, c, labels, weights, inv_temperature):
+        out3, state = pool_ce_forward(q, c, labels, inv_temperature, weights)
+        ctx.state, ctx.dtypes = state, (q.dtype, c.dtype)
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dq, dc = pool_ce_backward(ctx.state, grad_out)
+        tq, tc = ctx.dtypes
+        f32 = torch.float32
+        return (dq if tq == f32 else dq.to(tq)), (dc if tc == f32 else dc.to(tc)), None, None, None
+
+
+def pool_ce(q, c, labels, inv_temperature, weights=None):
+    """Weighted cross-entropy of n_q queries over a pool of n_c candidates (ccr_pool_ce_*): several hard negatives per query,
+    per-sample weights, or a pool gathered from other ranks.  labels [n_q] index the pool; labels and weights get no gradient;
+    gradients come back in the inputs' dtypes.  A label outside the pool gives a NaN loss and NaN gradients (checked on the
+    device, no read-back)."""
+    return _PoolCE.apply(q, c, labels, weights, inv_temperature)

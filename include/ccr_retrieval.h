@@ -392,6 +392,41 @@ int ccr_inbatch_ce_bwd_dev(const uint16_t *Qe, const uint16_t *Pe, const uint16_
                            void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * Contrastive cross-entropy of n_q queries over a pool of n_c candidates, with a label and a weight per query: the general form
+ * of the loss above (several hard negatives per query, per-sample weights, candidates gathered from other ranks).
+ *   Q [n_q][dim], C [n_c][dim] bf16 (16-byte aligned); label [n_q] int32 (DEVICE); weight [n_q] fp32 (DEVICE) or NULL = all ones
+ *   s_ij = inv_temperature <Q_i, C_j> (fp32 accumulate);  ce_i = logsumexp_j s_ij - s_{i,label_i};  loss = sum w_i ce_i / sum w_i
+ *   fwd: out3 [3] fp32 (DEVICE) = {loss, numerator sum w_i ce_i, denominator sum w_i}; lse [n_q] fp32 (saved for the backward)
+ *   bwd: dQ [n_q][dim], dC [n_c][dim] fp32 (16-byte aligned) = sum over the pool / the queries of
+ *        G_ij = (softmax_ij - [j = label_i]) w_i inv_temperature grad_out / W
+ *        grad_out_dev: the upstream gradient, one fp32 on the device; W_dev: NULL = the forward's own denominator, or one fp32 on the
+ *        device (the cross-rank form hands over the denominator summed over all ranks)
+ *   Sizes: n_q >= 1, n_c >= 1, dim % 8 == 0; n_q <= 65 536, n_c <= 1 048 576, dim <= 8 192 and at most 2^28 logits (1 GiB) after
+ *   padding both counts to multiples of 64: 4 096 x 65 536 at any supported width is the largest.  Beyond that: CCR_ERR_INVALID with a
+ *   ccr_last_error() text, and ccr_pool_ce_workspace_bytes returns 0.
+ *   workspace: ccr_pool_ce_workspace_bytes(n_q, n_c, dim) bytes of device memory (16-byte aligned).  The FORWARD leaves the scaled
+ *   logits ([n_q][n_c] fp32: 64 MB at 1 024 x 16 384), its numerator and denominator and a stamp {magic, n_q, n_c, dim,
+ *   inv_temperature} in it; pass the BACKWARD the same, unmodified workspace with the same label, weight and lse.  Checked ON THE
+ *   DEVICE, no read-back, hence no error code: a label outside [0, n_c) makes the loss, the numerator and every gradient NaN (no
+ *   address depends on a label's value); sum w = 0 gives NaN as the expression does; a workspace whose stamp is not this
+ *   forward's -- scratch memory, another shape's, or one another forward has started on -- makes every gradient NaN.
+ *   Launches: forward = logits GEMM, per-query log-sum-exp, finish (3); backward = transposes, dQ GEMM, dC GEMM, + one fixed-order sum
+ *   per GEMM whose contraction was split (3 to 5).  Every GEMM stages both operands in LDS; the gradient of the logits is evaluated
+ *   from the kept logits while it is staged and split into three bf16 parts (fp32-product accuracy).  Deterministic: no atomics.
+ *   ccr_pool_ce_fwd_f32 = fp32 -> bf16 (RNE, torch's .to(bfloat16) bits) of q and c into packed [(n_q + n_c)][dim] + the forward on
+ *   packed, packed + n_q dim, in one call (the backward takes the same two pointers).
+ */
+size_t ccr_pool_ce_workspace_bytes(int n_q, int n_c, int dim);
+int ccr_pool_ce_fwd(const uint16_t *Q, const uint16_t *C, const int32_t *label, const float *weight, int n_q, int n_c, int dim,
+                    float inv_temperature, float *out3, float *lse, void *workspace, size_t ws_bytes, void *stream);
+int ccr_pool_ce_fwd_f32(const float *q, const float *c, const int32_t *label, const float *weight, int n_q, int n_c, int dim,
+                        float inv_temperature, uint16_t *packed, float *out3, float *lse, void *workspace, size_t ws_bytes,
+                        void *stream);
+int ccr_pool_ce_bwd_dev(const uint16_t *Q, const uint16_t *C, const int32_t *label, const float *weight, const float *lse, int n_q,
+                        int n_c, int dim, float inv_temperature, const float *grad_out_dev, const float *W_dev, float *dQ, float *dC,
+                        void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * Reciprocal rank / hit counts of every query at several cut-offs, from the id tensor of ccr_search.
  * Replaces: EvaluateRetrieval.evaluate_custom(qrels, ranking_profile, [1,5,10,100], metric="mrr")
  * (scripts/al_0_rank.py:130-133) and its python-dict traversal; the caller averages over queries.
