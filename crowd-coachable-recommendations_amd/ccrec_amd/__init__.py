@@ -6,6 +6,7 @@ Mirrors (reference file:line):
   replica_cache.DataParallel.cache_replicas               src/ccrec/util/data_parallel.py:8-20
   rime_util._assign_topk                                  src/rime_lite/util/__init__.py:117-155
   bbpr_loss.multiple_nrl_loss / MultipleNrlStep           src/ccrec/models/bbpr.py:149-227
+  bbpr_loss.BprStep / item_proposal                       src/ccrec/models/bbpr.py:119,149-185 (objective == "bpr")
   bbpr_transform.get_all_embeddings / transform           src/ccrec/models/bbpr.py:466-550
   rime_util.evaluate_item_rec / evaluate_assigned         src/rime_lite/metrics/__init__.py:52-89
   al_rank.generate_ranking_profile                        scripts/al_0_rank.py:69-127
@@ -60,3 +61,4 @@ from . import _lib  # noqa: E402
 from .ops import (  # noqa: E402,F401
     CorpusIndex, apply_block, colsum_bf16, inbatch_ce, meanpool, meanpool_pack, merge_topk, pack_bf16, require_gpu,
 )
+from .bbpr_loss import BprStep, item_proposal  # noqa: E402,F401

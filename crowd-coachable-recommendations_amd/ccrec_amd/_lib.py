@@ -24,9 +24,11 @@ EXPORTS = [
     "ccr_attention_half", "ccr_add_layernorm_half", "ccr_embed_layernorm_half", "ccr_gelu_half", "ccr_merge_short_lists",
     "ccr_bm25_search_workspace_bytes_k", "ccr_bm25_search_last_stats", "ccr_bm25_index_set_idf", "ccr_inbatch_pack3_bf16", "ccr_inbatch_ce_fwd_f32",
     "ccr_search_stream_wait_main_pass", "ccr_pool_ce_workspace_bytes", "ccr_pool_ce_fwd", "ccr_pool_ce_fwd_f32", "ccr_pool_ce_bwd_dev",
+    "ccr_bpr_sample", "ccr_bpr_frozen_workspace_bytes", "ccr_bpr_frozen_fwd", "ccr_bpr_frozen_bwd_dev",
 ]
 
-MIN_VERSION = 101   # ccr_version() of the library this binding was written for (101: the ccr_pool_ce_* entry points)
+MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
+BPR_VERSION = 102   # ... and the one the ccr_bpr_* entry points came with (ops checks it on their first use)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -69,6 +71,9 @@ def load():
     if have < MIN_VERSION:   # a stale build would fail later, at the first missing symbol or with another argument list
         raise CcrError(f"{LIB_PATH} is version {have}, this binding needs {MIN_VERSION}: rebuild it "
                        f"(python -c 'import __graft_entry__ as g; g.build()')")
+    missing = [name for name in EXPORTS if not hasattr(lib, name)]
+    if missing:   # same version number, other entry points: a build from another tree
+        raise CcrError(f"{LIB_PATH} lacks {', '.join(missing)}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
     vp, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
     lib.ccr_last_error.restype = ctypes.c_char_p
     lib.ccr_last_error.argtypes = []
@@ -102,6 +107,11 @@ def load():
     lib.ccr_pool_ce_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, sz, vp]
     lib.ccr_pool_ce_fwd_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]
     lib.ccr_pool_ce_bwd_dev.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, sz, vp]
+    lib.ccr_bpr_sample.argtypes = [vp, i32, i32, i64, vp, vp, vp, f32, vp, vp, i32, vp, i32, vp, vp]
+    lib.ccr_bpr_frozen_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.ccr_bpr_frozen_workspace_bytes.restype = sz
+    lib.ccr_bpr_frozen_fwd.argtypes = [vp, i64, i32, vp, vp, f32, vp, vp, vp, vp, i32, i32, vp, vp, sz, vp]
+    lib.ccr_bpr_frozen_bwd_dev.argtypes = [vp, i64, i32, vp, vp, f32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]
     lib.ccr_rank_metrics.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]
     lib.ccr_search_finish.argtypes = [vp]
     lib.ccr_search_stream_wait_main_pass.argtypes = [vp, vp]

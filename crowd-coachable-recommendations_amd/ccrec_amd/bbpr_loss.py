@@ -1,6 +1,8 @@
 """The 'multiple_nrl' in-batch-negative objective of src/ccrec/models/bbpr.py:187-214 with the score
 GEMMs + softmax-CE in HIP (ccr_inbatch_ce_fwd/bwd).  Embeddings are the three encoder outputs
-(query, positive, hard negative); the round-robin negative picking (:188-193) stays host Python."""
+(query, positive, hard negative); the round-robin negative picking (:188-193) stays host Python.
+The 'bpr' objective of bbpr.py:153-185 (BprStep): prior-guided negative sampling in HIP (ccr_bpr_sample) and, when the
+encoder is frozen and the CLS rows are cached, the whole loss in HIP (ccr_bpr_frozen_*)."""
 import os
 
 import torch
@@ -99,5 +101,121 @@ class BertMTStep(MultipleNrlStep):
         ijw = batch[0] if isinstance(batch, (tuple, list)) else batch
         ft_loss = super().__call__(ijw, batch_idx)
         return (1 - self.alpha) / self.ct_cycles * 0.0 + self.alpha / self.ft_cycles * ft_loss.mean()
+
+    training_and_validation_step = __call__
+
+
+def item_proposal(item_freq, sample_with_posterior=0.5):
+    """bbpr.py:119: (item_freq + 0.1) ** sample_with_posterior, the proposal the negatives are drawn from."""
+    freq = torch.as_tensor(item_freq)
+    if not freq.is_floating_point():
+        freq = freq.to(torch.float64)   # (numpy's int + 0.1)
+    return (freq + 0.1) ** sample_with_posterior
+
+
+def prior_to_csr(tr_prior_score, training_prior_fcn=None):
+    """Sparse prior [n_users, n_items] (torch COO, as compute_user_to_negatives takes it; duplicate entries are summed, as
+    to_dense() would) -> (ptr [n_users + 1] int64, idx int64 ascending per row, t fp32, t0, max_row_nnz): the CSR form
+    ops.bpr_sample_negatives takes, with training_prior_fcn applied ONCE, to the stored values and to a zero (t0, the value of
+    every absent entry after to_dense()).  That is the reference's f(dense matrix) only for an ELEMENTWISE function."""
+    coo = tr_prior_score.coalesce()   # sorted by (row, column), duplicates summed
+    rows, cols = coo.indices()
+    vals = coo.values()
+    n_users = coo.shape[0]
+    counts = torch.bincount(rows, minlength=n_users)
+    ptr = torch.zeros(n_users + 1, dtype=torch.int64, device=rows.device)
+    ptr[1:] = torch.cumsum(counts, 0)
+    fcn = training_prior_fcn if training_prior_fcn is not None else (lambda x: x)
+    t = torch.as_tensor(fcn(vals)).to(torch.float32).contiguous()
+    t0 = float(fcn(torch.zeros((), dtype=vals.dtype, device=vals.device)))
+    return ptr, cols.contiguous(), t, t0, (int(counts.max()) if vals.numel() else 0)
+
+
+class BprStep:
+    """training_and_validation_step of _BertBPR for objective == "bpr" (bbpr.py:149-185) as a callable:
+    batch [B,3] = (i, j, w) -> scalar loss  (-logsigmoid(pos - neg) * w).sum() / (n_negatives * w.sum()).
+
+    Negatives: n_negatives per row (valid_n_negatives when .training is False) from softmax(training_prior_fcn(prior[i]) +
+    log item_proposal) when tr_prior_score is given and sample_with_prior, from item_proposal alone otherwise -- always through
+    ops.bpr_sample_negatives, never a dense [B, n_items] matrix.  The prior is turned into device CSR once (prior_to_csr):
+    training_prior_fcn must be ELEMENTWISE (it sees the stored values and one zero, not the dense matrix).  With replacement only.
+    all_cls [n_rows, dim] fp32 + layer_norm (the tower's torch.nn.LayerNorm; freeze_bert > 0, bbpr.py:436-438): the loss is
+    ops.bpr_frozen_loss, with gradients into the LayerNorm; at a width the kernel does not take (not a multiple of 64, above 2048)
+    the same expression in torch.  Otherwise forward(item pointers) -> embeddings [n, dim] with autograd (the item tower on
+    all_inputs[ptr]) and _pairwise is torch products + logsigmoid, as in the reference.
+    i_to_ptr / j_to_ptr: user / item index -> item pointer.  The last draw stays in .last_negatives [n_negatives, B]."""
+
+    def __init__(self, forward, i_to_ptr, j_to_ptr, item_freq, tr_prior_score=None, training_prior_fcn=None, n_negatives=10,
+                 valid_n_negatives=None, sample_with_prior=True, sample_with_posterior=0.5, replacement=True, all_cls=None,
+                 layer_norm=None, generator=None):
+        if not replacement:
+            raise ValueError("BprStep: replacement=False (sampling without replacement) is not supported")
+        if (all_cls is None) != (layer_norm is None):
+            raise ValueError("BprStep: all_cls and layer_norm go together")
+        if forward is None and all_cls is None:
+            raise ValueError("BprStep: needs forward, or all_cls and layer_norm")
+        self.n_negatives = int(n_negatives)
+        self.valid_n_negatives = self.n_negatives if valid_n_negatives is None else int(valid_n_negatives)
+        if self.n_negatives < 1 or self.valid_n_negatives < 1:
+            raise ValueError("n_negatives must be at least 1")
+        self.forward, self.all_cls, self.layer_norm = forward, all_cls, layer_norm
+        self.i_to_ptr, self.j_to_ptr = torch.as_tensor(i_to_ptr), torch.as_tensor(j_to_ptr)
+        self.sample_with_prior, self.sample_with_posterior, self.replacement = bool(sample_with_prior), sample_with_posterior, True
+        self.training_prior_fcn = training_prior_fcn if training_prior_fcn is not None else (lambda x: x)
+        self.training, self.generator, self.last_negatives = True, generator, None
+        self.item_proposal = item_proposal(item_freq, sample_with_posterior).to(torch.float32).contiguous()
+        self.prior_csr = None   # (ptr, idx, t, t0, max_row_nnz)
+        if tr_prior_score is not None and self.sample_with_prior:
+            self.prior_csr = prior_to_csr(tr_prior_score, self.training_prior_fcn)
+            assert tr_prior_score.shape[1] == self.item_proposal.numel(), "the prior's columns are the items of item_freq"
+        self._dev = {}   # device -> (i_to_ptr, j_to_ptr, proposal, proposal_cdf, prior)
+
+    def train(self, mode=True):
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def _on_device(self, dev):
+        st = self._dev.get(dev)
+        if st is None:
+            proposal = self.item_proposal.to(dev)
+            prior = None
+            if self.prior_csr is not None:
+                ptr, idx, t, _, max_row_nnz = self.prior_csr
+                prior = (ptr.to(dev), idx.to(dev), t.to(dev), max_row_nnz)
+            st = self._dev[dev] = (self.i_to_ptr.to(dev), self.j_to_ptr.to(dev), proposal, ops.bpr_proposal_cdf(proposal), prior)
+        return st
+
+    def sample_negatives(self, i, n_negatives):
+        """[n_negatives, B] item indices for the users i (bbpr.py:160-179)."""
+        _, _, proposal, cdf, prior = self._on_device(i.device)
+        return ops.bpr_sample_negatives(i, n_negatives, proposal, cdf, prior=prior, t0=self.prior_csr[3] if prior is not None else 0.0,
+                                        generator=self.generator)
+
+    def _embed(self, ptr):
+        if self.all_cls is not None:   # forward of bbpr.py:134-137 on the cached rows
+            return self.layer_norm(self.all_cls[ptr])
+        return self.forward(ptr)
+
+    def _pairwise(self, i, j):   # auto-broadcast on first dimension (bbpr.py:144-147)
+        i_to_ptr, j_to_ptr = self._on_device(i.device)[:2]
+        x = self._embed(i_to_ptr[i.ravel()]).reshape([*i.shape, -1])
+        y = self._embed(j_to_ptr[j.ravel()]).reshape([*j.shape, -1])
+        return (x * y).sum(-1)
+
+    def __call__(self, batch, batch_idx=0):
+        i, j, w = batch.T
+        i, j = i.to(int), j.to(int)
+        n_negatives = self.n_negatives if self.training else self.valid_n_negatives
+        with torch.no_grad():
+            nj = self.last_negatives = self.sample_negatives(i, n_negatives)
+        if self.all_cls is not None and ops.bpr_frozen_supported(self.all_cls.shape[1]):
+            i_to_ptr, j_to_ptr = self._on_device(i.device)[:2]
+            ln = self.layer_norm
+            return ops.bpr_frozen_loss(self.all_cls, ln.weight, ln.bias, ln.eps, i_to_ptr[i], j_to_ptr[j], j_to_ptr[nj], w)
+        loglik = torch.nn.functional.logsigmoid(self._pairwise(i, j) - self._pairwise(i, nj))   # n_negatives x B
+        return (-loglik * w).sum() / (n_negatives * w.sum())
 
     training_and_validation_step = __call__

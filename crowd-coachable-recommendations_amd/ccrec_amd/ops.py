@@ -738,3 +738,142 @@ def pool_ce(q, c, labels, inv_temperature, weights=None):
     gradients come back in the inputs' dtypes.  A label outside the pool gives a NaN loss and NaN gradients (checked on the
     device, no read-back)."""
     return _PoolCE.apply(q, c, labels, weights, inv_temperature)
+
+
+# ---- the "bpr" objective (ccr_bpr_*; src/ccrec/models/bbpr.py:153-185) ------------------------------------------------------------
+_BPR_CHECKED = False
+
+
+def _require_bpr():
+    """require_gpu() + once: the loaded library has the ccr_bpr_* entry points (ccr_version() >= 102)."""
+    global _BPR_CHECKED
+    lib = require_gpu()
+    if not _BPR_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.BPR_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, the bpr ops need {_lib.BPR_VERSION}: rebuild it "
+                                f"(python -c 'import __graft_entry__ as g; g.build()')")
+        _BPR_CHECKED = True
+    return lib
+
+
+def bpr_frozen_supported(dim):
+    """Widths the fused frozen-tower loss takes (ccr_bpr_frozen_*); BprStep runs its torch formulation at any other."""
+    return dim % 64 == 0 and 64 <= dim <= 2048
+
+
+def bpr_proposal_cdf(proposal):
+    """Inclusive fp64 prefix sums of the item proposal (once per training set): the second input of bpr_sample_negatives."""
+    return torch.cumsum(proposal.detach().to(torch.float64), 0)
+
+
+def bpr_sample_negatives(users, n_negatives, proposal, proposal_cdf, prior=None, t0=0.0, uniforms=None, generator=None):
+    """Negatives of bbpr.py:160-179 -> [n_negatives, B] int64, as multinomial(softmax(f(prior[users]) + log proposal), n, True).T
+    draws them, by inverse CDF over the sparse row (ccr_bpr_sample): no [B, n_items] matrix.
+    users [B] int64; proposal [n_items] fp32 > 0 and proposal_cdf = bpr_proposal_cdf(proposal); prior = None (draw from the
+    proposal alone, bbpr.py:176-179) or (ptr [n_users + 1] int64, idx int64 ascending and unique per row, t fp32 =
+    training_prior_fcn(value), max_row_nnz) on the device, with t0 = training_prior_fcn(0).  uniforms [n_negatives, B] fp64 in
+    [0, 1): drawn here with torch.rand (generator) when None.  With replacement only."""
+    lib = _require_bpr()
+    dev = proposal.device
+    users = users.detach().to(device=dev, dtype=torch.int64).contiguous()
+    B, n_neg, n_items = users.numel(), int(n_negatives), proposal.numel()
+    assert users.dim() == 1 and B >= 1 and n_neg >= 1, "users [B], n_negatives >= 1"
+    assert proposal.is_cuda and proposal.dtype == torch.float32 and proposal.is_contiguous(), "proposal: fp32 [n_items] on the device"
+    assert proposal_cdf.device == dev and proposal_cdf.dtype == torch.float64 and proposal_cdf.is_contiguous() and proposal_cdf.numel() == n_items, \
+        "proposal_cdf: bpr_proposal_cdf(proposal)"
+    if uniforms is None:
+        uniforms = torch.rand(n_neg, B, dtype=torch.float64, device=dev, generator=generator)
+    assert uniforms.device == dev and uniforms.dtype == torch.float64 and uniforms.is_contiguous() and uniforms.shape == (n_neg, B), \
+        "uniforms: fp64 [n_negatives, B] on the device"
+    if prior is not None:
+        ptr, idx, t, max_row_nnz = prior
+        assert ptr.device == idx.device == t.device == dev and ptr.dtype == idx.dtype == torch.int64 and t.dtype == torch.float32
+        assert ptr.is_contiguous() and idx.is_contiguous() and t.is_contiguous() and idx.numel() == t.numel()
+        n_users = ptr.numel() - 1
+    else:
+        ptr = idx = t = None
+        n_users, max_row_nnz = 0, 0
+    out = torch.empty(n_neg, B, dtype=torch.int64, device=dev)
+    with _on(proposal):
+        _lib.check(lib.ccr_bpr_sample(_ptr(users), B, n_neg, n_users, _ptr(ptr), _ptr(idx), _ptr(t), float(t0), _ptr(proposal), _ptr(proposal_cdf),
+                                      n_items, _ptr(uniforms), int(max_row_nnz), _ptr(out), _stream(proposal)), "ccr_bpr_sample")
+    return out
+
+
+def _bpr_frozen_args(table, ptr_i, ptr_j, ptr_nj, w):
+    assert table.is_cuda and table.dtype == torch.float32 and table.dim() == 2 and table.is_contiguous(), "table: fp32 [n_rows, dim] on the device"
+    dev = table.device
+    ptr_i = ptr_i.detach().to(device=dev, dtype=torch.int64).contiguous()
+    ptr_j = ptr_j.detach().to(device=dev, dtype=torch.int64).contiguous()
+    ptr_nj = ptr_nj.detach().to(device=dev, dtype=torch.int64).contiguous()
+    w = w.detach().to(device=dev, dtype=torch.float32).contiguous()
+    B = ptr_i.numel()
+    assert ptr_i.dim() == 1 and ptr_j.shape == (B,) and w.shape == (B,) and ptr_nj.dim() == 2 and ptr_nj.shape[1] == B, \
+        "ptr_i, ptr_j, w [B] and ptr_nj [n_negatives, B]"
+    return ptr_i, ptr_j, ptr_nj, w, B, ptr_nj.shape[0]
+
+
+def _bpr_workspace(lib, B, n_neg, dim, dev):
+    ws_bytes = int(lib.ccr_bpr_frozen_workspace_bytes(B, n_neg, dim))   # (host arithmetic only)
+    if ws_bytes == 0:
+        raise _lib.CcrError("ccr_bpr_frozen_workspace_bytes: " + lib.ccr_last_error().decode("utf-8", "replace"))
+    return torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes
+
+
+class _BprFrozen(torch.autograd.Function):
+    """loss = sum_nb w_b softplus(-(e_i . e_j - e_i . e_nb)) / (n_neg sum_b w_b),  e = LayerNorm(table[ptr]); gradients with respect to
+    the LayerNorm's weight and bias only (the table is a frozen buffer).  Nothing is saved but the inputs: the backward reads and
+    normalises the rows again."""
+
+    @staticmethod
+    def forward(ctx, table, weight, bias, eps, ptr_i, ptr_j, ptr_nj, w):
+        lib = _require_bpr()
+        ptr_i, ptr_j, ptr_nj, w, B, n_neg = _bpr_frozen_args(table, ptr_i, ptr_j, ptr_nj, w)
+        n_rows, dim = table.shape
+        dev = table.device
+        assert (weight is None) == (bias is None), "LayerNorm weight and bias: both or neither"
+        gb = None
+        if weight is not None:   # one [2, dim] block: gamma and beta 16-byte aligned whatever views the module holds
+            gb = torch.stack([weight.detach().to(device=dev, dtype=torch.float32), bias.detach().to(device=dev, dtype=torch.float32)])
+            assert gb.shape == (2, dim), "LayerNorm weight and bias [dim]"
+        ws, ws_bytes = _bpr_workspace(lib, B, n_neg, dim, dev)
+        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+        with _on(table):
+            _lib.check(lib.ccr_bpr_frozen_fwd(_ptr(table), n_rows, dim, gb.data_ptr() if gb is not None else None,
+                                              gb.data_ptr() + dim * 4 if gb is not None else None, float(eps), _ptr(ptr_i), _ptr(ptr_j), _ptr(ptr_nj),
+                                              _ptr(w), B, n_neg, _ptr(out3), _ptr(ws), ws_bytes, _stream(table)), "ccr_bpr_frozen_fwd")
+        ctx.save_for_backward(table, gb, ptr_i, ptr_j, ptr_nj, w, out3)
+        ctx.lay = (float(eps), weight.dtype if weight is not None else None, bias.dtype if bias is not None else None)
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _require_bpr()
+        table, gb, ptr_i, ptr_j, ptr_nj, w, out3 = ctx.saved_tensors
+        eps, tw, tb = ctx.lay
+        if gb is None:
+            raise _lib.CcrError("bpr_frozen_loss: no gradient without a LayerNorm weight and bias (elementwise_affine=False)")
+        n_rows, dim = table.shape
+        B, n_neg = ptr_i.numel(), ptr_nj.shape[0]
+        dev = table.device
+        g = grad_out
+        if g.dtype != torch.float32 or g.device != dev or not g.is_contiguous():
+            g = g.detach().to(device=dev, dtype=torch.float32).contiguous()   # stays on the device either way
+        grads = torch.empty(2, dim, dtype=torch.float32, device=dev)
+        ws, ws_bytes = _bpr_workspace(lib, B, n_neg, dim, dev)
+        with _on(table):
+            _lib.check(lib.ccr_bpr_frozen_bwd_dev(_ptr(table), n_rows, dim, gb.data_ptr(), gb.data_ptr() + dim * 4, eps, _ptr(ptr_i), _ptr(ptr_j),
+                                                  _ptr(ptr_nj), _ptr(w), B, n_neg, out3.data_ptr() + 8, _ptr(g), grads.data_ptr(),
+                                                  grads.data_ptr() + dim * 4, _ptr(ws), ws_bytes, _stream(table)), "ccr_bpr_frozen_bwd_dev")
+        dw, db = grads.unbind(0)
+        f32 = torch.float32
+        return None, (dw if tw == f32 else dw.to(tw)), (db if tb == f32 else db.to(tb)), None, None, None, None, None
+
+
+def bpr_frozen_loss(table, layer_norm_weight, layer_norm_bias, eps, ptr_i, ptr_j, ptr_nj, w):
+    """The bpr loss of one step over cached CLS rows (bbpr.py:144-147, 180-185 with forward = LayerNorm(all_cls[ptr])), fused
+    (ccr_bpr_frozen_*): table [n_rows, dim] fp32, dim a multiple of 64 up to 2048; ptr_i, ptr_j [B], ptr_nj [n_negatives, B] rows
+    of the table; w [B].  Autograd with respect to layer_norm_weight and layer_norm_bias (both None: forward only).  A pointer
+    outside the table gives a NaN loss and NaN gradients, all-zero weights NaN (checked on the device, no read-back)."""
+    return _BprFrozen.apply(table, layer_norm_weight, layer_norm_bias, eps, ptr_i, ptr_j, ptr_nj, w)

@@ -427,6 +427,51 @@ int ccr_pool_ce_bwd_dev(const uint16_t *Q, const uint16_t *C, const int32_t *lab
                         void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * The "bpr" objective of _BertBPR.training_and_validation_step (src/ccrec/models/bbpr.py:153-185).
+ *
+ * ccr_bpr_sample -- prior-guided negative sampling.  Replaces bbpr.py:160-179:
+ *   torch.multinomial((training_prior_fcn(prior[i].to_dense()) + item_proposal.log()).softmax(1), n_negatives, True).T
+ * without the dense [B][n_items] matrix.  All pointers DEVICE.
+ *   users [B] int64: the batch's rows of the prior.  prior CSR over all users: prior_ptr [n_users + 1] int64, prior_idx int64
+ *   ascending and unique per row, prior_t fp32 = training_prior_fcn(value), ALREADY applied; t0 = training_prior_fcn(0), the value of
+ *   every absent entry.  prior_ptr = NULL: the no-prior branch (bbpr.py:176-179), draws from the proposal alone.
+ *   proposal [n_items] fp32 > 0; proposal_cdf [n_items] fp64 = its inclusive prefix sums; uniforms [n_neg][B] fp64 in [0, 1).
+ *   In fp64, for the row's entries (c_1 < ... < c_m; t_1 ... t_m):  M = max(t0, max t_k), e0 = exp(t0 - M), e_k = exp(t_k - M),
+ *     F(j) = e0 cdf[j] + sum_{k: c_k <= j} proposal[c_k] (e_k - e0),   Z = F(n_items - 1)
+ *   out_nj[n][b] = the smallest j with F(j) > uniforms[n][b] Z: the inverse CDF of the softmax (its max-shift included, so
+ *   training_prior_fcn values of 1e5 do not overflow).  out_nj [n_neg][B] int64, laid out as multinomial(...).T is.
+ *   max_row_nnz (HOST): the longest row of the CSR; above 4096 (the limit of ccr_search_sparse_prior): CCR_ERR_INVALID.  A user
+ *   outside [0, n_users) or a row longer than max_row_nnz gives -1 for every draw of that batch row (checked on the device).
+ *   With replacement only.  One launch, one wave per batch row; the same uniforms give the same draws.
+ *
+ * ccr_bpr_frozen_* -- the loss of one step when the encoder is frozen and every item's CLS row is cached (all_cls, bbpr.py:436-438):
+ * gather -> LayerNorm -> _pairwise products -> logsigmoid -> weighted sum (bbpr.py:144-147, 180-185) in one pass over the rows.
+ *   table [n_rows][dim] fp32; gamma, beta [dim] fp32 and eps: the LayerNorm (biased variance, as torch); gamma and beta may both
+ *   be NULL (elementwise_affine=False: forward only).  ptr_i, ptr_j [B], ptr_nj [n_neg][B] int64 rows of the table; w [B] fp32.
+ *     e = LN(table[ptr]) gamma + beta;   D_nb = e_i . e_j - e_i . e_nb;   loss = sum_nb w_b softplus(-D_nb) / (n_neg sum_b w_b)
+ *   fwd: out3 [3] fp32 = {loss, numerator, denominator n_neg sum w}.  bwd: dgamma, dbeta [dim] fp32 (the table is a buffer: no
+ *   gradient) = grad_out_dev[0] times the gradient of numerator / den_dev[0] (den_dev: out3 + 2 of the forward); the rows are
+ *   read and normalised again, the forward saves nothing.  Both scalars are read on the device: no host synchronisation.
+ *   All fp32; softplus and sigmoid in their overflow-free forms (|D| in the hundreds is fine).  sum w = 0 gives NaN; a pointer
+ *   outside [0, n_rows) gives a NaN loss and NaN gradients (checked on the device, every address clamped).  Deterministic: no
+ *   atomics, fixed summation order.  dim % 64 == 0, dim <= 2048, B <= 2^20, n_neg <= 4096; anything else: CCR_ERR_INVALID, and
+ *   ccr_bpr_frozen_workspace_bytes returns 0 with a ccr_last_error() text.  table, gamma, beta, dgamma, dbeta 16-byte aligned.
+ *   workspace: ccr_bpr_frozen_workspace_bytes(B, n_neg, dim) bytes (DEVICE), scratch for either call.
+ *   Launches: forward 2 (one wave per batch row; finish), backward 2 (one wave per batch row; fixed-order sum of the partial rows).
+ */
+int ccr_bpr_sample(const int64_t *users, int B, int n_neg, int64_t n_users, const int64_t *prior_ptr, const int64_t *prior_idx,
+                   const float *prior_t, float t0, const float *proposal, const double *proposal_cdf, int n_items,
+                   const double *uniforms, int max_row_nnz, int64_t *out_nj, void *stream);
+size_t ccr_bpr_frozen_workspace_bytes(int B, int n_neg, int dim);
+int ccr_bpr_frozen_fwd(const float *table, int64_t n_rows, int dim, const float *gamma, const float *beta, float eps,
+                       const int64_t *ptr_i, const int64_t *ptr_j, const int64_t *ptr_nj, const float *w, int B, int n_neg,
+                       float *out3, void *workspace, size_t ws_bytes, void *stream);
+int ccr_bpr_frozen_bwd_dev(const float *table, int64_t n_rows, int dim, const float *gamma, const float *beta, float eps,
+                           const int64_t *ptr_i, const int64_t *ptr_j, const int64_t *ptr_nj, const float *w, int B, int n_neg,
+                           const float *den_dev, const float *grad_out_dev, float *dgamma, float *dbeta, void *workspace,
+                           size_t ws_bytes, void *stream);
+
+/*
  * Reciprocal rank / hit counts of every query at several cut-offs, from the id tensor of ccr_search.
  * Replaces: EvaluateRetrieval.evaluate_custom(qrels, ranking_profile, [1,5,10,100], metric="mrr")
  * (scripts/al_0_rank.py:130-133) and its python-dict traversal; the caller averages over queries.
