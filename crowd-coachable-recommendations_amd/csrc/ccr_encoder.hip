@@ -328,6 +328,20 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
     }   // query blocks of this wave
 }
 
+// The mean of a row held in registers (v[c][j] per lane), from a first estimate m0 = sum / DIM: one correction step m0 + mean(v - m0).
+// The fp32 sum of DIM elements leaves m0 an ulp or so off, which is harmless next to a variance but IS the whole deviation of a row
+// whose elements are all equal: there v - m0 is a few ulps, exactly, its sum is exact, and the corrected mean is v itself -- the row
+// normalises to beta for every eps, where the uncorrected mean left gamma (v - m0) / sqrt(eps): 0.18 to 1.0 gamma at eps = 1e-12, by width.
+template <int C>
+__device__ __forceinline__ float refined_mean(const float (&v)[C][4], float m0) {
+    float sd = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) sd += ((v[c][0] - m0) + (v[c][1] - m0)) + ((v[c][2] - m0) + (v[c][3] - m0));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sd += __shfl_xor(sd, o);
+    return m0 + sd * (1.f / (256 * C));
+}
+
 // One wave per row of dim = 256 * C elements; lane owns elements 4 * (64 c + lane) .. + 3 of every 256-element slice.
 template <int C, int DT>
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const uint16_t *__restrict__ x, const float *__restrict__ res,
@@ -354,7 +368,7 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const uint16_t *__re
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = sum * (1.f / DIM);
+    const float mean = refined_mean<C>(v, sum * (1.f / DIM));
     float sq = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c)
@@ -415,7 +429,7 @@ __global__ __launch_bounds__(256) void embed_layernorm_kernel(const float *__res
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = sum * (1.f / DIM);
+    const float mean = refined_mean<C>(v, sum * (1.f / DIM));
     float sq = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c)

@@ -45,6 +45,40 @@ def assert_rank_close(ids, scores, ref_ids, ref_scores, tol, truncated=False):
                 assert abs(s - cut) <= 2 * tol, f"query {q}: id {j} score {s} far from cut {cut}"
 
 
+# ---------------------------------------------------------------------------------------------- synthetic shard lists for the merges
+MERGE_LEVELS = np.array([-np.inf, -1.0, 0.0, 0.5, 2.0, np.inf], np.float32)
+MERGE_ID_SHIFT = 3_000_000_000   # added to the ids of the last shard: global ids that no 32-bit signed field holds
+
+# (R, k) of the full-list merge, one per launch path of csrc/ccr_merge.hip (R k < 600 ranks every element, then bisection; 256
+# threads below 2048 elements; R k 12 bytes > 48 KiB opts in to dynamic LDS; > 96 KiB or R > 64 merges from global memory)
+MERGE_CASES = [(1, 1), (1, 37), (2, 1), (64, 3), (5, 119), (6, 100), (7, 292), (8, 256), (4, 1024), (4, 1025), (8, 1001), (2, 4096),
+               (64, 128), (3, 2731), (9, 1001), (65, 8)]
+
+
+def canonical_order(scores, ids):
+    """The permutation that puts one list into the canonical order (score desc, id asc)."""
+    return np.lexsort((ids, -scores.astype(np.float64)))
+
+
+def synthetic_shard_lists(R, n_q, k, levels, seed):
+    """[R, n_q, k] per-shard lists as a search would leave them, built to stress the merge's order instead of a search's scores: per
+    query R k DISTINCT ids drawn from a range three times as large (the shards interleave), the last shard's shifted by MERGE_ID_SHIFT;
+    scores drawn from the first `levels` values of MERGE_LEVELS -- 1: the whole input is one plateau (of real -inf scores), 2 and 6:
+    plateaus straddle the cut of every list, +-inf included -- or, with levels = 0, continuous (standard normal); every list sorted
+    into the canonical order.  -> (scores fp32, ids int64)."""
+    rs = np.random.RandomState(seed)
+    scores = np.empty((R, n_q, k), np.float32)
+    ids = np.empty((R, n_q, k), np.int64)
+    for q in range(n_q):
+        i = rs.permutation(3 * R * k)[:R * k].astype(np.int64).reshape(R, k)
+        i[R - 1] += MERGE_ID_SHIFT
+        s = MERGE_LEVELS[rs.randint(0, levels, (R, k))] if levels else rs.standard_normal((R, k)).astype(np.float32)
+        for r in range(R):
+            o = canonical_order(s[r], i[r])
+            scores[r, q], ids[r, q] = s[r][o], i[r][o]
+    return scores, ids
+
+
 # ---------------------------------------------------------------------------------------------- child processes
 def _proc_state(pid):
     """What the kernel says a process and its threads are doing: state + wait channel of every thread (readable without root)."""
