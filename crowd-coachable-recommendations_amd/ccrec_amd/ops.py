@@ -604,7 +604,7 @@ class _InBatchCE(torch.autograd.Function):
         lse_ptr = base + total - B * 4
         stream = torch.cuda.current_stream(dev).cuda_stream
         fast = (q.dtype == p.dtype == n.dtype == torch.float32 and q.is_contiguous() and p.is_contiguous() and n.is_contiguous()
-                and dim % 8 == 0 and (q.data_ptr() | p.data_ptr() | n.data_ptr()) % 16 == 0)
+                and (q.data_ptr() | p.data_ptr() | n.data_ptr()) % 16 == 0)   # (dim % 16 == 0: inbatch_ce sends no other width here)
         with _on(q):
             if fast:
                 _lib.check(lib.ccr_inbatch_ce_fwd_f32(q.data_ptr(), p.data_ptr(), n.data_ptr(), B, dim, float(inv_temperature), base,
@@ -641,6 +641,12 @@ class _InBatchCE(torch.autograd.Function):
 
 
 def inbatch_ce(q, p, n, inv_temperature):
+    """The square loss of three [B, dim] blocks.  The square kernels take widths that are multiples of 16; any other width >= 1 is
+    the same loss in the pool form (pool = [p ; n], labels arange(B)), which zero-pads the width."""
+    assert q.dim() == 2 and p.shape == q.shape == n.shape, "three [B, dim] blocks"
+    if q.shape[1] % 16 != 0:
+        labels = torch.arange(q.shape[0], dtype=torch.int32, device=q.device)
+        return pool_ce(q, torch.cat([p, n]), labels, inv_temperature)
     return _InBatchCE.apply(q, p, n, inv_temperature)
 
 

@@ -363,7 +363,8 @@ int ccr_apply_block(const float *in_scores, const int64_t *in_ids, int n_q, int 
  *   Qe, Pe, Ne [B][dim] bf16; logits = [Qe Pe^T | Qe Ne^T] * inv_temperature (fp32 accumulate)
  *   fwd: loss (1 float, mean CE with labels arange(B)), lse [B] (saved for bwd)
  *   bwd: dQ, dP, dN [B][dim] fp32 = grad_out * dloss/d(.)
- *   workspace: ccr_inbatch_ce_workspace_bytes(B, dim) bytes of device memory (16-byte aligned); dim % 16 == 0; the embedding
+ *   workspace: ccr_inbatch_ce_workspace_bytes(B, dim) bytes of device memory (16-byte aligned); dim % 16 == 0 (the
+ *   Python ops.inbatch_ce sends every other width to ccr_pool_ce_* below, zero-padded to a multiple of 8); the embedding
  *   pointers 16-byte aligned.  The FORWARD leaves the scaled logits ([2B][B] fp32) in it and the BACKWARD reads them there
  *   instead of recomputing them: pass the backward the same, unmodified workspace its forward call used (the Python autograd
  *   function saves it with the operands).  The forward also leaves a stamp {magic, B, dim, inv_temperature} behind its logits and

@@ -210,3 +210,103 @@ def golden_texts(n, seed, longest=20, words=150):
     rs = np.random.RandomState(seed)
     vocab = [f"w{i}" for i in range(words)]
     return [" ".join(rs.choice(vocab, rs.randint(1, longest + 1))) for _ in range(n)]
+
+
+# ---------------------------------------------------------------------------------------------- the part probe of the contrastive losses
+# One operand of the loss is ONE-HOT, so every element of the gradient on the other side is a single product g * amplitude: the GEMM adds
+# nothing to the error and what is left is the accuracy of g itself -- fp32 lse, fp32 exp, the fp32 scale and the split into bf16 parts
+# (g = hi + mid + lo).  The kernels' bound is a third of what the same fp32 arithmetic gives with TWO parts (hi + mid), computed from the
+# same inputs by loss_probe_errors below; tests/test_cpu_loss_probe.py shows that three parts pass it and two cannot.
+LOSS_PROBE_INV_T = 4.0
+INBATCH_PROBE_SHAPES = [(40, 128), (33, 144), (64, 128), (96, 384)]         # (B, dim): row-major x 2, fragment-major with 2B = dim, and a wider one
+POOL_PROBE_SHAPES = [("dq", 40, 100, 128), ("dc", 100, 40, 128)]           # (side, n_q, n_c, dim)
+
+
+def bf16_round(x):
+    """float32 -> the nearest bf16 (ties to even), returned as float32.  Finite inputs."""
+    b = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    return ((b + 0x7FFF + ((b >> 16) & 1)) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def bf16_parts(g, n_parts):
+    """split3 of the kernels, cut after n_parts: g = p0 + p1 + ... with every p a bf16 and every residual taken in fp32."""
+    parts, r = [], np.asarray(g, np.float32)
+    for _ in range(n_parts):
+        p = bf16_round(r)
+        parts.append(p)
+        r = (r - p).astype(np.float32)
+    return parts
+
+
+def loss_probe(side, n_q, n_c, dim, seed):
+    """-> (q [n_q, dim], c [n_c, dim]) fp32 holding bf16 values.  side "dq": the candidates are one-hot (row j = b_j e_sigma(j), sigma
+    injective, b_j in {1/2, 1, 2}) and the queries dense (randn / 8), so dQ[i][sigma(j)] = G_ij b_j and every other column is 0;
+    side "dc": the mirror image, dC[j][pi(i)] = G_ij a_i."""
+    rs = np.random.RandomState(seed)
+    n_hot, n_dense = (n_c, n_q) if side == "dq" else (n_q, n_c)
+    assert n_hot <= dim, "one column per one-hot row"
+    dense = bf16_round((rs.standard_normal((n_dense, dim)) * 0.125).astype(np.float32))
+    hot = np.zeros((n_hot, dim), np.float32)
+    hot[np.arange(n_hot), rs.permutation(dim)[:n_hot]] = np.array([0.5, 1.0, 2.0], np.float32)[rs.randint(0, 3, n_hot)]
+    return (dense, hot) if side == "dq" else (hot, dense)
+
+
+def loss_probe_errors(side, q, c, labels, weights, grad_out, kind):
+    """The probe's fp64 gradient and what fp32 arithmetic with two and with three bf16 parts makes of it.
+    kind "inbatch": the scale is inv_T / n_q * grad_out (no weights); kind "pool": w_i * (inv_T * grad_out / sum w).
+    -> (ref fp64 [rows, dim], loss fp64, E3, E2): E = the largest relative error of an element whose reference is not 0."""
+    inv_t = LOSS_PROBE_INV_T
+    n_q = q.shape[0]
+    s = q.astype(np.float64) @ c.astype(np.float64).T * inv_t
+    s32 = s.astype(np.float32)
+    assert np.array_equal(s32.astype(np.float64), s), "the probe's logits are exact in fp32"
+    assert np.array_equal((q @ c.T) * np.float32(inv_t), s32), "... and an fp32 GEMM finds them"
+    w = np.ones(n_q) if weights is None else np.asarray(weights, np.float64)
+    hit = np.zeros(s.shape, bool)
+    hit[np.arange(n_q), labels] = True
+    # fp64
+    m = s.max(1, keepdims=True)
+    lse = m + np.log(np.exp(s - m).sum(1, keepdims=True))
+    assert np.abs(s - lse).max() <= 12.0, "the derivation of the kernel's own error assumes |s - lse| <= 12"
+    loss = float((w * (lse[:, 0] - s[hit])).sum() / w.sum())
+    G = (np.exp(s - lse) - hit) * (w[:, None] * inv_t * grad_out / w.sum())
+    ref = G @ c.astype(np.float64) if side == "dq" else G.T @ q.astype(np.float64)
+    # fp32, as the kernels evaluate it
+    f32 = np.float32
+    m32 = s32.max(1, keepdims=True)
+    lse32 = (m32 + np.log(np.exp(s32 - m32).sum(1, keepdims=True, dtype=f32))).astype(f32)
+    e32 = (np.exp(s32 - lse32) - hit.astype(f32)).astype(f32)
+    if kind == "inbatch":
+        coef = np.full((n_q, 1), f32(f32(inv_t) / f32(n_q)) * f32(grad_out), f32)
+    else:
+        coef = (w.astype(f32) * f32(f32(f32(inv_t) * f32(grad_out)) / f32(w.sum())))[:, None].astype(f32)
+    g32 = (e32 * coef).astype(f32)
+    hot = c if side == "dq" else q
+    errs = []
+    for n_parts in (3, 2):
+        acc = np.zeros(ref.shape, f32)
+        for p in bf16_parts(g32, n_parts):   # one product per element: the other terms of the GEMM are exact zeros
+            acc = (acc + (p @ hot if side == "dq" else p.T @ hot)).astype(f32)
+        errs.append(probe_error(acc, ref))
+    return ref, loss, errs[0], errs[1]
+
+
+def probe_error(got, ref):
+    """Largest relative error over the elements whose reference is not 0; where it is 0 the value must be exactly 0."""
+    got = np.asarray(got, np.float64)
+    nz = ref != 0
+    assert nz.any() and np.array_equal(got[~nz], np.zeros((~nz).sum())), "an element whose reference is 0 is not exactly 0"
+    return float((np.abs(got[nz] - ref[nz]) / np.abs(ref[nz])).max())
+
+
+def loss_probe_case(kind, side, n_q, n_c, dim):
+    """One probe, complete: operands, labels, weights (pool only; a fifth of them 0) and grad_out.  In-batch: n_c = 2 n_q."""
+    seed = 7 * n_q + n_c + dim + (side == "dc")
+    q, c = loss_probe(side, n_q, n_c, dim, seed)
+    rs = np.random.RandomState(seed + 1)
+    if kind == "inbatch":
+        assert n_c == 2 * n_q
+        return q, c, np.arange(n_q), None, 1.0
+    w = (rs.rand(n_q) + 0.1).astype(np.float32)
+    w[::5] = 0.0
+    return q, c, rs.randint(0, n_c, n_q), w, 1.0

@@ -2,6 +2,7 @@
 tokens -> encoder -> fused mean-pool -> bf16 pack -> fused search; checked against the oracle on the
 SAME encoder outputs, plus the ranking_profile.pt cache/resume behaviour."""
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -16,7 +17,7 @@ class ToyTokenizer:
     """Whitespace tokenizer with the HF call signature used by the reference (padding=True, truncation, max_length)."""
 
     def __call__(self, texts, truncation=True, padding=True, max_length=32, return_tensors="pt"):
-        ids = [[1] + [2 + (hash(w) % 500) for w in t.split()][: max_length - 2] + [3] for t in texts]
+        ids = [[1] + [2 + (zlib.crc32(w.encode()) % 500) for w in t.split()][: max_length - 2] + [3] for t in texts]
         L = max(len(r) for r in ids)
         input_ids = torch.zeros(len(ids), L, dtype=torch.long)
         mask = torch.zeros(len(ids), L, dtype=torch.long)
@@ -108,7 +109,7 @@ def test_generate_ranking_profile_length_sorted_route_gives_the_same_ranking():
     class UnpaddedToy(ToyTokenizer):      # the length-sorted encoder asks for padding=False
         def __call__(self, texts, truncation=True, padding=True, max_length=32, return_tensors="pt", **kw):
             if padding is False:
-                ids = [[1] + [2 + (hash(w) % 500) for w in t.split()][: max_length - 2] + [3] for t in texts]
+                ids = [[1] + [2 + (zlib.crc32(w.encode()) % 500) for w in t.split()][: max_length - 2] + [3] for t in texts]
                 return {"input_ids": ids, "attention_mask": [[1] * len(r) for r in ids]}
             return super().__call__(texts, truncation, padding, max_length, return_tensors)
 
