@@ -25,10 +25,12 @@ EXPORTS = [
     "ccr_bm25_search_workspace_bytes_k", "ccr_bm25_search_last_stats", "ccr_bm25_index_set_idf", "ccr_inbatch_pack3_bf16", "ccr_inbatch_ce_fwd_f32",
     "ccr_search_stream_wait_main_pass", "ccr_pool_ce_workspace_bytes", "ccr_pool_ce_fwd", "ccr_pool_ce_fwd_f32", "ccr_pool_ce_bwd_dev",
     "ccr_bpr_sample", "ccr_bpr_frozen_workspace_bytes", "ccr_bpr_frozen_fwd", "ccr_bpr_frozen_bwd_dev",
+    "ccr_attention_fwd_train_half", "ccr_attention_bwd_workspace_bytes", "ccr_attention_bwd_half", "ccr_add_layernorm_bwd_half", "ccr_gelu_bwd_half",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
 BPR_VERSION = 102   # ... and the one the ccr_bpr_* entry points came with (ops checks it on their first use)
+ENCODER_TRAIN_VERSION = 103   # ... and the encoder layer kernels' training forward and backward (ccr_attention_bwd_half and its kin)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -142,6 +144,12 @@ def load():
     lib.ccr_add_layernorm_half.argtypes = [vp, vp, vp, vp, ctypes.c_float, vp, vp, i64, i32, i32, vp]
     lib.ccr_embed_layernorm_half.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, i64, i32, i32, vp]
     lib.ccr_gelu_half.argtypes = [vp, vp, i64, i32, vp]
+    lib.ccr_attention_fwd_train_half.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, vp]
+    lib.ccr_attention_bwd_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.ccr_attention_bwd_workspace_bytes.restype = sz
+    lib.ccr_attention_bwd_half.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, vp, sz, vp]
+    lib.ccr_add_layernorm_bwd_half.argtypes = [vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, vp]
+    lib.ccr_gelu_bwd_half.argtypes = [vp, vp, vp, i64, i32, vp]
     lib.ccr_meanpool_pack_bf16_packed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.ccr_shard_message_bytes.argtypes = [i32, i32]
     lib.ccr_shard_message_bytes.restype = sz

@@ -11,7 +11,8 @@ Arithmetic: what autocast does in the reference's layer -- 16-bit projection ope
 softmax, fp32 residual stream and LayerNorm -- IN THE AUTOCAST CONTEXT'S OWN 16-BIT TYPE (kernel_dtype): fp16 under the reference's
 `torch.cuda.amp.autocast()` (scripts/al_0_rank.py:8,125: the CUDA default), bf16 under autocast(dtype=torch.bfloat16).  The hidden
 states agree with the module forward under the same autocast to that type's rounding (the tests compare both with the fp32 forward).
-Inference only (eval mode, no dropout, no autograd).
+forward / forward_packed are inference forwards (eval mode, no autograd); forward_train / forward_train_packed run the same layers with
+gradients on, on the kernels' backward (ops.attention_train, add_layernorm_train, gelu_train): no dropout there either.
 
 Only what the kernels cover is accepted (unsupported_reason): a BertModel or DistilBertModel encoder (post-LayerNorm layers, absolute
 positions, exact GELU), head width 64, hidden size a multiple of 256, at most 512 tokens, right-padded batches.  Every other encoder keeps
@@ -69,6 +70,38 @@ def unsupported_reason(model):
         return f"hidden size {hidden} (the LayerNorm kernel takes multiples of 256 up to 2048)"
     if arch.activation != "gelu":
         return f"activation {arch.activation!r} (exact GELU only)"
+    return None
+
+
+_DROPOUT_FIELDS = ("hidden_dropout_prob", "attention_probs_dropout_prob", "dropout", "attention_dropout")
+
+
+def train_unsupported_reason(model):
+    """None when FusedBertEncoder can run a TRAINING forward of `model`: what unsupported_reason asks, and no active dropout (the layer
+    kernels have none): a model in training mode with any dropout probability above 0 is refused; eval mode or all-zero dropout is fine."""
+    reason = unsupported_reason(model)
+    if reason is not None:
+        return reason
+    if getattr(model, "training", False):
+        cfg = getattr(model, "config", None)
+        active = [f"{name}={float(getattr(cfg, name)):g}" for name in _DROPOUT_FIELDS if float(getattr(cfg, name, 0.0) or 0.0) > 0.0]
+        active += [f"{name or 'model'}.p={m.p:g}" for name, m in model.named_modules() if isinstance(m, torch.nn.Dropout) and m.p > 0]
+        if active:
+            return f"dropout is active in training mode ({', '.join(active[:3])}): the layer kernels have no dropout"
+    return None
+
+
+def train_wanted():
+    """The opt-in of the training path: CCREC_FUSED_ENCODER_TRAIN=1 (default off: the torch module trains)."""
+    return os.environ.get("CCREC_FUSED_ENCODER_TRAIN", "").strip() == "1"
+
+
+def train_dtype():
+    """The 16-bit operand type of a training forward on the kernels = the CUDA autocast context's own type when that is fp16 or bf16;
+    None (the module trains) outside autocast or under any other type."""
+    if torch.cuda.is_available() and torch.is_autocast_enabled("cuda"):
+        dtype = torch.get_autocast_dtype("cuda")
+        return dtype if dtype in (torch.float16, torch.bfloat16) else None
     return None
 
 
@@ -236,6 +269,91 @@ class FusedBertEncoder:
         if last < 0 and cls_rows is not None:
             h = h[cls_rows].contiguous()
         return h
+
+    def _embed_train(self, token_ids, positions, token_types, dtype):
+        """_embed with gradients: F.embedding + F.layer_norm on the live tables (not a hot spot: one pass over T rows)."""
+        arch = _describe(self.model)
+        e = arch.embeddings
+        token_ids, positions = token_ids.long(), positions.long()
+        x = F.embedding(token_ids, e.word_embeddings.weight).float()
+        if arch.type_table is not None:
+            types = torch.zeros_like(token_ids) if token_types is None else token_types.long()
+            x = x + F.embedding(types, arch.type_table).float()
+        else:
+            assert token_types is None, "this architecture has no token types"
+        x = x + F.embedding(positions, e.position_embeddings.weight).float()
+        ln = e.LayerNorm
+        h = F.layer_norm(x, (self.hidden,), ln.weight.float(), ln.bias.float(), ln.eps).contiguous()
+        return h, h.to(dtype)
+
+    def _layers_forward_train(self, h, hb, seq_start, lengths, max_len, pad_len, cls_rows=None):
+        """_layers_forward with gradients.  The projections are F.linear on the LIVE parameters cast to hb's dtype: the gradients reach
+        the fp32 master weights and no 16-bit copy can go stale between optimizer steps; autograd keeps the layer activations."""
+        arch = _describe(self.model)
+        half = hb.dtype
+        mods = list(arch.stack.layer)
+        last = len(mods) - 1
+        for i, mod in enumerate(mods):
+            q, k, v, so, ln1, ff, out, ln2 = arch.layer_parts(mod)
+            wqkv = torch.cat([q.weight, k.weight, v.weight]).to(half)
+            bqkv = torch.cat([q.bias, k.bias, v.bias]).to(half)
+            qkv = F.linear(hb, wqkv, bqkv)
+            ctx = ops.attention_train(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=0.125)
+            if i == last and cls_rows is not None:
+                ctx, h = ctx[cls_rows], h[cls_rows]
+            h, hb = ops.add_layernorm_train(F.linear(ctx, so.weight.to(half), so.bias.to(half)), h, ln1.weight.float(), ln1.bias.float(), ln1.eps)
+            mid = ops.gelu_train(F.linear(hb, ff.weight.to(half), ff.bias.to(half)))
+            h, hb = ops.add_layernorm_train(F.linear(mid, out.weight.to(half), out.bias.to(half)), h, ln2.weight.float(), ln2.bias.float(), ln2.eps)
+        if last < 0 and cls_rows is not None:
+            h = h[cls_rows]
+        return h
+
+    def _check_train(self):
+        reason = train_unsupported_reason(self.model)
+        assert reason is None, f"FusedBertEncoder training forward: {reason}"
+
+    def forward_train_packed(self, token_ids, positions, seq_start, lengths, max_len, token_type_ids=None, cls_only=False, dtype=torch.bfloat16):
+        """forward_packed with gradients (same arguments, same result to the kernels' rounding): the parameters of the model receive
+        gradients through the layer kernels' backward.  The model is in eval mode or has all-zero dropout (train_unsupported_reason)."""
+        ops.require_gpu()
+        self._check_train()
+        assert token_ids.is_cuda and token_ids.dim() == 1 and positions.shape == token_ids.shape and 1 <= int(max_len) <= 512
+        with torch.autocast("cuda", enabled=False):
+            h, hb = self._embed_train(token_ids, positions, token_type_ids, dtype)
+            return self._layers_forward_train(h, hb, seq_start, lengths, int(max_len), 0, seq_start.long() if cls_only else None)
+
+    def forward_train(self, input_ids, lengths, token_type_ids=None, packed=None, lengths_host=None, cls_only=False, dtype=torch.bfloat16):
+        """forward with gradients: the same arguments and the same [B, L, hidden] (or [B, 1, hidden]) fp32 result; padding rows are zeros
+        (packed) or finite values nobody reads, and carry no gradient into the parameters."""
+        ops.require_gpu()
+        self._check_train()
+        assert input_ids.is_cuda and input_ids.dim() == 2
+        B, L = input_ids.shape
+        assert L <= 512 and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.numel() == B
+        dev = input_ids.device
+        if packed is None or packed:
+            lens_h = lengths.cpu() if lengths_host is None else torch.as_tensor(lengths_host)
+            total, longest = int(lens_h.sum()), int(lens_h.max()) if B else 0
+            if packed is None:
+                packed = total < 0.9 * B * L
+        with torch.autocast("cuda", enabled=False):
+            if packed:
+                keep = (torch.arange(L, device=dev)[None, :] < lengths[:, None]).flatten().nonzero().squeeze(1)   # rows of the real tokens
+                assert keep.numel() == total, "lengths_host does not match lengths"
+                h, hb = self._embed_train(input_ids.flatten()[keep], keep % L, None if token_type_ids is None else token_type_ids.flatten()[keep], dtype)
+                max_len, pad_len = max(longest, 1), 0
+                seq_start = (torch.cumsum(lengths, 0, dtype=torch.int32) - lengths).contiguous()
+            else:
+                h, hb = self._embed_train(input_ids.flatten(), torch.arange(L, device=dev).repeat(B),
+                                          None if token_type_ids is None else token_type_ids.flatten(), dtype)
+                max_len, pad_len = L, L
+                seq_start = torch.arange(B, dtype=torch.int32, device=dev) * L
+            h = self._layers_forward_train(h, hb, seq_start, lengths, max_len, pad_len, seq_start.long() if cls_only else None)
+            if cls_only:
+                return h.view(B, 1, self.hidden)
+            if packed:
+                h = torch.zeros(B * L, self.hidden, dtype=torch.float32, device=dev).index_copy(0, keep, h)
+        return h.view(B, L, self.hidden)
 
     @torch.no_grad()
     def forward_packed(self, token_ids, positions, seq_start, lengths, max_len, token_type_ids=None, cls_only=False, dtype=torch.bfloat16):

@@ -103,6 +103,8 @@ class NaiveItemTower(ItemTowerBase):
         caller asks for reduced precision (autocast -- al_0_rank.py:125 -- or CCREC_FUSED_ENCODER=1), the encoder is a BertModel the
         kernels cover, and the batch is plain right-padded token ids.  None = run the module."""
         from . import fused_bert
+        if torch.is_grad_enabled():      # a training forward: the module, unless CCREC_FUSED_ENCODER_TRAIN=1 opts into the kernels' backward
+            return self._train_on_kernels(inputs, cls_only)
         dtype = fused_bert.kernel_dtype("auto")      # the caller's autocast type: fp16 under the reference's autocast(), al_0_rank.py:125
         if dtype is None or torch.is_grad_enabled() or getattr(self.cls_model, "training", True):
             return None
@@ -118,6 +120,28 @@ class NaiveItemTower(ItemTowerBase):
             return None
         enc.refresh(dtype)      # the weight copies follow the module's parameters (fine-tuning between two ranking steps)
         return enc.forward(inputs["input_ids"], lengths, inputs.get("token_type_ids"), cls_only=cls_only, dtype=dtype)
+
+    def _train_on_kernels(self, inputs, cls_only=False):
+        """Training forward (gradients on; bbpr.py:195-197, bert_mt.py:105-113 call the tower three times per step) on the layer kernels
+        and their backward -- only when CCREC_FUSED_ENCODER_TRAIN=1 asks for it, the caller's autocast type is fp16 or bf16, the encoder
+        is covered and has no active dropout, and the batch is plain right-padded token ids.  None = run the module."""
+        from . import fused_bert
+        if not fused_bert.train_wanted():
+            return None
+        dtype = fused_bert.train_dtype()
+        if dtype is None or fused_bert.train_unsupported_reason(self.cls_model) is not None:
+            return None
+        if not set(inputs) <= {"input_ids", "attention_mask", "token_type_ids"} or "input_ids" not in inputs or "attention_mask" not in inputs:
+            return None
+        if not inputs["input_ids"].is_cuda:
+            return None
+        enc = fused_bert.for_model(self.cls_model)
+        if enc is None or ("token_type_ids" in inputs and not enc.has_token_types):
+            return None
+        lengths = fused_bert.prefix_lengths(inputs["attention_mask"])
+        if lengths is None:
+            return None
+        return enc.forward_train(inputs["input_ids"], lengths, inputs.get("token_type_ids"), cls_only=cls_only, dtype=dtype)
 
     def forward(self, cls=None, text=None, input_step="inputs", output_step="embedding", **inputs):
         if input_step == "text":

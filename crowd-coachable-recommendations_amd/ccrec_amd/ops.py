@@ -251,6 +251,177 @@ def add_layernorm(x, residual, gamma, beta, eps, want_f32=True, want_bf16=True):
     return f32, b16
 
 
+# ---- the layer kernels with a backward (ccr_attention_fwd_train_half / ccr_*_bwd_half): fine-tuning through the encoder, the three
+# encoder forwards + backward of a training step (src/ccrec/models/bbpr.py:195-197, bert_mt.py:105-113) ---------------------------------
+_ENCODER_TRAIN_CHECKED = False
+
+
+def _require_encoder_train():
+    """require_gpu() + once: the loaded library has the encoder layer backward entry points (ccr_version() >= 103)."""
+    global _ENCODER_TRAIN_CHECKED
+    lib = require_gpu()
+    if not _ENCODER_TRAIN_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.ENCODER_TRAIN_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, the encoder training ops need {_lib.ENCODER_TRAIN_VERSION}: rebuild it "
+                                f"(python -c 'import __graft_entry__ as g; g.build()')")
+        _ENCODER_TRAIN_CHECKED = True
+    return lib
+
+
+def attention_fwd_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125):
+    """attention() that also returns lse [T, n_heads] fp32, the log-sum-exp of every real query row's scaled scores (0 on padding
+    rows): what attention_bwd rebuilds the probabilities from (ccr_attention_fwd_train_half).  -> (out, lse); out has attention()'s bits."""
+    lib = _require_encoder_train()
+    code = _half_code(qkv.dtype)
+    assert qkv.is_cuda and qkv.dim() == 2 and qkv.is_contiguous()
+    T, width = qkv.shape
+    assert width == 3 * n_heads * 64, f"qkv rows are {width} wide, expected 3 x {n_heads} heads x 64"
+    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
+    assert seq_start.is_contiguous() and seq_len.is_contiguous() and seq_start.numel() == seq_len.numel()
+    out = torch.empty(T, n_heads * 64, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(T, n_heads, dtype=torch.float32, device=qkv.device)
+    with _on(qkv):
+        _lib.check(lib.ccr_attention_fwd_train_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), _ptr(lse), seq_len.numel(),
+                                                    int(n_heads), int(max_len), int(pad_len), float(scale), code, _stream(qkv)),
+                   "ccr_attention_fwd_train_half")
+    return out, lse
+
+
+def attention_bwd(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125):
+    """d_qkv [T, 3 * n_heads * 64] (qkv's dtype and layout) from attention_fwd_train's (out, lse) and d_out [T, n_heads * 64]
+    (ccr_attention_bwd_half).  Rows of the sequences' padding get zeros; so do rows that belong to no sequence."""
+    lib = _require_encoder_train()
+    code = _half_code(qkv.dtype)
+    T = qkv.shape[0]
+    assert qkv.is_cuda and qkv.is_contiguous() and tuple(qkv.shape) == (T, 3 * n_heads * 64)
+    for t in (out, d_out):
+        assert t.is_cuda and t.dtype == qkv.dtype and tuple(t.shape) == (T, n_heads * 64) and t.is_contiguous()
+    assert lse.is_cuda and lse.dtype == torch.float32 and tuple(lse.shape) == (T, n_heads) and lse.is_contiguous()
+    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_contiguous() and seq_len.is_contiguous()
+    n_seq = seq_len.numel()
+    need = int(lib.ccr_attention_bwd_workspace_bytes(n_seq, int(n_heads), int(max_len)))
+    if need == 0:
+        _lib.check(_lib.CCR_ERR_INVALID, "ccr_attention_bwd_workspace_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
+    d_qkv = torch.zeros_like(qkv)
+    with _on(qkv):
+        _lib.check(lib.ccr_attention_bwd_half(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(seq_start), _ptr(seq_len), _ptr(d_qkv),
+                                              n_seq, int(n_heads), int(max_len), int(pad_len), float(scale), code, _ptr(ws), need,
+                                              _stream(qkv)), "ccr_attention_bwd_half")
+    return d_qkv
+
+
+def add_layernorm_bwd(x, residual, gamma, eps, d_y, want_res=True, want_x=True, want_gamma=True, want_beta=True):
+    """The backward of add_layernorm (ccr_add_layernorm_bwd_half): d_y [rows, dim] fp32 = the summed gradient of the LayerNorm output
+    -> (d_res fp32 = the gradient of x + residual, d_x = the same rounded to x's dtype, d_gamma, d_beta [dim] fp32); None where not wanted."""
+    lib = _require_encoder_train()
+    code = _half_code(x.dtype)
+    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
+    rows, dim = x.shape
+    if residual is not None:
+        assert residual.is_cuda and residual.dtype == torch.float32 and tuple(residual.shape) == (rows, dim) and residual.is_contiguous()
+    assert gamma.is_cuda and gamma.dtype == torch.float32 and tuple(gamma.shape) == (dim,) and gamma.is_contiguous()
+    assert d_y.is_cuda and d_y.dtype == torch.float32 and tuple(d_y.shape) == (rows, dim) and d_y.is_contiguous()
+    dev = x.device
+    d_res = torch.empty(rows, dim, dtype=torch.float32, device=dev) if want_res else None
+    d_x = torch.empty(rows, dim, dtype=x.dtype, device=dev) if want_x else None
+    d_gamma = torch.empty(dim, dtype=torch.float32, device=dev) if want_gamma else None
+    d_beta = torch.empty(dim, dtype=torch.float32, device=dev) if want_beta else None
+    need = min((rows + 3) // 4, 512) * 2 * dim * 4 if (want_gamma or want_beta) else 0      # per-workgroup column sums (include/ccr_retrieval.h)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with _on(x):
+        _lib.check(lib.ccr_add_layernorm_bwd_half(_ptr(x), _ptr(residual), _ptr(gamma), float(eps), _ptr(d_y), _ptr(d_res), _ptr(d_x),
+                                                  _ptr(d_gamma), _ptr(d_beta), rows, dim, code, _ptr(ws), need, _stream(x)),
+                   "ccr_add_layernorm_bwd_half")
+    return d_res, d_x, d_gamma, d_beta
+
+
+def gelu_bwd(x, d_y):
+    """d_x = d_y (Phi(x) + x phi(x)) of the exact GELU from its pre-activation x (ccr_gelu_bwd_half); x's dtype."""
+    lib = _require_encoder_train()
+    code = _half_code(x.dtype)
+    assert x.is_cuda and x.is_contiguous() and x.numel() % 8 == 0
+    assert d_y.is_cuda and d_y.dtype == x.dtype and d_y.shape == x.shape and d_y.is_contiguous()
+    d_x = torch.empty_like(x)
+    with _on(x):
+        _lib.check(lib.ccr_gelu_bwd_half(_ptr(x), _ptr(d_y), _ptr(d_x), x.numel(), code, _stream(x)), "ccr_gelu_bwd_half")
+    return d_x
+
+
+class _AttentionTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale):
+        out, lse = attention_fwd_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale)
+        ctx.save_for_backward(qkv, out, lse, seq_start, seq_len)
+        ctx.shape = (int(n_heads), int(max_len), int(pad_len), float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        qkv, out, lse, seq_start, seq_len = ctx.saved_tensors
+        n_heads, max_len, pad_len, scale = ctx.shape
+        d_qkv = attention_bwd(qkv, out, lse, d_out.to(qkv.dtype).contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale)
+        return d_qkv, None, None, None, None, None, None
+
+
+def attention_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125):
+    """attention() with a backward: the same context rows, bit for bit; the gradient reaches qkv (the stacked projection's output)."""
+    return _AttentionTrain.apply(qkv.contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale)
+
+
+class _AddLayerNormTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, eps):
+        f32, b16 = add_layernorm(x, residual, gamma, beta, eps)
+        ctx.save_for_backward(x, residual, gamma)
+        ctx.eps = float(eps)
+        return f32, b16
+
+    @staticmethod
+    def backward(ctx, d_f32, d_b16):
+        x, residual, gamma = ctx.saved_tensors
+        # the two outputs are one value in two precisions: their gradients add up (fp32) before the kernel runs
+        if d_f32 is None:
+            d_y = d_b16.float()
+        elif d_b16 is None:
+            d_y = d_f32.float()
+        else:
+            d_y = d_f32.float() + d_b16
+        need = ctx.needs_input_grad
+        d_res, d_x, d_gamma, d_beta = add_layernorm_bwd(x, residual, gamma, ctx.eps, d_y.contiguous(), want_res=residual is not None and need[1],
+                                                        want_x=need[0], want_gamma=need[2], want_beta=need[3])
+        return d_x, d_res, d_gamma, d_beta, None
+
+
+def add_layernorm_train(x, residual, gamma, beta, eps):
+    """add_layernorm() with a backward -> (fp32 rows, their copy in x's dtype).  Both outputs are differentiable; the gradient reaches x
+    (in its dtype), residual, gamma and beta."""
+    return _AddLayerNormTrain.apply(x.contiguous(), None if residual is None else residual.contiguous(), gamma.contiguous(), beta.contiguous(), eps)
+
+
+class _GeluTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        lib = require_gpu()
+        y = torch.empty_like(x)
+        with _on(x):
+            _lib.check(lib.ccr_gelu_half(_ptr(x), _ptr(y), x.numel(), _half_code(x.dtype), _stream(x)), "ccr_gelu_half")
+        return y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        (x,) = ctx.saved_tensors
+        return gelu_bwd(x, d_y.to(x.dtype).contiguous())
+
+
+def gelu_train(x):
+    """Exact GELU, out of place, with a backward (gelu_() overwrites the pre-activation the backward needs)."""
+    assert x.is_cuda and x.numel() % 8 == 0
+    return _GeluTrain.apply(x.contiguous())
+
+
 class CorpusIndex:
     """A resident bf16 corpus shard + its search state (ccr_index).  Build once per AL step, query many.
 

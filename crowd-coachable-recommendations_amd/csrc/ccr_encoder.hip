@@ -13,66 +13,10 @@
 #include <stdlib.h>
 
 #include "ccr_common.h"
+#include "ccr_encoder_common.h"
 #include "ccr_index.h"
 
 namespace ccr {
-
-typedef __bf16 ebf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ef16x8 __attribute__((ext_vector_type(8)));
-typedef float ef32x16 __attribute__((ext_vector_type(16)));
-
-// The layer's 16-bit operand type: bf16 or fp16 -- whichever the caller's autocast context names (the reference's
-// torch.cuda.amp.autocast() at scripts/al_0_rank.py:125 is fp16).  Same kernels, same MFMA rate (v_mfma_f32_32x32x16_f16 /
-// _bf16), fp32 scores / softmax / residual stream / LayerNorm either way; only the rounding of the 16-bit operands differs.
-template <int DT>
-struct Half16;
-template <>
-struct Half16<CCR_DTYPE_BF16> {
-    typedef __bf16 elem;
-    typedef ebf16x8 vec8;
-    static __device__ __forceinline__ ef32x16 mfma(vec8 a, vec8 b, ef32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float lo(uint32_t w) { return __uint_as_float(w << 16); }
-    static __device__ __forceinline__ float hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-};
-template <>
-struct Half16<CCR_DTYPE_F16> {
-    typedef _Float16 elem;
-    typedef ef16x8 vec8;
-    static __device__ __forceinline__ ef32x16 mfma(vec8 a, vec8 b, ef32x16 c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ float lo(uint32_t w) {
-        union {
-            uint32_t u;
-            _Float16 h[2];
-        } x;
-        x.u = w;
-        return (float)x.h[0];
-    }
-    static __device__ __forceinline__ float hi(uint32_t w) {
-        union {
-            uint32_t u;
-            _Float16 h[2];
-        } x;
-        x.u = w;
-        return (float)x.h[1];
-    }
-};
-// four fp32 values -> four 16-bit values (round to nearest even; a NaN stays a NaN), 8 bytes
-template <class E>
-__device__ __forceinline__ uint2 round4(float a, float b, float c, float d) {
-    union {
-        E h[4];
-        uint2 u;
-    } w;
-    w.h[0] = (E)a;
-    w.h[1] = (E)b;
-    w.h[2] = (E)c;
-    w.h[3] = (E)d;
-    return w.u;
-}
 
 constexpr int ATT_MAX_THREADS = 512;   // up to 8 waves: one workgroup per (sequence, head) stages K / V once, wave w takes query blocks w, w + waves, ..
 constexpr int ATT_QW = 32;             // query rows per wave step (the N side of one 32x32 MFMA tile)
@@ -90,20 +34,30 @@ constexpr int ATT_KROW = 144;      // bytes per key row in LDS: 128 + 16, so the
 __host__ __device__ inline size_t attention_lds_bytes(int lk_pad) {
     return (size_t)lk_pad * ATT_KROW + (size_t)ATT_HEAD * (2 * (size_t)lk_pad + 8);   // (the row-major image needs 512 bytes less)
 }
-typedef short es16x4 __attribute__((ext_vector_type(4)));
-
 // S^T = K Q^T on v_mfma_f32_32x32x16_bf16: A = 32 keys (lane & 31) x 8 head columns (8 * (lane >> 5) + j), B = 32 queries
 // likewise -- both operands are 16 contiguous bytes of a row, no transposition.  C layout: lane -> query (lane & 31),
 // register e -> key (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5): a lane owns ONE query and 16 of the tile's 32 keys, so the
 // softmax row reductions are in-lane plus one exchange with lane ^ 32, and the probabilities, rounded to bf16, ARE the B
 // operand of O^T = V^T P^T (contraction index = key; the A operand V^T is read from the transposed LDS image with the
 // same key permutation: element j of lane half g <-> key 16 s + 4 g + (j & 3) + 8 (j >> 2)).
-template <int DT, bool TR>
+// LSE = true (the training forward, ccr_attention_fwd_train_half): the kernel also writes lse [T][H] fp32, the natural-log log-sum-exp of
+// every live query row's scaled scores (0 on padding rows) -- what the backward (ccr_encoder_bwd.hip) rebuilds the probabilities from.
+// LSE = false takes an empty struct in the pointer's place: the inference instantiations keep their argument layout and their code.
+struct NoLse {};
+template <bool LSE>
+struct LseArg {
+    typedef NoLse type;
+};
+template <>
+struct LseArg<true> {
+    typedef float *type;
+};
+template <int DT, bool TR, bool LSE = false>
 __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16_t *__restrict__ qkv,
                                                                   const int32_t *__restrict__ seq_start,
                                                                   const int32_t *__restrict__ seq_len,
                                                                   uint16_t *__restrict__ out, int H, int pad_len, int max_len,
-                                                                  int lk_pad, float scale_log2e) {
+                                                                  int lk_pad, float scale_log2e, typename LseArg<LSE>::type lse) {
     typedef Half16<DT> HT;
     typedef typename HT::vec8 vec8;
     typedef typename HT::elem elem;
@@ -132,6 +86,7 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
             uint4 *dst = reinterpret_cast<uint4 *>(Og + (int64_t)q * HD);
 #pragma unroll
             for (int i = 0; i < 8; ++i) dst[i] = make_uint4(0u, 0u, 0u, 0u);
+            if constexpr (LSE) lse[(row0 + q) * H + h] = 0.f;
         }
         return;
     }
@@ -210,6 +165,9 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
                 uint2 *dst = reinterpret_cast<uint2 *>(Og + (int64_t)q * HD);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) dst[i * 2 + g] = make_uint2(0u, 0u);
+                if constexpr (LSE) {
+                    if (g == 0) lse[(row0 + q) * H + h] = 0.f;
+                }
             }
             continue;
         }
@@ -310,6 +268,10 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
         }
 
         const float inv = 1.f / (lsum + __shfl_xor(lsum, 32));
+        if constexpr (LSE) {   // ln sum_k exp(scale s_k) = scale m + ln sum_k exp(scale (s_k - m)); m and the sum are the same in both lane halves
+            const float ltot = lsum + __shfl_xor(lsum, 32);
+            if (g == 0 && q < rows) lse[(row0 + q) * H + h] = q < len ? fmaf(m * scale_log2e, 0.6931471805599453f, logf(ltot)) : 0.f;
+        }
         if (q < len) {
             // O^T tile: lane -> query, register e -> head column 32 db + (e & 3) + 8 (e >> 2) + 4 g: four consecutive columns per 8-byte store
             uint16_t *dst = Og + (int64_t)q * HD + 4 * g;
@@ -326,20 +288,6 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
             for (int i = 0; i < 8; ++i) dst[i * 2 + g] = make_uint2(0u, 0u);
         }
     }   // query blocks of this wave
-}
-
-// The mean of a row held in registers (v[c][j] per lane), from a first estimate m0 = sum / DIM: one correction step m0 + mean(v - m0).
-// The fp32 sum of DIM elements leaves m0 an ulp or so off, which is harmless next to a variance but IS the whole deviation of a row
-// whose elements are all equal: there v - m0 is a few ulps, exactly, its sum is exact, and the corrected mean is v itself -- the row
-// normalises to beta for every eps, where the uncorrected mean left gamma (v - m0) / sqrt(eps): 0.18 to 1.0 gamma at eps = 1e-12, by width.
-template <int C>
-__device__ __forceinline__ float refined_mean(const float (&v)[C][4], float m0) {
-    float sd = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) sd += ((v[c][0] - m0) + (v[c][1] - m0)) + ((v[c][2] - m0) + (v[c][3] - m0));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sd += __shfl_xor(sd, o);
-    return m0 + sd * (1.f / (256 * C));
 }
 
 // One wave per row of dim = 256 * C elements; lane owns elements 4 * (64 c + lane) .. + 3 of every 256-element slice.
@@ -529,9 +477,9 @@ static int embed_layernorm_any(const float *word_table, int64_t vocab, const flo
     return CCR_OK;
 }
 
-template <int DT>
+template <int DT, bool LSE = false>
 static int attention_any(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, int n_seq, int n_heads,
-                         int max_len, int pad_len, float scale, hipStream_t stream) {
+                         int max_len, int pad_len, float scale, hipStream_t stream, typename LseArg<LSE>::type lse = {}) {
     const int lk_pad = (max_len + ATT_KB - 1) / ATT_KB * ATT_KB;
     const size_t lds = attention_lds_bytes(lk_pad);
     // the opt-in is cached per (kernel, device) whatever the size: ask for the kernel's maximum once (512 keys), not for this call's
@@ -540,7 +488,7 @@ static int attention_any(const uint16_t *qkv, const int32_t *seq_start, const in
         const char *e = getenv("CCR_ATT_TR");      // A/B knob: 0 = the transposed-image kernel of rounds 3-5
         return !(e && atoi(e) == 0);
     }();
-    const int rc = ensure_dynamic_lds(tr ? reinterpret_cast<const void *>(&attention_kernel<DT, true>) : reinterpret_cast<const void *>(&attention_kernel<DT, false>),
+    const int rc = ensure_dynamic_lds(tr ? reinterpret_cast<const void *>(&attention_kernel<DT, true, LSE>) : reinterpret_cast<const void *>(&attention_kernel<DT, false, LSE>),
                                       attention_lds_bytes(512));
     if (rc != CCR_OK) return rc;
     int waves = (max_len + ATT_QW - 1) / ATT_QW;   // one wave per 32 query rows, at most 8 (longer sequences: the waves loop)
@@ -552,11 +500,11 @@ static int attention_any(const uint16_t *qkv, const int32_t *seq_start, const in
     if (lk_pad == 192 && waves > 4) waves = 4;
     CCR_REQUIRE(lk_pad * 8 <= ATT_KMAX * 64 * waves && lk_pad * 4 <= ATT_VMAX * 64 * waves, "ccr_attention: staging bound (internal)");
     if (tr)
-        hipLaunchKernelGGL((attention_kernel<DT, true>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
-                           n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f);
+        hipLaunchKernelGGL((attention_kernel<DT, true, LSE>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
+                           n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f, lse);
     else
-        hipLaunchKernelGGL((attention_kernel<DT, false>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
-                           n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f);
+        hipLaunchKernelGGL((attention_kernel<DT, false, LSE>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
+                           n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f, lse);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
@@ -576,9 +524,6 @@ static int gelu_any(const uint16_t *x, uint16_t *y, int64_t n, hipStream_t strea
 
 using namespace ccr;
 
-#define CCR_REQUIRE_HALF(dtype, who) \
-    CCR_REQUIRE((dtype) == CCR_DTYPE_BF16 || (dtype) == CCR_DTYPE_F16, who ": half_dtype=%d (CCR_DTYPE_F16 or CCR_DTYPE_BF16)", (int)(dtype))
-
 extern "C" int ccr_attention_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, int n_seq,
                                   int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *stream) {
     CCR_REQUIRE(qkv && seq_start && seq_len && out, "ccr_attention_half: null pointer");
@@ -592,6 +537,21 @@ extern "C" int ccr_attention_half(const uint16_t *qkv, const int32_t *seq_start,
     return half_dtype == CCR_DTYPE_F16
                ? attention_any<CCR_DTYPE_F16>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream)
                : attention_any<CCR_DTYPE_BF16>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream);
+}
+
+extern "C" int ccr_attention_fwd_train_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, float *lse,
+                                            int n_seq, int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *stream) {
+    CCR_REQUIRE(qkv && seq_start && seq_len && out && lse, "ccr_attention_fwd_train_half: null pointer");
+    CCR_REQUIRE_HALF(half_dtype, "ccr_attention_fwd_train_half");
+    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024, "ccr_attention_fwd_train_half: bad shape n_seq=%d n_heads=%d",
+                n_seq, n_heads);
+    CCR_REQUIRE(max_len > 0 && max_len <= 512 && pad_len >= 0 && pad_len <= 512,
+                "ccr_attention_fwd_train_half: max_len=%d pad_len=%d (1..512 tokens per sequence)", max_len, pad_len);
+    CCR_REQUIRE(scale > 0.f, "ccr_attention_fwd_train_half: scale must be positive");
+    if (n_seq == 0) return CCR_OK;
+    return half_dtype == CCR_DTYPE_F16
+               ? attention_any<CCR_DTYPE_F16, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream, lse)
+               : attention_any<CCR_DTYPE_BF16, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream, lse);
 }
 
 extern "C" int ccr_attention_bf16(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out,

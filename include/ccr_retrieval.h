@@ -190,6 +190,42 @@ int ccr_embed_layernorm_half(const float *word_table, int64_t vocab, const float
 int ccr_gelu_half(const uint16_t *x, uint16_t *y, int64_t n, int half_dtype, void *stream);
 
 /*
+ * The layer kernels' training forward and backward (library version 103): fine-tuning through the encoder.  The reference's training
+ * steps run the encoder three times per step with gradients on, then its backward (src/ccrec/models/bbpr.py:195-197 _pairwise over
+ * i | j | k texts; bert_mt.py:105-113 the same three towers for the contrastive and the masked-token terms).  Arrays, layouts and
+ * half_dtype as in the forward entry points above; scores, probabilities, dS and every reduction are fp32; no atomics: results are
+ * bit-identical from run to run.
+ * ccr_attention_fwd_train_half (bbpr.py:195-197, bert_mt.py:105-113): the attention forward, `out` bit-identical to ccr_attention_half's,
+ *   which also writes lse [T][n_heads] fp32: the natural-log log-sum-exp of every real query row's scaled scores (0 on padding rows).
+ * ccr_attention_bwd_half (bbpr.py:195-197, bert_mt.py:105-113: loss.backward() through BertSelfAttention): d_qkv [T][3 * n_heads * 64],
+ *   the gradient of the stacked projection's output in qkv's type and layout, from qkv, the forward's out and lse, and d_out
+ *   [T][n_heads * 64].  Every row inside a sequence's max(seq_len, pad_len) rows is written: padding rows and empty sequences get
+ *   zeros; padding rows of qkv, out and d_out are never read.
+ *   workspace: ccr_attention_bwd_workspace_bytes(n_seq, n_heads, max_len) bytes of DEVICE memory, 4-byte aligned; CCR_ERR_WORKSPACE
+ *   if it is smaller.
+ * ccr_attention_bwd_workspace_bytes (bbpr.py:195-197, bert_mt.py:105-113: the scratch of that backward): one fp32 per query row (max_len
+ *   rounded up to 32) and head; 0 with a ccr_last_error() text for a shape outside the limits above.
+ * ccr_add_layernorm_bwd_half (bbpr.py:195-197, bert_mt.py:105-113: BertSelfOutput / BertOutput LayerNorm): from x_half, residual (or
+ *   NULL), gamma, eps as the forward took them and d_y [rows][dim] fp32, the summed gradient of the LayerNorm output:
+ *   d_res [rows][dim] fp32 = the gradient of x + residual; d_x = the same values rounded to x's type; d_gamma, d_beta [dim] fp32.
+ *   Any of the four may be NULL.  Mean and rstd are recomputed as the forward computes them.
+ *   workspace (DEVICE, 16-byte aligned), needed when d_gamma or d_beta is asked for: min((rows + 3) / 4, 512) * 2 * dim * 4 bytes
+ *   (per-workgroup column sums, added up by a second kernel in a fixed order); NULL / 0 otherwise.
+ * ccr_gelu_bwd_half (bert_mt.py:105-113, bbpr.py:195-197: BertIntermediate): d_x = d_y * (Phi(x) + x * phi(x)) from the pre-activation
+ *   x, n % 8 == 0, 16-byte aligned arrays, fp32 arithmetic rounded once (d_x may be d_y).
+ */
+int ccr_attention_fwd_train_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, float *lse,
+                                 int n_seq, int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *stream);
+size_t ccr_attention_bwd_workspace_bytes(int n_seq, int n_heads, int max_len);
+int ccr_attention_bwd_half(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *d_out, const int32_t *seq_start,
+                           const int32_t *seq_len, uint16_t *d_qkv, int n_seq, int n_heads, int max_len, int pad_len, float scale,
+                           int half_dtype, void *workspace, size_t workspace_bytes, void *stream);
+int ccr_add_layernorm_bwd_half(const uint16_t *x_half, const float *residual, const float *gamma, float eps, const float *d_y,
+                               float *d_res, uint16_t *d_x, float *d_gamma, float *d_beta, int64_t rows, int dim, int half_dtype,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int ccr_gelu_bwd_half(const uint16_t *x, const uint16_t *d_y, uint16_t *d_x, int64_t n, int half_dtype, void *stream);
+
+/*
  * Build a search index over a resident bf16 corpus shard (borrowed pointer, no copy).
  * Replaces: the host-resident fp32 passage matrix of scripts/ms_marco_eval.py:199-201,208-210.
  *   global_row_offset: id of row 0 of this shard in the whole corpus (multi-GPU row sharding).
