@@ -1,4 +1,5 @@
 """Shared test helpers: comparison of rank lists (tie-aware); child processes that must not hang silently."""
+import math
 import os
 import signal
 import subprocess
@@ -310,3 +311,289 @@ def loss_probe_case(kind, side, n_q, n_c, dim):
     w = (rs.rand(n_q) + 0.1).astype(np.float32)
     w[::5] = 0.0
     return q, c, rs.randint(0, n_c, n_q), w, 1.0
+
+
+# ---------------------------------------------------------------------------------------------- the selector probe of the attention backward
+# Inputs for which every element of dQ, dK and dV is a sum of a few exactly representable products, so that a streamed row that is dropped,
+# doubled or misplaced moves an element by many spacings instead of hiding in rounding noise.  One head (width 64, scale 1/8), before its roll:
+#   columns  0..47  the 8-bit CODE of a key group, as +-4, repeated 6 times: K holds the code of the key's own group, Q the code of the group
+#                   the query SELECTS.  A group is a pair of keys (partners drawn from different 32-row tiles where the length allows) or,
+#                   with an odd length, the one key left single.
+#   columns 48..55  Q payload, integers in [-2, 2]; K is zero there
+#   columns 56..63  K payload, integers in [-2, 2]; Q is zero there
+# so a query scores 48 * 16 / 8 = 96 on the keys of its group, both alike, and at most 96 - 2 * 16 * 6 / 8 = 72 on any other: the softmax is
+# (1/2, 1/2) on a pair or 1 on a single key up to e^-24, O = (V_a + V_b) / 2, dV = 1/2 sum d_out over the selecting queries,
+# dS = +-1/4 (dp_a - dp_b), dQ = 1/32 (dp_a - dp_b) (K_a - K_b) (non-zero on the K payload only: the codes cancel) and
+# dK = 1/32 sum_i +-(dp_a - dp_b)_i Q_i.  V has 4 non-zero columns per row and d_out is dense, integers in [-2, 2].
+# dQ lives on the 8 K-payload columns of a head, so it takes EIGHT heads, rolled by 0, 8, .., 56 columns, for every column of dQ to be
+# non-zero somewhere (four heads rolled by 16 reach 32 of the 64).  The query -> group map is many-to-one and drawn so that every
+# (query tile, key tile) pair of 32 x 32 rows holds a selected key in every head; a tile with too few queries for that (the one-row tile of
+# length 257) reaches every key tile over the eight heads.
+ENC_PROBE_LENS = [2, 31, 33, 64, 65, 257, 512]
+ENC_PROBE_HEADS = 8
+ENC_PROBE_MARGIN = 24.0        # lowest (own group's score - any other score), asserted by tests/test_cpu_encoder_probe.py
+ENC_PROBE_SNAP = 64.0          # every exact gradient is a multiple of 1 / 64
+
+
+def round16(x, kind):
+    """float32 -> the nearest value of the 16-bit type ("bf16" | "fp16", ties to even), as float32."""
+    x = np.ascontiguousarray(x, np.float32)
+    return bf16_round(x) if kind == "bf16" else x.astype(np.float16).astype(np.float32)
+
+
+def attention_grads_fp64(q, k, v, d_out, scale=0.125):
+    """Plain softmax attention of one head and its backward in numpy fp64 -> (out, lse, dq, dk, dv, p)."""
+    q, k, v, d_out = (np.asarray(a, np.float64) for a in (q, k, v, d_out))
+    s = q @ k.T * scale
+    m = s.max(1, keepdims=True)
+    e = np.exp(s - m)
+    lse = m[:, 0] + np.log(e.sum(1))
+    p = e / e.sum(1, keepdims=True)
+    out = p @ v
+    ds = p * (d_out @ v.T - (d_out * out).sum(1, keepdims=True))
+    return out, lse, ds @ k * scale, ds.T @ q * scale, p.T @ d_out, p
+
+
+def _probe_head_draw(length, head, rs):
+    tile = np.arange(length) // 32
+    n_tiles = int(tile[-1]) + 1
+    perm = rs.permutation(length)
+    a, b = perm[0:length - length % 2:2].copy(), perm[1:length:2].copy()
+    for i in np.nonzero(tile[a] == tile[b])[0]:          # partners into different tiles where a swap of two partners does it
+        for j in rs.permutation(len(a)):
+            if tile[a[i]] != tile[b[j]] and tile[a[j]] != tile[b[i]]:
+                b[i], b[j] = b[j], b[i]
+                break
+    groups = [(int(x), int(y)) for x, y in zip(a, b)] + ([(int(perm[-1]),)] if length % 2 else [])
+    codes = rs.permutation(256)[:len(groups)]
+    group_tiles = [set(int(tile[m]) for m in grp) for grp in groups]
+    select = np.empty(length, np.int64)
+    for t in range(n_tiles):                              # greedy: the tile's queries first reach every key tile, then draw freely
+        mine = np.nonzero(tile == t)[0]
+        missing = set(range(n_tiles))
+        if 2 * len(mine) < n_tiles:                       # too few queries for every key tile: each head takes its share of them
+            first = 2 * head % n_tiles
+            missing = {first, first + 1} & set(range(n_tiles))
+        for i in rs.permutation(mine):
+            choice = int(rs.randint(len(groups)))
+            if missing:
+                gain = np.array([len(gt & missing) for gt in group_tiles])
+                best = np.nonzero(gain == gain.max())[0]
+                choice = int(best[rs.randint(len(best))])
+                missing -= group_tiles[choice]
+            select[i] = choice
+    bits = lambda c: np.tile(((np.asarray(c)[:, None] >> np.arange(8)) & 1) * 8.0 - 4.0, (1, 6))      # [n, 48] of +-4
+    group_of_key = np.empty(length, np.int64)
+    for gi, grp in enumerate(groups):
+        group_of_key[list(grp)] = gi
+    q, k, v = np.zeros((length, 64)), np.zeros((length, 64)), np.zeros((length, 64))
+    q[:, :48], k[:, :48] = bits(codes[select]), bits(codes[group_of_key])
+    q[:, 48:56] = rs.randint(-2, 3, (length, 8))
+    k[:, 56:64] = rs.randint(-2, 3, (length, 8))
+    for r in range(length):
+        v[r, rs.permutation(64)[:4]] = rs.choice([-2.0, -1.0, 1.0, 2.0], 4)
+    d_out = rs.randint(-2, 3, (length, 64)).astype(np.float64)
+    return dict(q=q, k=k, v=v, d_out=d_out, groups=groups, select=select, group_of_key=group_of_key)
+
+
+def snap_exact(x):
+    """The exact value of a probe gradient: the fp64 result snapped to a multiple of 1 / 64 (what is left is the e^-24 leak)."""
+    return np.round(np.asarray(x, np.float64) * ENC_PROBE_SNAP) / ENC_PROBE_SNAP
+
+
+def encoder_probe_head(length, head, seed):
+    """One (sequence, head) of the probe, Q and K rolled by 8 * head columns.  Draws are repeated (seed + 1000 * attempt) until every exact
+    gradient is a bf16 value -- eight significant bits; fp16 holds whatever bf16 does at these magnitudes -- so the builder never hands
+    out a rounding lottery; tests/test_cpu_encoder_probe.py asserts the result again."""
+    for attempt in range(200):
+        h = _probe_head_draw(length, head, np.random.RandomState(seed + 1000 * attempt))
+        h["q"], h["k"] = np.roll(h["q"], 8 * head, axis=1), np.roll(h["k"], 8 * head, axis=1)
+        grads = attention_grads_fp64(h["q"], h["k"], h["v"], h["d_out"])[2:5]
+        exact = [snap_exact(g) for g in grads]
+        if all(np.array_equal(bf16_round(e.astype(np.float32)).astype(np.float64), e) for e in exact):
+            h["attempt"] = attempt
+            return h
+    raise AssertionError(f"no representable probe for length {length}, head {head}")
+
+
+_ENC_PROBE = {}
+
+
+def encoder_probe():
+    """The whole probe, built once per process: per sequence of ENC_PROBE_LENS qkv [len, 3, H, 64] and d_out [len, H, 64] (fp64 arrays of
+    integers), plus the per-head draws (groups, select) for the checks of the builder itself."""
+    if not _ENC_PROBE:
+        seqs = []
+        for si, length in enumerate(ENC_PROBE_LENS):
+            heads = [encoder_probe_head(length, h, seed=100 * si + h) for h in range(ENC_PROBE_HEADS)]
+            qkv = np.stack([np.stack([hd[name] for hd in heads], axis=1) for name in ("q", "k", "v")], axis=1)      # [len, 3, H, 64]
+            d_out = np.stack([hd["d_out"] for hd in heads], axis=1)                                                  # [len, H, 64]
+            seqs.append(dict(length=length, heads=heads, qkv=qkv, d_out=d_out))
+        _ENC_PROBE["seqs"] = seqs
+    return _ENC_PROBE["seqs"]
+
+
+def encoder_probe_leak_bound(length):
+    """What the unselected keys can add to any gradient element: at most `length` of them, each with P <= e^-margin, times 64 columns of
+    operands no larger than 4 -- from the margin, not measured."""
+    return length * np.exp(-ENC_PROBE_MARGIN) * 64 * 4
+
+
+def emulate_attention_bwd(q, k, v, d_out, kind, swap_rows=None, row_factor=True):
+    """The arithmetic of csrc/ccr_encoder_bwd.hip for one head on the CPU: fp32 scores, lse and P = exp2(s scale log2e - lse log2e), dS = P (dP -
+    delta) in fp32, dS and P rounded to the 16-bit type (fp16: under the per-own-row power-of-two factor 2^(8 - e_run), the accumulator rescaled
+    when e_run grows), fp32 accumulation over streamed tiles of 32 rows, `scale` applied once, one rounding at the end.
+    swap_rows = (i, j): the accumulating products read streamed rows i and j of every tile in each other's place (a misplaced transposed read).
+    -> (dq, dk, dv) float32 holding values of the type."""
+    f32 = np.float32
+    q, k, v, d_out = (np.asarray(a, f32) for a in (q, k, v, d_out))
+    n = q.shape[0]
+    scale, log2e = f32(0.125), f32(1.4426950408889634)
+    scale_log2e = f32(scale * log2e)
+    raw = q @ k.T
+    s = raw * scale
+    m = s.max(1, keepdims=True)
+    lse = (m[:, 0] + np.log(np.exp(s - m).sum(1, dtype=f32))).astype(f32)
+    out = round16(round16(np.exp(s - lse[:, None]), kind) @ v, kind)          # the forward's output, 16-bit
+    delta = (d_out * out).sum(1, dtype=f32)
+    lse2 = (lse * log2e).astype(f32)
+    p = np.exp2((raw.astype(np.float64) * np.float64(scale_log2e) - lse2[:, None].astype(np.float64)).astype(f32)).astype(f32)      # one fma
+    ds = (p * ((d_out @ v.T) - delta[:, None])).astype(f32)
+    scaled = kind == "fp16" and row_factor
+
+    def stream(ds_own, p_own, x1, x2):
+        """own rows x streamed rows: ds_own, p_own [own, streamed]; x1, x2 [streamed, 64] -> (acc, accv)."""
+        own = ds_own.shape[0]
+        acc, accv = np.zeros((own, 64), f32), np.zeros((own, 64), f32)
+        e_run = np.full(own, -1000)
+        for t0 in range(0, ds_own.shape[1], 32):
+            d_t, p_t = ds_own[:, t0:t0 + 32], p_own[:, t0:t0 + 32]
+            a1, a2 = x1[t0:t0 + 32].copy(), x2[t0:t0 + 32].copy()
+            if swap_rows is not None and max(swap_rows) < a1.shape[0]:
+                i, j = swap_rows
+                a1[[i, j]], a2[[i, j]] = a1[[j, i]], a2[[j, i]]
+            if scaled:
+                amax = np.abs(d_t).max(1)
+                ex = np.maximum(np.floor(np.log2(np.where(amax > 0, amax, 1.0))).astype(np.int64), -100)
+                grow = (amax > 0) & (ex > e_run)
+                shrink = np.where(e_run == -1000, 0.0, np.exp2((e_run - ex).astype(np.float64))).astype(f32)
+                acc[grow] *= shrink[grow][:, None]
+                e_run = np.where(grow, ex, e_run)
+                factor = np.where(e_run == -1000, 0.0, np.exp2((8 - e_run).astype(np.float64))).astype(f32)
+                d_t = d_t * factor[:, None]
+            acc += round16(d_t, kind) @ a1
+            accv += round16(p_t, kind) @ a2
+        unscale = np.full(own, scale, f32)
+        if scaled:
+            unscale = np.where(e_run == -1000, 0.0, scale * np.exp2((e_run - 8).astype(np.float64))).astype(f32)
+        return acc * unscale[:, None], accv
+
+    dq, _ = stream(ds, p, k, v)
+    dk, dv = stream(np.ascontiguousarray(ds.T), np.ascontiguousarray(p.T), q, d_out)
+    return tuple(round16(g, kind) for g in (dq, dk, dv))
+
+
+# ---------------------------------------------------------------------------------------------- encoder backward: cases, inputs, references
+# (shared by tests/test_gpu_encoder_train.py and tests/test_gpu_encoder_train_edges.py)
+import torch  # noqa: E402
+
+DTYPES = [torch.bfloat16, torch.float16]
+MANTISSA = {torch.bfloat16: 7, torch.float16: 10}      # explicit significand bits: one spacing at v is 2^(floor(log2 |v|) - bits)
+
+
+def spacing(value, dtype):
+    """One spacing (ulp) of the 16-bit type at |value| (a Python float; normal range)."""
+    return 2.0 ** (math.floor(math.log2(abs(value))) - MANTISSA[dtype])
+
+
+ATT_CASES = {
+    "padded_edges": ("padded", [1, 2, 31, 32, 33, 63, 64, 65], 2),
+    "packed_blocks": ("packed", [127, 128, 129, 255, 256, 257], 3),
+    "padded_512_empty": ("padded", [512, 300, 1, 0], 2),           # an empty sequence appended
+    "packed_12_heads": ("packed", [136, 17, 200], 12),
+}
+
+
+def att_inputs(kind, lens, H, dtype, seed):
+    """qkv ~ 1.5 N(0, 1), d_out ~ N(0, 1), rounded to the type; padding rows (padded batches) are NaN."""
+    g = torch.Generator().manual_seed(seed)
+    n = len(lens)
+    if kind == "padded":
+        L = max(lens)
+        starts, pad_len, T = [s * L for s in range(n)], L, n * L
+    else:
+        starts, pad_len, T = [sum(lens[:s]) for s in range(n)], 0, sum(lens)
+    qkv = (1.5 * torch.randn(T, 3 * H * 64, generator=g)).to(dtype)
+    d_out = torch.randn(T, H * 64, generator=g).to(dtype)
+    live = torch.zeros(T, dtype=torch.bool)
+    for s, ln in zip(starts, lens):
+        live[s:s + ln] = True
+    qkv[~live] = float("nan")
+    d_out[~live] = float("nan")
+    dev = "cuda"
+    return dict(qkv=qkv.to(dev), d_out=d_out.to(dev), live=live.to(dev), starts=starts, lens=lens, H=H, pad_len=pad_len, max_len=max(max(lens), 1),
+                seq_start=torch.tensor(starts, dtype=torch.int32, device=dev), seq_len=torch.tensor(lens, dtype=torch.int32, device=dev))
+
+
+def att_reference(case, half):
+    """Per (sequence, head): autograd of softmax(Q K^T / 8) V on the rounded operands.  half None: everything fp32 (the reference).
+    half = a 16-bit type: the matmul operands and results are 16-bit and the softmax fp32 -- autocast's arithmetic (the yardstick).
+    -> (d_qkv fp32 [T, 3 H 64] with zeros on padding rows, lse fp32 [T, H])."""
+    qkv, d_out, H = case["qkv"], case["d_out"], case["H"]
+    T = qkv.shape[0]
+    grad = torch.zeros(T, 3 * H * 64, dtype=torch.float32, device=qkv.device)
+    lse = torch.zeros(T, H, dtype=torch.float32, device=qkv.device)
+    for s, ln in zip(case["starts"], case["lens"]):
+        if ln == 0:
+            continue
+        rows = qkv[s:s + ln].view(ln, 3, H, 64).permute(1, 2, 0, 3)          # [3, H, len, 64]
+        dt = torch.float32 if half is None else half
+        q, k, v = (rows[i].to(dt).detach().clone().requires_grad_(True) for i in range(3))
+        scores = (q @ k.transpose(1, 2)).float() * 0.125
+        p = torch.softmax(scores, dim=-1)
+        o = p.to(dt) @ v
+        do = d_out[s:s + ln].view(ln, H, 64).permute(1, 0, 2).to(dt)
+        o.backward(do)
+        g3 = torch.stack([q.grad, k.grad, v.grad]).float()                    # [3, H, len, 64]
+        grad[s:s + ln] = g3.permute(2, 0, 1, 3).reshape(ln, 3 * H * 64)
+        lse[s:s + ln] = torch.logsumexp(scores.detach(), dim=-1).T
+    return grad, lse
+
+
+def run_att(case, d_out=None):
+    from ccrec_amd import ops
+    out, lse = ops.attention_fwd_train(case["qkv"], case["seq_start"], case["seq_len"], case["H"], case["max_len"], case["pad_len"])
+    out_nan = out.clone()
+    out_nan[~case["live"]] = float("nan")                 # the backward must not read the forward's padding rows either
+    d_qkv = ops.attention_bwd(case["qkv"], out_nan, lse, case["d_out"] if d_out is None else d_out, case["seq_start"], case["seq_len"],
+                              case["H"], case["max_len"], case["pad_len"])
+    return out, lse, d_qkv
+
+
+LN_EPS = 1e-12      # BERT's
+
+
+def ln_inputs(rows, dim, dtype, with_res, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(rows, dim, generator=g).to(dtype)
+    res = torch.randn(rows, dim, generator=g) if with_res else None
+    if rows >= 4:
+        x[1] = 0.5                       # a row of equal elements: 0.5 (+ 1.25) is exact in every format
+        if with_res:
+            res[1] = 1.25
+            res[2] += 1000.0             # a large common offset
+        else:
+            x[2] = (x[2].float() + 1000.0).to(dtype)
+    gamma = 1.0 + 0.2 * torch.randn(dim, generator=g)
+    d_y = torch.randn(rows, dim, generator=g)
+    dev = "cuda"
+    return x.to(dev), None if res is None else res.to(dev), gamma.to(dev), d_y.to(dev)
+
+
+def ln_torch_backward(v, gamma, d_y, dt):
+    """d v, d gamma, d beta of F.layer_norm(v) * gamma + beta in precision dt, from the SAME summed input v = x + residual (fp32)."""
+    v = v.to(dt).detach().requires_grad_(True)
+    gm = gamma.to(dt).detach().requires_grad_(True)
+    bt = torch.zeros_like(gm).requires_grad_(True)
+    torch.nn.functional.layer_norm(v, (v.shape[1],), gm, bt, LN_EPS).backward(d_y.to(dt))
+    return v.grad, gm.grad, bt.grad

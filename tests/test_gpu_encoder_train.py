@@ -14,73 +14,14 @@ import torch
 import torch.nn.functional as F
 
 from conftest import ROOT, PKG  # noqa: F401
+from helpers import (ATT_CASES, DTYPES, LN_EPS, MANTISSA, att_inputs as _att_inputs, att_reference as _att_reference,
+                     ln_inputs as _ln_inputs, ln_torch_backward as _ln_torch_backward, run_att as _run_att, spacing as _spacing)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = [torch.bfloat16, torch.float16]
-MANTISSA = {torch.bfloat16: 7, torch.float16: 10}      # explicit significand bits: one spacing at v is 2^(floor(log2 |v|) - bits)
-
-
-def _spacing(value, dtype):
-    """One spacing (ulp) of the 16-bit type at |value| (a Python float; normal range)."""
-    return 2.0 ** (math.floor(math.log2(abs(value))) - MANTISSA[dtype])
-
 
 # ---------------------------------------------------------------------------------------------------------------- attention backward
-ATT_CASES = {
-    "padded_edges": ("padded", [1, 2, 31, 32, 33, 63, 64, 65], 2),
-    "packed_blocks": ("packed", [127, 128, 129, 255, 256, 257], 3),
-    "padded_512_empty": ("padded", [512, 300, 1, 0], 2),           # an empty sequence appended
-    "packed_12_heads": ("packed", [136, 17, 200], 12),
-}
-
-
-def _att_inputs(kind, lens, H, dtype, seed):
-    """qkv ~ 1.5 N(0, 1), d_out ~ N(0, 1), rounded to the type; padding rows (padded batches) are NaN."""
-    g = torch.Generator().manual_seed(seed)
-    n = len(lens)
-    if kind == "padded":
-        L = max(lens)
-        starts, pad_len, T = [s * L for s in range(n)], L, n * L
-    else:
-        starts, pad_len, T = [sum(lens[:s]) for s in range(n)], 0, sum(lens)
-    qkv = (1.5 * torch.randn(T, 3 * H * 64, generator=g)).to(dtype)
-    d_out = torch.randn(T, H * 64, generator=g).to(dtype)
-    live = torch.zeros(T, dtype=torch.bool)
-    for s, ln in zip(starts, lens):
-        live[s:s + ln] = True
-    qkv[~live] = float("nan")
-    d_out[~live] = float("nan")
-    dev = "cuda"
-    return dict(qkv=qkv.to(dev), d_out=d_out.to(dev), live=live.to(dev), starts=starts, lens=lens, H=H, pad_len=pad_len, max_len=max(max(lens), 1),
-                seq_start=torch.tensor(starts, dtype=torch.int32, device=dev), seq_len=torch.tensor(lens, dtype=torch.int32, device=dev))
-
-
-def _att_reference(case, half):
-    """Per (sequence, head): autograd of softmax(Q K^T / 8) V on the rounded operands.  half None: everything fp32 (the reference).
-    half = a 16-bit type: the matmul operands and results are 16-bit and the softmax fp32 -- autocast's arithmetic (the yardstick).
-    -> (d_qkv fp32 [T, 3 H 64] with zeros on padding rows, lse fp32 [T, H])."""
-    qkv, d_out, H = case["qkv"], case["d_out"], case["H"]
-    T = qkv.shape[0]
-    grad = torch.zeros(T, 3 * H * 64, dtype=torch.float32, device=qkv.device)
-    lse = torch.zeros(T, H, dtype=torch.float32, device=qkv.device)
-    for s, ln in zip(case["starts"], case["lens"]):
-        if ln == 0:
-            continue
-        rows = qkv[s:s + ln].view(ln, 3, H, 64).permute(1, 2, 0, 3)          # [3, H, len, 64]
-        dt = torch.float32 if half is None else half
-        q, k, v = (rows[i].to(dt).detach().clone().requires_grad_(True) for i in range(3))
-        scores = (q @ k.transpose(1, 2)).float() * 0.125
-        p = torch.softmax(scores, dim=-1)
-        o = p.to(dt) @ v
-        do = d_out[s:s + ln].view(ln, H, 64).permute(1, 0, 2).to(dt)
-        o.backward(do)
-        g3 = torch.stack([q.grad, k.grad, v.grad]).float()                    # [3, H, len, 64]
-        grad[s:s + ln] = g3.permute(2, 0, 1, 3).reshape(ln, 3 * H * 64)
-        lse[s:s + ln] = torch.logsumexp(scores.detach(), dim=-1).T
-    return grad, lse
-
-
+# (cases, inputs and references: tests/helpers.py, shared with test_gpu_encoder_train_edges.py)
 _ATT_REF = {}
 
 
@@ -94,16 +35,6 @@ def _att_case(name, dtype):
         case["yard"], _ = _att_reference(case, dtype)
         _ATT_REF[key] = case
     return _ATT_REF[key]
-
-
-def _run_att(case, d_out=None):
-    from ccrec_amd import ops
-    out, lse = ops.attention_fwd_train(case["qkv"], case["seq_start"], case["seq_len"], case["H"], case["max_len"], case["pad_len"])
-    out_nan = out.clone()
-    out_nan[~case["live"]] = float("nan")                 # the backward must not read the forward's padding rows either
-    d_qkv = ops.attention_bwd(case["qkv"], out_nan, lse, case["d_out"] if d_out is None else d_out, case["seq_start"], case["seq_len"],
-                              case["H"], case["max_len"], case["pad_len"])
-    return out, lse, d_qkv
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])
@@ -156,33 +87,6 @@ def test_attention_train_autograd_function(dtype):
 
 # ---------------------------------------------------------------------------------------------------------------- LayerNorm backward
 LN_SHAPES = [(1, 256), (5, 768), (1031, 768), (4, 2048)]
-LN_EPS = 1e-12      # BERT's
-
-
-def _ln_inputs(rows, dim, dtype, with_res, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(rows, dim, generator=g).to(dtype)
-    res = torch.randn(rows, dim, generator=g) if with_res else None
-    if rows >= 4:
-        x[1] = 0.5                       # a row of equal elements: 0.5 (+ 1.25) is exact in every format
-        if with_res:
-            res[1] = 1.25
-            res[2] += 1000.0             # a large common offset
-        else:
-            x[2] = (x[2].float() + 1000.0).to(dtype)
-    gamma = 1.0 + 0.2 * torch.randn(dim, generator=g)
-    d_y = torch.randn(rows, dim, generator=g)
-    dev = "cuda"
-    return x.to(dev), None if res is None else res.to(dev), gamma.to(dev), d_y.to(dev)
-
-
-def _ln_torch_backward(v, gamma, d_y, dt):
-    """d v, d gamma, d beta of F.layer_norm(v) * gamma + beta in precision dt, from the SAME summed input v = x + residual (fp32)."""
-    v = v.to(dt).detach().requires_grad_(True)
-    gm = gamma.to(dt).detach().requires_grad_(True)
-    bt = torch.zeros_like(gm).requires_grad_(True)
-    F.layer_norm(v, (v.shape[1],), gm, bt, LN_EPS).backward(d_y.to(dt))
-    return v.grad, gm.grad, bt.grad
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])
