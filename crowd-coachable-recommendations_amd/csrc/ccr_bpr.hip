@@ -7,6 +7,7 @@
 //     is the running sum of the softmax's numerators (cdf = inclusive prefix sums of the proposal), and a draw is the smallest j
 //     with F(j) > u Z.  One wave per batch row: the m corrections' prefix sums S_k and F(c_k) go to LDS once, each lane then takes
 //     draws: a binary search over F(c_k) in LDS names the segment between two entries, a second one over cdf inside it the item.
+//     A draw that rounding put on an item of weight exactly 0 steps to the nearest live item (the reference never returns such an item).
 //     ptr = NULL is the no-prior branch (bbpr.py:176-179): F = cdf.
 // (b) bpr_frozen_*: the frozen-tower step (all_cls cached, only the LayerNorm trains, bbpr.py:436-438): gather -> LayerNorm ->
 //     products -> logsigmoid -> weighted sum (bbpr.py:144-147, 180-185) in ONE pass over the gathered rows.  With
@@ -108,7 +109,32 @@ __global__ __launch_bounds__(64) void bpr_sample_kernel(const int64_t *__restric
             const int mid = (jlo + jhi) >> 1;
             if (fma(e0, cdf[mid], S) > target) jhi = mid; else jlo = mid + 1;
         }
-        out[(int64_t)n * B + b] = bad ? -1 : (int64_t)min(jlo, n_items - 1);   // (the clamp acts only when the target is not a number)
+        // A draw never names an item of weight 0.  Its F equals its predecessor's in exact arithmetic, but the scan rounds S_k in an order
+        // that differs from lane to lane, so F of a zero-weight item can come out a spacing above it and win a target that lies in between
+        // (u = 1 - 2^-53 behind the last live item, u = 0 before the first): the draw then moves to the nearest live item before it, or
+        // after it when there is none.  k = the first entry whose column is >= j.
+        int j = min(jlo, n_items - 1), k = ks;   // (the clamp acts only when the target is not a number)
+        if (k > 0 && column(k - 1) >= j) --k;
+        auto dead = [&](int j_, int k_) {
+            if (proposal[j_] == 0.f) return true;
+            return k_ < m && column(k_) == j_ ? exp((double)t[p0 + k_] - M) == 0.0 : e0 == 0.0;
+        };
+        if (!bad && dead(j, k)) {
+            int jb = j, kb = k;
+            while (jb >= 0 && dead(jb, kb)) {
+                --jb;
+                if (kb > 0 && column(kb - 1) >= jb) --kb;
+            }
+            if (jb >= 0) {
+                j = jb;
+            } else {
+                while (j < n_items - 1 && dead(j, k)) {
+                    if (k < m && column(k) == j) ++k;
+                    ++j;
+                }
+            }
+        }
+        out[(int64_t)n * B + b] = bad ? -1 : (int64_t)j;
     }
 }
 

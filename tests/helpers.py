@@ -597,3 +597,195 @@ def ln_torch_backward(v, gamma, d_y, dt):
     bt = torch.zeros_like(gm).requires_grad_(True)
     torch.nn.functional.layer_norm(v, (v.shape[1],), gm, bt, LN_EPS).backward(d_y.to(dt))
     return v.grad, gm.grad, bt.grad
+
+
+# ---------------------------------------------------------------------------------------------- the bpr objective: builders and checks
+# (shared by tests/test_gpu_bpr.py and tests/test_gpu_bpr_edges.py; the integer probe also by tests/test_cpu_bpr_probe.py)
+LAST_U = 1.0 - 2.0 ** -53
+
+
+def make_prior(n_users, n_items, row_len, values, seed):
+    """CSR with row_len(u) entries in row u (columns ascending and unique), values(rng, m) fp32."""
+    rng = np.random.default_rng(seed)
+    ptr, idx, t = [0], [], []
+    for u in range(n_users):
+        m = row_len(u)
+        idx.append(np.sort(rng.choice(n_items, size=m, replace=False)).astype(np.int64))
+        t.append(np.asarray(values(rng, m), dtype=np.float32))
+        ptr.append(ptr[-1] + m)
+    return np.asarray(ptr, dtype=np.int64), np.concatenate(idx) if idx else np.zeros(0, np.int64), np.concatenate(t) if t else np.zeros(0, np.float32)
+
+
+def dense_weights(u, prior, t0, proposal):
+    """w_j = proposal_j exp(t_uj - M) of one user in fp64 (the numerators of the softmax after its max-shift)."""
+    trow = np.full(proposal.shape[0], np.float64(np.float32(t0)))
+    if prior is not None:
+        ptr, idx, t = prior
+        trow[idx[ptr[u]:ptr[u + 1]]] = t[ptr[u]:ptr[u + 1]].astype(np.float64)
+    return proposal.astype(np.float64) * np.exp(trow - trow.max())
+
+
+def run_sampler(users, n_neg, n_items, prior, t0, uniforms=None, seed=0, proposal=None):
+    from ccrec_amd import ops
+    rng = np.random.default_rng(seed)
+    drawn = ((rng.integers(0, 50, n_items) + 0.1) ** 0.5).astype(np.float32)   # (drawn either way: the uniforms stay the same)
+    proposal = drawn if proposal is None else np.ascontiguousarray(proposal, dtype=np.float32)
+    prop = torch.from_numpy(proposal).cuda()
+    cdf = ops.bpr_proposal_cdf(prop)
+    B = len(users)
+    if uniforms is None:
+        uniforms = rng.random((n_neg, B))
+    uni = torch.from_numpy(np.ascontiguousarray(uniforms, dtype=np.float64)).cuda()
+    dev_prior = None
+    if prior is not None:
+        ptr, idx, t = prior
+        dev_prior = (torch.from_numpy(ptr).cuda(), torch.from_numpy(idx).cuda(), torch.from_numpy(t).cuda(), int(np.diff(ptr).max()))
+    usr = torch.from_numpy(np.asarray(users, dtype=np.int64)).cuda()
+    got = ops.bpr_sample_negatives(usr, n_neg, prop, cdf, prior=dev_prior, t0=t0, uniforms=uni)
+    again = ops.bpr_sample_negatives(usr, n_neg, prop, cdf, prior=dev_prior, t0=t0, uniforms=uni)
+    assert got.shape == (n_neg, B) and got.dtype == torch.int64 and torch.equal(got, again)   # a second call: identical output
+    return got.cpu().numpy(), proposal, cdf.cpu().numpy(), np.asarray(uniforms, dtype=np.float64)
+
+
+def check_draws(got, users, prior, t0, proposal, cdf, uniforms):
+    """Every draw equals searchsorted(cumsum(w), u Z, 'right'), or the target lies within 1e-9 Z of the boundary between the two
+    answers and they are neighbours among the items of non-zero weight; at most 0.1 % of the draws may be excused that way."""
+    excused = 0
+    for b, u in enumerate(users):
+        w = dense_weights(u, prior, t0, proposal)
+        cum = np.cumsum(w) if prior is not None else cdf   # (no prior: the weights are the proposal, their running sum the cdf itself)
+        Z = cum[-1]
+        target = uniforms[:, b] * Z
+        ref = np.searchsorted(cum, target, side="right")
+        for n in np.nonzero(got[:, b] != ref)[0]:
+            lo, hi = sorted((int(got[n, b]), int(ref[n])))
+            assert 0 <= lo and hi < len(w), (b, n, got[n, b], ref[n])
+            assert w[lo] > 0 and w[hi] > 0 and not w[lo + 1:hi].any(), f"row {b} draw {n}: {got[n, b]} and {ref[n]} are not neighbours"
+            assert abs(target[n] - cum[lo]) <= 1e-9 * Z, f"row {b} draw {n}: {got[n, b]} != {ref[n]}, target {target[n]!r} boundary {cum[lo]!r}"
+            excused += 1
+    print(f"draws {got.size} excused {excused}")
+    assert excused <= 1e-3 * got.size
+
+
+def restate_frozen(table, gamma, beta, eps, ptr_i, ptr_j, ptr_nj, w):
+    """bbpr.py:144-147, 180-185 with forward = LayerNorm(all_cls[ptr]) in torch fp64 on the CPU -> loss, dgamma, dbeta (grad_out = 1)."""
+    T = table.detach().cpu().double()
+    dim = T.shape[1]
+    g = gamma.detach().cpu().double().requires_grad_(True) if gamma is not None else None
+    b = beta.detach().cpu().double().requires_grad_(True) if beta is not None else None
+    pi, pj, pnj, wd = ptr_i.cpu(), ptr_j.cpu(), ptr_nj.cpu(), w.detach().cpu().double()
+    emb = lambda p: torch.nn.functional.layer_norm(T[p], (dim,), g, b, eps)
+    pos = (emb(pi) * emb(pj)).sum(-1)
+    neg = (emb(pi) * emb(pnj)).sum(-1)
+    loglik = torch.nn.functional.logsigmoid(pos - neg)
+    loss = (-loglik * wd).sum() / (pnj.shape[0] * wd.sum())
+    if g is None:
+        return float(loss), None, None, (pos - neg).detach()
+    loss.backward()
+    return float(loss.detach()), g.grad.numpy(), b.grad.numpy(), (pos - neg).detach()
+
+
+def check_loss(got, ref):
+    print(f"loss {got!r} ref {ref!r} err {abs(got - ref):.3e}")
+    assert abs(got - ref) < 2e-5 * max(1.0, abs(ref))
+
+
+def check_grad(got, ref, scale=1.0, what=""):
+    got = got.detach().float().cpu().numpy()
+    print(f"{what} max |got - ref| {np.abs(got - scale * ref).max():.3e} of max |ref| {np.abs(scale * ref).max():.3e}")
+    np.testing.assert_allclose(got, scale * ref, rtol=2e-4, atol=3e-4 * np.abs(scale * ref).max())
+
+
+def frozen_problem(B, n_neg, dim, n_rows, gamma_scale=0.05, seed=None):
+    g = torch.Generator().manual_seed(B * 131 + dim if seed is None else seed)
+    table = torch.randn(n_rows, dim, generator=g) * (0.5 + torch.rand(n_rows, 1, generator=g)) + torch.randn(n_rows, 1, generator=g) * 0.3
+    if gamma_scale == 1.0:
+        gamma, beta = torch.ones(dim), torch.zeros(dim)
+    else:
+        gamma = gamma_scale * (1.0 + 0.2 * torch.randn(dim, generator=g))
+        beta = 0.02 * torch.randn(dim, generator=g)
+    ptr_i = torch.randint(0, n_rows, (B,), generator=g)
+    ptr_j = torch.randint(0, n_rows, (B,), generator=g)
+    ptr_nj = torch.randint(0, n_rows, (n_neg, B), generator=g)
+    if B > 2:
+        ptr_nj[0, ::3] = ptr_j[::3]      # duplicate pointers: these differences are exactly 0
+    else:                                # one row: three different pointers (with ptr_nj == ptr_j the true gradient is zero, and a
+        ptr_i[0], ptr_j[0], ptr_nj[0, 0] = 0, 1, 2                           # bound relative to max |ref| says nothing about it)
+    if gamma_scale == 1.0 and B > 2 and n_neg > 1:
+        ptr_j[1], ptr_nj[1, 2] = ptr_i[1], ptr_i[2]      # e_i . e_i = dim: differences of about +dim and -dim
+    w = torch.rand(B, generator=g) + 0.1
+    w[::5] = 0.0
+    if B == 1:
+        w[0] = 0.7
+    return table, gamma, beta, ptr_i, ptr_j, ptr_nj, w
+
+
+def run_frozen(table, gamma, beta, eps, ptr_i, ptr_j, ptr_nj, w, scale=3.0):
+    from ccrec_amd import ops
+    gc, bc = gamma.cuda().requires_grad_(True), beta.cuda().requires_grad_(True)
+    loss = ops.bpr_frozen_loss(table.cuda(), gc, bc, eps, ptr_i.cuda(), ptr_j.cuda(), ptr_nj.cuda(), w.cuda())
+    (loss * scale).backward()
+    return loss.detach(), gc.grad, bc.grad
+
+
+# The integer probe of the frozen loss: table rows of +-1 with as many +1 as -1, so that with eps = 0 the LayerNorm's mean is 0, its variance
+# 1, rstd 1 and xh = x, all exact in fp32.  x_n is x_j with 2p columns flipped (p of each sign: x_n stays balanced), x_i is x_j with q of
+# those columns flipped (and as many columns outside them as keep it balanced), so with beta = 0
+#   D = gamma^2 sum_d x_i (x_j - x_n) = gamma^2 * 2 (2p - 2q) = gamma^2 * 4 (p - q):   every multiple of 4 at gamma = 1, every integer at 1/2,
+# and the gradients live on the flipped columns alone: R = -sigmoid(-D) (x_j - x_n), dbeta = R gamma, dgamma = R 2 x_i gamma.
+BPR_PROBE_KS = list(range(-32, 33))      # k = p - q
+
+
+def bpr_integer_probe(dim, k, variant):
+    """-> (x_i, x_j, x_n [dim] fp32 of +-1, the flipped columns).  variant 0: the fewest flips (p = |k|; k = 0: one agreeing and one
+    disagreeing flip); variant 1: p drawn from [max(|k|, 1), 31] and the columns spread over the row."""
+    half = dim // 2
+    assert dim % 2 == 0 and abs(k) <= 32 <= half
+    rng = np.random.default_rng(1000 * dim + 10 * (k + 32) + variant)
+    perm = rng.permutation(dim) if variant else np.arange(dim).reshape(half, 2).T.reshape(-1)      # variant 0: x_j = +1 on the even columns
+    plus, minus = perm[:half], perm[half:]
+    p = max(abs(k), 1)
+    if variant and abs(k) < 31:
+        p = int(rng.integers(p, 32))
+    q = p - k
+    assert 0 <= q <= 2 * p
+    q_plus, q_minus = (q + 1) // 2, q // 2
+    extra = q_plus - q_minus                                  # an odd q: one more disagreement outside the flips, on a -1 column
+    r = int(rng.integers(0, half - p - extra + 1)) if variant else 0
+    assert p + extra + r <= half
+    xj = np.empty(dim, np.float32)
+    xj[plus], xj[minus] = 1.0, -1.0
+    flipped = np.sort(np.concatenate([plus[:p], minus[:p]]))
+    xn = xj.copy()
+    xn[flipped] *= -1.0
+    xi = xj.copy()
+    for cols in (plus[:q_plus], minus[:q_minus], plus[p:p + r], minus[p:p + extra + r]):
+        xi[cols] *= -1.0
+    assert xi.sum() == 0 and xj.sum() == 0 and xn.sum() == 0 and float((xi * (xj - xn)).sum()) == 4.0 * k
+    return xi, xj, xn, flipped
+
+
+def bpr_probe_reference(xi, xj, xn, gamma):
+    """fp64: D, softplus(-D), dgamma and dbeta of the probe (w = 1, one negative, grad_out = 1)."""
+    xi, xj, xn = (np.asarray(a, np.float64) for a in (xi, xj, xn))
+    D = gamma * gamma * float((xi * (xj - xn)).sum())
+    loss = max(-D, 0.0) + math.log1p(math.exp(-abs(D)))
+    sig = math.exp(-D) / (1.0 + math.exp(-D)) if D >= 0 else 1.0 / (1.0 + math.exp(D))      # sigmoid(-D)
+    R = -sig * (xj - xn)
+    return D, loss, R * 2.0 * xi * gamma, R * gamma
+
+
+BPR_SUBNORMAL = 2.0 ** -149
+
+
+def bpr_relative_error(got, ref):
+    """max |got - ref| / |ref| over the elements whose reference is not 0, one subnormal step (2^-149) forgiven where |ref| < 2^-126;
+    where the reference is 0 the value must be exactly 0."""
+    got, ref = np.atleast_1d(np.asarray(got, np.float64)), np.atleast_1d(np.asarray(ref, np.float64))
+    nz = ref != 0
+    assert np.array_equal(got[~nz], np.zeros((~nz).sum())), "an element whose reference is 0 is not exactly 0"
+    if not nz.any():
+        return 0.0
+    err = np.abs(got[nz] - ref[nz])
+    err = np.where(np.abs(ref[nz]) < 2.0 ** -126, np.maximum(err - BPR_SUBNORMAL, 0.0), err)
+    return float((err / np.abs(ref[nz])).max())

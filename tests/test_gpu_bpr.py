@@ -8,74 +8,13 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from helpers import (LAST_U, check_draws, check_grad, check_loss, dense_weights, frozen_problem, make_prior, restate_frozen, run_frozen,
+                     run_sampler)
 
-LAST_U = 1.0 - 2.0 ** -53
+pytestmark = pytest.mark.gpu
 
 
 # ---------------------------------------------------------------------------------------------- sampler
-def make_prior(n_users, n_items, row_len, values, seed):
-    """CSR with row_len(u) entries in row u (columns ascending and unique), values(rng, m) fp32."""
-    rng = np.random.default_rng(seed)
-    ptr, idx, t = [0], [], []
-    for u in range(n_users):
-        m = row_len(u)
-        idx.append(np.sort(rng.choice(n_items, size=m, replace=False)).astype(np.int64))
-        t.append(np.asarray(values(rng, m), dtype=np.float32))
-        ptr.append(ptr[-1] + m)
-    return np.asarray(ptr, dtype=np.int64), np.concatenate(idx) if idx else np.zeros(0, np.int64), np.concatenate(t) if t else np.zeros(0, np.float32)
-
-
-def dense_weights(u, prior, t0, proposal):
-    """w_j = proposal_j exp(t_uj - M) of one user in fp64 (the numerators of the softmax after its max-shift)."""
-    trow = np.full(proposal.shape[0], np.float64(np.float32(t0)))
-    if prior is not None:
-        ptr, idx, t = prior
-        trow[idx[ptr[u]:ptr[u + 1]]] = t[ptr[u]:ptr[u + 1]].astype(np.float64)
-    return proposal.astype(np.float64) * np.exp(trow - trow.max())
-
-
-def run_sampler(users, n_neg, n_items, prior, t0, uniforms=None, seed=0):
-    from ccrec_amd import ops
-    rng = np.random.default_rng(seed)
-    proposal = ((rng.integers(0, 50, n_items) + 0.1) ** 0.5).astype(np.float32)
-    prop = torch.from_numpy(proposal).cuda()
-    cdf = ops.bpr_proposal_cdf(prop)
-    B = len(users)
-    if uniforms is None:
-        uniforms = rng.random((n_neg, B))
-    uni = torch.from_numpy(np.ascontiguousarray(uniforms, dtype=np.float64)).cuda()
-    dev_prior = None
-    if prior is not None:
-        ptr, idx, t = prior
-        dev_prior = (torch.from_numpy(ptr).cuda(), torch.from_numpy(idx).cuda(), torch.from_numpy(t).cuda(), int(np.diff(ptr).max()))
-    usr = torch.from_numpy(np.asarray(users, dtype=np.int64)).cuda()
-    got = ops.bpr_sample_negatives(usr, n_neg, prop, cdf, prior=dev_prior, t0=t0, uniforms=uni)
-    again = ops.bpr_sample_negatives(usr, n_neg, prop, cdf, prior=dev_prior, t0=t0, uniforms=uni)
-    assert got.shape == (n_neg, B) and got.dtype == torch.int64 and torch.equal(got, again)   # a second call: identical output
-    return got.cpu().numpy(), proposal, cdf.cpu().numpy(), np.asarray(uniforms, dtype=np.float64)
-
-
-def check_draws(got, users, prior, t0, proposal, cdf, uniforms):
-    """Every draw equals searchsorted(cumsum(w), u Z, 'right'), or the target lies within 1e-9 Z of the boundary between the two
-    answers and they are neighbours among the items of non-zero weight; at most 0.1 % of the draws may be excused that way."""
-    excused = 0
-    for b, u in enumerate(users):
-        w = dense_weights(u, prior, t0, proposal)
-        cum = np.cumsum(w) if prior is not None else cdf   # (no prior: the weights are the proposal, their running sum the cdf itself)
-        Z = cum[-1]
-        target = uniforms[:, b] * Z
-        ref = np.searchsorted(cum, target, side="right")
-        for n in np.nonzero(got[:, b] != ref)[0]:
-            lo, hi = sorted((int(got[n, b]), int(ref[n])))
-            assert 0 <= lo and hi < len(w), (b, n, got[n, b], ref[n])
-            assert w[lo] > 0 and w[hi] > 0 and not w[lo + 1:hi].any(), f"row {b} draw {n}: {got[n, b]} and {ref[n]} are not neighbours"
-            assert abs(target[n] - cum[lo]) <= 1e-9 * Z, f"row {b} draw {n}: {got[n, b]} != {ref[n]}, target {target[n]!r} boundary {cum[lo]!r}"
-            excused += 1
-    print(f"draws {got.size} excused {excused}")
-    assert excused <= 1e-3 * got.size
-
-
 def test_sampler_rows_of_0_to_40_entries():
     n_users, n_items, B, n_neg = 300, 3001, 257, 10
     prior = make_prior(n_users, n_items, lambda u: u % 41, lambda rng, m: rng.normal(size=m) * 2, seed=1)
@@ -159,67 +98,6 @@ def test_sampler_marks_a_user_outside_the_prior():
 
 
 # ---------------------------------------------------------------------------------------------- frozen loss
-def restate_frozen(table, gamma, beta, eps, ptr_i, ptr_j, ptr_nj, w):
-    """bbpr.py:144-147, 180-185 with forward = LayerNorm(all_cls[ptr]) in torch fp64 on the CPU -> loss, dgamma, dbeta (grad_out = 1)."""
-    T = table.detach().cpu().double()
-    dim = T.shape[1]
-    g = gamma.detach().cpu().double().requires_grad_(True) if gamma is not None else None
-    b = beta.detach().cpu().double().requires_grad_(True) if beta is not None else None
-    pi, pj, pnj, wd = ptr_i.cpu(), ptr_j.cpu(), ptr_nj.cpu(), w.detach().cpu().double()
-    emb = lambda p: torch.nn.functional.layer_norm(T[p], (dim,), g, b, eps)
-    pos = (emb(pi) * emb(pj)).sum(-1)
-    neg = (emb(pi) * emb(pnj)).sum(-1)
-    loglik = torch.nn.functional.logsigmoid(pos - neg)
-    loss = (-loglik * wd).sum() / (pnj.shape[0] * wd.sum())
-    if g is None:
-        return float(loss), None, None, (pos - neg).detach()
-    loss.backward()
-    return float(loss.detach()), g.grad.numpy(), b.grad.numpy(), (pos - neg).detach()
-
-
-def check_loss(got, ref):
-    print(f"loss {got!r} ref {ref!r} err {abs(got - ref):.3e}")
-    assert abs(got - ref) < 2e-5 * max(1.0, abs(ref))
-
-
-def check_grad(got, ref, scale=1.0, what=""):
-    got = got.detach().float().cpu().numpy()
-    print(f"{what} max |got - ref| {np.abs(got - scale * ref).max():.3e} of max |ref| {np.abs(scale * ref).max():.3e}")
-    np.testing.assert_allclose(got, scale * ref, rtol=2e-4, atol=3e-4 * np.abs(scale * ref).max())
-
-
-def frozen_problem(B, n_neg, dim, n_rows, gamma_scale=0.05, seed=None):
-    g = torch.Generator().manual_seed(B * 131 + dim if seed is None else seed)
-    table = torch.randn(n_rows, dim, generator=g) * (0.5 + torch.rand(n_rows, 1, generator=g)) + torch.randn(n_rows, 1, generator=g) * 0.3
-    if gamma_scale == 1.0:
-        gamma, beta = torch.ones(dim), torch.zeros(dim)
-    else:
-        gamma = gamma_scale * (1.0 + 0.2 * torch.randn(dim, generator=g))
-        beta = 0.02 * torch.randn(dim, generator=g)
-    ptr_i = torch.randint(0, n_rows, (B,), generator=g)
-    ptr_j = torch.randint(0, n_rows, (B,), generator=g)
-    ptr_nj = torch.randint(0, n_rows, (n_neg, B), generator=g)
-    if B > 2:
-        ptr_nj[0, ::3] = ptr_j[::3]      # duplicate pointers: these differences are exactly 0
-    else:                                # one row: three different pointers (with ptr_nj == ptr_j the true gradient is zero, and a
-        ptr_i[0], ptr_j[0], ptr_nj[0, 0] = 0, 1, 2                           # bound relative to max |ref| says nothing about it)
-    if gamma_scale == 1.0 and B > 2 and n_neg > 1:
-        ptr_j[1], ptr_nj[1, 2] = ptr_i[1], ptr_i[2]      # e_i . e_i = dim: differences of about +dim and -dim
-    w = torch.rand(B, generator=g) + 0.1
-    w[::5] = 0.0
-    if B == 1:
-        w[0] = 0.7
-    return table, gamma, beta, ptr_i, ptr_j, ptr_nj, w
-
-
-def run_frozen(table, gamma, beta, eps, ptr_i, ptr_j, ptr_nj, w, scale=3.0):
-    from ccrec_amd import ops
-    gc, bc = gamma.cuda().requires_grad_(True), beta.cuda().requires_grad_(True)
-    loss = ops.bpr_frozen_loss(table.cuda(), gc, bc, eps, ptr_i.cuda(), ptr_j.cuda(), ptr_nj.cuda(), w.cuda())
-    (loss * scale).backward()
-    return loss.detach(), gc.grad, bc.grad
-
-
 @pytest.mark.parametrize("B,n_neg,dim,n_rows,gamma_scale", [(1, 1, 64, 3, 0.05), (33, 10, 768, 500, 0.05), (257, 3, 256, 1000, 0.05),
                                                           (64, 10, 2048, 100, 0.05), (33, 10, 768, 500, 1.0)])
 def test_frozen_loss_and_gradients_vs_fp64_restatement(B, n_neg, dim, n_rows, gamma_scale):
