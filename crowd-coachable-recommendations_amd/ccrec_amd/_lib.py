@@ -26,11 +26,14 @@ EXPORTS = [
     "ccr_search_stream_wait_main_pass", "ccr_pool_ce_workspace_bytes", "ccr_pool_ce_fwd", "ccr_pool_ce_fwd_f32", "ccr_pool_ce_bwd_dev",
     "ccr_bpr_sample", "ccr_bpr_frozen_workspace_bytes", "ccr_bpr_frozen_fwd", "ccr_bpr_frozen_bwd_dev",
     "ccr_attention_fwd_train_half", "ccr_attention_bwd_workspace_bytes", "ccr_attention_bwd_half", "ccr_add_layernorm_bwd_half", "ccr_gelu_bwd_half",
+    "ccr_dropout_bits_rows", "ccr_dropout_bits_attention", "ccr_dropout_apply", "ccr_attention_fwd_train_drop_half", "ccr_attention_bwd_drop_half",
+    "ccr_add_layernorm_drop_half", "ccr_add_layernorm_bwd_drop_half",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
 BPR_VERSION = 102   # ... and the one the ccr_bpr_* entry points came with (ops checks it on their first use)
 ENCODER_TRAIN_VERSION = 103   # ... and the encoder layer kernels' training forward and backward (ccr_attention_bwd_half and its kin)
+ENCODER_DROPOUT_VERSION = 104   # ... and the keep-bit generators and the layer kernels that read the bits (ccr_dropout_bits_rows and its kin)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -150,6 +153,14 @@ def load():
     lib.ccr_attention_bwd_half.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, vp, sz, vp]
     lib.ccr_add_layernorm_bwd_half.argtypes = [vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, vp]
     lib.ccr_gelu_bwd_half.argtypes = [vp, vp, vp, i64, i32, vp]
+    u64, u32, f64 = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double
+    lib.ccr_dropout_bits_rows.argtypes = [vp, i64, i32, u64, u32, f64, vp]
+    lib.ccr_dropout_bits_attention.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, u64, u32, f64, vp]
+    lib.ccr_dropout_apply.argtypes = [vp, vp, f32, vp, vp, i64, i32, i32, vp]
+    lib.ccr_attention_fwd_train_drop_half.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, f32, i32, vp]
+    lib.ccr_attention_bwd_drop_half.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, f32, i32, vp, sz, vp]
+    lib.ccr_add_layernorm_drop_half.argtypes = [vp, vp, f32, vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]
+    lib.ccr_add_layernorm_bwd_drop_half.argtypes = [vp, vp, f32, vp, vp, f32, vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, vp]
     lib.ccr_meanpool_pack_bf16_packed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.ccr_shard_message_bytes.argtypes = [i32, i32]
     lib.ccr_shard_message_bytes.restype = sz

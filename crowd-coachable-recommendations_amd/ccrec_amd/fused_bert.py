@@ -12,7 +12,10 @@ softmax, fp32 residual stream and LayerNorm -- IN THE AUTOCAST CONTEXT'S OWN 16-
 `torch.cuda.amp.autocast()` (scripts/al_0_rank.py:8,125: the CUDA default), bf16 under autocast(dtype=torch.bfloat16).  The hidden
 states agree with the module forward under the same autocast to that type's rounding (the tests compare both with the fp32 forward).
 forward / forward_packed are inference forwards (eval mode, no autograd); forward_train / forward_train_packed run the same layers with
-gradients on, on the kernels' backward (ops.attention_train, add_layernorm_train, gelu_train): no dropout there either.
+gradients on, on the kernels' backward (ops.attention_train, add_layernorm_train, gelu_train).  Dropout there is a second opt-in
+(CCREC_FUSED_ENCODER_TRAIN_DROPOUT=1, train_dropout_wanted): a model in train() with live dropout then runs on the same kernels reading
+packed keep bits that a generator kernel writes from one 64-bit seed per call (ops.dropout_bits_rows / dropout_bits_attention, restated on
+the CPU in dropout_ref); without that opt-in such a model is refused and keeps training as its torch module.
 
 Only what the kernels cover is accepted (unsupported_reason): a BertModel or DistilBertModel encoder (post-LayerNorm layers, absolute
 positions, exact GELU), head width 64, hidden size a multiple of 256, at most 512 tokens, right-padded batches.  Every other encoder keeps
@@ -29,11 +32,12 @@ from . import ops
 class _Arch:
     """Where a supported architecture keeps the pieces of its (post-LayerNorm, GELU) encoder layer."""
 
-    def __init__(self, heads, hidden, activation, stack, embeddings, type_table, layer_parts):
+    def __init__(self, heads, hidden, activation, stack, embeddings, type_table, layer_parts, dropout_parts):
         self.heads, self.hidden, self.activation = heads, hidden, activation
         self.stack = stack                    # the module whose parameters are the layers' weights
         self.embeddings, self.type_table = embeddings, type_table
         self.layer_parts = layer_parts        # layer module -> (q, k, v, attention out, LayerNorm 1, ffn in, ffn out, LayerNorm 2)
+        self.dropout_parts = dropout_parts    # layer module -> the Dropout modules on (probabilities, attention output or None, ffn output)
 
 
 def _describe(model):
@@ -50,11 +54,13 @@ def _describe(model):
         return _Arch(int(cfg.num_attention_heads), int(cfg.hidden_size), getattr(cfg, "hidden_act", "gelu"), model.encoder, e,
                      e.token_type_embeddings.weight,
                      lambda m: (m.attention.self.query, m.attention.self.key, m.attention.self.value, m.attention.output.dense,
-                                m.attention.output.LayerNorm, m.intermediate.dense, m.output.dense, m.output.LayerNorm))
+                                m.attention.output.LayerNorm, m.intermediate.dense, m.output.dense, m.output.LayerNorm),
+                     lambda m: (m.attention.self.dropout, m.attention.output.dropout, m.output.dropout))
     if name == "DistilBertModel" and hasattr(model, "embeddings") and hasattr(model, "transformer"):
         return _Arch(int(cfg.n_heads), int(cfg.dim), getattr(cfg, "activation", "gelu"), model.transformer, model.embeddings, None,
                      lambda m: (m.attention.q_lin, m.attention.k_lin, m.attention.v_lin, m.attention.out_lin, m.sa_layer_norm,
-                                m.ffn.lin1, m.ffn.lin2, m.output_layer_norm))
+                                m.ffn.lin1, m.ffn.lin2, m.output_layer_norm),
+                     lambda m: (m.attention.dropout, None, m.ffn.dropout))      # (nothing between out_lin and sa_layer_norm)
     return f"{name} is not a BertModel or DistilBertModel"
 
 
@@ -76,12 +82,44 @@ def unsupported_reason(model):
 _DROPOUT_FIELDS = ("hidden_dropout_prob", "attention_probs_dropout_prob", "dropout", "attention_dropout")
 
 
+def _dropout_sites(model):
+    """The Dropout modules the kernels' training path knows how to replace: the one after the embedding LayerNorm and, per layer, those on
+    the attention probabilities, the attention output (BERT only) and the FFN output.  -> the set of their ids."""
+    arch = _describe(model)
+    known = [getattr(arch.embeddings, "dropout", None)]
+    for mod in arch.stack.layer:
+        known.extend(arch.dropout_parts(mod))
+    return {id(m) for m in known if m is not None}
+
+
+def _live(m):
+    """Is this module a dropout torch would apply right now?  (Its own training flag counts: a Dropout put in eval() inside a train() model
+    is inactive.)"""
+    return isinstance(m, torch.nn.Dropout) and m.training and m.p > 0
+
+
+def _dropout_refusal(model):
+    """With both opt-ins set: None if every live Dropout module of a model in training mode is a known site with p < 1; else why not."""
+    known = _dropout_sites(model)
+    for name, m in model.named_modules():
+        if _live(m):
+            if id(m) not in known:
+                return f"dropout module {name or 'model'} (p={m.p:g}) is active in training mode and is not a site the layer kernels cover"
+            if not m.p < 1:
+                return f"dropout module {name} has p={m.p:g}: the keep bits take 0 <= p < 1"
+    return None
+
+
 def train_unsupported_reason(model):
-    """None when FusedBertEncoder can run a TRAINING forward of `model`: what unsupported_reason asks, and no active dropout (the layer
-    kernels have none): a model in training mode with any dropout probability above 0 is refused; eval mode or all-zero dropout is fine."""
+    """None when FusedBertEncoder can run a TRAINING forward of `model`: what unsupported_reason asks, and no active dropout: a model in
+    training mode with any dropout probability above 0 is refused; eval mode or all-zero dropout is fine.  With the second opt-in
+    (train_wanted() and train_dropout_wanted()) active dropout is accepted where every live torch.nn.Dropout module is one of the known
+    sites (_dropout_sites: their p is read from the modules at call time); any other live Dropout module is refused by name."""
     reason = unsupported_reason(model)
     if reason is not None:
         return reason
+    if getattr(model, "training", False) and train_wanted() and train_dropout_wanted():
+        return _dropout_refusal(model)
     if getattr(model, "training", False):
         cfg = getattr(model, "config", None)
         active = [f"{name}={float(getattr(cfg, name)):g}" for name in _DROPOUT_FIELDS if float(getattr(cfg, name, 0.0) or 0.0) > 0.0]
@@ -94,6 +132,49 @@ def train_unsupported_reason(model):
 def train_wanted():
     """The opt-in of the training path: CCREC_FUSED_ENCODER_TRAIN=1 (default off: the torch module trains)."""
     return os.environ.get("CCREC_FUSED_ENCODER_TRAIN", "").strip() == "1"
+
+
+def train_dropout_wanted():
+    """The opt-in of dropout on the training path: CCREC_FUSED_ENCODER_TRAIN_DROPOUT=1, read at call time (default off: a model with
+    active dropout trains as its torch module).  Honoured only together with CCREC_FUSED_ENCODER_TRAIN=1."""
+    return os.environ.get("CCREC_FUSED_ENCODER_TRAIN_DROPOUT", "").strip() == "1"
+
+
+SITE_PROBABILITIES, SITE_ATTENTION_OUTPUT, SITE_FFN_OUTPUT = 0, 1, 2
+EMBEDDINGS_STREAM = 0
+
+
+def dropout_stream(layer, site):
+    """The generator's stream id of a layer's dropout site: 4 * layer + site, plus one for the embeddings' (EMBEDDINGS_STREAM = 0).  The
+    cls_only last layer draws its row-wise bits for the rows it runs on (one per sequence) under layer = the number of layers."""
+    return 4 * int(layer) + int(site) + 1
+
+
+def draw_seed():
+    """One 64-bit seed from torch's default CPU generator (torch.manual_seed makes a step reproducible; no device sync)."""
+    lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+    return (hi << 32) | lo
+
+
+class _DropoutDraw:
+    """The dropout decisions of one training forward: every site's keep bits come from (seed, the site's stream id)."""
+
+    def __init__(self, seed):
+        from . import dropout_ref
+        self.seed, self._ref = seed, dropout_ref
+
+    def rows(self, module, stream, rows, dim, device):
+        """-> (bits, inv_keep) of a row-wise site, or (None, 1.0) when its module is absent or has p = 0 (not a dropout site)."""
+        p = float(module.p) if module is not None and _live(module) else 0.0
+        if p <= 0.0:
+            return None, 1.0
+        return ops.dropout_bits_rows(rows, dim, self.seed, stream, p, device=device), self._ref.inv_keep(p)
+
+    def attention(self, module, stream, seq_start, lengths, n_tokens, heads, max_len):
+        p = float(module.p) if module is not None and _live(module) else 0.0
+        if p <= 0.0:
+            return None, 1.0
+        return ops.dropout_bits_attention(seq_start, lengths, n_tokens, heads, max_len, self.seed, stream, p), self._ref.inv_keep(p)
 
 
 def train_dtype():
@@ -183,6 +264,7 @@ class FusedBertEncoder:
         self.heads, self.hidden = arch.heads, arch.hidden
         self.has_token_types = arch.type_table is not None
         self._layers, self._signature, self._no_types = {}, None, None
+        self.last_seed = None      # the seed of the latest training forward that ran with dropout (dropout_ref rebuilds its masks from it)
 
     def __getstate__(self):      # pickled with its model (torch.save(model)): without the 16-bit weight copies
         return {"model": self.model, "heads": self.heads, "hidden": self.hidden, "has_token_types": self.has_token_types}
@@ -190,6 +272,7 @@ class FusedBertEncoder:
     def __setstate__(self, state):
         self.__dict__.update(state)
         self._layers, self._signature, self._no_types = {}, None, None
+        self.last_seed = None
 
     def _params_signature(self):
         return tuple((p.data_ptr(), p._version, p.device) for p in _describe(self.model).stack.parameters())
@@ -270,8 +353,9 @@ class FusedBertEncoder:
             h = h[cls_rows].contiguous()
         return h
 
-    def _embed_train(self, token_ids, positions, token_types, dtype):
-        """_embed with gradients: F.embedding + F.layer_norm on the live tables (not a hot spot: one pass over T rows)."""
+    def _embed_train(self, token_ids, positions, token_types, dtype, drop=None):
+        """_embed with gradients: F.embedding + F.layer_norm on the live tables (not a hot spot: one pass over T rows); drop (a
+        _DropoutDraw): then the embeddings' dropout from its keep bits (ops.dropout_train)."""
         arch = _describe(self.model)
         e = arch.embeddings
         token_ids, positions = token_ids.long(), positions.long()
@@ -284,11 +368,17 @@ class FusedBertEncoder:
         x = x + F.embedding(positions, e.position_embeddings.weight).float()
         ln = e.LayerNorm
         h = F.layer_norm(x, (self.hidden,), ln.weight.float(), ln.bias.float(), ln.eps).contiguous()
+        if drop is not None:
+            bits, inv_keep = drop.rows(getattr(e, "dropout", None), EMBEDDINGS_STREAM, h.shape[0], self.hidden, h.device)
+            if bits is not None:
+                return ops.dropout_train(h, bits, inv_keep, dtype)
         return h, h.to(dtype)
 
-    def _layers_forward_train(self, h, hb, seq_start, lengths, max_len, pad_len, cls_rows=None):
+    def _layers_forward_train(self, h, hb, seq_start, lengths, max_len, pad_len, cls_rows=None, drop=None):
         """_layers_forward with gradients.  The projections are F.linear on the LIVE parameters cast to hb's dtype: the gradients reach
-        the fp32 master weights and no 16-bit copy can go stale between optimizer steps; autograd keeps the layer activations."""
+        the fp32 master weights and no 16-bit copy can go stale between optimizer steps; autograd keeps the layer activations.
+        drop (a _DropoutDraw, a model in train() with live dropout): every site reads keep bits generated for its own stream id; the
+        cls_only last layer generates its row-wise bits for the n_seq rows it runs on."""
         arch = _describe(self.model)
         half = hb.dtype
         mods = list(arch.stack.layer)
@@ -298,35 +388,54 @@ class FusedBertEncoder:
             wqkv = torch.cat([q.weight, k.weight, v.weight]).to(half)
             bqkv = torch.cat([q.bias, k.bias, v.bias]).to(half)
             qkv = F.linear(hb, wqkv, bqkv)
-            ctx = ops.attention_train(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=0.125)
+            bits_a = bits_o = bits_f = None
+            inv_a = inv_o = inv_f = 1.0
+            if drop is not None:
+                d_prob, d_attn, d_ffn = arch.dropout_parts(mod)
+                bits_a, inv_a = drop.attention(d_prob, dropout_stream(i, SITE_PROBABILITIES), seq_start, lengths, hb.shape[0], self.heads, max_len)
+            ctx = ops.attention_train(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=0.125, keep_bits=bits_a,
+                                      inv_keep=inv_a)
             if i == last and cls_rows is not None:
                 ctx, h = ctx[cls_rows], h[cls_rows]
-            h, hb = ops.add_layernorm_train(F.linear(ctx, so.weight.to(half), so.bias.to(half)), h, ln1.weight.float(), ln1.bias.float(), ln1.eps)
+            if drop is not None:
+                li = len(mods) if (i == last and cls_rows is not None) else i      # the rows it runs on are another index space: own streams
+                bits_o, inv_o = drop.rows(d_attn, dropout_stream(li, SITE_ATTENTION_OUTPUT), ctx.shape[0], self.hidden, ctx.device)
+                bits_f, inv_f = drop.rows(d_ffn, dropout_stream(li, SITE_FFN_OUTPUT), ctx.shape[0], self.hidden, ctx.device)
+            h, hb = ops.add_layernorm_train(F.linear(ctx, so.weight.to(half), so.bias.to(half)), h, ln1.weight.float(), ln1.bias.float(), ln1.eps,
+                                            keep_bits=bits_o, inv_keep=inv_o)
             mid = ops.gelu_train(F.linear(hb, ff.weight.to(half), ff.bias.to(half)))
-            h, hb = ops.add_layernorm_train(F.linear(mid, out.weight.to(half), out.bias.to(half)), h, ln2.weight.float(), ln2.bias.float(), ln2.eps)
+            h, hb = ops.add_layernorm_train(F.linear(mid, out.weight.to(half), out.bias.to(half)), h, ln2.weight.float(), ln2.bias.float(), ln2.eps,
+                                            keep_bits=bits_f, inv_keep=inv_f)
         if last < 0 and cls_rows is not None:
             h = h[cls_rows]
         return h
 
     def _check_train(self):
+        """Refuse what train_unsupported_reason refuses; -> the call's _DropoutDraw (one fresh seed, kept in last_seed) when the model is
+        in training mode with live dropout, else None (the dropout-free kernels run)."""
         reason = train_unsupported_reason(self.model)
         assert reason is None, f"FusedBertEncoder training forward: {reason}"
+        if not self.model.training or not any(_live(m) for m in self.model.modules()):
+            return None
+        self.last_seed = draw_seed()
+        return _DropoutDraw(self.last_seed)
 
     def forward_train_packed(self, token_ids, positions, seq_start, lengths, max_len, token_type_ids=None, cls_only=False, dtype=torch.bfloat16):
         """forward_packed with gradients (same arguments, same result to the kernels' rounding): the parameters of the model receive
-        gradients through the layer kernels' backward.  The model is in eval mode or has all-zero dropout (train_unsupported_reason)."""
+        gradients through the layer kernels' backward.  The model is in eval mode or has all-zero dropout, or CCREC_FUSED_ENCODER_TRAIN_DROPOUT=1
+        opted into dropout from keep bits (train_unsupported_reason)."""
         ops.require_gpu()
-        self._check_train()
+        drop = self._check_train()
         assert token_ids.is_cuda and token_ids.dim() == 1 and positions.shape == token_ids.shape and 1 <= int(max_len) <= 512
         with torch.autocast("cuda", enabled=False):
-            h, hb = self._embed_train(token_ids, positions, token_type_ids, dtype)
-            return self._layers_forward_train(h, hb, seq_start, lengths, int(max_len), 0, seq_start.long() if cls_only else None)
+            h, hb = self._embed_train(token_ids, positions, token_type_ids, dtype, drop)
+            return self._layers_forward_train(h, hb, seq_start, lengths, int(max_len), 0, seq_start.long() if cls_only else None, drop)
 
     def forward_train(self, input_ids, lengths, token_type_ids=None, packed=None, lengths_host=None, cls_only=False, dtype=torch.bfloat16):
         """forward with gradients: the same arguments and the same [B, L, hidden] (or [B, 1, hidden]) fp32 result; padding rows are zeros
         (packed) or finite values nobody reads, and carry no gradient into the parameters."""
         ops.require_gpu()
-        self._check_train()
+        drop = self._check_train()
         assert input_ids.is_cuda and input_ids.dim() == 2
         B, L = input_ids.shape
         assert L <= 512 and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.numel() == B
@@ -340,15 +449,16 @@ class FusedBertEncoder:
             if packed:
                 keep = (torch.arange(L, device=dev)[None, :] < lengths[:, None]).flatten().nonzero().squeeze(1)   # rows of the real tokens
                 assert keep.numel() == total, "lengths_host does not match lengths"
-                h, hb = self._embed_train(input_ids.flatten()[keep], keep % L, None if token_type_ids is None else token_type_ids.flatten()[keep], dtype)
+                h, hb = self._embed_train(input_ids.flatten()[keep], keep % L, None if token_type_ids is None else token_type_ids.flatten()[keep], dtype,
+                                          drop)
                 max_len, pad_len = max(longest, 1), 0
                 seq_start = (torch.cumsum(lengths, 0, dtype=torch.int32) - lengths).contiguous()
             else:
                 h, hb = self._embed_train(input_ids.flatten(), torch.arange(L, device=dev).repeat(B),
-                                          None if token_type_ids is None else token_type_ids.flatten(), dtype)
+                                          None if token_type_ids is None else token_type_ids.flatten(), dtype, drop)
                 max_len, pad_len = L, L
                 seq_start = torch.arange(B, dtype=torch.int32, device=dev) * L
-            h = self._layers_forward_train(h, hb, seq_start, lengths, max_len, pad_len, seq_start.long() if cls_only else None)
+            h = self._layers_forward_train(h, hb, seq_start, lengths, max_len, pad_len, seq_start.long() if cls_only else None, drop)
             if cls_only:
                 return h.view(B, 1, self.hidden)
             if packed:

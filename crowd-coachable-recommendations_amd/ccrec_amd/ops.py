@@ -365,9 +365,12 @@ class _AttentionTrain(torch.autograd.Function):
         return d_qkv, None, None, None, None, None, None
 
 
-def attention_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125):
-    """attention() with a backward: the same context rows, bit for bit; the gradient reaches qkv (the stacked projection's output)."""
-    return _AttentionTrain.apply(qkv.contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale)
+def attention_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, keep_bits=None, inv_keep=1.0):
+    """attention() with a backward: the same context rows, bit for bit; the gradient reaches qkv (the stacked projection's output).
+    keep_bits = (keep_q, keep_k) of dropout_bits_attention: dropout on the probabilities, scaled by inv_keep, the bits saved for the backward."""
+    if keep_bits is None:
+        return _AttentionTrain.apply(qkv.contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale)
+    return _AttentionTrainDrop.apply(qkv.contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_bits[0], keep_bits[1], inv_keep)
 
 
 class _AddLayerNormTrain(torch.autograd.Function):
@@ -394,9 +397,12 @@ class _AddLayerNormTrain(torch.autograd.Function):
         return d_x, d_res, d_gamma, d_beta, None
 
 
-def add_layernorm_train(x, residual, gamma, beta, eps):
+def add_layernorm_train(x, residual, gamma, beta, eps, keep_bits=None, inv_keep=1.0):
     """add_layernorm() with a backward -> (fp32 rows, their copy in x's dtype).  Both outputs are differentiable; the gradient reaches x
-    (in its dtype), residual, gamma and beta."""
+    (in its dtype), residual, gamma and beta.  keep_bits (dropout_bits_rows): LayerNorm(x * keep * inv_keep + residual)."""
+    if keep_bits is not None:
+        return _AddLayerNormTrainDrop.apply(x.contiguous(), None if residual is None else residual.contiguous(), gamma.contiguous(),
+                                            beta.contiguous(), eps, keep_bits, inv_keep)
     return _AddLayerNormTrain.apply(x.contiguous(), None if residual is None else residual.contiguous(), gamma.contiguous(), beta.contiguous(), eps)
 
 
@@ -420,6 +426,231 @@ def gelu_train(x):
     """Exact GELU, out of place, with a backward (gelu_() overwrites the pre-activation the backward needs)."""
     assert x.is_cuda and x.numel() % 8 == 0
     return _GeluTrain.apply(x.contiguous())
+
+
+# ---- training dropout from explicit keep bits (library version 104, csrc/ccr_dropout.hip): the reference's towers train in train() mode
+# with dropout 0.1 (src/ccrec/models/bbpr.py:195-197, bert_mt.py:105-113).  A generator kernel writes packed keep bits; the layer kernels
+# read them with one scale factor.  ccrec_amd/dropout_ref.py restates the generator on the CPU ---------------------------------------------
+_ENCODER_DROPOUT_CHECKED = False
+
+
+def _require_encoder_dropout():
+    """require_gpu() + once: the loaded library has the keep-bit entry points (ccr_version() >= 104)."""
+    global _ENCODER_DROPOUT_CHECKED
+    lib = require_gpu()
+    if not _ENCODER_DROPOUT_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.ENCODER_DROPOUT_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, the encoder dropout ops need {_lib.ENCODER_DROPOUT_VERSION}: rebuild it "
+                                f"(python -c 'import __graft_entry__ as g; g.build()')")
+        _ENCODER_DROPOUT_CHECKED = True
+    return lib
+
+
+def dropout_bits_rows(rows, dim, seed, stream_id, p, device="cuda"):
+    """Packed keep bits uint32 (stored as int32) [rows, dim / 32] of a row-wise dropout site (ccr_dropout_bits_rows): bit i of word w <->
+    column 32 w + i, 1 = keep; a pure function of (seed, stream_id, p, row, column) -- dropout_ref.rows_bits gives the same words."""
+    lib = _require_encoder_dropout()
+    bits = torch.empty(int(rows), int(dim) // 32, dtype=torch.int32, device=device)
+    with _on(bits):
+        _lib.check(lib.ccr_dropout_bits_rows(_ptr(bits), int(rows), int(dim), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF,
+                                             float(p), _stream(bits)), "ccr_dropout_bits_rows")
+    return bits
+
+
+def dropout_bits_attention(seq_start, seq_len, n_tokens, n_heads, max_len, seed, stream_id, p):
+    """(keep_q, keep_k) int32 [n_tokens, n_heads, ceil(max_len / 32)] of an attention dropout site (ccr_dropout_bits_attention): the same
+    decisions by query row (bit = key position) and by key row (bit = query position).  Zero-filled first: words of rows outside every
+    sequence and bits beyond a length carry no meaning, and no kernel reads them into a result."""
+    lib = _require_encoder_dropout()
+    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
+    assert seq_start.is_contiguous() and seq_len.is_contiguous() and seq_start.numel() == seq_len.numel()
+    W = (int(max_len) + 31) // 32
+    both = torch.zeros(2, int(n_tokens), int(n_heads), W, dtype=torch.int32, device=seq_start.device)
+    with _on(both):
+        _lib.check(lib.ccr_dropout_bits_attention(_ptr(both[0]), _ptr(both[1]), _ptr(seq_start), _ptr(seq_len), int(n_tokens), seq_len.numel(),
+                                                  int(n_heads), int(max_len), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF,
+                                                  float(p), _stream(both)), "ccr_dropout_bits_attention")
+    return both[0], both[1]
+
+
+def _check_bits(bits, shape):
+    assert bits.is_cuda and bits.dtype == torch.int32 and tuple(bits.shape) == tuple(shape) and bits.is_contiguous(), \
+        f"keep bits: contiguous int32 {tuple(shape)}, got {bits.dtype} {tuple(bits.shape)}"
+
+
+def dropout_apply(x, bits, inv_keep, dtype=torch.bfloat16, want_f32=True, want_half=True):
+    """x * keep * inv_keep of fp32 rows [rows, dim] (ccr_dropout_apply; dim % 256 == 0) -> (fp32 or None, its copy in `dtype` or None)."""
+    lib = _require_encoder_dropout()
+    code = _half_code(dtype)
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and (want_f32 or want_half)
+    rows, dim = x.shape
+    _check_bits(bits, (rows, dim // 32))
+    f32 = torch.empty_like(x) if want_f32 else None
+    b16 = torch.empty(rows, dim, dtype=dtype, device=x.device) if want_half else None
+    with _on(x):
+        _lib.check(lib.ccr_dropout_apply(_ptr(x), _ptr(bits), float(inv_keep), _ptr(f32), _ptr(b16), rows, dim, code, _stream(x)),
+                   "ccr_dropout_apply")
+    return f32, b16
+
+
+def attention_fwd_train_drop(qkv, seq_start, seq_len, n_heads, max_len, keep_q, inv_keep, pad_len=0, scale=0.125):
+    """attention_fwd_train with dropout on the probabilities (ccr_attention_fwd_train_drop_half): the value rounded for the P V product is
+    p * keep * inv_keep; lse is that of the undropped scores.  -> (out, lse)."""
+    lib = _require_encoder_dropout()
+    code = _half_code(qkv.dtype)
+    assert qkv.is_cuda and qkv.dim() == 2 and qkv.is_contiguous()
+    T, width = qkv.shape
+    assert width == 3 * n_heads * 64, f"qkv rows are {width} wide, expected 3 x {n_heads} heads x 64"
+    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
+    assert seq_start.is_contiguous() and seq_len.is_contiguous() and seq_start.numel() == seq_len.numel()
+    _check_bits(keep_q, (T, n_heads, (int(max_len) + 31) // 32))
+    out = torch.empty(T, n_heads * 64, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(T, n_heads, dtype=torch.float32, device=qkv.device)
+    with _on(qkv):
+        _lib.check(lib.ccr_attention_fwd_train_drop_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), _ptr(lse), _ptr(keep_q),
+                                                         float(inv_keep), seq_len.numel(), int(n_heads), int(max_len), int(pad_len),
+                                                         float(scale), code, _stream(qkv)), "ccr_attention_fwd_train_drop_half")
+    return out, lse
+
+
+def attention_bwd_drop(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, keep_q, keep_k, inv_keep, pad_len=0, scale=0.125):
+    """attention_bwd for attention_fwd_train_drop's (out, lse) and the same bits (ccr_attention_bwd_drop_half)."""
+    lib = _require_encoder_dropout()
+    code = _half_code(qkv.dtype)
+    T = qkv.shape[0]
+    assert qkv.is_cuda and qkv.is_contiguous() and tuple(qkv.shape) == (T, 3 * n_heads * 64)
+    for t in (out, d_out):
+        assert t.is_cuda and t.dtype == qkv.dtype and tuple(t.shape) == (T, n_heads * 64) and t.is_contiguous()
+    assert lse.is_cuda and lse.dtype == torch.float32 and tuple(lse.shape) == (T, n_heads) and lse.is_contiguous()
+    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_contiguous() and seq_len.is_contiguous()
+    for bits in (keep_q, keep_k):
+        _check_bits(bits, (T, n_heads, (int(max_len) + 31) // 32))
+    n_seq = seq_len.numel()
+    need = int(lib.ccr_attention_bwd_workspace_bytes(n_seq, int(n_heads), int(max_len)))
+    if need == 0:
+        _lib.check(_lib.CCR_ERR_INVALID, "ccr_attention_bwd_workspace_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
+    d_qkv = torch.zeros_like(qkv)
+    with _on(qkv):
+        _lib.check(lib.ccr_attention_bwd_drop_half(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(seq_start), _ptr(seq_len), _ptr(keep_q),
+                                                   _ptr(keep_k), float(inv_keep), _ptr(d_qkv), n_seq, int(n_heads), int(max_len), int(pad_len),
+                                                   float(scale), code, _ptr(ws), need, _stream(qkv)), "ccr_attention_bwd_drop_half")
+    return d_qkv
+
+
+def add_layernorm_drop(x, bits, inv_keep, residual, gamma, beta, eps, want_f32=True, want_bf16=True):
+    """add_layernorm on x * keep * inv_keep + residual (ccr_add_layernorm_drop_half); bits int32 [rows, dim / 32]."""
+    lib = _require_encoder_dropout()
+    code = _half_code(x.dtype)
+    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
+    rows, dim = x.shape
+    _check_bits(bits, (rows, dim // 32))
+    if residual is not None:
+        assert residual.is_cuda and residual.dtype == torch.float32 and tuple(residual.shape) == (rows, dim) and residual.is_contiguous()
+    for t in (gamma, beta):
+        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (dim,) and t.is_contiguous()
+    assert want_f32 or want_bf16
+    f32 = torch.empty(rows, dim, dtype=torch.float32, device=x.device) if want_f32 else None
+    b16 = torch.empty(rows, dim, dtype=x.dtype, device=x.device) if want_bf16 else None
+    with _on(x):
+        _lib.check(lib.ccr_add_layernorm_drop_half(_ptr(x), _ptr(bits), float(inv_keep), _ptr(residual), _ptr(gamma), _ptr(beta), float(eps),
+                                                   _ptr(f32), _ptr(b16), rows, dim, code, _stream(x)), "ccr_add_layernorm_drop_half")
+    return f32, b16
+
+
+def add_layernorm_bwd_drop(x, bits, inv_keep, residual, gamma, eps, d_y, want_res=True, want_x=True, want_gamma=True, want_beta=True):
+    """add_layernorm_bwd for add_layernorm_drop (ccr_add_layernorm_bwd_drop_half): d_res = the gradient of the summed input, d_x = d_res *
+    keep * inv_keep rounded to x's dtype, d_gamma, d_beta; None where not wanted."""
+    lib = _require_encoder_dropout()
+    code = _half_code(x.dtype)
+    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
+    rows, dim = x.shape
+    _check_bits(bits, (rows, dim // 32))
+    if residual is not None:
+        assert residual.is_cuda and residual.dtype == torch.float32 and tuple(residual.shape) == (rows, dim) and residual.is_contiguous()
+    assert gamma.is_cuda and gamma.dtype == torch.float32 and tuple(gamma.shape) == (dim,) and gamma.is_contiguous()
+    assert d_y.is_cuda and d_y.dtype == torch.float32 and tuple(d_y.shape) == (rows, dim) and d_y.is_contiguous()
+    dev = x.device
+    d_res = torch.empty(rows, dim, dtype=torch.float32, device=dev) if want_res else None
+    d_x = torch.empty(rows, dim, dtype=x.dtype, device=dev) if want_x else None
+    d_gamma = torch.empty(dim, dtype=torch.float32, device=dev) if want_gamma else None
+    d_beta = torch.empty(dim, dtype=torch.float32, device=dev) if want_beta else None
+    need = min((rows + 3) // 4, 512) * 2 * dim * 4 if (want_gamma or want_beta) else 0
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with _on(x):
+        _lib.check(lib.ccr_add_layernorm_bwd_drop_half(_ptr(x), _ptr(bits), float(inv_keep), _ptr(residual), _ptr(gamma), float(eps), _ptr(d_y),
+                                                       _ptr(d_res), _ptr(d_x), _ptr(d_gamma), _ptr(d_beta), rows, dim, code, _ptr(ws), need,
+                                                       _stream(x)), "ccr_add_layernorm_bwd_drop_half")
+    return d_res, d_x, d_gamma, d_beta
+
+
+class _AttentionTrainDrop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q, keep_k, inv_keep):
+        out, lse = attention_fwd_train_drop(qkv, seq_start, seq_len, n_heads, max_len, keep_q, inv_keep, pad_len, scale)
+        ctx.save_for_backward(qkv, out, lse, seq_start, seq_len, keep_q, keep_k)
+        ctx.shape = (int(n_heads), int(max_len), int(pad_len), float(scale), float(inv_keep))
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        qkv, out, lse, seq_start, seq_len, keep_q, keep_k = ctx.saved_tensors
+        n_heads, max_len, pad_len, scale, inv_keep = ctx.shape
+        d_qkv = attention_bwd_drop(qkv, out, lse, d_out.to(qkv.dtype).contiguous(), seq_start, seq_len, n_heads, max_len, keep_q, keep_k, inv_keep,
+                                   pad_len, scale)
+        return (d_qkv,) + (None,) * 9
+
+
+class _AddLayerNormTrainDrop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, eps, bits, inv_keep):
+        f32, b16 = add_layernorm_drop(x, bits, inv_keep, residual, gamma, beta, eps)
+        ctx.save_for_backward(x, residual, gamma, bits)
+        ctx.eps, ctx.inv_keep = float(eps), float(inv_keep)
+        return f32, b16
+
+    @staticmethod
+    def backward(ctx, d_f32, d_b16):
+        x, residual, gamma, bits = ctx.saved_tensors
+        if d_f32 is None:
+            d_y = d_b16.float()
+        elif d_b16 is None:
+            d_y = d_f32.float()
+        else:
+            d_y = d_f32.float() + d_b16
+        need = ctx.needs_input_grad
+        d_res, d_x, d_gamma, d_beta = add_layernorm_bwd_drop(x, bits, ctx.inv_keep, residual, gamma, ctx.eps, d_y.contiguous(),
+                                                             want_res=residual is not None and need[1], want_x=need[0], want_gamma=need[2],
+                                                             want_beta=need[3])
+        return d_x, d_res, d_gamma, d_beta, None, None, None
+
+
+class _DropoutTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bits, inv_keep, dtype):
+        f32, b16 = dropout_apply(x, bits, inv_keep, dtype)
+        ctx.save_for_backward(bits)
+        ctx.inv_keep, ctx.dtype = float(inv_keep), dtype
+        return f32, b16
+
+    @staticmethod
+    def backward(ctx, d_f32, d_b16):
+        (bits,) = ctx.saved_tensors
+        if d_f32 is None:
+            d_y = d_b16.float()
+        elif d_b16 is None:
+            d_y = d_f32.float()
+        else:
+            d_y = d_f32.float() + d_b16
+        d_x, _ = dropout_apply(d_y.contiguous(), bits, ctx.inv_keep, ctx.dtype, want_half=False)
+        return d_x, None, None, None
+
+
+def dropout_train(x, bits, inv_keep, dtype=torch.bfloat16):
+    """Dropout of fp32 rows [rows, dim] from explicit keep bits, with a backward (the same operation on the gradient) -> (fp32 rows, their
+    copy in `dtype`); both outputs are differentiable.  The site after the embedding LayerNorm."""
+    return _DropoutTrain.apply(x.contiguous(), bits, inv_keep, dtype)
 
 
 class CorpusIndex:

@@ -43,6 +43,9 @@ __host__ __device__ inline size_t attention_lds_bytes(int lk_pad) {
 // LSE = true (the training forward, ccr_attention_fwd_train_half): the kernel also writes lse [T][H] fp32, the natural-log log-sum-exp of
 // every live query row's scaled scores (0 on padding rows) -- what the backward (ccr_encoder_bwd.hip) rebuilds the probabilities from.
 // LSE = false takes an empty struct in the pointer's place: the inference instantiations keep their argument layout and their code.
+// DROP = true (ccr_attention_fwd_train_drop_half): the probability that is rounded to 16 bits for the P V product becomes
+// p * keep * inv_keep with the keep bit of (query row, head, key) from keep_q [T][H][W]; the online softmax, lsum and lse stay those of
+// the undropped scores.  A lane's 32 keys of a 64-key step are 16 bits each of words 2 kb and 2 kb + 1 of its own query's row.
 struct NoLse {};
 template <bool LSE>
 struct LseArg {
@@ -52,12 +55,13 @@ template <>
 struct LseArg<true> {
     typedef float *type;
 };
-template <int DT, bool TR, bool LSE = false>
+template <int DT, bool TR, bool LSE = false, bool DROP = false>
 __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16_t *__restrict__ qkv,
                                                                   const int32_t *__restrict__ seq_start,
                                                                   const int32_t *__restrict__ seq_len,
                                                                   uint16_t *__restrict__ out, int H, int pad_len, int max_len,
-                                                                  int lk_pad, float scale_log2e, typename LseArg<LSE>::type lse) {
+                                                                  int lk_pad, float scale_log2e, typename LseArg<LSE>::type lse,
+                                                                  typename KeepArg<DROP>::type keep = {}) {
     typedef Half16<DT> HT;
     typedef typename HT::vec8 vec8;
     typedef typename HT::elem elem;
@@ -181,8 +185,15 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
 #pragma unroll
         for (int e = 0; e < 16; ++e) o0[e] = o1[e] = 0.f;
         float m = -INFINITY, lsum = 0.f;
+        const uint32_t *keep_row = nullptr;   // DROP: the words of this lane's query row (a lane beyond the sequence repeats its last row)
+        if constexpr (DROP) keep_row = keep.bits + ((row0 + (q < len ? q : len - 1)) * H + h) * keep.W;
 
         for (int kb = 0; kb < nkb; ++kb) {
+            uint32_t kw0 = 0, kw1 = 0;   // DROP: bit (e & 3) + 8 ((e & 15) >> 2) of kw0 >> 4 g <-> register e < 16, of kw1 >> 4 g <-> register 16 + e
+            if constexpr (DROP) {
+                kw0 = keep_row[2 * kb] >> (4 * g);                          // 2 kb < W: the step holds a key below len <= max_len
+                if (2 * kb + 1 < keep.W) kw1 = keep_row[2 * kb + 1] >> (4 * g);   // (keys of a word beyond W are beyond len: their x is 0)
+            }
             ef32x16 s0, s1;
 #pragma unroll
             for (int e = 0; e < 16; ++e) s0[e] = s1[e] = 0.f;
@@ -233,7 +244,15 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
                 for (int s2 = 0; s2 < 2; ++s2) {
                     vec8 pf;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[j] = (elem)x[hb * 16 + s2 * 8 + j];
+                    for (int j = 0; j < 8; ++j) {
+                        if constexpr (DROP) {
+                            const int e = s2 * 8 + j;
+                            const uint32_t bit = ((hb ? kw1 : kw0) >> ((e & 3) + 8 * (e >> 2))) & 1u;
+                            pf[j] = (elem)(x[hb * 16 + e] * (bit ? keep.inv_keep : 0.f));
+                        } else {
+                            pf[j] = (elem)x[hb * 16 + s2 * 8 + j];
+                        }
+                    }
                     if constexpr (TR) {
                         // keys kbase .. + 3 and kbase + 8 .. + 11 (kbase = kb * 64 + hb * 32 + s2 * 16 + 4 g) of this lane's column d (a0) and d + 32 (a1)
                         typedef __attribute__((address_space(3))) es16x4 *lds_tr_ptr;
@@ -291,11 +310,14 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
 }
 
 // One wave per row of dim = 256 * C elements; lane owns elements 4 * (64 c + lane) .. + 3 of every 256-element slice.
-template <int C, int DT>
+// DROP = true (ccr_add_layernorm_drop_half): v = x * keep * inv_keep + residual, one fp32 fma per element (the product is not rounded);
+// the lane's four columns are one nibble of word (64 c + lane) >> 3 of its row of bits [rows][DIM / 32].
+template <int C, int DT, bool DROP = false>
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const uint16_t *__restrict__ x, const float *__restrict__ res,
                                                            const float *__restrict__ gamma, const float *__restrict__ beta,
                                                            float eps, float *__restrict__ out_f32,
-                                                           uint16_t *__restrict__ out_bf16, int64_t rows) {
+                                                           uint16_t *__restrict__ out_bf16, int64_t rows,
+                                                           typename KeepArg<DROP>::type keep = {}) {
     constexpr int DIM = 256 * C;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -308,10 +330,19 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const uint16_t *__re
         const uint2 xb = *reinterpret_cast<const uint2 *>(x + row * DIM + col);
         float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
         if (res) r = *reinterpret_cast<const float4 *>(res + row * DIM + col);
-        v[c][0] = Half16<DT>::lo(xb.x) + r.x;
-        v[c][1] = Half16<DT>::hi(xb.x) + r.y;
-        v[c][2] = Half16<DT>::lo(xb.y) + r.z;
-        v[c][3] = Half16<DT>::hi(xb.y) + r.w;
+        if constexpr (DROP) {
+            float mk[4];
+            keep_nibble(keep, row * (DIM / 32), 64 * c + lane, mk);
+            v[c][0] = fmaf(Half16<DT>::lo(xb.x), mk[0], r.x);
+            v[c][1] = fmaf(Half16<DT>::hi(xb.x), mk[1], r.y);
+            v[c][2] = fmaf(Half16<DT>::lo(xb.y), mk[2], r.z);
+            v[c][3] = fmaf(Half16<DT>::hi(xb.y), mk[3], r.w);
+        } else {
+            v[c][0] = Half16<DT>::lo(xb.x) + r.x;
+            v[c][1] = Half16<DT>::hi(xb.x) + r.y;
+            v[c][2] = Half16<DT>::lo(xb.y) + r.z;
+            v[c][3] = Half16<DT>::hi(xb.y) + r.w;
+        }
         sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
     }
 #pragma unroll
@@ -425,27 +456,27 @@ __global__ __launch_bounds__(256) void gelu_kernel(const uint4 *__restrict__ x, 
     }
 }
 
-template <int C, int DT>
+template <int C, int DT, bool DROP>
 static int launch_add_layernorm(const uint16_t *x, const float *res, const float *gamma, const float *beta, float eps,
-                                float *out_f32, uint16_t *out_half, int64_t rows, hipStream_t s) {
-    hipLaunchKernelGGL((add_layernorm_kernel<C, DT>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, res, gamma, beta, eps,
-                       out_f32, out_half, rows);
+                                float *out_f32, uint16_t *out_half, int64_t rows, hipStream_t s, typename KeepArg<DROP>::type keep) {
+    hipLaunchKernelGGL((add_layernorm_kernel<C, DT, DROP>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, res, gamma, beta, eps,
+                       out_f32, out_half, rows, keep);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
 
-template <int DT>
+template <int DT, bool DROP = false>
 static int add_layernorm_any(const uint16_t *x, const float *res, const float *gamma, const float *beta, float eps, float *out_f32,
-                             uint16_t *out_half, int64_t rows, int dim, hipStream_t s) {
+                             uint16_t *out_half, int64_t rows, int dim, hipStream_t s, typename KeepArg<DROP>::type keep = {}) {
     switch (dim / 256) {
-        case 1: return launch_add_layernorm<1, DT>(x, res, gamma, beta, eps, out_f32, out_half, rows, s);
-        case 2: return launch_add_layernorm<2, DT>(x, res, gamma, beta, eps, out_f32, out_half, rows, s);
-        case 3: return launch_add_layernorm<3, DT>(x, res, gamma, beta, eps, out_f32, out_half, rows, s);
-        case 4: return launch_add_layernorm<4, DT>(x, res, gamma, beta, eps, out_f32, out_half, rows, s);
-        case 5: return launch_add_layernorm<5, DT>(x, res, gamma, beta, eps, out_f32, out_half, rows, s);
-        case 6: return launch_add_layernorm<6, DT>(x, res, gamma, beta, eps, out_f32, out_half, rows, s);
-        case 7: return launch_add_layernorm<7, DT>(x, res, gamma, beta, eps, out_f32, out_half, rows, s);
-        default: return launch_add_layernorm<8, DT>(x, res, gamma, beta, eps, out_f32, out_half, rows, s);
+        case 1: return launch_add_layernorm<1, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
+        case 2: return launch_add_layernorm<2, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
+        case 3: return launch_add_layernorm<3, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
+        case 4: return launch_add_layernorm<4, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
+        case 5: return launch_add_layernorm<5, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
+        case 6: return launch_add_layernorm<6, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
+        case 7: return launch_add_layernorm<7, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
+        default: return launch_add_layernorm<8, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
     }
 }
 
@@ -477,9 +508,10 @@ static int embed_layernorm_any(const float *word_table, int64_t vocab, const flo
     return CCR_OK;
 }
 
-template <int DT, bool LSE = false>
+template <int DT, bool LSE = false, bool DROP = false>
 static int attention_any(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, int n_seq, int n_heads,
-                         int max_len, int pad_len, float scale, hipStream_t stream, typename LseArg<LSE>::type lse = {}) {
+                         int max_len, int pad_len, float scale, hipStream_t stream, typename LseArg<LSE>::type lse = {},
+                         typename KeepArg<DROP>::type keep = {}) {
     const int lk_pad = (max_len + ATT_KB - 1) / ATT_KB * ATT_KB;
     const size_t lds = attention_lds_bytes(lk_pad);
     // the opt-in is cached per (kernel, device) whatever the size: ask for the kernel's maximum once (512 keys), not for this call's
@@ -488,7 +520,7 @@ static int attention_any(const uint16_t *qkv, const int32_t *seq_start, const in
         const char *e = getenv("CCR_ATT_TR");      // A/B knob: 0 = the transposed-image kernel of rounds 3-5
         return !(e && atoi(e) == 0);
     }();
-    const int rc = ensure_dynamic_lds(tr ? reinterpret_cast<const void *>(&attention_kernel<DT, true, LSE>) : reinterpret_cast<const void *>(&attention_kernel<DT, false, LSE>),
+    const int rc = ensure_dynamic_lds(tr ? reinterpret_cast<const void *>(&attention_kernel<DT, true, LSE, DROP>) : reinterpret_cast<const void *>(&attention_kernel<DT, false, LSE, DROP>),
                                       attention_lds_bytes(512));
     if (rc != CCR_OK) return rc;
     int waves = (max_len + ATT_QW - 1) / ATT_QW;   // one wave per 32 query rows, at most 8 (longer sequences: the waves loop)
@@ -500,11 +532,11 @@ static int attention_any(const uint16_t *qkv, const int32_t *seq_start, const in
     if (lk_pad == 192 && waves > 4) waves = 4;
     CCR_REQUIRE(lk_pad * 8 <= ATT_KMAX * 64 * waves && lk_pad * 4 <= ATT_VMAX * 64 * waves, "ccr_attention: staging bound (internal)");
     if (tr)
-        hipLaunchKernelGGL((attention_kernel<DT, true, LSE>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
-                           n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f, lse);
+        hipLaunchKernelGGL((attention_kernel<DT, true, LSE, DROP>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
+                           n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f, lse, keep);
     else
-        hipLaunchKernelGGL((attention_kernel<DT, false, LSE>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
-                           n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f, lse);
+        hipLaunchKernelGGL((attention_kernel<DT, false, LSE, DROP>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
+                           n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f, lse, keep);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
@@ -554,6 +586,25 @@ extern "C" int ccr_attention_fwd_train_half(const uint16_t *qkv, const int32_t *
                : attention_any<CCR_DTYPE_BF16, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream, lse);
 }
 
+extern "C" int ccr_attention_fwd_train_drop_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out,
+                                                 float *lse, const uint32_t *keep_q, float inv_keep, int n_seq, int n_heads, int max_len,
+                                                 int pad_len, float scale, int half_dtype, void *stream) {
+    CCR_REQUIRE(qkv && seq_start && seq_len && out && lse && keep_q, "ccr_attention_fwd_train_drop_half: null pointer");
+    CCR_REQUIRE_HALF(half_dtype, "ccr_attention_fwd_train_drop_half");
+    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024,
+                "ccr_attention_fwd_train_drop_half: bad shape n_seq=%d n_heads=%d", n_seq, n_heads);
+    CCR_REQUIRE(max_len > 0 && max_len <= 512 && pad_len >= 0 && pad_len <= 512,
+                "ccr_attention_fwd_train_drop_half: max_len=%d pad_len=%d (1..512 tokens per sequence)", max_len, pad_len);
+    CCR_REQUIRE(scale > 0.f, "ccr_attention_fwd_train_drop_half: scale must be positive");
+    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "ccr_attention_fwd_train_drop_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
+    if (n_seq == 0) return CCR_OK;
+    const KeepBits keep = {keep_q, inv_keep, (max_len + 31) / 32};
+    return half_dtype == CCR_DTYPE_F16 ? attention_any<CCR_DTYPE_F16, true, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len,
+                                                                                  scale, (hipStream_t)stream, lse, keep)
+                                       : attention_any<CCR_DTYPE_BF16, true, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len,
+                                                                                   scale, (hipStream_t)stream, lse, keep);
+}
+
 extern "C" int ccr_attention_bf16(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out,
                                   int n_seq, int n_heads, int max_len, int pad_len, float scale, void *stream) {
     return ccr_attention_half(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, CCR_DTYPE_BF16, stream);
@@ -569,6 +620,22 @@ extern "C" int ccr_add_layernorm_half(const uint16_t *x_half, const float *resid
     hipStream_t s = (hipStream_t)stream;
     return half_dtype == CCR_DTYPE_F16 ? add_layernorm_any<CCR_DTYPE_F16>(x_half, residual, gamma, beta, eps, out_f32, out_half, rows, dim, s)
                                        : add_layernorm_any<CCR_DTYPE_BF16>(x_half, residual, gamma, beta, eps, out_f32, out_half, rows, dim, s);
+}
+
+extern "C" int ccr_add_layernorm_drop_half(const uint16_t *x_half, const uint32_t *bits, float inv_keep, const float *residual,
+                                           const float *gamma, const float *beta, float eps, float *out_f32, uint16_t *out_half, int64_t rows,
+                                           int dim, int half_dtype, void *stream) {
+    CCR_REQUIRE(x_half && bits && gamma && beta && (out_f32 || out_half), "ccr_add_layernorm_drop_half: null pointer");
+    CCR_REQUIRE_HALF(half_dtype, "ccr_add_layernorm_drop_half");
+    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
+                "ccr_add_layernorm_drop_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
+    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "ccr_add_layernorm_drop_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
+    if (rows == 0) return CCR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const KeepBits keep = {bits, inv_keep, 0};
+    return half_dtype == CCR_DTYPE_F16
+               ? add_layernorm_any<CCR_DTYPE_F16, true>(x_half, residual, gamma, beta, eps, out_f32, out_half, rows, dim, s, keep)
+               : add_layernorm_any<CCR_DTYPE_BF16, true>(x_half, residual, gamma, beta, eps, out_f32, out_half, rows, dim, s, keep);
 }
 
 extern "C" int ccr_add_layernorm(const uint16_t *x_bf16, const float *residual, const float *gamma, const float *beta, float eps,

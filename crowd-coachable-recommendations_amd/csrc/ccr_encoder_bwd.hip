@@ -36,13 +36,16 @@ __host__ __device__ inline size_t attention_bwd_lds_bytes(int lpad) { return 2 *
 // forward's row permutation (element j of lane half g <-> streamed row 16 s + 4 g + (j & 3) + 8 (j >> 2)).
 // delta = sum_d dO O per query: computed in the dQ pass (a lane holds half of its query's columns: in-lane + one exchange), written to
 // the workspace [n_seq][H][lpad], read back by the dK / dV pass that the launcher orders after it on the stream.
-template <int DT, bool KV>
+// DROP = true (ccr_attention_bwd_drop_half): with m = keep * inv_keep of (query, head, key), the P operand of dV is P m and
+// dS = P (dp m - delta); delta = sum_d dO O stays as computed (sum_k P_k dP_k = dO . O holds with the dropped O).  Word t of the OWN
+// row holds the 32 bits of streamed tile t: keep_q [query row][H][W] in the dQ pass, keep_k [key row][H][W] in the dK / dV pass.
+template <int DT, bool KV, bool DROP = false>
 __global__ __launch_bounds__(BWD_THREADS) void attention_bwd_kernel(const uint16_t *__restrict__ qkv, const uint16_t *__restrict__ out,
                                                                     const uint16_t *__restrict__ d_out, const float *__restrict__ lse,
                                                                     float *__restrict__ delta, const int32_t *__restrict__ seq_start,
                                                                     const int32_t *__restrict__ seq_len, uint16_t *__restrict__ d_qkv,
                                                                     int H, int pad_len, int max_len, int lpad, float scale,
-                                                                    float scale_log2e) {
+                                                                    float scale_log2e, typename KeepArg<DROP>::type keep = {}) {
     typedef Half16<DT> HT;
     typedef typename HT::vec8 vec8;
     typedef typename HT::elem elem;
@@ -166,8 +169,12 @@ __global__ __launch_bounds__(BWD_THREADS) void attention_bwd_kernel(const uint16
         constexpr bool DS_SCALED = DT == CCR_DTYPE_F16;
         constexpr int DS_TOP = 8, DS_NONE = -1000, DS_MIN = -100;
         int e_run = DS_NONE;
+        const uint32_t *keep_row = nullptr;   // DROP: the words of this lane's own row
+        if constexpr (DROP) keep_row = keep.bits + ((row0 + rr) * H + h) * keep.W;
 
         for (int t = 0; t < ntile; ++t) {
+            uint32_t kw = 0;   // DROP: bit (e & 3) + 8 (e >> 2) of kw <-> register e (ntile <= W: len <= max_len)
+            if constexpr (DROP) kw = keep_row[t] >> (4 * g);
             ef32x16 sc, dp;
 #pragma unroll
             for (int e = 0; e < 16; ++e) sc[e] = dp[e] = 0.f;
@@ -193,8 +200,14 @@ __global__ __launch_bounds__(BWD_THREADS) void attention_bwd_kernel(const uint16
                 for (int i = 0; i < 4; ++i) {
                     const int e = 4 * c4 + i;
                     const float pe = srow + i < len ? __builtin_amdgcn_exp2f(fmaf(sc[e], scale_log2e, -l4[i])) : 0.f;
-                    p[e] = pe;
-                    ds[e] = pe * (dp[e] - d4[i]);   // (without `scale`: the accumulator takes it at the end)
+                    if constexpr (DROP) {
+                        const float mk = (kw >> (i + 8 * c4)) & 1u ? keep.inv_keep : 0.f;
+                        p[e] = pe * mk;
+                        ds[e] = pe * (dp[e] * mk - d4[i]);
+                    } else {
+                        p[e] = pe;
+                        ds[e] = pe * (dp[e] - d4[i]);   // (without `scale`: the accumulator takes it at the end)
+                    }
                 }
             }
             if constexpr (DS_SCALED) {
@@ -286,11 +299,14 @@ __global__ __launch_bounds__(BWD_THREADS) void attention_bwd_kernel(const uint16
 // workgroup's rows, the four waves add up through LDS in a fixed order, and the workgroup's sums go to partial [gridDim.x][2][DIM].
 constexpr int LN_BWD_MAX_BLOCKS = 512;
 
-template <int C, int DT>
+// DROP = true (ccr_add_layernorm_bwd_drop_half): v is recomputed as x * keep * inv_keep + residual with the forward's bits and fma, so
+// mean and rstd are the forward's; d_res = d_v as ever, d_x = d_v * keep * inv_keep rounded to x's type.
+template <int C, int DT, bool DROP = false>
 __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const uint16_t *__restrict__ x, const float *__restrict__ res,
                                                                const float *__restrict__ gamma, float eps, const float *__restrict__ dy,
                                                                float *__restrict__ d_res, uint16_t *__restrict__ d_x,
-                                                               float *__restrict__ partial, int64_t rows) {
+                                                               float *__restrict__ partial, int64_t rows,
+                                                               typename KeepArg<DROP>::type keep = {}) {
     constexpr int DIM = 256 * C;
     __shared__ float red[3][DIM];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -313,10 +329,19 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const uint16_t *
             if (res) r = *reinterpret_cast<const float4 *>(res + row * DIM + col);
             const float4 t = *reinterpret_cast<const float4 *>(dy + row * DIM + col);
             d[c][0] = t.x, d[c][1] = t.y, d[c][2] = t.z, d[c][3] = t.w;
-            v[c][0] = Half16<DT>::lo(xb.x) + r.x;
-            v[c][1] = Half16<DT>::hi(xb.x) + r.y;
-            v[c][2] = Half16<DT>::lo(xb.y) + r.z;
-            v[c][3] = Half16<DT>::hi(xb.y) + r.w;
+            if constexpr (DROP) {
+                float mk[4];
+                keep_nibble(keep, row * (DIM / 32), 64 * c + lane, mk);
+                v[c][0] = fmaf(Half16<DT>::lo(xb.x), mk[0], r.x);
+                v[c][1] = fmaf(Half16<DT>::hi(xb.x), mk[1], r.y);
+                v[c][2] = fmaf(Half16<DT>::lo(xb.y), mk[2], r.z);
+                v[c][3] = fmaf(Half16<DT>::hi(xb.y), mk[3], r.w);
+            } else {
+                v[c][0] = Half16<DT>::lo(xb.x) + r.x;
+                v[c][1] = Half16<DT>::hi(xb.x) + r.y;
+                v[c][2] = Half16<DT>::lo(xb.y) + r.z;
+                v[c][3] = Half16<DT>::hi(xb.y) + r.w;
+            }
             sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
         }
 #pragma unroll
@@ -361,7 +386,16 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const uint16_t *
             y.z = rstd * ((d[c][2] * gm[c][2] - m1) - v[c][2] * m2);
             y.w = rstd * ((d[c][3] * gm[c][3] - m1) - v[c][3] * m2);
             if (d_res) *reinterpret_cast<float4 *>(d_res + row * DIM + col) = y;
-            if (d_x) *reinterpret_cast<uint2 *>(d_x + row * DIM + col) = round4<typename Half16<DT>::elem>(y.x, y.y, y.z, y.w);
+            if constexpr (DROP) {
+                if (d_x) {
+                    float mk[4];
+                    keep_nibble(keep, row * (DIM / 32), 64 * c + lane, mk);
+                    *reinterpret_cast<uint2 *>(d_x + row * DIM + col) =
+                        round4<typename Half16<DT>::elem>(y.x * mk[0], y.y * mk[1], y.z * mk[2], y.w * mk[3]);
+                }
+            } else {
+                if (d_x) *reinterpret_cast<uint2 *>(d_x + row * DIM + col) = round4<typename Half16<DT>::elem>(y.x, y.y, y.z, y.w);
+            }
         }
     }
     if (!partial) return;   // (workgroup-uniform)
@@ -440,50 +474,52 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const uint4 *__restrict__
 
 static inline int bwd_lpad(int max_len) { return (max_len + BWD_TILE - 1) / BWD_TILE * BWD_TILE; }
 
-template <int DT>
+template <int DT, bool DROP = false>
 static int attention_bwd_any(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *d_out, const int32_t *seq_start,
                              const int32_t *seq_len, uint16_t *d_qkv, int n_seq, int n_heads, int max_len, int pad_len, float scale,
-                             float *delta, hipStream_t stream) {
+                             float *delta, hipStream_t stream, typename KeepArg<DROP>::type keep_q = {},
+                             typename KeepArg<DROP>::type keep_k = {}) {
     const int lpad = bwd_lpad(max_len);
     const size_t lds = attention_bwd_lds_bytes(lpad);
     // the opt-in is cached per (kernel, device): ask for the kernel's maximum (512 tokens) once
-    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&attention_bwd_kernel<DT, false>), attention_bwd_lds_bytes(BWD_MAX_LEN));
+    int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&attention_bwd_kernel<DT, false, DROP>), attention_bwd_lds_bytes(BWD_MAX_LEN));
     if (rc != CCR_OK) return rc;
-    rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&attention_bwd_kernel<DT, true>), attention_bwd_lds_bytes(BWD_MAX_LEN));
+    rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&attention_bwd_kernel<DT, true, DROP>), attention_bwd_lds_bytes(BWD_MAX_LEN));
     if (rc != CCR_OK) return rc;
     int waves = lpad / BWD_TILE;
     if (waves > BWD_THREADS / 64) waves = BWD_THREADS / 64;
     const float scale_log2e = scale * 1.4426950408889634f;
-    hipLaunchKernelGGL((attention_bwd_kernel<DT, false>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, out, d_out, lse, delta,
-                       seq_start, seq_len, d_qkv, n_heads, pad_len, max_len, lpad, scale, scale_log2e);
+    hipLaunchKernelGGL((attention_bwd_kernel<DT, false, DROP>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, out, d_out, lse, delta,
+                       seq_start, seq_len, d_qkv, n_heads, pad_len, max_len, lpad, scale, scale_log2e, keep_q);
     CCR_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attention_bwd_kernel<DT, true>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, out, d_out, lse, delta,
-                       seq_start, seq_len, d_qkv, n_heads, pad_len, max_len, lpad, scale, scale_log2e);
+    hipLaunchKernelGGL((attention_bwd_kernel<DT, true, DROP>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, out, d_out, lse, delta,
+                       seq_start, seq_len, d_qkv, n_heads, pad_len, max_len, lpad, scale, scale_log2e, keep_k);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
 
-template <int C, int DT>
+template <int C, int DT, bool DROP>
 static int launch_add_layernorm_bwd(const uint16_t *x, const float *res, const float *gamma, float eps, const float *dy, float *d_res,
-                                    uint16_t *d_x, float *partial, int nblk, int64_t rows, hipStream_t s) {
-    hipLaunchKernelGGL((add_layernorm_bwd_kernel<C, DT>), dim3((unsigned)nblk), dim3(256), 0, s, x, res, gamma, eps, dy, d_res, d_x, partial,
-                       rows);
+                                    uint16_t *d_x, float *partial, int nblk, int64_t rows, hipStream_t s, typename KeepArg<DROP>::type keep) {
+    hipLaunchKernelGGL((add_layernorm_bwd_kernel<C, DT, DROP>), dim3((unsigned)nblk), dim3(256), 0, s, x, res, gamma, eps, dy, d_res, d_x, partial,
+                       rows, keep);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
 
-template <int DT>
+template <int DT, bool DROP = false>
 static int add_layernorm_bwd_any(const uint16_t *x, const float *res, const float *gamma, float eps, const float *dy, float *d_res,
-                                 uint16_t *d_x, float *partial, int nblk, int64_t rows, int dim, hipStream_t s) {
+                                 uint16_t *d_x, float *partial, int nblk, int64_t rows, int dim, hipStream_t s,
+                                 typename KeepArg<DROP>::type keep = {}) {
     switch (dim / 256) {
-        case 1: return launch_add_layernorm_bwd<1, DT>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s);
-        case 2: return launch_add_layernorm_bwd<2, DT>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s);
-        case 3: return launch_add_layernorm_bwd<3, DT>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s);
-        case 4: return launch_add_layernorm_bwd<4, DT>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s);
-        case 5: return launch_add_layernorm_bwd<5, DT>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s);
-        case 6: return launch_add_layernorm_bwd<6, DT>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s);
-        case 7: return launch_add_layernorm_bwd<7, DT>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s);
-        default: return launch_add_layernorm_bwd<8, DT>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s);
+        case 1: return launch_add_layernorm_bwd<1, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
+        case 2: return launch_add_layernorm_bwd<2, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
+        case 3: return launch_add_layernorm_bwd<3, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
+        case 4: return launch_add_layernorm_bwd<4, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
+        case 5: return launch_add_layernorm_bwd<5, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
+        case 6: return launch_add_layernorm_bwd<6, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
+        case 7: return launch_add_layernorm_bwd<7, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
+        default: return launch_add_layernorm_bwd<8, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
     }
 }
 
@@ -534,6 +570,73 @@ extern "C" int ccr_attention_bwd_half(const uint16_t *qkv, const uint16_t *out, 
     return half_dtype == CCR_DTYPE_F16
                ? attention_bwd_any<CCR_DTYPE_F16>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads, max_len, pad_len, scale, delta, s)
                : attention_bwd_any<CCR_DTYPE_BF16>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads, max_len, pad_len, scale, delta, s);
+}
+
+extern "C" int ccr_attention_bwd_drop_half(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *d_out,
+                                           const int32_t *seq_start, const int32_t *seq_len, const uint32_t *keep_q, const uint32_t *keep_k,
+                                           float inv_keep, uint16_t *d_qkv, int n_seq, int n_heads, int max_len, int pad_len, float scale,
+                                           int half_dtype, void *workspace, size_t workspace_bytes, void *stream) {
+    CCR_REQUIRE(qkv && out && lse && d_out && seq_start && seq_len && keep_q && keep_k && d_qkv && workspace,
+                "ccr_attention_bwd_drop_half: null pointer");
+    CCR_REQUIRE_HALF(half_dtype, "ccr_attention_bwd_drop_half");
+    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024, "ccr_attention_bwd_drop_half: bad shape n_seq=%d n_heads=%d",
+                n_seq, n_heads);
+    CCR_REQUIRE(max_len > 0 && max_len <= BWD_MAX_LEN && pad_len >= 0 && pad_len <= BWD_MAX_LEN,
+                "ccr_attention_bwd_drop_half: max_len=%d pad_len=%d (1..512 tokens per sequence)", max_len, pad_len);
+    CCR_REQUIRE(scale > 0.f, "ccr_attention_bwd_drop_half: scale must be positive");
+    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "ccr_attention_bwd_drop_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
+    const size_t need = ccr_attention_bwd_workspace_bytes(n_seq, n_heads, max_len);
+    if (workspace_bytes < need) {
+        set_error("ccr_attention_bwd_drop_half: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        return CCR_ERR_WORKSPACE;
+    }
+    CCR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "ccr_attention_bwd_drop_half: 4-byte aligned workspace");
+    if (n_seq == 0) return CCR_OK;
+    float *delta = static_cast<float *>(workspace);
+    hipStream_t s = (hipStream_t)stream;
+    const int W = (max_len + 31) / 32;
+    const KeepBits kq = {keep_q, inv_keep, W}, kk = {keep_k, inv_keep, W};
+    return half_dtype == CCR_DTYPE_F16 ? attention_bwd_any<CCR_DTYPE_F16, true>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads,
+                                                                                max_len, pad_len, scale, delta, s, kq, kk)
+                                       : attention_bwd_any<CCR_DTYPE_BF16, true>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads,
+                                                                                 max_len, pad_len, scale, delta, s, kq, kk);
+}
+
+extern "C" int ccr_add_layernorm_bwd_drop_half(const uint16_t *x_half, const uint32_t *bits, float inv_keep, const float *residual,
+                                               const float *gamma, float eps, const float *d_y, float *d_res, uint16_t *d_x, float *d_gamma,
+                                               float *d_beta, int64_t rows, int dim, int half_dtype, void *workspace, size_t workspace_bytes,
+                                               void *stream) {
+    CCR_REQUIRE(x_half && bits && gamma && d_y, "ccr_add_layernorm_bwd_drop_half: null pointer");
+    CCR_REQUIRE_HALF(half_dtype, "ccr_add_layernorm_bwd_drop_half");
+    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
+                "ccr_add_layernorm_bwd_drop_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
+    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "ccr_add_layernorm_bwd_drop_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
+    const bool params = d_gamma || d_beta;
+    int64_t nblk = (rows + 3) / 4;
+    if (nblk > LN_BWD_MAX_BLOCKS) nblk = LN_BWD_MAX_BLOCKS;
+    const size_t need = params ? (size_t)nblk * 2 * dim * sizeof(float) : 0;
+    if (need && (!workspace || workspace_bytes < need)) {
+        set_error("ccr_add_layernorm_bwd_drop_half: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+        return CCR_ERR_WORKSPACE;
+    }
+    CCR_REQUIRE(!need || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ccr_add_layernorm_bwd_drop_half: 16-byte aligned workspace");
+    if (!d_res && !d_x && !params) return CCR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (rows == 0) {   // sums over no rows
+        if (d_gamma) CCR_HIP_CHECK(hipMemsetAsync(d_gamma, 0, (size_t)dim * sizeof(float), s));
+        if (d_beta) CCR_HIP_CHECK(hipMemsetAsync(d_beta, 0, (size_t)dim * sizeof(float), s));
+        return CCR_OK;
+    }
+    float *partial = params ? static_cast<float *>(workspace) : nullptr;
+    const KeepBits keep = {bits, inv_keep, 0};
+    const int rc = half_dtype == CCR_DTYPE_F16 ? add_layernorm_bwd_any<CCR_DTYPE_F16, true>(x_half, residual, gamma, eps, d_y, d_res, d_x, partial,
+                                                                                            (int)nblk, rows, dim, s, keep)
+                                               : add_layernorm_bwd_any<CCR_DTYPE_BF16, true>(x_half, residual, gamma, eps, d_y, d_res, d_x, partial,
+                                                                                             (int)nblk, rows, dim, s, keep);
+    if (rc != CCR_OK || !params) return rc;
+    hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((unsigned)(2 * dim / 64)), dim3(256), 0, s, partial, (int)nblk, dim, d_gamma, d_beta);
+    CCR_LAUNCH_CHECK();
+    return CCR_OK;
 }
 
 extern "C" int ccr_add_layernorm_bwd_half(const uint16_t *x_half, const float *residual, const float *gamma, float eps, const float *d_y,

@@ -79,6 +79,31 @@ __device__ __forceinline__ float refined_mean(const float (&v)[C][4], float m0) 
     return m0 + sd * (1.f / (256 * C));
 }
 
+// Training dropout (ccr_dropout.hip writes the bits): a kernel instantiated with DROP = true takes the packed keep bits of its site and
+// the scale 1 / (1 - p_eff) of a kept element; DROP = false takes an empty struct in their place, as NoLse does for lse -- the
+// dropout-free instantiations keep their argument layout and their code.
+struct NoKeep {};
+struct KeepBits {
+    const uint32_t *bits;   // row-wise sites: [rows][dim / 32]; attention: keep_q (forward, dQ pass) or keep_k (dK / dV pass) [T][H][W]
+    float inv_keep;
+    int W;                  // attention only: words per (token row, head) = ceil(max_len / 32)
+};
+template <bool DROP>
+struct KeepArg {
+    typedef NoKeep type;
+};
+template <>
+struct KeepArg<true> {
+    typedef KeepBits type;
+};
+
+// row-wise sites: the factors of the four columns 4 u .. 4 u + 3 (u = 64 c + lane) of the row whose words start at bits[word0]
+__device__ __forceinline__ void keep_nibble(const KeepBits &keep, int64_t word0, int u, float (&mk)[4]) {
+    const uint32_t nib = keep.bits[word0 + (u >> 3)] >> (4 * (u & 7));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mk[j] = (nib >> j) & 1u ? keep.inv_keep : 0.f;
+}
+
 #define CCR_REQUIRE_HALF(dtype, who) \
     CCR_REQUIRE((dtype) == CCR_DTYPE_BF16 || (dtype) == CCR_DTYPE_F16, who ": half_dtype=%d (CCR_DTYPE_F16 or CCR_DTYPE_BF16)", (int)(dtype))
 

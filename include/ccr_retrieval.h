@@ -226,6 +226,56 @@ int ccr_add_layernorm_bwd_half(const uint16_t *x_half, const float *residual, co
 int ccr_gelu_bwd_half(const uint16_t *x, const uint16_t *d_y, uint16_t *d_x, int64_t n, int half_dtype, void *stream);
 
 /*
+ * Training dropout for the layer kernels (library version 104).  The reference fine-tunes its towers in train() mode with the
+ * checkpoints' own dropout 0.1 (src/ccrec/models/bbpr.py:195-197, bert_mt.py:105-113).  No layer kernel draws a random number: two
+ * generator kernels write PACKED KEEP BITS (1 = keep), and the *_drop_* entry points below are the layer kernels above reading those
+ * bits plus one scale factor, so the forward and both backward passes see the same stored decisions and a caller may pass any mask.
+ * A decision is a pure function of (seed, stream_id, indices): Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9 / 0xBB67AE85, key = seed's low and high word); the four output words are eight 16-bit lanes (low half of word 0, high
+ * half of word 0, low half of word 1, ..), lane j decides element 8 * group + j, keep iff lane >= thr = floor(p * 65536 + 0.5).  The
+ * probability actually used is p_eff = thr / 65536 and the matching scale is inv_keep = 65536 / (65536 - thr).  0 <= p and thr < 65536,
+ * else CCR_ERR_INVALID.  ccrec_amd/dropout_ref.py restates the generator on the CPU.
+ * ccr_dropout_bits_rows (bbpr.py:195-197, bert_mt.py:105-113: the hidden-state dropouts of BertEmbeddings / BertSelfOutput / BertOutput):
+ *   bits [rows][dim / 32] uint32 for a [rows][dim] tensor, dim % 256 == 0, dim <= 2048; bit i of word w <-> column 32 * w + i; counter =
+ *   (row, column >> 3, stream_id, 0).
+ * ccr_dropout_bits_attention (bbpr.py:195-197, bert_mt.py:105-113: the dropout on BertSelfAttention's probabilities): counter = (token
+ *   row of the query = seq_start[s] + q, k >> 3, stream_id, head).  Two arrays [n_tokens][n_heads][W] uint32, W = ceil(max_len / 32), hold
+ *   the same decisions: keep_q row = the query's token row, bit = key position; keep_k row = the key's token row, bit = query
+ *   position (what the dK / dV pass reads).  Bits of positions >= seq_len[s] are unspecified, and no kernel lets them matter; rows of
+ *   no sequence are not written.
+ * ccr_dropout_apply (bbpr.py:195-197, bert_mt.py:105-113: BertEmbeddings.dropout after the embedding LayerNorm): y = x * keep * inv_keep
+ *   elementwise, x [rows][dim] fp32 -> out_f32 and / or out_half (either may be NULL); its backward is the same call on the gradient.
+ * ccr_attention_fwd_train_drop_half (bbpr.py:195-197, bert_mt.py:105-113): ccr_attention_fwd_train_half where the probability that is
+ *   rounded to 16 bits for the P.V product is p * keep * inv_keep; the softmax and lse are those of the undropped scores.
+ * ccr_attention_bwd_drop_half (bbpr.py:195-197, bert_mt.py:105-113): ccr_attention_bwd_half for that forward; with m = keep * inv_keep
+ *   the P operand of dV is P * m and dS = P * (dP * m - delta).  Same workspace as ccr_attention_bwd_half.
+ * ccr_add_layernorm_drop_half (bbpr.py:195-197, bert_mt.py:105-113: LayerNorm(dropout(dense(h)) + input)): ccr_add_layernorm_half on
+ *   v = x * keep * inv_keep + residual, one fp32 fused multiply-add per element.
+ * ccr_add_layernorm_bwd_drop_half (bbpr.py:195-197, bert_mt.py:105-113): ccr_add_layernorm_bwd_half with v recomputed from the same bits;
+ *   d_res as there, d_x = d_res * keep * inv_keep rounded to x's type.
+ * inv_keep: 1 .. 65536.  With all-ones bits and inv_keep = 1 every *_drop_* entry point returns the bits of its dropout-free twin.
+ */
+int ccr_dropout_bits_rows(uint32_t *bits, int64_t rows, int dim, uint64_t seed, uint32_t stream_id, double p, void *stream);
+int ccr_dropout_bits_attention(uint32_t *keep_q, uint32_t *keep_k, const int32_t *seq_start, const int32_t *seq_len, int64_t n_tokens,
+                               int n_seq, int n_heads, int max_len, uint64_t seed, uint32_t stream_id, double p, void *stream);
+int ccr_dropout_apply(const float *x, const uint32_t *bits, float inv_keep, float *out_f32, uint16_t *out_half, int64_t rows, int dim,
+                      int half_dtype, void *stream);
+int ccr_attention_fwd_train_drop_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, float *lse,
+                                      const uint32_t *keep_q, float inv_keep, int n_seq, int n_heads, int max_len, int pad_len,
+                                      float scale, int half_dtype, void *stream);
+int ccr_attention_bwd_drop_half(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *d_out,
+                                const int32_t *seq_start, const int32_t *seq_len, const uint32_t *keep_q, const uint32_t *keep_k,
+                                float inv_keep, uint16_t *d_qkv, int n_seq, int n_heads, int max_len, int pad_len, float scale,
+                                int half_dtype, void *workspace, size_t workspace_bytes, void *stream);
+int ccr_add_layernorm_drop_half(const uint16_t *x_half, const uint32_t *bits, float inv_keep, const float *residual, const float *gamma,
+                                const float *beta, float eps, float *out_f32, uint16_t *out_half, int64_t rows, int dim, int half_dtype,
+                                void *stream);
+int ccr_add_layernorm_bwd_drop_half(const uint16_t *x_half, const uint32_t *bits, float inv_keep, const float *residual,
+                                    const float *gamma, float eps, const float *d_y, float *d_res, uint16_t *d_x, float *d_gamma,
+                                    float *d_beta, int64_t rows, int dim, int half_dtype, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+
+/*
  * Build a search index over a resident bf16 corpus shard (borrowed pointer, no copy).
  * Replaces: the host-resident fp32 passage matrix of scripts/ms_marco_eval.py:199-201,208-210.
  *   global_row_offset: id of row 0 of this shard in the whole corpus (multi-GPU row sharding).
