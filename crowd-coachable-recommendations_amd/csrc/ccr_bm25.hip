@@ -111,6 +111,7 @@ __device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
 // collect pass in r4: 8 of the call's 13.6 GB of fabric traffic) never exist.
 enum { BM25_STORE = 0, BM25_SAMPLE = 1, BM25_FILTER = 2 };
 constexpr int BM25_LIST_CAP = 16384;         // candidate records per row (128 KiB of keys in the top-k kernel)
+constexpr uint32_t BM25_ODD_NAN = 0x80000000u;   // odd_cnt[row]: the waves that saw a negative / NaN score (fewer than 2^31), this bit: a NaN
 
 // grid = any, block = 256 (four independent waves).  T documents per tile, U 64-posting chunks per step, run_tiles tiles per ticket.
 // row_map (STORE only, may be null): the launch scores table rows row_map[0 .. n_rows) into score rows 0 .. n_rows (the redo list).
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(256) void bm25_tile_kernel(const Bm25Term *__restri
         }
         float *out_row = MODE == BM25_SAMPLE ? scores + ((int64_t)row * n_runs + run) * T : scores + (int64_t)row * n_docs;
         float thr = 0.f;
-        bool odd = false;
+        bool neg = false, nan = false;
         if (MODE == BM25_FILTER) thr = tau[row];
         for (int64_t tile_base = run_base; tile_base < run_end; tile_base += T) {
             const int tile_end = (int)(tile_base + T < n_docs ? tile_base + T : n_docs);
@@ -283,7 +284,8 @@ __global__ __launch_bounds__(256) void bm25_tile_kernel(const Bm25Term *__restri
                     const int x = j * 64 + lane;
                     const float v = (float)acc[x];
                     const bool in = tile_base + x < n_docs;
-                    odd = odd || (in && (v < 0.f || v != v));
+                    neg = neg || (in && v < 0.f);
+                    nan = nan || (in && v != v);
                     hits += __popcll(__ballot(in && v >= thr && (thr > 0.f || v > 0.f)));
                 }
                 if (hits != 0) {   // wave-uniform
@@ -317,7 +319,9 @@ __global__ __launch_bounds__(256) void bm25_tile_kernel(const Bm25Term *__restri
                 }
             }
         }
-        if (MODE == BM25_FILTER && __ballot(odd) != 0ull && lane == 0) atomicAdd(&odd_cnt[row], 1u);
+        // a NaN fails every comparison with tau, so it is never listed, but the order ranks it above +inf: such a row is never finished here
+        if (MODE == BM25_FILTER && __ballot(neg || nan) != 0ull && lane == 0) atomicAdd(&odd_cnt[row], 1u);
+        if (MODE == BM25_FILTER && __ballot(nan) != 0ull && lane == 0) atomicOr(&odd_cnt[row], BM25_ODD_NAN);
     }
 }
 
@@ -407,9 +411,10 @@ __global__ __launch_bounds__(NT) void bm25_topk_kernel(const uint2 *__restrict__
     // Fewer than k documents passed.  With tau <= 0 and no negative / NaN score in the row the list holds EVERY non-zero document, all
     // others score exactly zero, and the row's top-k is the sorted list followed by the k - n lowest-numbered documents outside it
     // (a query whose terms match fewer than k documents: common for rare terms).  Anything else -- an estimate that came out too high,
-    // a flooded list -- goes to the exact dense selection.
-    const bool zero_fill = n < (uint32_t)k && tau[r] <= 0.f && odd_cnt[r] == 0u;
-    if ((n < (uint32_t)k && !zero_fill) || n > (uint32_t)BM25_LIST_CAP) {   // block-uniform
+    // a flooded list, a row with a NaN score (NaN ranks first and is never listed) -- goes to the exact dense selection.
+    const uint32_t odd = odd_cnt[r];
+    const bool zero_fill = n < (uint32_t)k && tau[r] <= 0.f && odd == 0u;
+    if ((n < (uint32_t)k && !zero_fill) || n > (uint32_t)BM25_LIST_CAP || (odd & BM25_ODD_NAN) != 0u) {   // block-uniform
         if (tid == 0) redo_list[atomicAdd(redo_cnt, 1u)] = (uint32_t)r;
         continue;
     }
@@ -434,7 +439,7 @@ __global__ __launch_bounds__(NT) void bm25_topk_kernel(const uint2 *__restrict__
     if (zero_fill) {
         // the j-th lowest document that is NOT in the list (j = 0 .. k - n - 1) is document j + (number of listed documents <= it): at most
         // n < k listed documents lie below it, so thread j walks candidates j, j + 1, ... and counts the listed ones below by scanning the
-        // list (n < k <= 8 192 entries in LDS; this path serves a few rare-term queries)
+        // list (n < k <= MAX_K = 4 096 entries: the SMALL class, keys and documents in its 48 KiB of LDS; this path serves a few rare-term queries)
         __syncthreads();
         unsigned int *s_doc = reinterpret_cast<unsigned int *>(s_keys + np2);     // the listed documents, unsorted
         for (int i = tid; i < (int)n; i += NT) s_doc[i] = key_idx(s_keys[i]);
@@ -624,7 +629,7 @@ Bm25Sample bm25_sample_plan(const ccr_bm25_index *ix, int k) {
     S.rank = bm25_sample_rank(k, fs);
     // the sampled filter needs a sample that holds several times the rank; smaller corpora keep the exact dense selection
     S.ok = getenv("CCR_BM25_DENSE_SELECT") == nullptr && (int64_t)S.n_pieces * BM25_SAMPLE_PIECE >= 8 * (int64_t)S.rank &&
-           (double)S.rank / fs * 2.0 + 1024.0 <= (double)BM25_LIST_CAP && k <= BM25_LIST_CAP / 2;
+           (double)S.rank / fs * 2.0 + 1024.0 <= (double)BM25_LIST_CAP && k <= BM25_LIST_CAP / 2;   // (a search has k <= MAX_K; the workspace query may ask beyond)
     return S;
 }
 
@@ -787,7 +792,7 @@ extern "C" int ccr_bm25_search(const ccr_bm25_index *ix, const int64_t *q_ptr_ho
     uint2 *cand_list = (uint2 *)sel;                             // fused only from here on
     float *tau = (float *)(sel + (size_t)rows * BM25_LIST_CAP * 8);
     uint32_t *list_cnt = (uint32_t *)(tau + rows);
-    uint32_t *odd_cnt = list_cnt + rows;           // [rows]: waves that saw a negative / NaN score
+    uint32_t *odd_cnt = list_cnt + rows;           // [rows]: waves that saw a negative / NaN score; BM25_ODD_NAN: a NaN
     uint32_t *ctl = L.fused ? odd_cnt + rows : (uint32_t *)sel;   // [0] redo count, [1..3] tickets of the sample / filter / store launches
     uint32_t *redo_list = ctl + 4;                 // [rows]
     float *sample = (float *)(ws + L.sample_off);

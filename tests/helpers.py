@@ -789,3 +789,264 @@ def bpr_relative_error(got, ref):
     err = np.abs(got[nz] - ref[nz])
     err = np.where(np.abs(ref[nz]) < 2.0 ** -126, np.maximum(err - BPR_SUBNORMAL, 0.0), err)
     return float((err / np.abs(ref[nz])).max())
+
+
+# ---------------------------------------------------------------------------------------------- BM25: reference, builders and probes
+# (shared by tests/test_bm25.py, tests/test_cpu_bm25_reference.py and tests/test_gpu_bm25_edges.py)
+def _random_postings(rs, n_docs, n_terms, dense_terms):
+    """Term-major postings of a random count matrix: `dense_terms` terms in ~half of the documents, the others with Zipf-like
+    document frequencies down to a single posting and a few empty terms."""
+    indptr, rows, counts = [0], [], []
+    for t in range(n_terms):
+        if t < dense_terms:
+            df = int(n_docs * rs.uniform(0.3, 0.98))
+        elif t % 97 == 5:
+            df = 0
+        else:
+            df = max(1, int(n_docs * 0.2 / (t - dense_terms + 1) ** 1.1))
+        r = np.sort(rs.choice(n_docs, df, replace=False)) if df else np.zeros(0, np.int64)
+        rows.append(r)
+        counts.append(rs.randint(1, 6, df))
+        indptr.append(indptr[-1] + df)
+    idf = np.log(n_docs / np.maximum(np.diff(indptr), 1).astype(np.float64))
+    doc_k = 1.2 * (0.25 + 0.75 * rs.uniform(0.3, 2.5, n_docs))
+    return np.asarray(indptr, np.int64), np.concatenate(rows).astype(np.int32), np.concatenate(counts).astype(np.float32), doc_k, idf
+
+
+BM25_SAMPLE_PIECE = 1024     # csrc/ccr_bm25.hip: documents per sampled piece, one piece out of every BM25_SAMPLE_EVERY
+BM25_SAMPLE_EVERY = 64
+BM25_LIST_CAP = 16384        # candidate records per row
+BM25_SLICE_KINDS = ("0", "1", "step-1", "step", "step+1", "2step", "2step+1", "tile")
+
+
+def bm25_reference_rows(indptr, rows, counts, doc_k, weights, queries, k1):
+    """fp32 [n_q, n_docs]: acc[d] = acc[d] + ((f * w_t) * (k1 + 1)) / (f + doc_k[d]) in numpy fp64, one operation at a time, the query's
+    terms in ascending id, then ONE cast to fp32.  (A term's documents are distinct, so the fancy-indexed add is one add per cell.)"""
+    doc_k = np.asarray(doc_k, np.float64)
+    weights = np.asarray(weights, np.float64)
+    out = np.zeros((len(queries), len(doc_k)), np.float32)
+    k1p1 = np.float64(k1) + 1.0
+    with np.errstate(invalid="ignore", over="ignore"):
+        for qi, q in enumerate(queries):
+            acc = np.zeros(len(doc_k), np.float64)
+            for t in sorted(int(t) for t in q):
+                d = rows[indptr[t]:indptr[t + 1]]
+                f = counts[indptr[t]:indptr[t + 1]].astype(np.float64)
+                numer = (f * weights[t]) * k1p1
+                denom = f + doc_k[d]
+                acc[d] = acc[d] + numer / denom
+            out[qi] = acc.astype(np.float32)
+    return out
+
+
+def bm25_reference_topk(rows_fp32, k):
+    """(ids int64 [n_q, k], scores fp32 [n_q, k]) in the total order (score descending, document ascending).  No NaN rows."""
+    rows_fp32 = np.atleast_2d(rows_fp32)
+    assert not np.isnan(rows_fp32).any(), "rows with NaN are compared between the paths, not with this order"
+    ids = np.empty((rows_fp32.shape[0], k), np.int64)
+    sc = np.empty((rows_fp32.shape[0], k), np.float32)
+    doc = np.arange(rows_fp32.shape[1])
+    for r, row in enumerate(rows_fp32):
+        o = np.lexsort((doc, -row.astype(np.float64)))[:k]
+        ids[r], sc[r] = o, row[o]
+    return ids, sc
+
+
+def _f32_order_key(x):
+    """The unsigned key whose order is the order of the floats, -NaN < -inf < .. < -0 < +0 < .. < +inf < +NaN (ccr_common.h)."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    return np.where(u >> 31 != 0, ~u, u | np.uint32(0x80000000))
+
+
+def bm25_reference_filter(row_fp32, n_docs, rank, k):
+    """What the fused selection must do with one row -> (tau, n, redo): tau = the rank-th largest score of the sampled documents (pieces
+    of 1 024 out of every 64 pieces; a piece that reaches beyond the corpus is filled with -inf), n = #{score >= tau and (tau > 0 or
+    score > 0)}, redo = (n < k and not (tau <= 0 and no negative / NaN score)) or n > 16 384."""
+    row = np.asarray(row_fp32, np.float32)
+    assert row.shape == (n_docs,)
+    n_all = (n_docs + BM25_SAMPLE_PIECE - 1) // BM25_SAMPLE_PIECE
+    assert (n_all + BM25_SAMPLE_EVERY - 1) // BM25_SAMPLE_EVERY * BM25_SAMPLE_PIECE <= 16384, "larger corpora sample more sparsely"
+    pieces = []
+    for p in range(0, n_all, BM25_SAMPLE_EVERY):
+        piece = np.full(BM25_SAMPLE_PIECE, -np.inf, np.float32)
+        part = row[p * BM25_SAMPLE_PIECE:(p + 1) * BM25_SAMPLE_PIECE]
+        piece[:len(part)] = part
+        pieces.append(piece)
+    sample = np.concatenate(pieces)
+    assert 1 <= rank <= len(sample)
+    tau = sample[np.argsort(_f32_order_key(sample), kind="stable")[len(sample) - rank]]
+    with np.errstate(invalid="ignore"):
+        n = int(((row >= tau) & ((tau > 0) | (row > 0))).sum())
+        odd = bool(((row < 0) | np.isnan(row)).any())
+        redo = (n < k and not (tau <= 0 and not odd)) or n > BM25_LIST_CAP
+    return tau, n, bool(redo)
+
+
+def bm25_structured_postings(n_docs, tile, step, seed, n_regular=64):
+    """A term-major index written around the tile scorer's control flow (tile = documents per tile, step = postings per cursor step).
+    Terms, in id order:
+      0                      empty
+      1 .. n_regular         "regular": the slice of term j in tile i has the length BM25_SLICE_KINDS[(j + 3 i + seed) % 8] (clipped to the
+                             tile: 2 step + 1 does not fit a tile of 2 step documents, and the last tile may be short) and lies at the
+                             front of the tile, at its end, or scattered, by (j + i) % 3; an empty PAIR sits after the first half of them
+      E                      a posting at every multiple of 512 and at every multiple of 512 minus 1 (the run and tile boundaries)
+      A                      every document
+      L                      `step` consecutive postings: the LAST list of the index, ending exactly at a full step
+      last                   empty
+    tf is 1 .. 5, on a few postings up to 2^24 (exact in fp32); doc_k is log-uniform over [1e-3, 1e3]; idf is uniform over [0.1, 8), all
+    different.  -> (indptr, rows, counts, doc_k, idf); bm25_structured_layout() names the special terms."""
+    rs = np.random.RandomState(seed)
+    lay = bm25_structured_layout(n_regular)
+    lens = {"0": 0, "1": 1, "step-1": step - 1, "step": step, "step+1": step + 1, "2step": 2 * step, "2step+1": 2 * step + 1, "tile": tile}
+    n_tiles = (n_docs + tile - 1) // tile
+    lists = [np.zeros(0, np.int64) for _ in range(lay["n_terms"])]
+    for j, t in enumerate(lay["regular"]):
+        parts = []
+        for i in range(n_tiles):
+            lo, hi = i * tile, min(n_docs, (i + 1) * tile)
+            n = min(lens[BM25_SLICE_KINDS[(j + 3 * i + seed) % 8]], hi - lo)
+            place = (j + i) % 3
+            parts.append(np.arange(lo, lo + n) if place == 0 else np.arange(hi - n, hi) if place == 1 else
+                         lo + np.sort(rs.choice(hi - lo, n, replace=False)))
+        lists[t] = np.concatenate(parts).astype(np.int64)
+    edges = np.arange(0, n_docs + 512, 512)
+    e = np.unique(np.concatenate([edges, edges - 1]))
+    lists[lay["E"]] = e[(e >= 0) & (e < n_docs)]
+    lists[lay["A"]] = np.arange(n_docs)
+    full = [i for i in range(n_tiles) if min(n_docs, (i + 1) * tile) - i * tile >= step][-1]      # the last tile that holds a whole step
+    lists[lay["L"]] = full * tile + np.arange(step)
+    indptr = np.zeros(lay["n_terms"] + 1, np.int64)
+    indptr[1:] = np.cumsum([len(x) for x in lists])
+    rows = np.concatenate(lists).astype(np.int32)
+    counts = rs.randint(1, 6, len(rows)).astype(np.float32)
+    big = rs.choice(len(rows), min(40, len(rows)), replace=False)
+    counts[big] = np.float32(2.0) ** rs.randint(10, 25, len(big))
+    counts[big[0]] = np.float32(2.0 ** 24)
+    doc_k = 10.0 ** rs.uniform(-3.0, 3.0, n_docs)
+    doc_k[0], doc_k[-1] = 1e-3, 1e3
+    idf = rs.uniform(0.1, 8.0, lay["n_terms"])
+    return indptr, rows, counts, doc_k, idf
+
+
+def bm25_structured_layout(n_regular=64):
+    """Term ids of bm25_structured_postings: regular (non-empty by construction except where a slice kind says 0), the empty terms and
+    the special lists."""
+    half = n_regular // 2
+    regular = list(range(1, 1 + half)) + list(range(3 + half, 3 + n_regular))
+    E = 3 + n_regular
+    return dict(regular=regular, empty=[0, 1 + half, 2 + half, E + 3], E=E, A=E + 1, L=E + 2, n_terms=E + 4)
+
+
+def bm25_slice_lengths(indptr, rows, term, n_docs, tile):
+    """Postings of `term` per tile."""
+    d = rows[indptr[term]:indptr[term + 1]]
+    return np.bincount(d // tile, minlength=(n_docs + tile - 1) // tile)
+
+
+def bm25_structured_queries(indptr, rows, n_docs, tile, seed, n_regular=64):
+    """The query set of the every-document tests: each single term (the empty ones and the every-document term among them), for
+    n in 1, 4, 5, 8, 9 and every tile i two queries with exactly n terms active in tile i (plus two that are not), 64 regular terms, an
+    empty query, a query of empty terms only."""
+    lay = bm25_structured_layout(n_regular)
+    rs = np.random.RandomState(seed + 77)
+    queries = [np.asarray([t], np.int32) for t in range(lay["n_terms"])]
+    reg = np.asarray(lay["regular"])
+    per_tile = np.stack([bm25_slice_lengths(indptr, rows, t, n_docs, tile) for t in reg])      # [regular, tiles]
+    for i in range(per_tile.shape[1]):
+        on, off = reg[per_tile[:, i] > 0], reg[per_tile[:, i] == 0]
+        for n in (1, 4, 5, 8, 9):
+            for _ in range(2):
+                q = np.concatenate([rs.choice(on, n, replace=False), rs.choice(off, min(2, len(off)), replace=False)])
+                queries.append(np.sort(q).astype(np.int32))
+    queries.append(np.sort(reg[:64]).astype(np.int32))
+    queries.append(np.zeros(0, np.int32))
+    queries.append(np.asarray(lay["empty"], np.int32))
+    return queries
+
+
+# The exact probes: k1 = 1, tf = 1 and doc_k = 1 make a posting's contribution (1 w)(1 + 1) / (1 + 1) = w, exactly.
+BM25_PROBE_DOCS = 4096
+BM25_PROBE_TERMS = 260
+# (first term, weights in term order, document, fp32 bits the score must have)
+BM25_ROUNDING_PROBES = [
+    (3, [1.0 + 2.0 ** -24, 2.0 ** -53, 2.0 ** -53], 1024, 0x3F800000),        # ascending ids: each 2^-53 is dropped by a tie to even
+    (63, [1.0 + 2.0 ** -24, 2.0 ** -53, 2.0 ** -53], 1535, 0x3F800000),       # .. across the cursor groups 0 | 1
+    (191, [1.0 + 2.0 ** -24, 2.0 ** -53, 2.0 ** -53], 1536, 0x3F800000),      # .. across the cursor groups 2 | 3
+    (7, [2.0 ** -53, 2.0 ** -53, 1.0 + 2.0 ** -24], 1025, 0x3F800001),        # the reversed ids: 2^-52 survives, fp32 rounds up
+    (127, [2.0 ** -53, 2.0 ** -53, 1.0 + 2.0 ** -24], 2047, 0x3F800001),      # .. across the cursor groups 1 | 2
+    (195, [2.0 ** -53, 2.0 ** -53, 1.0 + 2.0 ** -24], 1537, 0x3F800001),
+    (11, [1.0, 2.0 ** -24, 2.0 ** -50], 1026, 0x3F800001),                    # one rounding: fp32 accumulation gives 0x3F800000
+    (15, [1.0, 2.0 ** -24], 1027, 0x3F800000),                                # the tie itself
+]
+BM25_PROBE_SHARED_DOC = 1500      # holds every term
+
+
+def bm25_order_probe(seed=0):
+    """260 terms over 4 096 documents, tf = 1, doc_k = 1, k1 = 1.  Every term has a posting in document BM25_PROBE_SHARED_DOC and six more
+    in tile [1024, 2048) and elsewhere (none in a probe document), with weights in [2^-8, 2^-4); the terms of BM25_ROUNDING_PROBES carry the
+    probes' weights instead and meet in the probe's document.  A query of the first n terms puts term i at position i, so the probes sit
+    across the fetch groups of four (3|4, 7|8, 11|12, 15|16) and across the cursor groups (63|64, 127|128, 191|192).
+    -> (indptr, rows, counts, doc_k, weights)."""
+    rs = np.random.RandomState(seed)
+    n_docs, n_terms = BM25_PROBE_DOCS, BM25_PROBE_TERMS
+    weights = rs.uniform(2.0 ** -8, 2.0 ** -4, n_terms)
+    probe_docs = {p[2] for p in BM25_ROUNDING_PROBES}
+    free = np.asarray([d for d in range(n_docs) if d not in probe_docs and d != BM25_PROBE_SHARED_DOC])
+    in_tile = free[(free >= 1024) & (free < 2048)]
+    lists = []
+    for t in range(n_terms):
+        d = np.concatenate([rs.choice(in_tile, 3, replace=False), rs.choice(free, 3, replace=False), [BM25_PROBE_SHARED_DOC]])
+        lists.append(set(int(x) for x in d))
+    for first, w, doc, _ in BM25_ROUNDING_PROBES:
+        for j, wj in enumerate(w):
+            weights[first + j] = wj
+            lists[first + j].add(doc)
+    lists = [np.asarray(sorted(s), np.int64) for s in lists]
+    indptr = np.zeros(n_terms + 1, np.int64)
+    indptr[1:] = np.cumsum([len(x) for x in lists])
+    rows = np.concatenate(lists).astype(np.int32)
+    return indptr, rows, np.ones(len(rows), np.float32), np.ones(n_docs, np.float64), weights
+
+
+BM25_MASK_EDGE_DOCS = [0, 1, 63, 64, 511, 512, 513, 1023, 1024, 1025, 1535, 1536, 2047, 2048, 2049, 2559, 2560, 3071, 3072, 3073, 4094, 4095]
+BM25_MASK_WINDOWS = [0, 24, 40]      # positions [w, w + 24) of a 64-term query: 24 different residues mod 24; lanes 0, 1 and 62, 63 are inside
+
+
+def bm25_mask_probe(seed=0):
+    """The presence mask: 256 terms over 4 096 documents (tf = 1, doc_k = 1, k1 = 1), term t weighs 2^-(t % 24).  Per block of 64 terms a
+    document is in a non-empty subset of ONE window of 24 consecutive terms, so the query of that block scores it with the subset's
+    bitmask, sum of 2^-(t % 24), exact in fp32: a dropped, doubled or misplaced posting changes named bits.  Documents: the tile and
+    run edges plus 300 others.  -> (indptr, rows, counts, doc_k, weights, member [n_docs, 256] bool)."""
+    rs = np.random.RandomState(seed + 5)
+    n_docs, n_terms = BM25_PROBE_DOCS, 256
+    docs = sorted(set(BM25_MASK_EDGE_DOCS) | set(int(d) for d in rs.choice(n_docs, 300, replace=False)))
+    member = np.zeros((n_docs, n_terms), bool)
+    for n, d in enumerate(docs):
+        for g in range(4):
+            w = BM25_MASK_WINDOWS[(n + g) % 3]
+            sub = rs.rand(24) < 0.5
+            sub[rs.randint(24)] = True
+            if n % 7 == 0:
+                sub[:] = True
+            member[d, 64 * g + w:64 * g + w + 24] = sub
+    weights = 2.0 ** -(np.arange(n_terms) % 24).astype(np.float64)
+    lists = [np.flatnonzero(member[:, t]) for t in range(n_terms)]
+    indptr = np.zeros(n_terms + 1, np.int64)
+    indptr[1:] = np.cumsum([len(x) for x in lists])
+    rows = np.concatenate(lists).astype(np.int32)
+    return indptr, rows, np.ones(len(rows), np.float32), np.ones(n_docs, np.float64), weights, member
+
+
+def bm25_mask_value(member_row, block):
+    """The bitmask score of one document under the query of terms [64 block, 64 block + 64)."""
+    t = np.flatnonzero(member_row[64 * block:64 * block + 64])
+    return np.float32((2.0 ** -((64 * block + t) % 24).astype(np.float64)).sum())
+
+
+def bm25_postings_from_lists(lists):
+    """[(documents, tf)] per term -> (indptr, rows, counts)."""
+    indptr = np.zeros(len(lists) + 1, np.int64)
+    indptr[1:] = np.cumsum([len(d) for d, _ in lists])
+    rows = np.concatenate([np.asarray(d, np.int64) for d, _ in lists]).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
+    counts = np.concatenate([np.asarray(f, np.float32) for _, f in lists]).astype(np.float32) if indptr[-1] else np.zeros(0, np.float32)
+    return indptr, rows, counts

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import _random_postings
 from oracle import oracle as orc
 
 
@@ -185,26 +186,6 @@ def test_hip_bm25_rows_the_filter_cannot_finish_are_redone_exactly(k, monkeypatc
     s2, i2 = model.transform_terms_topk(queries, k)
     assert model.last_stats()["path"] == "tile+stored_rows"
     assert torch.equal(i, i2) and torch.equal(s.view(torch.int32), s2.view(torch.int32))
-
-
-def _random_postings(rs, n_docs, n_terms, dense_terms):
-    """Term-major postings of a random count matrix: `dense_terms` terms in ~half of the documents, the others with Zipf-like
-    document frequencies down to a single posting and a few empty terms."""
-    indptr, rows, counts = [0], [], []
-    for t in range(n_terms):
-        if t < dense_terms:
-            df = int(n_docs * rs.uniform(0.3, 0.98))
-        elif t % 97 == 5:
-            df = 0
-        else:
-            df = max(1, int(n_docs * 0.2 / (t - dense_terms + 1) ** 1.1))
-        r = np.sort(rs.choice(n_docs, df, replace=False)) if df else np.zeros(0, np.int64)
-        rows.append(r)
-        counts.append(rs.randint(1, 6, df))
-        indptr.append(indptr[-1] + df)
-    idf = np.log(n_docs / np.maximum(np.diff(indptr), 1).astype(np.float64))
-    doc_k = 1.2 * (0.25 + 0.75 * rs.uniform(0.3, 2.5, n_docs))
-    return np.asarray(indptr, np.int64), np.concatenate(rows).astype(np.int32), np.concatenate(counts).astype(np.float32), doc_k, idf
 
 
 @pytest.mark.gpu
