@@ -45,6 +45,8 @@ Knobs read_knobs() {
     kn.opt_rank = env_int("CCR_OPT_RANK", 0);
     kn.narrow = env_int("CCR_NARROW", -1);
     kn.wide = env_int("CCR_WIDE", -1);
+    kn.skip_sampled = env_int("CCR_SKIP_SAMPLED", -1);
+    kn.skip_list = env_int("CCR_SKIP_LIST", 1);
     kn.narrow_grid = env_int("CCR_NARROW_GRID", 0);
     kn.narrow_groups = env_int("CCR_NARROW_GROUPS", NARROW_MAX_GROUPS);
     return kn;
@@ -119,7 +121,17 @@ struct MainPassChoice {
     int64_t sample, ranges;
     int item_a, item_b;   // phase ends in work items of one XCD set (0 = absent)
     int opt_rank;         // > 0: ESTIMATED thresholds (the opt_rank-th largest sampled group maximum), single launch, verified by the select
+    int skip;             // 1: that launch leaves out the sampled tiles (the select joins their rows from the group maxima)
 };
+
+// May a single-launch estimated-threshold main pass leave out the `sample` sampled tiles?  Only a tile kernel (not the streaming
+// kernel of small batches), only when unsampled tiles lie between the sampled ones (stride >= 2) and every sampled tile is a full
+// tile.  Every other plan -- conservative, phased, streaming -- and the retry, margin and dense paths score every tile.
+static bool may_skip_sampled(const Plan &p, int64_t sample, bool streaming, const Knobs &kn) {
+    if (kn.skip_sampled == 0 || streaming || sample < 1) return false;
+    const int64_t stride = std::max<int64_t>(1, p.full_tiles / sample);
+    return stride >= 2 && (sample - 1) * stride < p.full_tiles && sample < p.tiles;
+}
 
 // Estimated ("optimistic") thresholds.  The conservative threshold -- the k-th largest group maximum of a sample of the corpus
 // fraction fs -- lets k / fs rows per query through the first phase, so large k needs a big sample (1/16 at k = 1001: 1/16 of the
@@ -134,9 +146,10 @@ struct MainPassChoice {
 // bench corpus: one query in 3 452 fails the check, and its retry costs 5 ms of an 18-ms step), with r >= 40 at least three
 // tiles contribute (k = 1001, same corpus: nobody fails).  With the floor the planner keeps the conservative plan at small k
 // (2 560 rows would pass at k = 100 against 1 296), where the phased plan is cheap anyway.  Exact either way.
-static int optimistic_rank(int k, int64_t sample, int64_t tiles, const Knobs &kn) {
+// (skip: the main pass leaves out the sampled tiles, so the k rows must pass among the unsampled fraction 1 - fs: k fs / (1 - fs))
+static int optimistic_rank(int k, int64_t sample, int64_t tiles, const Knobs &kn, bool skip = false) {
     if (kn.opt_rank > 0) return kn.opt_rank;   // tests: a small rank makes most queries fail the check
-    const double need = (double)k * (double)sample / (double)tiles;
+    const double need = (double)k * (double)sample / (double)(skip ? tiles - sample : tiles);
     int r = 40;
     for (; r < 1 << 20; ++r) {
         const double a = 1.0 / (9.0 * r), t = 1.0 - a - 5.2 * sqrt(a);
@@ -145,8 +158,13 @@ static int optimistic_rank(int k, int64_t sample, int64_t tiles, const Knobs &kn
     return r;
 }
 
+// skip_only > 0: the second call for a plan whose first choice was a single launch under estimated thresholds on the sample
+// skip_only and which may leave out the sampled tiles -- only that kind of plan on that sample is priced, now over the
+// tiles - sample virtual tiles its launch walks (ranges, rounds, item cost).  The sample size and the kind of plan stay chosen on the
+// price of scoring every tile: the re-priced model prefers twice the sample at NQ by less than its own error (the sample pass's
+// tiles count as main-pass tiles that need not be walked), and the select's walk over the group maxima grows with the sample.
 static MainPassChoice choose_main_pass(const Plan &p, int k, int64_t sample_a, int64_t sample_b, int64_t sample_c, const Knobs &kn,
-                                       bool single_only = false) {
+                                       bool single_only = false, int64_t skip_only = 0) {
     const int nrc = NUM_XCD / p.main_qgroups, qb_per = p.main_qblocks / p.main_qgroups, per_x = p.grid / NUM_XCD;
     // a 256 x 384 tile in units of the 256 x 256 tile the other terms were measured in (1.5x the multiply-adds at ~1.09x the rate)
     const double tile_cost = p.tile_q == WIDE_Q ? 1.37 : 1.0;
@@ -170,11 +188,12 @@ static MainPassChoice choose_main_pass(const Plan &p, int k, int64_t sample_a, i
         return (double)((smp * p.qblocks + p.grid - 1) / p.grid) + 0.015 * (double)smp * std::max(1.0, qscale);
     };
 
-    MainPassChoice best_choice = {sample_a, target, 0, 0, 0};
+    MainPassChoice best_choice = {sample_a, target, 0, 0, 0, 0};
     double best = 1e300;
     for (int pass = 0; pass < 3; ++pass) {
         const int64_t smp = pass == 0 ? sample_a : (pass == 1 ? sample_b : sample_c);
         if ((pass >= 1 && smp == sample_a) || (pass == 2 && smp == sample_b)) continue;
+        if (skip_only && smp != skip_only) continue;
         const double fs = (double)smp / (double)p.tiles;
         const double smp_cost = sample_cost(smp);
         auto survivors = [&](double fa, double fb) -> double {   // fa, fb: corpus fractions of phases A and B1 (0 = absent)
@@ -195,28 +214,31 @@ static MainPassChoice choose_main_pass(const Plan &p, int k, int64_t sample_a, i
             auto rounds = [&](int64_t n) { return (double)((n + per_x - 1) / per_x); };
             const double common = smp_cost + select_per_range * (double)R + 1e-3 * std::abs((double)(R - target));
             const double single = rounds(items) * item_cost + hit_w * survivors(0.0, 0.0) + common;
-            if (single < best && kn.optimistic != 1) {
+            if (single < best && kn.optimistic != 1 && !skip_only) {
                 best = single;
-                best_choice = {smp, R, 0, 0, 0};
+                best_choice = {smp, R, 0, 0, 0, 0};
             }
             if (kn.optimistic != 0 && smp * GROUPS_PER_TILE >= 4 * 40) {   // estimated thresholds: one launch, ~rank / fs rows pass
-                const int rank = optimistic_rank(k, smp, p.tiles, kn);
+                // (a main pass that leaves out the sampled tiles walks tiles - smp virtual tiles)
+                const bool skip = skip_only && may_skip_sampled(p, smp, single_only, kn);
+                const int rank = optimistic_rank(k, smp, p.tiles, kn, skip);
                 if ((int64_t)rank * 4 <= smp * GROUPS_PER_TILE) {
                     const double pass = std::max((double)rank / fs, (double)k);
-                    const double opt = rounds(items) * item_cost + hit_w * pass + common - (kn.optimistic == 1 ? 1e9 : 0.0);
+                    const double opt_item = skip ? ((double)((p.tiles - smp + R - 1) / R) + 0.15) * tile_cost : item_cost;
+                    const double opt = rounds(items) * opt_item + hit_w * pass + common - (kn.optimistic == 1 ? 1e9 : 0.0);
                     if (opt < best) {
                         best = opt;
-                        best_choice = {smp, R, 0, 0, rank};
+                        best_choice = {smp, R, 0, 0, rank, skip ? 1 : 0};
                     }
                 }
             }
-            if (!(prog_on && items > per_x && (double)p.tiles / (double)R >= 8.0)) continue;
+            if (skip_only || !(prog_on && items > per_x && (double)p.tiles / (double)R >= 8.0)) continue;
             // the thresholds after phase A come from the ranges it completed (+ the started one for part of the queries)
             const double fa = (double)per_x / (double)items;
             const double two = (1.0 + rounds(items - per_x)) * item_cost + phase_w + hit_w * survivors(fa, 0.0) + common;
             if (two < best) {
                 best = two;
-                best_choice = {smp, R, per_x, 0, 0};
+                best_choice = {smp, R, per_x, 0, 0, 0};
             }
             if (max_phases < 3) continue;
             for (int m = 1; m <= 3; ++m) {   // a second re-tightening after m more rounds
@@ -226,7 +248,7 @@ static MainPassChoice choose_main_pass(const Plan &p, int k, int64_t sample_a, i
                 const double three = (1.0 + m + rounds(items - ib)) * item_cost + 2.0 * phase_w + hit_w * survivors(fa, fb) + common;
                 if (three < best) {
                     best = three;
-                    best_choice = {smp, R, per_x, (int)ib, 0};
+                    best_choice = {smp, R, per_x, (int)ib, 0, 0};
                 }
             }
         }
@@ -259,7 +281,7 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
         p.mfma16 = mfma16;   // main pass on v_mfma_f32_16x16x32_bf16 (8 sub-lists per (range, query)) or 32x32x16 (4)
         p.sublists = p.mfma16 ? 8 : 4;
     }
-    p.rescore_cap = std::min(8192, std::max(256, 2 * pow2_ceil(k)));
+    p.rescore_cap = p.rescore_regular = std::min(8192, std::max(256, 2 * pow2_ceil(k)));
 
     // sample pass: group maxima of 16 rows; need comfortably more groups than k
     const int64_t min_sample = (2 * (int64_t)k + GROUPS_PER_TILE - 1) / GROUPS_PER_TILE;
@@ -324,7 +346,11 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
             }
         }
         p.main_qgroups = pick_qgroups(p.main_qblocks, dim, kn, p.tile_q);
-        const MainPassChoice choice = choose_main_pass(p, k, sample, sample_alt, sample_big, kn, narrow);
+        MainPassChoice choice = choose_main_pass(p, k, sample, sample_alt, sample_big, kn, narrow);
+        if (choice.opt_rank > 0 && may_skip_sampled(p, choice.sample, narrow, kn)) {
+            const MainPassChoice skipped = choose_main_pass(p, k, sample, sample_alt, sample_big, kn, narrow, choice.sample);
+            if (skipped.skip) choice = skipped;   // (else: the rank the unsampled fraction needs does not fit the sample)
+        }
         sample = choice.sample;
         const int64_t R = choice.ranges;
         p.sample_tiles = (int)sample;
@@ -334,6 +360,29 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
         p.item_a = choice.item_a;
         p.item_b = choice.item_b;
         p.opt_rank = choice.opt_rank;
+        p.skip_sampled = (p.opt_rank > 0 && !p.narrow) ? choice.skip : 0;
+        // the join can add a whole sampled tile to a query's collected rows (a corpus in topical order): room for one beside the
+        // regular rows (about k, and ties around the cut) -- 512 at k = 100, which keeps the select's 256-thread form.  On iid rows a
+        // sampled group of 16 holds a row of the top k with probability 1 - (1 - k / n)^16 and joins whole: J rows per query (50 at NQ,
+        // k = 100; 1 700 for k = 1001 of 300 000 rows with a tenth of them sampled: measured, every query overflowed 2 048) -- room
+        // for 1.5 J of them; where even 8 192 do not hold that, every tile is scored
+        if (p.skip_sampled) {
+            const double join_rows = 256.0 * (double)choice.sample * (1.0 - pow(1.0 - std::min(1.0, (double)k / (double)n_rows), 16.0));
+            const double need = (double)k + (double)(k / 4) + 1.5 * join_rows + TILE_DOCS + 16;
+            // the planner's own choice prices the join: a joined row costs the select 0.065 tile units (measured at NQ: + 0.06 ms for
+            // 50 rows per query at k = 100, + 0.42 ms for 250 at k = 1001), the main pass saves sample x blocks / grid tiles per
+            // workgroup of which the item rounding returns about half (0.29 of 0.35 ms at k = 100, 0.08 of 0.17 at k = 1001: there the
+            // search got SLOWER, 13.46 against 13.10 ms) -- CCR_SKIP_SAMPLED=1 skips wherever the plan allows.
+            // The three constants (0.065, the 3 584-query scale of the planner's other per-query terms, the half) are fitted to
+            // those TWO measured points: at NQ the rule switches the skip off above k of about 240; nothing between the points and
+            // no other query count has been measured.
+            const double saved = 0.5 * (double)choice.sample * p.main_qblocks * (p.tile_q == WIDE_Q ? 1.37 : 1.0) / (double)p.grid;
+            const bool pays = 0.065 * join_rows * ((double)p.nq_pad / 3584.0) < saved;
+            if (need > 8192.0 || (kn.skip_sampled < 0 && !pays))
+                p.skip_sampled = 0;
+            else
+                p.rescore_cap = std::min(8192, std::max(p.rescore_cap, pow2_ceil((int)need)));
+        }
         // ranges that hold items of a phase: the candidate segments (a range started in phase A keeps phase A's capacity)
         const int nrc_p = NUM_XCD / p.main_qgroups, qb_per_p = p.main_qblocks / p.main_qgroups;
         const int64_t RA = p.item_a ? std::min<int64_t>(R, (int64_t)nrc_p * ((p.item_a + qb_per_p - 1) / qb_per_p)) : 0;
@@ -457,6 +506,7 @@ SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char 
     w.top = (uint32_t *)take(p.item_b ? (nq_pad + (size_t)n_q * k) * 4 : 0);
     w.thr_safe = (float *)take(p.opt_rank ? nq_pad * 8 : 0);
     w.cq_safe = w.thr_safe + nq_pad;
+    w.glist = (uint32_t *)take(p.skip_sampled ? nq_pad * (size_t)(skip_list_cap(p.opt_rank) + 1) * 4 : 0);
     w.dense_bytes = (size_t)p.dense_rows_per_chunk * n_rows * 4;
     w.dense = (float *)take(w.dense_bytes);
     // the retry area keeps its reserved size: its nine sub-buffers plus up to 255 bytes of rounding each
@@ -786,6 +836,11 @@ static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float 
 static int run_main_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, const uint16_t *Q, int n_q, int k, hipStream_t s) {
     // (blocks of p.tile_q queries; the sample pass walks blocks of TILE_Q)
     GemmArgs gm = filter_args(ix, p, w, Q, n_q, p.nq_pad, p.main_qblocks, p.main_qgroups, w.thr, w.cq, p.cand);
+    if (p.skip_sampled) {   // the unsampled tiles only, in ascending order (unsampled_tile); the select joins the sampled ones
+        gm.n_vt = p.tiles - p.sample_tiles;
+        gm.skip_stride = (int)p.sample_stride;
+        gm.skip_count = p.sample_tiles;
+    }
     const int nrc = NUM_XCD / gm.qgroups, qb_per = gm.qblocks / gm.qgroups, items = p.ranges / nrc * qb_per;
     const int bounds[4] = {0, p.item_a, p.item_b, items};
     int done = 0, updates = 0, prev_full = 0, prev_part = 0, prev_blocks = 0;
@@ -869,6 +924,7 @@ static int fused_stats(ccr_index *ix, uint32_t nflag, unsigned long long ncand) 
     st.sublists = p.narrow ? p.first_sp : p.sublists;
     st.main_launches = 1 + (p.item_a ? 1 : 0) + (p.item_b ? 1 : 0);
     st.opt_rank = p.opt_rank;
+    st.skipped_tiles = p.skip_sampled ? p.sample_tiles : 0;
     st.main_tile_queries = p.narrow ? 0 : p.tile_q;
     st.n_candidates = (int64_t)ncand;
     return CCR_OK;
@@ -913,7 +969,7 @@ static int retry_group(ccr_index *ix, const SearchWs &w, const uint32_t *cur, in
         if (rc != CCR_OK) return rc;
         rc = launch_select_rescore(w.cand, w.cnt, nsub_all, p.sublists, n_cur, pad2, lay2, pd.k, p.rescore_cap, p.select_compact, ix->n_rows,
                                    w.thr2, w.cq2, ix->tile_norm, ix->row_norm, ix->dmax_bits, w.Q2, ix->D, ix->dim, ix->id_out, pd.out_scores, pd.out_ids,
-                                   w.flag2, w.flag2 + 16, nullptr, cur, s);
+                                   w.flag2, w.flag2 + 16, nullptr, cur, s, nullptr, 0, 0, 0, nullptr, 0, p.rescore_regular);
         if (rc != CCR_OK) return rc;
         ix->stats.n_retried += n_cur;
         uint32_t again = 0;
@@ -1118,7 +1174,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     // every (range, query block) item with at least one tile writes its counters at its end, for the columns below
     // main_qblocks * tile_q (the 256 x 384 kernel leaves [main_qblocks * 384, nq_pad) unwritten: no reader goes past n_q);
     // only a plan with more ranges than tiles (forced fused searches of tiny corpora) leaves counters unwritten
-    if ((int64_t)p.ranges > p.tiles) CCR_HIP_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)p.ranges * p.nq_pad * p.sublists * 4, s));
+    if ((int64_t)p.ranges > p.tiles - (p.skip_sampled ? p.sample_tiles : 0)) CCR_HIP_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)p.ranges * p.nq_pad * p.sublists * 4, s));
     int rc = launch_row_norms_bf16(Q_bf16, n_q, ix->dim, w.qnorm, nullptr, nullptr, s);
     if (rc != CCR_OK) return rc;
 
@@ -1135,7 +1191,8 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SAMPLE_END], s));
     // (small batches: the streaming pass's sub-list counters are cleared by the threshold launch)
     rc = launch_threshold(w.gmax, (int64_t)p.sample_tiles * GROUPS_PER_TILE, n_q, p.nq_pad, p.opt_rank ? p.opt_rank : k, w.qnorm, ix->dmax_bits,
-                          ix->dim, ix->tile_norm, p.sample_stride, w.thr, w.cq, s, p.narrow ? w.cnt : nullptr, p.narrow ? NARROW_SUBLISTS : 0);
+                          ix->dim, ix->tile_norm, p.sample_stride, w.thr, w.cq, s, p.narrow ? w.cnt : nullptr, p.narrow ? NARROW_SUBLISTS : 0,
+                          p.skip_sampled && ix->knobs.skip_list ? w.glist : nullptr, skip_list_cap(p.opt_rank));
     if (rc != CCR_OK) return rc;
 
     // main pass -> candidates -> select
@@ -1146,7 +1203,9 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     ix->main_pass_recorded = true;
     rc = launch_select_rescore(w.cand, w.cnt, p.first_nsub, p.first_sp, n_q, p.nq_pad, p.first_lay, k, p.rescore_cap, p.select_compact, ix->n_rows, w.thr,
                                w.cq, ix->tile_norm, ix->row_norm, ix->dmax_bits, Q_bf16, ix->D, ix->dim, ix->id_out, out_scores, out_ids,
-                               w.flag_count, w.flag_list, w.stat_cand, nullptr, s);
+                               w.flag_count, w.flag_list, w.stat_cand, nullptr, s, p.skip_sampled ? w.gmax : nullptr, p.sample_tiles,
+                               (int)p.sample_stride, p.nq_pad, ix->knobs.skip_list ? w.glist : nullptr, skip_list_cap(p.opt_rank),
+                               p.rescore_regular);
     if (rc != CCR_OK) return rc;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SELECT_END], s));
 

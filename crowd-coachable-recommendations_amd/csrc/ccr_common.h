@@ -90,11 +90,13 @@ struct Plan {
     int item_a;           // phase A = work items [0, item_a) of every XCD set (0 = single phase); thresholds are re-tightened after it
     int item_b;           // end of the second phase in items (0: two phases)
     int opt_rank;         // > 0: estimated thresholds = the opt_rank-th largest sampled group maximum (single launch; the select verifies)
+    int skip_sampled;     // 1: the main pass does not score the sample_tiles sampled tiles again; the select joins their rows from gmax
     int qgroups;          // query-block groups over the XCDs
     int cap;              // candidate slots per sub-list (the largest segment's: statistics)
     CandLayout cand;      // per-phase segments of the candidate area
     int grid;             // persistent workgroups (multiple of NUM_XCD)
     int rescore_cap;      // max rows re-scored per query (power of two)
+    int rescore_regular;  // ... of them recorded candidates (skip_sampled: rescore_cap also holds the joined rows of the sampled tiles)
     int select_compact;   // candidates per query the select kernel gathers into LDS
     int mfma16;           // 1: main pass on the 16x16x32 MFMA kernel
     int sublists;         // candidate sub-lists per (range, query): 4 (32x32x16 kernel) or 8 (16x16x32 kernel)
@@ -111,6 +113,15 @@ struct Plan {
     int64_t dense_rows_per_chunk;  // queries per dense chunk
 };
 
+// The sample pass scores the tiles j * s, j < n (s = sample stride, n = sample tiles).  The v-th of the OTHER tiles in ascending
+// order: below n * (s - 1) every run of s - 1 unsampled tiles sits behind one sampled tile, beyond the last sampled tile the shift
+// is n.  s = 0: no tile is left out.  Tile counts fit 32 bits (n_rows < 2^32).
+__host__ __device__ __forceinline__ int64_t unsampled_tile(int64_t v, int s, int n) {
+    if (s == 0) return v;
+    const uint32_t u = (uint32_t)v, d = (uint32_t)(s - 1);
+    return u < (uint32_t)n * d ? (int64_t)(u + u / d + 1u) : v + n;
+}
+
 // epilogues of the fused GEMM kernel; EPI_FILTER's candidate record = one corpus row {MFMA score, row}
 enum { EPI_FILTER = 0, EPI_GMAX = 1, EPI_STORE = 2 };
 
@@ -126,6 +137,9 @@ struct GemmArgs {
     int64_t n_vt;         // virtual tiles; real tile = vt * tile_stride
     int64_t tile_stride;
     int ranges;           // item (r, qb) covers virtual tiles r, r + ranges, ...
+    // main pass that leaves out the sampled tiles j * skip_stride, j < skip_count: virtual tile v is real tile unsampled_tile(v)
+    // (0 / 0: every tile -- all the sample pass, the retry pass and EPI_STORE ever see)
+    int skip_stride, skip_count;
     int qgroups;          // query-block groups spread over the XCDs (1, 2, 4 or 8; divides qblocks)
     // Work items of an XCD set are numbered item = (range / classes) * blocks_per_group + block_in_group; a launch covers the
     // items [item_begin, item_end) of every XCD set, so a phase can be EXACTLY whole rounds of items whatever the range count

@@ -68,6 +68,12 @@ __device__ __forceinline__ float max3_asm(float a, float b, float c) {
     return m;
 }
 
+// Real corpus tile of virtual tile vt (wave-uniform: scalar registers).  A main pass that leaves out the sampled tiles (a.skip_stride:
+// its tile_stride is 1) maps through unsampled_tile(); every other launch keeps vt * tile_stride.
+__device__ __forceinline__ int64_t real_tile(const GemmArgs &a, int64_t vt) {
+    return a.skip_stride ? unsampled_tile(vt, a.skip_stride, a.skip_count) : vt * a.tile_stride;
+}
+
 // Work items (range r, query block qb) of a main-pass launch.  Blocks b and b+8 share an XCD (its 4-MiB L2), so XCD x takes
 // query-block group x % qgroups (its query rows stay L2-resident) and the ranges r = x / qgroups (mod 8 / qgroups).  Item order:
 // consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for different query blocks.
@@ -383,7 +389,7 @@ __device__ __forceinline__ void main_pass_256(const GemmArgs &a) {
         int iks = 0;
         const uint16_t *dsrc[2];
         auto tile_ptrs = [&]() {
-            const int64_t row0 = (r + it * a.ranges) * a.tile_stride * TILE_DOCS;
+            const int64_t row0 = real_tile(a, r + it * a.ranges) * TILE_DOCS;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 int64_t drow = row0 + (i * 128 + srow);
@@ -418,8 +424,8 @@ __device__ __forceinline__ void main_pass_256(const GemmArgs &a) {
         };
 
         // ---- epilogue of a finished 256x256 tile (accumulators still live)
-        auto epilogue = [&](int64_t vt, float nt) {   // nt: norm bound of the tile's rows (wave-uniform)
-            const int64_t row_base = vt * a.tile_stride * TILE_DOCS + wd * 128 + 4 * lh;   // + dt * TILE + 8 * group + register
+        auto epilogue = [&](int64_t vt, int64_t rt, float nt) {   // rt: the real tile; nt: norm bound of its rows (wave-uniform)
+            const int64_t row_base = rt * TILE_DOCS + wd * 128 + 4 * lh;   // + dt * TILE + 8 * group + register
             if constexpr (EPI == EPI_GMAX) {
                 S::gmax(acc, a, vt, q0, wd, wq, lane);
             } else if constexpr (EPI == EPI_FILTER) {
@@ -462,12 +468,12 @@ __device__ __forceinline__ void main_pass_256(const GemmArgs &a) {
         int cks = 0;
         int64_t ct = 0;
         bool pending = false;
-        int64_t pending_vt = 0;
+        int64_t pending_vt = 0, pending_rt = 0;
         float pending_nt = 0.f;
         for (int64_t u = 0; u < U; ++u) {
             // ================= mem phase
             if (pending) {
-                epilogue(pending_vt, pending_nt);
+                epilogue(pending_vt, pending_rt, pending_nt);
                 pending = false;
             }
             if (u + 1 < U) {  // confirm OWN DMA of sub-stage u+1 (published by the barrier below)
@@ -493,19 +499,21 @@ __device__ __forceinline__ void main_pass_256(const GemmArgs &a) {
                 // (the tile's norm bound: a SCALAR load + wait right here, behind the MFMAs just issued -- a vector load would
                 // sit in vmcnt among the LDS-DMA pieces and hipcc's own wait for it would drain the ring)
                 const int64_t vt_done = r + ct * a.ranges;
-                const float nt_done = EPI == EPI_FILTER ? load_uniform_f32(a.tile_norm + vt_done * a.tile_stride) : 0.f;
+                const int64_t rt_done = real_tile(a, vt_done);
+                const float nt_done = EPI == EPI_FILTER ? load_uniform_f32(a.tile_norm + rt_done) : 0.f;
                 if (g1) {
-                    epilogue(vt_done, nt_done);
+                    epilogue(vt_done, rt_done, nt_done);
                 } else {
                     pending = true;
                     pending_vt = vt_done;
+                    pending_rt = rt_done;
                     pending_nt = nt_done;
                 }
                 ++ct;
             }
             CCR_BARRIER();
         }
-        if (pending) epilogue(pending_vt, pending_nt);
+        if (pending) epilogue(pending_vt, pending_rt, pending_nt);
         if (!g1) CCR_BARRIER();  // every wave executes the same number of barriers
 
         if (EPI == EPI_FILTER) {
@@ -645,7 +653,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
         const char *dtile = nullptr;
         int dlimit = 0;
         auto tile_base = [&]() __attribute__((always_inline)) {
-            const int64_t row0 = (r + it * a.ranges) * a.tile_stride * TILE_DOCS;
+            const int64_t row0 = real_tile(a, r + it * a.ranges) * TILE_DOCS;
             dlimit = (a.n_rows - 1 - row0 < TILE_DOCS - 1) ? (int)(a.n_rows - 1 - row0) : TILE_DOCS - 1;
             dtile = reinterpret_cast<const char *>(a.D) + row0 * pitch;
         };
@@ -701,7 +709,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             }
         };
 
-        auto epilogue = [&](int64_t vt, float nt) __attribute__((always_inline)) {   // nt: norm bound of the tile's rows (wave-uniform)
+        auto epilogue = [&](int64_t rt, float nt) __attribute__((always_inline)) {   // rt: the real tile; nt: norm bound of its rows (wave-uniform)
             // (every address below is rebuilt here instead of living in registers across the K loop)
             const int eln = fresh_lane();
             const int l15o = eln & 15, lqo = eln >> 4;
@@ -711,7 +719,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             const uint32_t row_lo = (uint32_t)(wd * 128 + 4 * lqo);       // + dt * 16 + e: row inside the tile
             const uint32_t tc_addr = lds_offset(s_tc) + (uint32_t)l15o * 8u;            // + (wq * 96 + qt * 16) * 8
             const uint32_t cnt_addr = lds_offset(s_cnt) + (uint32_t)(lqo * 16 + l15o) * 4u;   // + ((wv * 6 + qt) * 64) * 4
-            const int64_t tile_row0 = vt * a.tile_stride * TILE_DOCS;      // wave-uniform
+            const int64_t tile_row0 = rt * TILE_DOCS;      // wave-uniform
             const uint32_t rows_left = a.n_rows - tile_row0 < TILE_DOCS ? (uint32_t)(a.n_rows - tile_row0) : (uint32_t)TILE_DOCS;
 #pragma unroll
             for (int qt = 0; qt < WIDE_QT; ++qt) {
@@ -759,7 +767,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
         int cks = 0;
         int64_t ct = 0;
         bool pending = false;
-        int64_t pending_vt = 0;
+        int64_t pending_rt = 0;
         float pending_nt = 0.f;
         int uslot = 0;
         for (int u = 0; u < U; ++u) {
@@ -769,7 +777,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             if (u + 2 < U) issue();
             __builtin_amdgcn_sched_barrier(0);
             if (pending) {
-                epilogue(pending_vt, pending_nt);
+                epilogue(pending_rt, pending_nt);
                 pending = false;
             }
             const char *abuf = smem + uslot * WIDE_SUB_BYTES;
@@ -817,13 +825,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             if (++cks == KS2) {
                 cks = 0;
                 // (the tile's norm bound: a SCALAR load + wait right here, behind the MFMAs just issued)
-                const int64_t vt_done = r + ct * a.ranges;
-                const float nt_done = load_uniform_f32(a.tile_norm + vt_done * a.tile_stride);
+                const int64_t rt_done = real_tile(a, r + ct * a.ranges);
+                const float nt_done = load_uniform_f32(a.tile_norm + rt_done);
                 if (g1) {
-                    epilogue(vt_done, nt_done);
+                    epilogue(rt_done, nt_done);
                 } else {
                     pending = true;
-                    pending_vt = vt_done;
+                    pending_rt = rt_done;
                     pending_nt = nt_done;
                 }
                 ++ct;
@@ -831,7 +839,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             CCR_WAIT_LGKM0();   // the refills of this K step are retired before the barrier behind which group 1 rewrites their rows
             CCR_BARRIER();
         }
-        if (pending) epilogue(pending_vt, pending_nt);
+        if (pending) epilogue(pending_rt, pending_nt);
         if (!g1) CCR_BARRIER();
 
         {
@@ -937,20 +945,30 @@ __global__ __launch_bounds__(1024) void max_tile_norm_kernel(const uint32_t *__r
 // One workgroup = 16 queries x 16 group phases: a gmax row is read as 64-byte segments (query-contiguous
 // layout), every query has its own 256-bin LDS histogram (no same-address atomics), 4 MSB-first passes.
 // grid = nq_pad / 16, block = 256.
+// glist (may be null; [nq_pad][list_cap + 1]): the query's SHORT LIST for the select stage's join of the sampled tiles -- entry 0 the
+// count, then the groups whose UPPER bound m + cq * nt reaches tau (written in the last radix pass against tau's upper 24 bits, a value
+// <= tau).  The select joins groups whose upper bound reaches L >= tau: all of them are on the list.  About k of the groups qualify
+// (k is the threshold's rank here); a count above list_cap tells the select to walk the query's whole column instead.
+// (LIST: a kernel of its own, so that the search without lists keeps the registers and the time of the plain kernel)
+template <bool LIST>
 __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict__ gmax, int64_t n_groups, int n_q, int nq_pad,
                                                        int k, const float *__restrict__ qnorm,
                                                        const uint32_t *__restrict__ dmax_bits, float gamma,
                                                        const float *__restrict__ tile_norm, int64_t sample_stride,
-                                                       float *__restrict__ thr, float *__restrict__ cq) {
+                                                       float *__restrict__ thr, float *__restrict__ cq,
+                                                       uint32_t *__restrict__ glist, int list_cap) {
     __shared__ uint32_t s_hist[16][256];
-    __shared__ uint32_t s_prefix[16], s_remaining[16];
+    __shared__ uint32_t s_prefix[16], s_remaining[16], s_nlist[16];
     const int tid = threadIdx.x;
     const int ql = tid & 15, ph = tid >> 4;
     const int q = blockIdx.x * 16 + ql;
     if (tid < 16) {
         s_prefix[tid] = 0;
         s_remaining[tid] = (uint32_t)k;
+        s_nlist[tid] = 0;
     }
+    uint32_t *const my_list = LIST ? glist + (int64_t)q * (list_cap + 1) : nullptr;
+
     // |mfma - exact| <= gamma * ||q|| * ||d||; a non-finite row norm anywhere in the shard (NaN / Inf embeddings) poisons
     // every threshold, so that all queries take the exact dense path
     const float dmax = __uint_as_float(*dmax_bits);
@@ -958,8 +976,15 @@ __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict_
     // norm bound of the sampled tile of group g (plain vector loads: staging them in LDS, or scalar loads of the wave-uniform
     // index, both made this kernel slower -- 84 vs 70 us at NQ: they share lgkmcnt with the histogram's LDS atomics)
     auto tile_of = [&](int64_t g) { return tile_norm[(g / GROUPS_PER_TILE) * sample_stride]; };
+    auto emit = [&](int64_t g, float v, float tn, uint32_t prefix) {   // last pass only: prefix = tau's upper 24 bits
+        if (f32_orderable(fmaf(c, tn, v)) >= prefix) {
+            const uint32_t p = atomicAdd(&s_nlist[ql], 1u);
+            if (p < (uint32_t)list_cap) my_list[1 + p] = (uint32_t)g;
+        }
+    };
     uint32_t mask = 0;
     for (int shift = 24; shift >= 0; shift -= 8) {
+        const bool listing = LIST && shift == 0;
         for (int b = tid; b < 16 * 256; b += 256) (&s_hist[0][0])[b] = 0;
         __syncthreads();
         const uint32_t prefix = s_prefix[ql];
@@ -976,11 +1001,14 @@ __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict_
             for (int j = 0; j < 16; ++j) {
                 const uint32_t o = f32_orderable(fmaf(-c, tn[j], v[j]));
                 if ((o & mask) == prefix) atomicAdd(&s_hist[ql][(o >> shift) & 255u], 1u);
+                if (listing) emit(i + 16 * j, v[j], tn[j], prefix);
             }
         }
         for (; i < n_groups; i += 16) {
-            const uint32_t o = f32_orderable(fmaf(-c, tile_of(i), gmax[i * nq_pad + q]));
+            const float v = gmax[i * nq_pad + q], tn = tile_of(i);
+            const uint32_t o = f32_orderable(fmaf(-c, tn, v));
             if ((o & mask) == prefix) atomicAdd(&s_hist[ql][(o >> shift) & 255u], 1u);
+            if (listing) emit(i, v, tn, prefix);
         }
         __syncthreads();
         {   // digit pick: 16 lanes per query (16 bins each), shuffle suffix-scan instead of a 256-step serial walk
@@ -1029,6 +1057,7 @@ __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict_
             cq[qq] = c;   // tid < 16: q == qq
             thr[qq] = (c < INFINITY) ? tau : __builtin_nanf("");
         }
+        if (LIST) my_list[0] = s_nlist[tid];
     }
 }
 
@@ -1191,6 +1220,17 @@ __global__ __launch_bounds__(256) void threshold_update_kernel(const uint2 *__re
 
 // Stage-2: per query, candidates -> exact canonical top-k.  grid = n_q, block = THREADS (256; 1024 for large k).
 // dyn LDS: [dim bf16 query row][sub-list counts][sub-list offsets][rescore_cap u64 keys][compact x 8-byte candidates]
+//
+// JOIN of the sampled tiles (gmax != null: the main pass left out the tiles j * sample_stride, j < sample_tiles, and gmax[group][query],
+// pitch gmax_pitch, still holds the sample pass's maximum MFMA score of each of their 16-row groups).  Why the result is unchanged:
+//   * L, the k-th largest lower bound of the recorded candidates, is the k-th largest lower bound of a SUBSET of the rows, so it is
+//     at most the k-th largest exact score -- and it is still taken from the recorded candidates alone;
+//   * an unsampled row whose exact score reaches L >= tau was recorded by the filter (the argument without the join);
+//   * a sampled row's exact score is at most its sample-pass MFMA score + c ||d||, at most gmax + c * tile_norm of its group: the
+//     margin holds for any fp32 summation order, the sample pass's 32x32 shape included;
+//   * so a group with gmax + c * tile_norm < L holds no result row, and a group at or above L is re-scored WHOLE (its 16 rows
+//     join the collected rows through the same counter and capacity check; an overflow takes the dense path);
+//   * ties are settled by the sort on (score, ~row) as before.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void select_rescore_kernel(const uint2 *__restrict__ cand, const uint32_t *__restrict__ cnt,
                                                             int ranges, int sp, int nq_pad, const CandLayout lay, int k, int rescore_cap, int compact,
@@ -1202,7 +1242,9 @@ __global__ __launch_bounds__(THREADS) void select_rescore_kernel(const uint2 *__
                                                             int64_t *__restrict__ out_ids, uint32_t *__restrict__ flag_count,
                                                             uint32_t *__restrict__ flag_list,
                                                             unsigned long long *__restrict__ stat_cand,
-                                                            const uint32_t *__restrict__ out_rows) {
+                                                            const uint32_t *__restrict__ out_rows, const float *__restrict__ gmax,
+                                                            int sample_tiles, int sample_stride, int gmax_pitch,
+                                                            const uint32_t *__restrict__ glist, int list_cap, int regular_cap) {
     extern __shared__ __attribute__((aligned(16))) char sm[];
     const size_t cnt_bytes = ((size_t)(ranges + 1) * 4 + 15) & ~(size_t)15;
     uint16_t *s_q = reinterpret_cast<uint16_t *>(sm);
@@ -1424,8 +1466,40 @@ __global__ __launch_bounds__(THREADS) void select_rescore_kernel(const uint2 *__
                 if (p < (uint32_t)coll_cap) s_keys[p] = (unsigned long long)e.y;  // local row for now
             }
         }
+        // INVARIANT: `bad` and `dense_only` are workgroup-uniform -- every thread takes the same returns and the same barriers.  So the
+        // counter is read where nobody can be adding to it: behind the barrier that ends the collection, and (join) in front of the
+        // barrier that starts the joiners.
+        // The recorded candidates keep their own limit (regular_cap: what rescore_cap is without the join -- mass ties around the cut
+        // take the dense path exactly as they do when every tile is scored, in the retry pass too); joined rows may fill the rest.
         __syncthreads();
-        if (s_ncoll > (uint32_t)coll_cap) bad = dense_only = true;  // mass ties around the cut
+        const uint32_t n_recorded = s_ncoll;
+        if (n_recorded > (uint32_t)regular_cap) bad = dense_only = true;  // mass ties around the cut
+        if (gmax && !bad) {
+            __syncthreads();   // every thread has read n_recorded: the joiners may add
+            // The groups to test: the threshold kernel's short list of this query (the groups whose upper bound reaches tau <= L: a
+            // few dozen 4-byte reads) -- or, without a list or when it overflowed, the query's whole column of the group maxima
+            // (one value per 128-byte line: 2.3 GB of line traffic at NQ, measured +0.12 ms of select and a slower pack beside it).
+            // Group gi of a sampled tile (Mfma32::gmax): wave row gi >> 3, MFMA tile (gi >> 1) & 3, lane half gi & 1; register e of its
+            // 16 holds row (e & 3) + 8 * (e >> 2) of the lane half's rows.
+            const int ngroups = sample_tiles * GROUPS_PER_TILE;
+            const uint32_t *const my_list = glist ? glist + (int64_t)q * (list_cap + 1) : nullptr;
+            const int nlist = my_list ? (int)min(my_list[0], (uint32_t)list_cap + 1u) : list_cap + 1;
+            const bool listed = nlist <= list_cap;
+            for (int x = tid; x < (listed ? nlist : ngroups); x += THREADS) {
+                const int g = listed ? (int)my_list[1 + x] : x;
+                const int64_t tile = (int64_t)(g / GROUPS_PER_TILE) * sample_stride;
+                if (fmaf(c, tile_norm[tile], gmax[(int64_t)g * gmax_pitch + q]) >= low) {
+                    const int gi = g % GROUPS_PER_TILE;
+                    const uint32_t row0 = (uint32_t)(tile * TILE_DOCS) + (uint32_t)((gi >> 3) * 128 + ((gi >> 1) & 3) * 32 + (gi & 1) * 4);
+                    for (int e = 0; e < 16; ++e) {   // (one slot at a time, exactly as the recorded candidates above)
+                        const uint32_t p = atomicAdd(&s_ncoll, 1u);
+                        if (p < (uint32_t)coll_cap) s_keys[p] = (unsigned long long)(row0 + (uint32_t)((e & 3) + 8 * (e >> 2)));
+                    }
+                }
+            }
+            __syncthreads();   // (no thread adds behind this barrier: the read below is uniform)
+            if (s_ncoll > (uint32_t)coll_cap) bad = dense_only = true;  // the joined rows do not fit beside the recorded ones
+        }
     }
     if (bad) {
         if (tid == 0) {
@@ -1673,10 +1747,11 @@ __global__ __launch_bounds__(256) void threshold_small_kernel(const float *__res
                                                              const float *__restrict__ qnorm, const uint32_t *__restrict__ dmax_bits,
                                                              float gamma, const float *__restrict__ tile_norm, int64_t sample_stride,
                                                              float *__restrict__ thr, float *__restrict__ cq, uint32_t *__restrict__ zero_cnt,
-                                                             int zero_per_query) {
+                                                             int zero_per_query, uint32_t *__restrict__ glist, int list_cap) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_low[];
     __shared__ uint32_t s_hist[256];
     __shared__ uint32_t s_ctl[4];
+    __shared__ uint32_t s_nlist;
     const int tid = threadIdx.x, q = blockIdx.x;
     const float dmax = __uint_as_float(*dmax_bits);
     const float c = (dmax < INFINITY) ? gamma * (qnorm[q] * 1.001f) * 1.001f : __builtin_nanf("");
@@ -1696,11 +1771,25 @@ __global__ __launch_bounds__(256) void threshold_small_kernel(const float *__res
         cq[q] = c;
         thr[q] = (c < INFINITY) ? orderable_to_f32(kth) : __builtin_nanf("");
     }
+    if (glist) {   // the select's short list (threshold_kernel): groups whose upper bound reaches tau
+        uint32_t *const my_list = glist + (int64_t)q * (list_cap + 1);
+        if (tid == 0) s_nlist = 0u;
+        __syncthreads();
+        for (int g = tid; g < n_groups; g += 256) {
+            const float up = fmaf(c, tile_norm[(int64_t)(g / GROUPS_PER_TILE) * sample_stride], gmax[(int64_t)g * nq_pad + q]);
+            if (f32_orderable(up) >= kth) {
+                const uint32_t p = atomicAdd(&s_nlist, 1u);
+                if (p < (uint32_t)list_cap) my_list[1 + p] = (uint32_t)g;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) my_list[0] = s_nlist;
+    }
 }
 
 int launch_threshold(const float *gmax, int64_t n_groups, int n_q, int nq_pad, int k, const float *qnorm,
                      const uint32_t *dmax_bits, int dim, const float *tile_norm, int64_t sample_stride, float *thr, float *cq,
-                     hipStream_t s, uint32_t *zero_cnt, int zero_per_query) {
+                     hipStream_t s, uint32_t *zero_cnt, int zero_per_query, uint32_t *glist, int list_cap) {
     // small batches: a workgroup per query (needs k <= n_groups -- the planner samples >= 2k groups -- and the bounds in 64 KiB of LDS);
     // *zero_cnt tells the caller whether its counters have been cleared here
     if (n_q <= 128 && n_groups >= k && n_groups <= 16384 && zero_per_query <= 256) {
@@ -1709,13 +1798,13 @@ int launch_threshold(const float *gmax, int64_t n_groups, int n_q, int nq_pad, i
             if (rc != CCR_OK) return rc;
         }
         hipLaunchKernelGGL(threshold_small_kernel, dim3(n_q), dim3(256), (size_t)n_groups * 4, s, gmax, (int)n_groups, nq_pad, k, qnorm, dmax_bits,
-                           mfma_gamma(dim), tile_norm, sample_stride, thr, cq, zero_cnt, zero_per_query);
+                           mfma_gamma(dim), tile_norm, sample_stride, thr, cq, zero_cnt, zero_per_query, glist, list_cap);
         CCR_LAUNCH_CHECK();
         return CCR_OK;
     }
     if (zero_cnt) CCR_HIP_CHECK(hipMemsetAsync(zero_cnt, 0, (size_t)n_q * zero_per_query * 4, s));
-    hipLaunchKernelGGL(threshold_kernel, dim3(nq_pad / 16), dim3(256), 0, s, gmax, n_groups, n_q, nq_pad, k, qnorm, dmax_bits,
-                       mfma_gamma(dim), tile_norm, sample_stride, thr, cq);
+    hipLaunchKernelGGL(glist ? threshold_kernel<true> : threshold_kernel<false>, dim3(nq_pad / 16), dim3(256), 0, s, gmax, n_groups, n_q, nq_pad, k, qnorm, dmax_bits,
+                       mfma_gamma(dim), tile_norm, sample_stride, thr, cq, glist, list_cap);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
@@ -1795,7 +1884,9 @@ int launch_select_rescore(const uint2 *cand, const uint32_t *cnt, int ranges, in
                           const uint32_t *dmax_bits, const uint16_t *Q,
                           const uint16_t *D, int dim, int64_t id_offset, float *out_scores, int64_t *out_ids,
                           uint32_t *flag_count, uint32_t *flag_list, unsigned long long *stat_cand, const uint32_t *out_rows,
-                          hipStream_t s) {
+                          hipStream_t s, const float *gmax, int sample_tiles, int sample_stride, int gmax_pitch, const uint32_t *glist, int list_cap,
+                          int regular_cap) {
+    if (regular_cap <= 0 || regular_cap > rescore_cap) regular_cap = rescore_cap;
     const size_t lds = select_fixed_lds(dim, ranges, rescore_cap) + (size_t)compact * 8;
     const bool wide = rescore_cap > 512 || compact > 8192 || ranges > 1024;   // 1024 threads: one re-scored row per thread at large k
     auto go = [&](auto kernel, int threads) -> int {
@@ -1805,7 +1896,7 @@ int launch_select_rescore(const uint2 *cand, const uint32_t *cnt, int ranges, in
         }
         hipLaunchKernelGGL(kernel, dim3(n_q), dim3(threads), lds, s, cand, cnt, ranges, sp, nq_pad, lay, k, rescore_cap, compact,
                            n_rows, thr, cq, tile_norm, row_norm, dmax_bits, Q, D, dim, id_offset, out_scores, out_ids, flag_count, flag_list, stat_cand,
-                           out_rows);
+                           out_rows, gmax, sample_tiles, sample_stride, gmax_pitch, glist, list_cap, regular_cap);
         CCR_LAUNCH_CHECK();
         return CCR_OK;
     };

@@ -18,6 +18,8 @@ struct Knobs {
     int max_lists;     // CCR_MAX_LISTS    0 = planner's limit, else a cap on ranges x sublists (A/B of the select stage's walk)
     int narrow;        // CCR_NARROW       -1 = planner's choice (n_q <= 64 whose rows fit the LDS), 0 = tile kernels only (the A/B knob)
     int narrow_grid;   // CCR_NARROW_GRID  0 = planner's choice, else workgroups of the streaming kernel
+    int skip_sampled;  // CCR_SKIP_SAMPLED -1 = planner's choice, 0 = the main pass scores every tile (the A/B knob), 1 = it leaves out the sampled tiles wherever the plan allows
+    int skip_list;     // CCR_SKIP_LIST    1 = the select's join reads the threshold kernel's short list of sampled groups (default), 0 = it walks the query's column of group maxima (the A/B knob)
     int wide;          // CCR_WIDE         -1 = planner's choice, 0 = 256 x 256 main-pass tiles only (the A/B knob), 1 = 256 x 384 wherever the kernel applies
     int narrow_groups; // CCR_NARROW_GROUPS 2 = batches of 65 .. 128 queries stream as two query groups (default), 1 = tile kernels above 64 queries (the A/B knob)
 };
@@ -43,6 +45,7 @@ struct SearchWs {
     unsigned long long *stat_cand;
     uint32_t *top;                      // the k best lower bounds per query between two re-tightenings (three-phase plans)
     float *thr_safe, *cq_safe, *dense;  // estimated thresholds: the conservative bounds of a failing search; dense scratch (dense_bytes)
+    uint32_t *glist;                    // skip_sampled: [nq_pad][skip_list_cap(opt_rank) + 1] short lists of sampled groups for the select's join
     // retry area (retry_bytes from Q2 on): compact query rows, their thresholds and margin coefficients, the retry and dense
     // lists, two partition counts, a second flag area, and the two lists the rounds of a group alternate on
     uint16_t *Q2;
@@ -51,6 +54,8 @@ struct SearchWs {
     size_t cand_bytes, dense_bytes, retry_bytes, total;
 };
 SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char *base);
+// entries of a query's short list: about opt_rank groups reach tau (it IS the opt_rank-th largest lower bound), a few more inside the margin
+inline int skip_list_cap(int opt_rank) { return 2 * opt_rank + 30; }
 
 // kernels implemented in the other translation units
 // the fused GEMM + top-k kernels: 256 x 256 tiles on the 32x32x16 MFMA (every epi) or the 16x16x32 MFMA (no EPI_GMAX), or
@@ -66,16 +71,21 @@ int launch_tile_norms(const float *row_bounds, int64_t rows, uint32_t *tile_bits
 // thr[q] = tau_q (lower bound of the k-th largest exact score), cq[q] = gamma ||q|| (margin per unit of row norm)
 int launch_threshold(const float *gmax, int64_t n_groups, int n_q, int nq_pad, int k, const float *qnorm,
                      const uint32_t *dmax_bits, int dim, const float *tile_norm, int64_t sample_stride, float *thr, float *cq,
-                     hipStream_t s, uint32_t *zero_cnt = nullptr, int zero_per_query = 0);   // zero_cnt: n_q x zero_per_query counters to clear on the way
+                     hipStream_t s, uint32_t *zero_cnt = nullptr, int zero_per_query = 0,   // zero_cnt: n_q x zero_per_query counters to clear on the way
+                     uint32_t *glist = nullptr, int list_cap = 0);   // glist [nq_pad][list_cap + 1]: per query {count, groups whose upper bound reaches tau}
 int select_compact_entries(int dim, int ranges, int rescore_cap, int64_t want);
 // thr (device, [n_q], may be null): the thresholds the main pass filtered with.  The select VERIFIES them -- the k-th largest lower
 // bound L of the candidates must reach thr[q], else rows below an over-estimated threshold may be missing: the query is flagged
 // for the retry pass and thr[q] is replaced by L (a valid bound); with fewer than k candidates thr[q] = -inf and the dense path.
+// gmax (device, null: no join): the sample pass's group maxima [sample_tiles * 16][gmax_pitch] of a search whose main pass left out
+// the sampled tiles j * sample_stride -- every group that can reach L joins the re-scored rows (the first select of such a search only).
+// glist / list_cap (may be null): launch_threshold's short lists of the groups to test; without one the query's column of gmax is walked.
 int launch_select_rescore(const uint2 *cand, const uint32_t *cnt, int ranges, int sp, int n_q, int nq_pad, const CandLayout &lay, int k,
                           int rescore_cap, int compact, int64_t n_rows, float *thr, const float *cq, const float *tile_norm, const float *row_norm,
                           const uint32_t *dmax_bits, const uint16_t *Q, const uint16_t *D, int dim, int64_t id_offset, float *out_scores, int64_t *out_ids,
                           uint32_t *flag_count, uint32_t *flag_list, unsigned long long *stat_cand, const uint32_t *out_rows,
-                          hipStream_t s);
+                          hipStream_t s, const float *gmax = nullptr, int sample_tiles = 0, int sample_stride = 0, int gmax_pitch = 0,
+                          const uint32_t *glist = nullptr, int list_cap = 0, int regular_cap = 0);   // regular_cap: limit of the recorded rows (0: rescore_cap)
 int launch_partition_flags(const uint32_t *flags, int begin, int n, uint32_t *retry_list, uint32_t *dense_list, uint32_t *counts,
                            hipStream_t s);
 int launch_underfilled_to_retry(uint32_t *flags, int begin, int n, const float *thr_safe, float *thr, hipStream_t s);

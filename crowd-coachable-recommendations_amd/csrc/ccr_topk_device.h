@@ -115,6 +115,11 @@ __device__ __forceinline__ void block_bitonic_sort_desc(unsigned long long *keys
     const int nt = blockDim.x;
     for (int size = 2; size <= n; size <<= 1) {
         for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            // The step's ds_write must have COMPLETED before the barrier: from n = 256 on a step reads what another wave wrote in the
+            // step before.  hipcc emits a bare s_barrier for the __syncthreads() inside this loop (its memory model takes the LDS
+            // operations of one workgroup as ordered), and on gfx950 that left single keys out of place in about 2 % of repeated
+            // searches -- a wave was through the barrier while its 8-byte writes were still in flight.  With the wait: none.
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __syncthreads();
             for (int i = tid; i < (n >> 1); i += nt) {
                 const int pos = 2 * i - (i & (stride - 1));

@@ -74,7 +74,8 @@ typedef struct ccr_search_stats {
                                   the select stage); 0: conservative lower bounds with re-tightening */
     int32_t main_tile_queries; /* queries per tile of the main pass: 256, or 384 (the 256 x 384 form, gemm_topk16w_kernel); 0 on the
                                   dense path and for the streaming pass of small batches */
-    int32_t reserved0;
+    int32_t skipped_tiles;     /* corpus tiles the main pass did not score: the sampled tiles, whose rows the select stage joins from the
+                                  sample pass's group maxima (CCR_SKIP_SAMPLED); 0: every tile was scored */
 } ccr_search_stats;
 
 const char *ccr_last_error(void);
