@@ -27,13 +27,14 @@ EXPORTS = [
     "ccr_bpr_sample", "ccr_bpr_frozen_workspace_bytes", "ccr_bpr_frozen_fwd", "ccr_bpr_frozen_bwd_dev",
     "ccr_attention_fwd_train_half", "ccr_attention_bwd_workspace_bytes", "ccr_attention_bwd_half", "ccr_add_layernorm_bwd_half", "ccr_gelu_bwd_half",
     "ccr_dropout_bits_rows", "ccr_dropout_bits_attention", "ccr_dropout_apply", "ccr_attention_fwd_train_drop_half", "ccr_attention_bwd_drop_half",
-    "ccr_add_layernorm_drop_half", "ccr_add_layernorm_bwd_drop_half",
+    "ccr_add_layernorm_drop_half", "ccr_add_layernorm_bwd_drop_half", "ccr_search_last_main_split",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
 BPR_VERSION = 102   # ... and the one the ccr_bpr_* entry points came with (ops checks it on their first use)
 ENCODER_TRAIN_VERSION = 103   # ... and the encoder layer kernels' training forward and backward (ccr_attention_bwd_half and its kin)
 ENCODER_DROPOUT_VERSION = 104   # ... and the keep-bit generators and the layer kernels that read the bits (ccr_dropout_bits_rows and its kin)
+QSPLIT_VERSION = 105   # ... and the main pass's unequal query groups with their getter (ccr_search_last_main_split)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -120,6 +121,7 @@ def load():
     lib.ccr_rank_metrics.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]
     lib.ccr_search_finish.argtypes = [vp]
     lib.ccr_search_stream_wait_main_pass.argtypes = [vp, vp]
+    lib.ccr_search_last_main_split.argtypes = [vp]
     lib.ccr_scores.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.ccr_search_blocked_workspace_bytes.argtypes = [vp, i32, i32, vp]
     lib.ccr_search_blocked_workspace_bytes.restype = sz

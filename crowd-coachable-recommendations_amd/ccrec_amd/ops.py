@@ -853,6 +853,10 @@ class CorpusIndex:
         _lib.check(self._lib.ccr_search_last_stats(self._h, ctypes.byref(st)), "ccr_search_last_stats")
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    def last_main_split(self):
+        """Unequal query groups (2, 4, 8) of the last search's main pass; 0: equal groups (ccr_search_last_main_split)."""
+        return int(self._lib.ccr_search_last_main_split(self._h))
+
     def scores(self, queries_bf16, mode="canonical"):
         """Dense score matrix [n_q, n_rows] fp32 (ccr_scores).  mode "canonical": the fp64-ordered values the ranking
         reports; "mfma": the same bf16 rows through the MFMA tile kernel (fp32 accumulation)."""

@@ -25,8 +25,10 @@ void set_error(const char *fmt, ...) {
 }
 
 // ------------------------------------------------------------------ planner
-// Query-block groups per XCD set: the smallest divisor of qblocks among {1,2,4,8} that keeps one XCD's
-// query rows (qblocks / groups blocks of 256 rows) within ~3 MiB of its 4-MiB L2.
+// Query-block groups per XCD set (pick_qgroups): the smallest divisor of qblocks among {1,2,4,8} that keeps one XCD's
+// query rows (qblocks / groups blocks of tile_q rows) within ~3 MiB of its 4-MiB L2.  These are the EQUAL groups every launch
+// knows; a block count they cannot cut small enough (nine = 3 x 3, a prime) gets unequal groups in a single-launch main pass
+// (pick_qsplit).
 static int env_int(const char *name, int dflt) {
     const char *e = getenv(name);
     return e ? atoi(e) : dflt;
@@ -47,6 +49,7 @@ Knobs read_knobs() {
     kn.wide = env_int("CCR_WIDE", -1);
     kn.skip_sampled = env_int("CCR_SKIP_SAMPLED", -1);
     kn.skip_list = env_int("CCR_SKIP_LIST", 1);
+    kn.qsplit = env_int("CCR_QSPLIT", -1);
     kn.narrow_grid = env_int("CCR_NARROW_GRID", 0);
     kn.narrow_groups = env_int("CCR_NARROW_GROUPS", NARROW_MAX_GROUPS);
     return kn;
@@ -65,6 +68,29 @@ static int pick_qgroups(int qblocks, int dim, const Knobs &kn, int tile_q = TILE
         if ((size_t)(qblocks / gq) * block_bytes <= (size_t)3 << 20) break;
     }
     return best;
+}
+
+// Price class of the query bytes one XCD walks in a main pass (the per-flop table of the wide tile): they stay in its 4-MiB L2
+// beside the corpus stream (0), mostly (1), or stream past it (2).
+static int footprint_class(double bytes) { return bytes <= 3.2 * 1048576.0 ? 0 : (bytes <= 5.5 * 1048576.0 ? 1 : 2); }
+
+// Unequal query groups of a single-launch main pass (main_item() in ccr_common.h): G in {2, 4, 8} that does NOT divide the block
+// count, each group base = qblocks / G whole blocks, the qblocks % G left-over blocks shared range row by range row, so that an XCD
+// walks base + rem blocks.  0 = keep the equal groups.  The planner's own choice: the smallest G whose footprint reaches a better
+// price class than the equal groups' (NQ on the wide tile: nine blocks = 5.06 MiB in one group, five = 2.81 MiB with G = 2).
+// CCR_QSPLIT=1: any block count that has a split gets one; a CCR_QGROUPS that does not divide the block count names G.
+static int pick_qsplit(int qblocks, int equal_groups, int dim, int tile_q, const Knobs &kn) {
+    if (kn.qsplit == 0) return 0;
+    const int v = kn.qgroups;
+    if (v == 2 || v == 4 || v == 8) return qblocks % v ? v : 0;
+    const double block_bytes = (double)tile_q * dim * 2.0;
+    const int equal_class = footprint_class((double)(qblocks / equal_groups) * block_bytes);
+    for (int G = 2; G <= NUM_XCD; G *= 2)
+        if (qblocks % G && footprint_class((double)(qblocks / G + qblocks % G) * block_bytes) < equal_class) return G;
+    if (kn.qsplit == 1)
+        for (int G = 2; G <= NUM_XCD; G *= 2)
+            if (qblocks % G) return G;
+    return 0;
 }
 
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
@@ -329,8 +355,10 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
         // kernel: 0.92-0.96 while the query rows one XCD walks stay L2-resident (300 and 1 100 queries: main pass -31 % / -14 %, most
         // of it the padding: one block instead of two, three instead of five), 0.97 at 5 MiB per XCD (3 452 queries: nine blocks =
         // 3 456 columns against fourteen = 3 584: -6.5 %), and SLOWER beyond -- 4 096 queries = eleven blocks, 6 980 = nineteen: a prime
-        // block count cannot be split over the XCDs, every XCD streams all the query rows past its 4-MiB L2 (L2 hit rate 0.71 against
+        // block count has no equal groups over the XCDs, every XCD streams all the query rows past its 4-MiB L2 (L2 hit rate 0.71 against
         // 0.91, +3.4 % main pass) while sixteen / twenty-eight 256-blocks split into groups that fit.
+        // (The tile is priced on its EQUAL groups: the unequal ones of pick_qsplit exist for a single-launch plan only, which is not
+        // known yet, and they have been measured at nine blocks alone -- eleven and nineteen blocks stay on the 256 x 256 tile.)
         p.tile_q = TILE_Q;
         p.main_qblocks = p.qblocks;
         if (!narrow && p.mfma16 && dim % 32 == 0 && kn.wide != 0) {
@@ -361,6 +389,9 @@ static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, in
         p.item_b = choice.item_b;
         p.opt_rank = choice.opt_rank;
         p.skip_sampled = (p.opt_rank > 0 && !p.narrow) ? choice.skip : 0;
+        // unequal query groups: a single launch of a tile kernel only (phase ends are item indices of the equal groups' map, and
+        // the re-tightening between two phases takes a query's finished ranges from its block's place in an equal group)
+        p.main_qsplit = (!p.narrow && p.item_a == 0 && p.item_b == 0) ? pick_qsplit(p.main_qblocks, p.main_qgroups, dim, p.tile_q, kn) : 0;
         // the join can add a whole sampled tile to a query's collected rows (a corpus in topical order): room for one beside the
         // regular rows (about k, and ties around the cut) -- 512 at k = 100, which keeps the select's 256-thread form.  On iid rows a
         // sampled group of 16 holds a row of the top k with probability 1 - (1 - k / n)^16 and joins whole: J rows per query (50 at NQ,
@@ -587,7 +618,7 @@ void slab_give(int device, uint32_t *p) {
 }  // namespace
 
 extern "C" const char *ccr_last_error(void) { return g_err; }
-extern "C" int ccr_version(void) { return 104; }
+extern "C" int ccr_version(void) { return 105; }
 
 extern "C" int ccr_index_destroy(ccr_index *ix);
 
@@ -748,6 +779,11 @@ extern "C" int ccr_search_last_stats(const ccr_index *ix, ccr_search_stats *stat
     return CCR_OK;
 }
 
+extern "C" int ccr_search_last_main_split(const ccr_index *ix) {
+    if (!ix || ix->plan_nq <= 0 || !ix->plan.fused) return 0;   // no search yet / dense path
+    return ix->plan.main_qsplit;
+}
+
 // Exact dense path for n queries: the rows d_qlist[0 .. n) (or 0 .. n when d_qlist is null), results to the same rows of the outputs.
 static int dense_for_list(const ccr_index *ix, const uint16_t *Q, const uint32_t *d_qlist, int n, int k, float *scratch, int64_t rows_per_chunk,
                           float *out_scores, int64_t *out_ids, hipStream_t s) {
@@ -836,6 +872,7 @@ static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float 
 static int run_main_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, const uint16_t *Q, int n_q, int k, hipStream_t s) {
     // (blocks of p.tile_q queries; the sample pass walks blocks of TILE_Q)
     GemmArgs gm = filter_args(ix, p, w, Q, n_q, p.nq_pad, p.main_qblocks, p.main_qgroups, w.thr, w.cq, p.cand);
+    gm.qsplit = p.main_qsplit;   // (single launch: items keeps its value, every XCD set holds ranges / 8 * blocks items either way)
     if (p.skip_sampled) {   // the unsampled tiles only, in ascending order (unsampled_tile); the select joins the sampled ones
         gm.n_vt = p.tiles - p.sample_tiles;
         gm.skip_stride = (int)p.sample_stride;

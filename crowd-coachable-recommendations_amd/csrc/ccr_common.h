@@ -81,6 +81,7 @@ struct Plan {
     int tile_q;           // queries per tile of the MAIN pass: TILE_Q, or 384 (gemm_topk16w_kernel)
     int main_qblocks;     // query blocks of the main pass: ceil(n_q / tile_q)
     int main_qgroups;     // ... and their groups over the XCDs (divides main_qblocks)
+    int main_qsplit;      // 0, or the UNEQUAL groups (2, 4, 8; do not divide main_qblocks) of a single-launch main pass: main_item()
     int64_t tiles;        // ceil(n_rows / TILE_DOCS)
     int64_t full_tiles;   // floor(n_rows / TILE_DOCS)
     int sample_tiles;     // tiles scored by the threshold pass
@@ -122,6 +123,44 @@ __host__ __device__ __forceinline__ int64_t unsampled_tile(int64_t v, int s, int
     return u < (uint32_t)n * d ? (int64_t)(u + u / d + 1u) : v + n;
 }
 
+// Work items of a main-pass launch: item i of the XCD set of XCD `xcd` -> range r and query block qb; returns the range's count of
+// virtual tiles (<= 0: nothing to do).  Every XCD set holds (ranges / 8) * qblocks items.
+//   qsplit == 0   EQUAL groups: qgroups divides qblocks.  XCD x keeps the qblocks / qgroups blocks of group x % qgroups and the ranges
+//                 x / qgroups + (8 / qgroups) * rl; item = rl * blocks_per_group + block_in_group.
+//   qsplit == G   UNEQUAL groups, G in {2, 4, 8} with qblocks = G * base + rem: group g = x % G owns the blocks [g * base, (g + 1) * base)
+//                 in every range row rl of its range class x / G, as above; the rem SHARED blocks G * base ... of range row rl go to
+//                 the group rl % G -- the XCD that walks this very range for its own blocks -- and sit behind them in that row.  G range
+//                 rows hold G * base + rem = qblocks items of the XCD, so item i lies in the period i / qblocks; an XCD touches base + rem
+//                 blocks, and consecutive items still share a range.
+__host__ __device__ __forceinline__ int64_t main_item(int i, int xcd, int qblocks, int qgroups, int qsplit, int ranges, int64_t n_vt, int &r,
+                                                      int &qb) {
+    const int groups = qsplit ? qsplit : qgroups, g = xcd % groups, rc = xcd / groups, nrc = NUM_XCD / groups;
+    const int base = qblocks / groups;   // whole blocks of a group
+    int rl, b;
+    if (qsplit == 0) {
+        rl = i / base;
+        b = g * base + i % base;
+    } else {
+        const int rem = qblocks - base * groups;
+        const int period = i / qblocks, o = i - period * qblocks;   // position in the period's G rows: g short rows, the long row g, ...
+        int row = g, k = o - g * base;                  // the long row: base own blocks, then the rem shared ones
+        if (k < 0) {                                    // a short row before it (base >= 1 here)
+            row = o / base;
+            k = o - row * base;
+        } else if (k >= base + rem) {                   // ... or behind it
+            row = (o - rem) / base;
+            k = o - rem - row * base;
+        }
+        rl = period * groups + row;
+        b = k >= base ? groups * base + (k - base) : g * base + k;
+    }
+    const int ri = rc + nrc * rl;
+    const int64_t ntile = (n_vt - ri + ranges - 1) / ranges;
+    r = ri;   // (outputs written last: storing r before the division changes hipcc's code for the division)
+    qb = b;
+    return ntile;
+}
+
 // epilogues of the fused GEMM kernel; EPI_FILTER's candidate record = one corpus row {MFMA score, row}
 enum { EPI_FILTER = 0, EPI_GMAX = 1, EPI_STORE = 2 };
 
@@ -141,6 +180,7 @@ struct GemmArgs {
     // (0 / 0: every tile -- all the sample pass, the retry pass and EPI_STORE ever see)
     int skip_stride, skip_count;
     int qgroups;          // query-block groups spread over the XCDs (1, 2, 4 or 8; divides qblocks)
+    int qsplit;           // 0, or unequal groups (2, 4, 8) that replace qgroups: main_item() (single-launch main pass only)
     // Work items of an XCD set are numbered item = (range / classes) * blocks_per_group + block_in_group; a launch covers the
     // items [item_begin, item_end) of every XCD set, so a phase can be EXACTLY whole rounds of items whatever the range count
     int item_begin, item_end;

@@ -75,32 +75,23 @@ __device__ __forceinline__ int64_t real_tile(const GemmArgs &a, int64_t vt) {
 }
 
 // Work items (range r, query block qb) of a main-pass launch.  Blocks b and b+8 share an XCD (its 4-MiB L2), so XCD x takes
-// query-block group x % qgroups (its query rows stay L2-resident) and the ranges r = x / qgroups (mod 8 / qgroups).  Item order:
+// query-block group x % groups (its query rows stay L2-resident) and the ranges r = x / groups (mod 8 / groups).  Item order:
 // consecutive items (the co-resident workgroups of an XCD) share a RANGE and walk its corpus tiles for different query blocks.
+// The map itself is main_item() (ccr_common.h: equal groups, or a.qsplit unequal ones whose left-over blocks are shared).
 //   for (int item = walk.first(a); item < walk.end; item += walk.step) { ntile = walk.item(a, item, r, qb); ... }
 struct ItemWalk {
-    int jx, step, qg, rc, nrc, qb_per, end;   // end: one past this XCD set's last item of the launch
+    int jx, step, xcd, end;   // end: one past this XCD set's last item of the launch
     __device__ __forceinline__ explicit ItemWalk(const GemmArgs &a) {
-        const int xcd = blockIdx.x & (NUM_XCD - 1);
+        xcd = blockIdx.x & (NUM_XCD - 1);
         jx = blockIdx.x >> 3;
         step = gridDim.x >> 3;
-        qg = xcd % a.qgroups;
-        rc = xcd / a.qgroups;
-        nrc = NUM_XCD / a.qgroups;           // range classes
-        qb_per = a.qblocks / a.qgroups;      // query blocks of this XCD (qgroups divides qblocks)
-        const int count_x = (a.ranges / nrc) * qb_per;   // items of this XCD set over the whole pass
+        const int count_x = (a.ranges / NUM_XCD) * a.qblocks;   // items of this XCD set over the whole pass (any grouping)
         end = a.item_end < count_x ? a.item_end : count_x;
     }
     __device__ __forceinline__ int first(const GemmArgs &a) const { return a.item_begin + jx; }
     // range r and query block qb of item i; returns the range's tile count (nothing to do when <= 0)
     __device__ __forceinline__ int64_t item(const GemmArgs &a, int i, int &r, int &qb) const {
-        const int rl = i / qb_per;
-        const int b = qg * qb_per + i % qb_per;
-        const int ri = rc + nrc * rl;
-        const int64_t ntile = (a.n_vt - ri + a.ranges - 1) / a.ranges;
-        r = ri;   // (outputs written last: storing r before the division changes hipcc's code for the division)
-        qb = b;
-        return ntile;
+        return main_item(i, xcd, a.qblocks, a.qgroups, a.qsplit, a.ranges, a.n_vt, r, qb);
     }
 };
 

@@ -20,6 +20,7 @@ struct Knobs {
     int narrow_grid;   // CCR_NARROW_GRID  0 = planner's choice, else workgroups of the streaming kernel
     int skip_sampled;  // CCR_SKIP_SAMPLED -1 = planner's choice, 0 = the main pass scores every tile (the A/B knob), 1 = it leaves out the sampled tiles wherever the plan allows
     int skip_list;     // CCR_SKIP_LIST    1 = the select's join reads the threshold kernel's short list of sampled groups (default), 0 = it walks the query's column of group maxima (the A/B knob)
+    int qsplit;        // CCR_QSPLIT       -1 = planner's choice, 0 = equal query groups only (the A/B knob), 1 = unequal groups (left-over blocks shared) wherever a single-launch main pass has a block count they apply to; a CCR_QGROUPS that does not divide the block count names their number
     int wide;          // CCR_WIDE         -1 = planner's choice, 0 = 256 x 256 main-pass tiles only (the A/B knob), 1 = 256 x 384 wherever the kernel applies
     int narrow_groups; // CCR_NARROW_GROUPS 2 = batches of 65 .. 128 queries stream as two query groups (default), 1 = tile kernels above 64 queries (the A/B knob)
 };

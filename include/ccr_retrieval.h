@@ -325,6 +325,12 @@ int ccr_search_last_stats(const ccr_index *index, ccr_search_stats *stats /* hos
  * last search took the dense path (nothing recorded).  No host synchronisation.
  */
 int ccr_search_stream_wait_main_pass(const ccr_index *index, void *stream);
+/*
+ * Query groups of the last search's main pass when they were UNEQUAL (2, 4 or 8 groups over the XCDs that do not divide the count
+ * of query blocks: each keeps its whole blocks, the left-over blocks are shared range by range -- CCR_QSPLIT); 0: equal groups, the
+ * streaming pass of a small batch, the dense path, or no search yet.  ccr_version() >= 105.
+ */
+int ccr_search_last_main_split(const ccr_index *index);
 
 /*
  * Dense score matrix of n_q queries against the shard: out [n_q][n_rows] fp32.

@@ -92,6 +92,10 @@ def main():
         ("nq_k1001", {}, ["--k", "1001"]),
         ("nq_shard8", {}, ["--rows", "335184"]),
         ("msmarco_shard8", {}, ["--rows", "1105228", "--queries", "6980"]),
+        # unequal query groups of the wide tile's nine blocks (CCR_QSPLIT; nq_default is the planner's G = 2): equal groups, G = 4, G = 8
+        ("nq_qsplit0", {"CCR_QSPLIT": "0"}, nq),
+        ("nq_qsplit_g4", {"CCR_QSPLIT": "1", "CCR_QGROUPS": "4"}, nq),
+        ("nq_qsplit_g8", {"CCR_QSPLIT": "1", "CCR_QGROUPS": "8"}, nq),
     ]
     if quick:
         variants = variants[:2]
