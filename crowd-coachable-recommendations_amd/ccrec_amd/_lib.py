@@ -28,6 +28,7 @@ EXPORTS = [
     "ccr_attention_fwd_train_half", "ccr_attention_bwd_workspace_bytes", "ccr_attention_bwd_half", "ccr_add_layernorm_bwd_half", "ccr_gelu_bwd_half",
     "ccr_dropout_bits_rows", "ccr_dropout_bits_attention", "ccr_dropout_apply", "ccr_attention_fwd_train_drop_half", "ccr_attention_bwd_drop_half",
     "ccr_add_layernorm_drop_half", "ccr_add_layernorm_bwd_drop_half", "ccr_search_last_main_split",
+    "ccr_search_last_threshold_phases",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
@@ -35,6 +36,7 @@ BPR_VERSION = 102   # ... and the one the ccr_bpr_* entry points came with (ops 
 ENCODER_TRAIN_VERSION = 103   # ... and the encoder layer kernels' training forward and backward (ccr_attention_bwd_half and its kin)
 ENCODER_DROPOUT_VERSION = 104   # ... and the keep-bit generators and the layer kernels that read the bits (ccr_dropout_bits_rows and its kin)
 QSPLIT_VERSION = 105   # ... and the main pass's unequal query groups with their getter (ccr_search_last_main_split)
+THR_PHASES_VERSION = 106   # ... and the threshold kernel's 64-phase form with its getter (ccr_search_last_threshold_phases)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -122,6 +124,7 @@ def load():
     lib.ccr_search_finish.argtypes = [vp]
     lib.ccr_search_stream_wait_main_pass.argtypes = [vp, vp]
     lib.ccr_search_last_main_split.argtypes = [vp]
+    lib.ccr_search_last_threshold_phases.argtypes = [vp]
     lib.ccr_scores.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.ccr_search_blocked_workspace_bytes.argtypes = [vp, i32, i32, vp]
     lib.ccr_search_blocked_workspace_bytes.restype = sz

@@ -857,6 +857,11 @@ class CorpusIndex:
         """Unequal query groups (2, 4, 8) of the last search's main pass; 0: equal groups (ccr_search_last_main_split)."""
         return int(self._lib.ccr_search_last_main_split(self._h))
 
+    def last_threshold_phases(self):
+        """Group phases per query (16 / 64) of the last search's threshold kernel; 0: small-batch kernel or dense path
+        (ccr_search_last_threshold_phases)."""
+        return int(self._lib.ccr_search_last_threshold_phases(self._h))
+
     def scores(self, queries_bf16, mode="canonical"):
         """Dense score matrix [n_q, n_rows] fp32 (ccr_scores).  mode "canonical": the fp64-ordered values the ranking
         reports; "mfma": the same bf16 rows through the MFMA tile kernel (fp32 accumulation)."""

@@ -50,6 +50,7 @@ Knobs read_knobs() {
     kn.skip_sampled = env_int("CCR_SKIP_SAMPLED", -1);
     kn.skip_list = env_int("CCR_SKIP_LIST", 1);
     kn.qsplit = env_int("CCR_QSPLIT", -1);
+    kn.thr_phases = env_int("CCR_THR_PHASES", 0);
     kn.narrow_grid = env_int("CCR_NARROW_GRID", 0);
     kn.narrow_groups = env_int("CCR_NARROW_GROUPS", NARROW_MAX_GROUPS);
     return kn;
@@ -618,7 +619,7 @@ void slab_give(int device, uint32_t *p) {
 }  // namespace
 
 extern "C" const char *ccr_last_error(void) { return g_err; }
-extern "C" int ccr_version(void) { return 105; }
+extern "C" int ccr_version(void) { return 106; }
 
 extern "C" int ccr_index_destroy(ccr_index *ix);
 
@@ -782,6 +783,11 @@ extern "C" int ccr_search_last_stats(const ccr_index *ix, ccr_search_stats *stat
 extern "C" int ccr_search_last_main_split(const ccr_index *ix) {
     if (!ix || ix->plan_nq <= 0 || !ix->plan.fused) return 0;   // no search yet / dense path
     return ix->plan.main_qsplit;
+}
+
+extern "C" int ccr_search_last_threshold_phases(const ccr_index *ix) {
+    if (!ix || ix->plan_nq <= 0 || !ix->plan.fused) return 0;   // no search yet / dense path
+    return ix->thr_phases_used;
 }
 
 // Exact dense path for n queries: the rows d_qlist[0 .. n) (or 0 .. n when d_qlist is null), results to the same rows of the outputs.
@@ -973,7 +979,8 @@ static int fused_stats(ccr_index *ix, uint32_t nflag, unsigned long long ncand) 
 static int recover_thresholds(const ccr_index *ix, const SearchWs &w, int nflag) {
     const auto &pd = ix->pending;
     const int rc = launch_threshold(w.gmax, (int64_t)ix->plan.sample_tiles * GROUPS_PER_TILE, pd.n_q, ix->plan.nq_pad, pd.k, w.qnorm, ix->dmax_bits,
-                                    ix->dim, ix->tile_norm, ix->plan.sample_stride, w.thr_safe, w.cq_safe, pd.stream);
+                                    ix->dim, ix->tile_norm, ix->plan.sample_stride, w.thr_safe, w.cq_safe, pd.stream, nullptr, 0, nullptr, 0,
+                                    ix->knobs.thr_phases);
     if (rc != CCR_OK) return rc;
     return launch_underfilled_to_retry(w.flag_list, 0, nflag, w.thr_safe, w.thr, pd.stream);
 }
@@ -1182,6 +1189,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     CCR_REQUIRE(!ix->pending.active, "ccr_search: an asynchronous search is pending on this index (call ccr_search_finish first)");
     memset(&ix->stats, 0, sizeof(ix->stats));
     ix->main_pass_recorded = false;
+    ix->thr_phases_used = 0;
     if (n_q == 0) return CCR_OK;
     hipStream_t s = (hipStream_t)stream;
     ix->id_out = id_out;
@@ -1229,7 +1237,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     // (small batches: the streaming pass's sub-list counters are cleared by the threshold launch)
     rc = launch_threshold(w.gmax, (int64_t)p.sample_tiles * GROUPS_PER_TILE, n_q, p.nq_pad, p.opt_rank ? p.opt_rank : k, w.qnorm, ix->dmax_bits,
                           ix->dim, ix->tile_norm, p.sample_stride, w.thr, w.cq, s, p.narrow ? w.cnt : nullptr, p.narrow ? NARROW_SUBLISTS : 0,
-                          p.skip_sampled && ix->knobs.skip_list ? w.glist : nullptr, skip_list_cap(p.opt_rank));
+                          p.skip_sampled && ix->knobs.skip_list ? w.glist : nullptr, skip_list_cap(p.opt_rank), ix->knobs.thr_phases, &ix->thr_phases_used);
     if (rc != CCR_OK) return rc;
 
     // main pass -> candidates -> select

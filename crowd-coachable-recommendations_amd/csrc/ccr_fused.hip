@@ -564,15 +564,33 @@ __device__ __forceinline__ int fresh_lane() {
 __device__ __forceinline__ uint32_t lds_offset(const void *p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
 }
-__device__ __forceinline__ float2 lds_read_f2(uint32_t addr) {   // complete on return
+// The wide epilogue's cells -- a lane's {tau, cq} pairs and its sub-list counters -- are LANE-PRIVATE: no other lane or wave reads or
+// writes them between the item's set-up and its last tile, so nothing here is atomic.  The reads are ISSUED ONLY (no wait): a tile's
+// twelve go out back to back and lds_wait_cells() retires them in one round trip instead of twelve.  (Its "+v" operands make every
+// use of a cell depend on the wait.)  The counter store is issued only as well: LDS serves a wave's accesses in order, so the next
+// tile's read of the same cell sees it, and the K loop's s_waitcnt lgkmcnt(0) in front of the next barrier retires it.
+template <int OFF>
+__device__ __forceinline__ uint64_t lds_issue_read_b64(uint32_t addr) {
     uint64_t v;
-    asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32)));
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+    return v;
 }
-__device__ __forceinline__ uint32_t lds_add_rtn(uint32_t addr, uint32_t x) {   // complete on return
-    uint32_t r;
-    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(addr), "v"(x) : "memory");
-    return r;
+template <int OFF>
+__device__ __forceinline__ uint32_t lds_issue_read_b32(uint32_t addr) {
+    uint32_t v;
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+    return v;
+}
+template <int OFF>
+__device__ __forceinline__ void lds_issue_write_b32(uint32_t addr, uint32_t v) {
+    asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
+}
+__device__ __forceinline__ void lds_wait_cells(uint64_t (&tc)[6], uint32_t (&cn)[6]) {
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(tc[0]), "+v"(tc[1]), "+v"(tc[2]), "+v"(tc[3]), "+v"(tc[4]), "+v"(tc[5]), "+v"(cn[0]), "+v"(cn[1]), "+v"(cn[2]), "+v"(cn[3]),
+                   "+v"(cn[4]), "+v"(cn[5])
+                 :
+                 : "memory");
 }
 constexpr int WIDE_SUB_BYTES = (TILE_DOCS + WIDE_Q) * SUB_K * 2;   // 40960
 constexpr int WIDE_Q_REGION = TILE_DOCS * SUB_K * 2;               // 16384
@@ -708,17 +726,38 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             // (slot-major: slot n of the cell is 8 records further; 384 queries x 8 x cap <= 8192 x 8 B < 2^32)
             char *const cbase = reinterpret_cast<char *>(a.cand + seg_base + ((int64_t)(r - seg_r0) * a.nq_pad + q0) * 8 * cap + wd * 4);
             const uint32_t row_lo = (uint32_t)(wd * 128 + 4 * lqo);       // + dt * 16 + e: row inside the tile
-            const uint32_t tc_addr = lds_offset(s_tc) + (uint32_t)l15o * 8u;            // + (wq * 96 + qt * 16) * 8
-            const uint32_t cnt_addr = lds_offset(s_cnt) + (uint32_t)(lqo * 16 + l15o) * 4u;   // + ((wv * 6 + qt) * 64) * 4
+            const uint32_t tc_addr = lds_offset(s_tc) + (uint32_t)(wq * 96 + l15o) * 8u;                        // + qt * 16 * 8
+            const uint32_t cnt_addr = lds_offset(s_cnt) + (uint32_t)(wv * WIDE_QT * 64 + lqo * 16 + l15o) * 4u;   // + qt * 64 * 4
             const int64_t tile_row0 = rt * TILE_DOCS;      // wave-uniform
             const uint32_t rows_left = a.n_rows - tile_row0 < TILE_DOCS ? (uint32_t)(a.n_rows - tile_row0) : (uint32_t)TILE_DOCS;
+            // ONE LDS round trip per tile: the six {tau, cq} pairs and the lane's six counters go out back to back, the row maxima of the
+            // first query tile are taken while they travel, one wait.  (The operand fragments are dead here in both groups: the registers exist.)
+            uint64_t tcr[WIDE_QT];
+            uint32_t cnr[WIDE_QT];
+            tcr[0] = lds_issue_read_b64<0 * 128>(tc_addr);
+            tcr[1] = lds_issue_read_b64<1 * 128>(tc_addr);
+            tcr[2] = lds_issue_read_b64<2 * 128>(tc_addr);
+            tcr[3] = lds_issue_read_b64<3 * 128>(tc_addr);
+            tcr[4] = lds_issue_read_b64<4 * 128>(tc_addr);
+            tcr[5] = lds_issue_read_b64<5 * 128>(tc_addr);
+            cnr[0] = lds_issue_read_b32<0 * 256>(cnt_addr);
+            cnr[1] = lds_issue_read_b32<1 * 256>(cnt_addr);
+            cnr[2] = lds_issue_read_b32<2 * 256>(cnt_addr);
+            cnr[3] = lds_issue_read_b32<3 * 256>(cnt_addr);
+            cnr[4] = lds_issue_read_b32<4 * 256>(cnt_addr);
+            cnr[5] = lds_issue_read_b32<5 * 256>(cnt_addr);
+            float sub0[8];
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt) sub0[dt] = max4_asm(acc[dt][0]);
+            __builtin_amdgcn_sched_barrier(0);
+            lds_wait_cells(tcr, cnr);
 #pragma unroll
             for (int qt = 0; qt < WIDE_QT; ++qt) {
                 float sub[8];
 #pragma unroll
-                for (int dt = 0; dt < 8; ++dt) sub[dt] = max4_asm(acc[dt][qt]);
-                const float2 tc = lds_read_f2(tc_addr + (uint32_t)(wq * 96 + qt * 16) * 8u);
-                const float t = fmaf(-tc.y, nt, tc.x);   // per-tile margin: mfma + cq * ||d|| >= tau_q with ||d|| <= nt
+                for (int dt = 0; dt < 8; ++dt) sub[dt] = qt == 0 ? sub0[dt] : max4_asm(acc[dt][qt]);
+                // per-tile margin: mfma + cq * ||d|| >= tau_q with ||d|| <= nt
+                const float t = fmaf(-__uint_as_float((uint32_t)(tcr[qt] >> 32)), nt, __uint_as_float((uint32_t)tcr[qt]));
                 float mall = max3_asm(sub[0], sub[1], sub[2]);
                 mall = max3_asm(mall, sub[3], sub[4]);
                 mall = max3_asm(mall, sub[5], sub[6]);
@@ -726,16 +765,15 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
                 if (__ballot(mall >= t) != 0ull) {
                     const uint32_t ql = (uint32_t)(wq * 96 + qt * 16 + l15o);
                     const uint32_t cell = (ql * 8u * (uint32_t)cap + (uint32_t)lqo) * 8u;    // byte offset of slot 0
-                    const uint32_t cn = cnt_addr + (uint32_t)((wv * WIDE_QT + qt) * 64) * 4u;
 #pragma unroll
                     for (int dt = 0; dt < 8; ++dt) {
-                        if (sub[dt] >= t) {  // rare, divergent: 4 rows to test
+                        if (sub[dt] >= t) {  // divergent: 4 rows to test
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 const float v = acc[dt][qt][e];
                                 const uint32_t row = row_lo + dt * 16 + e;
                                 if (v >= t && row < rows_left) {
-                                    const uint32_t n = lds_add_rtn(cn, 1u);   // lane-private cell
+                                    const uint32_t n = cnr[qt]++;   // the count keeps running past cap: the select flags the overflow
                                     if (n < (uint32_t)cap)
                                         *reinterpret_cast<uint2 *>(cbase + (cell + n * 64u)) = make_uint2(__float_as_uint(v), (uint32_t)tile_row0 + row);
                                 }
@@ -744,6 +782,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
                     }
                 }
             }
+            lds_issue_write_b32<0 * 256>(cnt_addr, cnr[0]);
+            lds_issue_write_b32<1 * 256>(cnt_addr, cnr[1]);
+            lds_issue_write_b32<2 * 256>(cnt_addr, cnr[2]);
+            lds_issue_write_b32<3 * 256>(cnt_addr, cnr[3]);
+            lds_issue_write_b32<4 * 256>(cnt_addr, cnr[4]);
+            lds_issue_write_b32<5 * 256>(cnt_addr, cnr[5]);
         };
 
         const int npro = U < 2 ? U : 2;
@@ -831,6 +875,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
             CCR_BARRIER();
         }
         if (pending) epilogue(pending_rt, pending_nt);
+        CCR_WAIT_LGKM0();   // the last tile's counter stores, in front of the barrier and the read-out below
         if (!g1) CCR_BARRIER();
 
         {
@@ -930,30 +975,45 @@ __global__ __launch_bounds__(1024) void max_tile_norm_kernel(const uint32_t *__r
     }
 }
 
+// The wide threshold form: queries per workgroup (x 64 phases) and the smallest sample it is launched for (launch_threshold).
+// 16 queries = 1 024 threads reading 64-byte segments of a gmax row: 113 us at NQ (5 248 groups x 3 584 columns) against 161 us for
+// the 16-phase form.  8 queries x 64 phases (512 threads, twice the workgroups, 32-byte segments) took 187 us: half-used 64-byte
+// sectors cost more than the second workgroup per CU hides (profiles/threshold_epilogue.md).
+constexpr int THR_WIDE_QUERIES = 16;
+constexpr int THR_WIDE_MIN_BATCHES = 2;
+
 // Sample thresholds.  A sampled 16-row group whose maximum MFMA score is m holds a row whose EXACT score is at least
 // m - cq * nt (cq = gamma * ||q||, nt = norm bound of the group's tile), so tau_q = the k-th largest of those lower bounds is
 // a lower bound of the query's k-th largest exact score: thr[q] = tau_q, cq[q] = the margin coefficient the later stages use.
-// One workgroup = 16 queries x 16 group phases: a gmax row is read as 64-byte segments (query-contiguous
-// layout), every query has its own 256-bin LDS histogram (no same-address atomics), 4 MSB-first passes.
-// grid = nq_pad / 16, block = 256.
+// One workgroup = QB queries x PH group phases (thread = ql + QB * ph): a gmax row is read as QB * 4-byte segments (query-contiguous
+// layout), every query has its own 256-bin LDS histogram (no same-address atomics), 4 MSB-first passes.  A pass is a chain of
+// n_groups / (16 PH) dependent batches of 16 loads per thread and nothing bounds the kernel but that chain: the launcher gives a
+// large sample 64 phases (16 waves per workgroup) instead of 16.  The histogram counts do not depend on the order of the adds: every
+// form computes the same thresholds bit for bit and the same short list as a set.
+// grid = nq_pad / QB, block = QB * PH.
 // glist (may be null; [nq_pad][list_cap + 1]): the query's SHORT LIST for the select stage's join of the sampled tiles -- entry 0 the
 // count, then the groups whose UPPER bound m + cq * nt reaches tau (written in the last radix pass against tau's upper 24 bits, a value
 // <= tau).  The select joins groups whose upper bound reaches L >= tau: all of them are on the list.  About k of the groups qualify
 // (k is the threshold's rank here); a count above list_cap tells the select to walk the query's whole column instead.
 // (LIST: a kernel of its own, so that the search without lists keeps the registers and the time of the plain kernel)
-template <bool LIST>
-__global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict__ gmax, int64_t n_groups, int n_q, int nq_pad,
-                                                       int k, const float *__restrict__ qnorm,
-                                                       const uint32_t *__restrict__ dmax_bits, float gamma,
-                                                       const float *__restrict__ tile_norm, int64_t sample_stride,
-                                                       float *__restrict__ thr, float *__restrict__ cq,
-                                                       uint32_t *__restrict__ glist, int list_cap) {
-    __shared__ uint32_t s_hist[16][256];
-    __shared__ uint32_t s_prefix[16], s_remaining[16], s_nlist[16];
+// Barriers: the waves exchange histogram data through LDS, so every __syncthreads() has its explicit s_waitcnt lgkmcnt(0) in front
+// (hipcc emits a bare s_barrier in loops of this kind).
+template <bool LIST, int PH, int QB>
+__global__ __launch_bounds__(QB * PH) void threshold_kernel(const float *__restrict__ gmax, int64_t n_groups, int n_q, int nq_pad,
+                                                           int k, const float *__restrict__ qnorm,
+                                                           const uint32_t *__restrict__ dmax_bits, float gamma,
+                                                           const float *__restrict__ tile_norm, int64_t sample_stride,
+                                                           float *__restrict__ thr, float *__restrict__ cq,
+                                                           uint32_t *__restrict__ glist, int list_cap) {
+    constexpr int THREADS = QB * PH;
+    constexpr int PICK = QB * 16;   // threads of the digit pick: 16 per query, the first PICK of the workgroup (whole waves)
+    static_assert(THREADS >= PICK && PICK % 64 == 0 && (QB & (QB - 1)) == 0, "threshold_kernel: shape");
+    __shared__ uint32_t s_hist[QB][256];
+    __shared__ uint32_t s_prefix[QB], s_remaining[QB], s_nlist[QB];
     const int tid = threadIdx.x;
-    const int ql = tid & 15, ph = tid >> 4;
-    const int q = blockIdx.x * 16 + ql;
-    if (tid < 16) {
+    const int ql = tid & (QB - 1), ph = tid / QB;
+    const int q = blockIdx.x * QB + ql;
+    if (tid < QB) {
         s_prefix[tid] = 0;
         s_remaining[tid] = (uint32_t)k;
         s_nlist[tid] = 0;
@@ -976,51 +1036,58 @@ __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict_
     uint32_t mask = 0;
     for (int shift = 24; shift >= 0; shift -= 8) {
         const bool listing = LIST && shift == 0;
-        for (int b = tid; b < 16 * 256; b += 256) (&s_hist[0][0])[b] = 0;
+        for (int b = tid; b < QB * 256; b += THREADS) (&s_hist[0][0])[b] = 0;
+        CCR_WAIT_LGKM0();
         __syncthreads();
         const uint32_t prefix = s_prefix[ql];
-        // 4 independent loads in flight per thread (the loop is latency-bound otherwise)
         int64_t i = ph;
-        for (; i + 240 < n_groups; i += 256) {   // 16 independent loads in flight per thread
+        for (; i + 15 * PH < n_groups; i += 16 * PH) {   // 16 independent loads in flight per thread (the loop is latency-bound)
             float v[16], tn[16];
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                v[j] = gmax[(i + 16 * j) * nq_pad + q];
-                tn[j] = tile_of(i + 16 * j);
+                v[j] = gmax[(i + PH * j) * nq_pad + q];
+                tn[j] = tile_of(i + PH * j);
             }
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const uint32_t o = f32_orderable(fmaf(-c, tn[j], v[j]));
                 if ((o & mask) == prefix) atomicAdd(&s_hist[ql][(o >> shift) & 255u], 1u);
-                if (listing) emit(i + 16 * j, v[j], tn[j], prefix);
+                if (listing) emit(i + PH * j, v[j], tn[j], prefix);
             }
         }
-        for (; i < n_groups; i += 16) {
+        for (; i < n_groups; i += PH) {
             const float v = gmax[i * nq_pad + q], tn = tile_of(i);
             const uint32_t o = f32_orderable(fmaf(-c, tn, v));
             if ((o & mask) == prefix) atomicAdd(&s_hist[ql][(o >> shift) & 255u], 1u);
             if (listing) emit(i, v, tn, prefix);
         }
+        CCR_WAIT_LGKM0();
         __syncthreads();
-        {   // digit pick: 16 lanes per query (16 bins each), shuffle suffix-scan instead of a 256-step serial walk
-            const int qi = tid >> 4, part = tid & 15;
-            const uint32_t remaining = s_remaining[qi];
-            uint32_t hb[16];
-            uint32_t own = 0;
+        // digit pick on the first PICK threads: 16 lanes per query (16 bins each), shuffle suffix-scan instead of a 256-step serial
+        // walk.  Every thread of the workgroup passes the same barriers.
+        const bool picker = tid < PICK;
+        const int qi = (tid >> 4) & (QB - 1), part = tid & 15;
+        uint32_t remaining = 0, own = 0, incl = 0, above = 0, total = 0;
+        uint32_t hb[16];
+        if (picker) {
+            remaining = s_remaining[qi];
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 hb[j] = s_hist[qi][16 * part + j];
                 own += hb[j];
             }
-            uint32_t incl = own;
+            incl = own;
 #pragma unroll
             for (int off = 1; off < 16; off <<= 1) {
                 const uint32_t t = __shfl_down(incl, off, 16);
                 if (part + off < 16) incl += t;
             }
-            const uint32_t above = incl - own;
-            const uint32_t total = __shfl(incl, 0, 16);
-            __syncthreads();   // every lane has read s_remaining before the crossing lane rewrites it
+            above = incl - own;
+            total = __shfl(incl, 0, 16);
+        }
+        CCR_WAIT_LGKM0();
+        __syncthreads();   // every lane has read s_remaining before the crossing lane rewrites it
+        if (picker) {
             if (above < remaining && remaining <= incl) {
                 uint32_t cum = above;
                 int d = 16 * part;
@@ -1039,13 +1106,14 @@ __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict_
             }
         }
         mask |= 0xffu << shift;
+        CCR_WAIT_LGKM0();
         __syncthreads();
     }
-    if (tid < 16) {
-        const int qq = blockIdx.x * 16 + tid;
+    if (tid < QB) {
+        const int qq = blockIdx.x * QB + tid;
         if (qq < n_q) {
             const float tau = orderable_to_f32(s_prefix[tid]);
-            cq[qq] = c;   // tid < 16: q == qq
+            cq[qq] = c;   // tid < QB: q == qq
             thr[qq] = (c < INFINITY) ? tau : __builtin_nanf("");
         }
         if (LIST) my_list[0] = s_nlist[tid];
@@ -1780,7 +1848,8 @@ __global__ __launch_bounds__(256) void threshold_small_kernel(const float *__res
 
 int launch_threshold(const float *gmax, int64_t n_groups, int n_q, int nq_pad, int k, const float *qnorm,
                      const uint32_t *dmax_bits, int dim, const float *tile_norm, int64_t sample_stride, float *thr, float *cq,
-                     hipStream_t s, uint32_t *zero_cnt, int zero_per_query, uint32_t *glist, int list_cap) {
+                     hipStream_t s, uint32_t *zero_cnt, int zero_per_query, uint32_t *glist, int list_cap, int phases, int *phases_used) {
+    if (phases_used) *phases_used = 0;
     // small batches: a workgroup per query (needs k <= n_groups -- the planner samples >= 2k groups -- and the bounds in 64 KiB of LDS);
     // *zero_cnt tells the caller whether its counters have been cleared here
     if (n_q <= 128 && n_groups >= k && n_groups <= 16384 && zero_per_query <= 256) {
@@ -1794,8 +1863,18 @@ int launch_threshold(const float *gmax, int64_t n_groups, int n_q, int nq_pad, i
         return CCR_OK;
     }
     if (zero_cnt) CCR_HIP_CHECK(hipMemsetAsync(zero_cnt, 0, (size_t)n_q * zero_per_query * 4, s));
-    hipLaunchKernelGGL(glist ? threshold_kernel<true> : threshold_kernel<false>, dim3(nq_pad / 16), dim3(256), 0, s, gmax, n_groups, n_q, nq_pad, k, qnorm, dmax_bits,
-                       mfma_gamma(dim), tile_norm, sample_stride, thr, cq, glist, list_cap);
+    // The wide form (THR_WIDE_QUERIES x 64 phases) wherever every phase still walks at least THR_WIDE_MIN_BATCHES full batches of 16
+    // loads per radix pass, n_groups >= 2 x 16 x 64 = 2 048: below that a 64-phase pass is mostly its remainder loop and its barriers
+    // across 16 waves, and the 16-phase chain it would shorten is only a few batches long.  `phases` (16 / 64, CCR_THR_PHASES) pins the form.
+    const bool wide = phases == 64 || (phases != 16 && n_groups >= (int64_t)THR_WIDE_MIN_BATCHES * 16 * 64);
+    if (phases_used) *phases_used = wide ? 64 : 16;
+    if (wide)
+        hipLaunchKernelGGL((glist ? threshold_kernel<true, 64, THR_WIDE_QUERIES> : threshold_kernel<false, 64, THR_WIDE_QUERIES>),
+                           dim3(nq_pad / THR_WIDE_QUERIES), dim3(64 * THR_WIDE_QUERIES), 0, s, gmax, n_groups, n_q, nq_pad, k, qnorm, dmax_bits,
+                           mfma_gamma(dim), tile_norm, sample_stride, thr, cq, glist, list_cap);
+    else
+        hipLaunchKernelGGL((glist ? threshold_kernel<true, 16, 16> : threshold_kernel<false, 16, 16>), dim3(nq_pad / 16), dim3(256), 0, s, gmax,
+                           n_groups, n_q, nq_pad, k, qnorm, dmax_bits, mfma_gamma(dim), tile_norm, sample_stride, thr, cq, glist, list_cap);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }

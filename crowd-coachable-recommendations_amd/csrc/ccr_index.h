@@ -22,6 +22,7 @@ struct Knobs {
     int skip_list;     // CCR_SKIP_LIST    1 = the select's join reads the threshold kernel's short list of sampled groups (default), 0 = it walks the query's column of group maxima (the A/B knob)
     int qsplit;        // CCR_QSPLIT       -1 = planner's choice, 0 = equal query groups only (the A/B knob), 1 = unequal groups (left-over blocks shared) wherever a single-launch main pass has a block count they apply to; a CCR_QGROUPS that does not divide the block count names their number
     int wide;          // CCR_WIDE         -1 = planner's choice, 0 = 256 x 256 main-pass tiles only (the A/B knob), 1 = 256 x 384 wherever the kernel applies
+    int thr_phases;    // CCR_THR_PHASES   0 = launcher's choice by the sample's size, 16 / 64 = the threshold kernel's group phases per query, pinned (tests, the A/B)
     int narrow_groups; // CCR_NARROW_GROUPS 2 = batches of 65 .. 128 queries stream as two query groups (default), 1 = tile kernels above 64 queries (the A/B knob)
 };
 Knobs read_knobs();
@@ -73,7 +74,8 @@ int launch_tile_norms(const float *row_bounds, int64_t rows, uint32_t *tile_bits
 int launch_threshold(const float *gmax, int64_t n_groups, int n_q, int nq_pad, int k, const float *qnorm,
                      const uint32_t *dmax_bits, int dim, const float *tile_norm, int64_t sample_stride, float *thr, float *cq,
                      hipStream_t s, uint32_t *zero_cnt = nullptr, int zero_per_query = 0,   // zero_cnt: n_q x zero_per_query counters to clear on the way
-                     uint32_t *glist = nullptr, int list_cap = 0);   // glist [nq_pad][list_cap + 1]: per query {count, groups whose upper bound reaches tau}
+                     uint32_t *glist = nullptr, int list_cap = 0,   // glist [nq_pad][list_cap + 1]: per query {count, groups whose upper bound reaches tau}
+                     int phases = 0, int *phases_used = nullptr);   // phases: 0 = by the sample's size, 16 / 64 = pinned; *phases_used: 16 / 64, 0 = the small-batch kernel
 int select_compact_entries(int dim, int ranges, int rescore_cap, int64_t want);
 // thr (device, [n_q], may be null): the thresholds the main pass filtered with.  The select VERIFIES them -- the k-th largest lower
 // bound L of the candidates must reach thr[q], else rows below an over-estimated threshold may be missing: the query is flagged
@@ -138,6 +140,7 @@ struct ccr_index {
     float *row_norm_own;     // the latter (per-device block cache), else null
     size_t row_bytes;
     bool have_events;
+    int thr_phases_used;       // group phases of the last search's threshold kernel (16 / 64; 0: the small-batch kernel, or no fused search yet)
     bool main_pass_recorded;   // EV_MAIN_END was recorded by the last search (fused path): ccr_search_stream_wait_main_pass has something to wait for
     int num_cu;
     int device;

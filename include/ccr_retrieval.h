@@ -331,6 +331,12 @@ int ccr_search_stream_wait_main_pass(const ccr_index *index, void *stream);
  * streaming pass of a small batch, the dense path, or no search yet.  ccr_version() >= 105.
  */
 int ccr_search_last_main_split(const ccr_index *index);
+/*
+ * Group phases per query of the last search's threshold kernel: 16 (workgroups of 256 threads) or 64 (1 024 threads, the form a
+ * large sample gets; CCR_THR_PHASES = 16 / 64 pins it).  Both forms compute the same thresholds bit for bit.  0: the small-batch
+ * threshold kernel, the dense path, or no search yet.  ccr_version() >= 106.
+ */
+int ccr_search_last_threshold_phases(const ccr_index *index);
 
 /*
  * Dense score matrix of n_q queries against the shard: out [n_q][n_rows] fp32.
