@@ -28,7 +28,7 @@ EXPORTS = [
     "ccr_attention_fwd_train_half", "ccr_attention_bwd_workspace_bytes", "ccr_attention_bwd_half", "ccr_add_layernorm_bwd_half", "ccr_gelu_bwd_half",
     "ccr_dropout_bits_rows", "ccr_dropout_bits_attention", "ccr_dropout_apply", "ccr_attention_fwd_train_drop_half", "ccr_attention_bwd_drop_half",
     "ccr_add_layernorm_drop_half", "ccr_add_layernorm_bwd_drop_half", "ccr_search_last_main_split",
-    "ccr_search_last_threshold_phases",
+    "ccr_search_last_threshold_phases", "ccr_adamw_step",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
@@ -37,6 +37,7 @@ ENCODER_TRAIN_VERSION = 103   # ... and the encoder layer kernels' training forw
 ENCODER_DROPOUT_VERSION = 104   # ... and the keep-bit generators and the layer kernels that read the bits (ccr_dropout_bits_rows and its kin)
 QSPLIT_VERSION = 105   # ... and the main pass's unequal query groups with their getter (ccr_search_last_main_split)
 THR_PHASES_VERSION = 106   # ... and the threshold kernel's 64-phase form with its getter (ccr_search_last_threshold_phases)
+OPTIM_VERSION = 107   # ... and the multi-tensor AdamW step that keeps the encoder's 16-bit weights current (ccr_adamw_step)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -56,6 +57,13 @@ class SearchStats(ctypes.Structure):
                 ("ms_total", ctypes.c_float), ("n_retried", ctypes.c_int32), ("n_dense", ctypes.c_int32),
                 ("main_launches", ctypes.c_int32), ("opt_rank", ctypes.c_int32), ("main_tile_queries", ctypes.c_int32),
                 ("skipped_tiles", ctypes.c_int32)]
+
+
+class AdamwSegment(ctypes.Structure):
+    """ccr_adamw_segment (include/ccr_retrieval.h)."""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("shadow", ctypes.c_void_p), ("n", ctypes.c_int64), ("decay", ctypes.c_float), ("step_size", ctypes.c_float),
+                ("bc2_sqrt", ctypes.c_float), ("shadow_dtype", ctypes.c_int32)]
 
 
 class CcrError(RuntimeError):
@@ -166,6 +174,7 @@ def load():
     lib.ccr_attention_bwd_drop_half.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, f32, i32, vp, sz, vp]
     lib.ccr_add_layernorm_drop_half.argtypes = [vp, vp, f32, vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]
     lib.ccr_add_layernorm_bwd_drop_half.argtypes = [vp, vp, f32, vp, vp, f32, vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, vp]
+    lib.ccr_adamw_step.argtypes = [vp, i32, f32, f32, f32, f32, vp]
     lib.ccr_meanpool_pack_bf16_packed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.ccr_shard_message_bytes.argtypes = [i32, i32]
     lib.ccr_shard_message_bytes.restype = sz

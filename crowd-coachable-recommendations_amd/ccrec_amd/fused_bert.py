@@ -249,6 +249,34 @@ class _Layer:
     __slots__ = ("wqkv", "bqkv", "wo", "bo", "g1", "b1", "eps1", "wi", "bi", "wo2", "bo2", "g2", "b2", "eps2")
 
 
+_LAYER_16BIT = ("wqkv", "bqkv", "wo", "bo", "wi", "bi", "wo2", "bo2")      # a layer's 16-bit copies (the LayerNorm tensors are the fp32 masters)
+_LAYER_FP32 = ("g1", "b1", "eps1", "g2", "b2", "eps2")
+
+
+_DEFERRED = object()      # FusedBertEncoder._signature after a maintained step: taken at the next refresh() (adopted_stepped)
+
+
+class _ShadowWeights(torch.autograd.Function):
+    """A layer's maintained 16-bit weights in the place of cat(q, k, v).to(half) and the seven other casts: forward hands out the eight
+    copies an optimizer keeps current (optim.FusedAdamW), backward returns each incoming 16-bit gradient as fp32 to its masters -- wqkv's
+    and bqkv's row-sliced into the three projections' -- the values the cast graph gives.  One node per layer."""
+
+    @staticmethod
+    def forward(ctx, layer, *masters):      # masters: the layer's twelve weights and biases in _live_masters' order
+        ctx.rows = masters[0].shape[0]
+        return tuple(getattr(layer, name).detach() for name in _LAYER_16BIT)
+
+    @staticmethod
+    def backward(ctx, g_wqkv, g_bqkv, g_wo, g_bo, g_wi, g_bi, g_wo2, g_bo2):
+        r = ctx.rows
+        w = None if g_wqkv is None else g_wqkv.float()
+        b = None if g_bqkv is None else g_bqkv.float()
+        qkv_w = (None, None, None) if w is None else (w[:r], w[r:2 * r], w[2 * r:])
+        qkv_b = (None, None, None) if b is None else (b[:r], b[r:2 * r], b[2 * r:])
+        rest = tuple(None if g is None else g.float() for g in (g_wo, g_bo, g_wi, g_bi, g_wo2, g_bo2))
+        return (None, *qkv_w, *qkv_b, *rest)
+
+
 class FusedBertEncoder:
     """16-bit (bf16 or fp16: the `dtype` of each call) forward of a transformers BertModel / DistilBertModel: forward(input_ids [B, L]
     right-padded, lengths [B]) -> last hidden state fp32 [B, L, hidden]; forward_packed(...) over a packed token array.  Holds 16-bit
@@ -264,6 +292,7 @@ class FusedBertEncoder:
         self.heads, self.hidden = arch.heads, arch.hidden
         self.has_token_types = arch.type_table is not None
         self._layers, self._signature, self._no_types = {}, None, None
+        self._adopted = self._adopted_stamp = None      # (dtype, layers): a weight set an optimizer keeps current (adopt_weights), and its stamp
         self.last_seed = None      # the seed of the latest training forward that ran with dropout (dropout_ref rebuilds its masks from it)
 
     def __getstate__(self):      # pickled with its model (torch.save(model)): without the 16-bit weight copies
@@ -272,6 +301,7 @@ class FusedBertEncoder:
     def __setstate__(self, state):
         self.__dict__.update(state)
         self._layers, self._signature, self._no_types = {}, None, None
+        self._adopted = self._adopted_stamp = None
         self.last_seed = None
 
     def _params_signature(self):
@@ -281,12 +311,107 @@ class FusedBertEncoder:
         """Drop the 16-bit weight copies if the module's parameters changed since they were made (-> True), and build the set of
         `dtype` (torch.bfloat16 / torch.float16) if one is named and missing."""
         sig = self._params_signature()
-        changed = sig != self._signature
-        if changed:
-            self._layers, self._signature = {}, sig
+        if self._signature is _DEFERRED:      # a maintained step left its set as the only copies: current iff its stamp still holds
+            changed = not self.adopted_current()
+            self._signature = sig
+            if changed:
+                self._layers = {}
+        else:
+            changed = sig != self._signature
+            if changed:
+                self._layers, self._signature = {}, sig
         if dtype is not None and dtype not in self._layers:
-            self._layers[dtype] = self._build_layers(dtype)
+            if self._adopted is not None and self._adopted[0] == dtype:
+                self._rebuild_adopted()      # (in place: the optimizer that maintains the set holds its addresses)
+            else:
+                self._layers[dtype] = self._build_layers(dtype)
         return changed
+
+    # ---- a weight set that an optimizer maintains (optim.FusedAdamW(shadow_for=...)): the set of `dtype` is built once from the masters;
+    # every step of that optimizer writes the new 16-bit values into it and calls adopted_stepped.  Whether it may be read is decided by
+    # its STAMP: (address, _version) of every tensor of every layer's parts, taken from the live module when the set was last made
+    # current.  A parameter that changed any other way -- load_state_dict, an in-place operation, another optimizer, .to() -- has another
+    # stamp: the set is stale, and a stale set is never read.  (Like _params_signature, the stamp sees what autograd's version counter sees.)
+    def _live_masters(self):
+        """Per layer the sixteen tensors the set derives from: q, k, v weight; q, k, v bias; attention output, FFN in, FFN out weight and
+        bias; both LayerNorms' weight and bias."""
+        arch = _describe(self.model)
+        out = []
+        for mod in arch.stack.layer:
+            q, k, v, so, ln1, ff, fo, ln2 = arch.layer_parts(mod)
+            out.append((q.weight, k.weight, v.weight, q.bias, k.bias, v.bias, so.weight, so.bias, ff.weight, ff.bias, fo.weight, fo.bias,
+                        ln1.weight, ln1.bias, ln2.weight, ln2.bias))
+        return out
+
+    @staticmethod
+    def _stamp(masters):
+        return tuple((t.data_ptr(), t._version) for layer in masters for t in layer)
+
+    def adopt_weights(self, dtype):
+        """Build the weight set of `dtype` from the masters and keep it as the maintained one -> its layers (exactly _build_layers'
+        tensors: the caller writes into wqkv / bqkv / wo / bo / wi / bi / wo2 / bo2)."""
+        self.refresh()
+        layers = self._build_layers(dtype)
+        self._layers[dtype] = layers
+        self._adopted, self._adopted_stamp = (dtype, layers), self._stamp(self._live_masters())
+        return layers
+
+    def adopted_masters(self):
+        """The tensors the stamp is taken over, for a caller that checks it every step (it holds the same parameters)."""
+        return self._live_masters()
+
+    def adopted_current(self, dtype=None, masters=None):
+        """Is there a maintained set (of `dtype`, if named) that matches the parameters as they are now?"""
+        a = self._adopted
+        return (a is not None and (dtype is None or a[0] == dtype) and self._layers.get(a[0]) is a[1]
+                and self._adopted_stamp == self._stamp(self._live_masters() if masters is None else masters))
+
+    def adopted_stepped(self, was_current, masters=None):
+        """The maintaining optimizer has just updated the parameters and written their 16-bit values into the set.  was_current (taken
+        before the update): the set is current at the new stamp and the copies of any other type are dropped; the signature that
+        refresh() compares is taken at the next refresh() -- which trusts the stamp.  Otherwise something else had moved the
+        parameters first, and the whole set is rebuilt from the masters."""
+        if self._adopted is None:
+            return
+        dtype, layers = self._adopted
+        if was_current:
+            self._layers, self._signature = {dtype: layers}, _DEFERRED
+            self._adopted_stamp = self._stamp(self._live_masters() if masters is None else masters)
+        else:
+            self._layers = {}
+            self._rebuild_adopted()
+
+    def _rebuild_adopted(self):
+        """Fill the maintained set from the masters IN PLACE (the optimizer holds its addresses) and stamp it.  If the parameters have
+        moved to another device or changed shape the set is given up: the next forwards cast, as without one."""
+        dtype, layers = self._adopted
+        sig = self._params_signature()
+        if sig != self._signature:
+            self._layers, self._signature = {}, sig
+        fresh = self._build_layers(dtype)
+        if len(fresh) != len(layers) or any(f.wqkv.device != l.wqkv.device or f.wqkv.shape != l.wqkv.shape for f, l in zip(fresh, layers)):
+            self._adopted = self._adopted_stamp = None
+            self._layers[dtype] = fresh
+            return
+        with torch.no_grad():
+            for l, f in zip(layers, fresh):
+                for name in _LAYER_16BIT:
+                    getattr(l, name).copy_(getattr(f, name))
+                for name in _LAYER_FP32:
+                    setattr(l, name, getattr(f, name))
+        self._layers[dtype] = layers
+        self._adopted_stamp = self._stamp(self._live_masters())
+
+    def _train_weights(self, half, masters):
+        """The maintained set's layers when a training forward in `half` over the live `masters` may read them, else None = cast the
+        live parameters for this call (no set, the other 16-bit type, or a stale set -- which is rebuilt from the masters here)."""
+        a = self._adopted
+        if a is None:
+            return None
+        if self._layers.get(a[0]) is a[1] and self._adopted_stamp == self._stamp(masters):
+            return a[1] if a[0] == half else None
+        self._rebuild_adopted()
+        return None
 
     def _build_layers(self, half):
         assert half in (torch.bfloat16, torch.float16), half
@@ -376,17 +501,26 @@ class FusedBertEncoder:
 
     def _layers_forward_train(self, h, hb, seq_start, lengths, max_len, pad_len, cls_rows=None, drop=None):
         """_layers_forward with gradients.  The projections are F.linear on the LIVE parameters cast to hb's dtype: the gradients reach
-        the fp32 master weights and no 16-bit copy can go stale between optimizer steps; autograd keeps the layer activations.
+        the fp32 master weights and no 16-bit copy can go stale between optimizer steps; autograd keeps the layer activations.  Where an
+        optimizer maintains a weight set in hb's dtype and it is current (_train_weights), the projections read that set through
+        _ShadowWeights instead of casting: the same operand bits, the same gradients.
         drop (a _DropoutDraw, a model in train() with live dropout): every site reads keep bits generated for its own stream id; the
         cls_only last layer generates its row-wise bits for the n_seq rows it runs on."""
         arch = _describe(self.model)
         half = hb.dtype
         mods = list(arch.stack.layer)
         last = len(mods) - 1
+        masters = self._live_masters() if self._adopted is not None else None
+        kept = None if masters is None else self._train_weights(half, masters)      # a current maintained weight set (optim.FusedAdamW): no cast, no cat
         for i, mod in enumerate(mods):
             q, k, v, so, ln1, ff, out, ln2 = arch.layer_parts(mod)
-            wqkv = torch.cat([q.weight, k.weight, v.weight]).to(half)
-            bqkv = torch.cat([q.bias, k.bias, v.bias]).to(half)
+            if kept is not None:
+                wqkv, bqkv, w_so, b_so, w_ff, b_ff, w_out, b_out = _ShadowWeights.apply(kept[i], *masters[i][:12])
+            else:
+                wqkv = torch.cat([q.weight, k.weight, v.weight]).to(half)
+                bqkv = torch.cat([q.bias, k.bias, v.bias]).to(half)
+                w_so, b_so, w_ff, b_ff = so.weight.to(half), so.bias.to(half), ff.weight.to(half), ff.bias.to(half)
+                w_out, b_out = out.weight.to(half), out.bias.to(half)
             qkv = F.linear(hb, wqkv, bqkv)
             bits_a = bits_o = bits_f = None
             inv_a = inv_o = inv_f = 1.0
@@ -401,10 +535,10 @@ class FusedBertEncoder:
                 li = len(mods) if (i == last and cls_rows is not None) else i      # the rows it runs on are another index space: own streams
                 bits_o, inv_o = drop.rows(d_attn, dropout_stream(li, SITE_ATTENTION_OUTPUT), ctx.shape[0], self.hidden, ctx.device)
                 bits_f, inv_f = drop.rows(d_ffn, dropout_stream(li, SITE_FFN_OUTPUT), ctx.shape[0], self.hidden, ctx.device)
-            h, hb = ops.add_layernorm_train(F.linear(ctx, so.weight.to(half), so.bias.to(half)), h, ln1.weight.float(), ln1.bias.float(), ln1.eps,
+            h, hb = ops.add_layernorm_train(F.linear(ctx, w_so, b_so), h, ln1.weight.float(), ln1.bias.float(), ln1.eps,
                                             keep_bits=bits_o, inv_keep=inv_o)
-            mid = ops.gelu_train(F.linear(hb, ff.weight.to(half), ff.bias.to(half)))
-            h, hb = ops.add_layernorm_train(F.linear(mid, out.weight.to(half), out.bias.to(half)), h, ln2.weight.float(), ln2.bias.float(), ln2.eps,
+            mid = ops.gelu_train(F.linear(hb, w_ff, b_ff))
+            h, hb = ops.add_layernorm_train(F.linear(mid, w_out, b_out), h, ln2.weight.float(), ln2.bias.float(), ln2.eps,
                                             keep_bits=bits_f, inv_keep=inv_f)
         if last < 0 and cls_rows is not None:
             h = h[cls_rows]

@@ -447,6 +447,22 @@ def _require_encoder_dropout():
     return lib
 
 
+_OPTIM_CHECKED = False
+
+
+def _require_optim():
+    """require_gpu() + once: the loaded library has the multi-tensor AdamW step (ccr_version() >= 107; ccrec_amd/optim.py calls it)."""
+    global _OPTIM_CHECKED
+    lib = require_gpu()
+    if not _OPTIM_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.OPTIM_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, the fused optimizer step needs {_lib.OPTIM_VERSION}: rebuild it "
+                                f"(python -c 'import __graft_entry__ as g; g.build()')")
+        _OPTIM_CHECKED = True
+    return lib
+
+
 def dropout_bits_rows(rows, dim, seed, stream_id, p, device="cuda"):
     """Packed keep bits uint32 (stored as int32) [rows, dim / 32] of a row-wise dropout site (ccr_dropout_bits_rows): bit i of word w <->
     column 32 w + i, 1 = keep; a pure function of (seed, stream_id, p, row, column) -- dropout_ref.rows_bits gives the same words."""

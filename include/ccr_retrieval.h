@@ -621,6 +621,35 @@ int ccr_bm25_search(const ccr_bm25_index *index, const int64_t *q_ptr_host, cons
                     const double *q_idf_host, int n_q, int k, float *out_scores, int64_t *out_ids, void *workspace,
                     size_t ws_bytes, void *stream);
 
+/*
+ * One AdamW step over a list of fp32 parameter tensors in a single pass, which also keeps 16-bit copies of the new values current
+ * (the weight set FusedBertEncoder's layer kernels read: no forward casts a weight again).
+ * Replaces: torch.optim.AdamW of configure_optimizers (src/ccrec/models/bert_mt.py:115-146).
+ *   segments  HOST array, one entry per tensor: param / grad / exp_avg / exp_avg_sq fp32 [n] (DEVICE, contiguous), shadow = NULL or a
+ *             16-bit buffer [n] (DEVICE; may be a row block of a larger tensor) of type shadow_dtype (0 none, 1 bf16, 2 fp16).
+ *             decay = 1 - lr * wd, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t): formed in double by the caller from the
+ *             tensor's own 1-based step count t and rounded once to fp32.
+ *   per element, every operation fp32, round to nearest, not contracted, divide and square root correctly rounded:
+ *     p1 = p * decay;  m' = m + w1 * (g - m);  v' = v * beta2 + (w2 * g) * g;  d = sqrt(v') / bc2_sqrt + eps;
+ *     p' = p1 - step_size * (m' / d);  shadow = p' rounded to nearest even      (w1 = one_minus_beta1, w2 = one_minus_beta2)
+ *   16-byte accesses where all four fp32 pointers of a segment sit on 16-byte boundaries (and the shadow on an 8-byte one), 4-byte
+ *   accesses otherwise and on the last n % 4 elements.  The list is walked on the host and travels in the kernel arguments, 48 segments
+ *   per launch: no device table, no copy, no allocation, no host wait.  n_segments == 0 and segments with n == 0 ask for nothing;
+ *   n < 0, a NULL pointer of a non-empty segment or an unknown shadow_dtype: CCR_ERR_INVALID before anything is launched.
+ */
+typedef struct ccr_adamw_segment {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    void *shadow;
+    int64_t n;
+    float decay, step_size, bc2_sqrt;
+    int32_t shadow_dtype;
+} ccr_adamw_segment;
+int ccr_adamw_step(const ccr_adamw_segment *segments, int n_segments, float one_minus_beta1, float beta2, float one_minus_beta2,
+                   float eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
