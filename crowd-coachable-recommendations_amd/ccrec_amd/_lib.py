@@ -29,6 +29,7 @@ EXPORTS = [
     "ccr_dropout_bits_rows", "ccr_dropout_bits_attention", "ccr_dropout_apply", "ccr_attention_fwd_train_drop_half", "ccr_attention_bwd_drop_half",
     "ccr_add_layernorm_drop_half", "ccr_add_layernorm_bwd_drop_half", "ccr_search_last_main_split",
     "ccr_search_last_threshold_phases", "ccr_adamw_step",
+    "ccr_embed_layernorm_train_half", "ccr_embed_layernorm_bwd_half", "ccr_embedding_grad", "ccr_meanpool_bwd_packed",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
@@ -38,6 +39,7 @@ ENCODER_DROPOUT_VERSION = 104   # ... and the keep-bit generators and the layer 
 QSPLIT_VERSION = 105   # ... and the main pass's unequal query groups with their getter (ccr_search_last_main_split)
 THR_PHASES_VERSION = 106   # ... and the threshold kernel's 64-phase form with its getter (ccr_search_last_threshold_phases)
 OPTIM_VERSION = 107   # ... and the multi-tensor AdamW step that keeps the encoder's 16-bit weights current (ccr_adamw_step)
+ENCODER_PACKED_TRAIN_VERSION = 108   # ... and the embedding block's and the packed pooling's backward (ccr_embed_layernorm_bwd_half and its kin)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -175,6 +177,10 @@ def load():
     lib.ccr_add_layernorm_drop_half.argtypes = [vp, vp, f32, vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]
     lib.ccr_add_layernorm_bwd_drop_half.argtypes = [vp, vp, f32, vp, vp, f32, vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, vp]
     lib.ccr_adamw_step.argtypes = [vp, i32, f32, f32, f32, f32, vp]
+    lib.ccr_embed_layernorm_train_half.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, f32, vp, f32, vp, vp, i64, i32, i32, vp]
+    lib.ccr_embed_layernorm_bwd_half.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, f32, vp, f32, vp, vp, vp, vp, i64, i32, vp, sz, vp]
+    lib.ccr_embedding_grad.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp]
+    lib.ccr_meanpool_bwd_packed.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.ccr_meanpool_pack_bf16_packed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.ccr_shard_message_bytes.argtypes = [i32, i32]
     lib.ccr_shard_message_bytes.restype = sz

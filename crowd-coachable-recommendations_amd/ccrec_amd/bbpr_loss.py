@@ -66,22 +66,40 @@ class MultipleNrlStep:
     batch [B,3] = (i, j, w) -> scalar loss with autograd through `forward`.
 
     forward: item pointer tensor -> embeddings [n, dim] (the item tower on self.all_inputs[ptr] in the reference);
-    i_to_ptr / j_to_ptr: user / item index -> item pointer; user_to_negs: round-robin hard-negative lists (mutated)."""
+    i_to_ptr / j_to_ptr: user / item index -> item pointer; user_to_negs: round-robin hard-negative lists (mutated).
 
-    def __init__(self, forward, i_to_ptr, j_to_ptr, user_to_negs, n_negatives=1, use_weights=False):
+    one_pass (default False): the reference calls the tower three times (bbpr.py:195-197: queries, positives, negatives), and so does
+    this step.  With one_pass=True it calls `forward` ONCE on cat(i_to_ptr[i], j_to_ptr[j], j_to_ptr[nj]) and splits the rows into the
+    three blocks: one encoder forward and one backward per step instead of three.  Every operation of the tower is row-wise or
+    per-sequence, so without dropout the two differ only by what the projection GEMMs do at another row count (a pure table lookup gives
+    the same bits).  Under live dropout on the kernels' training path the one-pass step draws ONE seed where the three-pass step draws
+    three; keep bits are a function of (seed, stream, row), so the rows of the one call still get independent masks."""
+
+    def __init__(self, forward, i_to_ptr, j_to_ptr, user_to_negs, n_negatives=1, use_weights=False, one_pass=False):
         self.forward, self.i_to_ptr, self.j_to_ptr, self.user_to_negs = forward, i_to_ptr, j_to_ptr, user_to_negs
-        self.n_negatives, self.use_weights = int(n_negatives), bool(use_weights)
+        self.n_negatives, self.use_weights, self.one_pass = int(n_negatives), bool(use_weights), bool(one_pass)
         if self.n_negatives < 1:
             raise ValueError("n_negatives must be at least 1")
+
+    def _encode_one_pass(self, i, j, nj):
+        ptr_i, ptr_j = torch.as_tensor(self.i_to_ptr[i.ravel()]), torch.as_tensor(self.j_to_ptr[j.ravel()])
+        ptr_n = torch.as_tensor(self.j_to_ptr[nj])
+        emb = self.forward(torch.cat([ptr_i.ravel(), ptr_j.ravel(), ptr_n.ravel()]))
+        n_i, n_j = ptr_i.numel(), ptr_j.numel()
+        return emb[:n_i], emb[n_i:n_i + n_j], emb[n_i + n_j:]
 
     def __call__(self, batch, batch_idx=0):
         i, j, w = batch.T
         i, j = i.to(int), j.to(int)
         with torch.no_grad():
             nj = pick_round_robin_negatives(self.user_to_negs, i, self.n_negatives)
-        qid_emb = self.forward(self.i_to_ptr[i.ravel()]).reshape([*i.shape, -1])
-        pos_emb = self.forward(self.j_to_ptr[j.ravel()]).reshape([*j.shape, -1])
-        neg_emb = self.forward(self.j_to_ptr[nj])
+        if self.one_pass:
+            qid_emb, pos_emb, neg_emb = self._encode_one_pass(i, j, nj)
+            qid_emb, pos_emb = qid_emb.reshape([*i.shape, -1]), pos_emb.reshape([*j.shape, -1])
+        else:
+            qid_emb = self.forward(self.i_to_ptr[i.ravel()]).reshape([*i.shape, -1])
+            pos_emb = self.forward(self.j_to_ptr[j.ravel()]).reshape([*j.shape, -1])
+            neg_emb = self.forward(self.j_to_ptr[nj])
         neg_emb = neg_emb.reshape([self.n_negatives * j.shape[0], *j.shape[1:], -1])   # m blocks of B: block k = every user's k-th negative
         return multiple_nrl_loss(qid_emb, pos_emb, neg_emb, weights=w if self.use_weights else None)
 
@@ -93,8 +111,9 @@ class BertMTStep(MultipleNrlStep):
     weighted alpha / ft_cycles; the corpus-tuning (VAE) term is identically zero for contriever models there
     ((1 - alpha) / ct_cycles * 0).  batch = (ijw, inputs) as the reference's CombinedLoader hands it over."""
 
-    def __init__(self, forward, i_to_ptr, j_to_ptr, user_to_negs, alpha=1.0, ct_cycles=1, ft_cycles=1, n_negatives=1, use_weights=False):
-        super().__init__(forward, i_to_ptr, j_to_ptr, user_to_negs, n_negatives=n_negatives, use_weights=use_weights)
+    def __init__(self, forward, i_to_ptr, j_to_ptr, user_to_negs, alpha=1.0, ct_cycles=1, ft_cycles=1, n_negatives=1, use_weights=False,
+                 one_pass=False):
+        super().__init__(forward, i_to_ptr, j_to_ptr, user_to_negs, n_negatives=n_negatives, use_weights=use_weights, one_pass=one_pass)
         self.alpha, self.ct_cycles, self.ft_cycles = float(alpha), ct_cycles, ft_cycles
 
     def __call__(self, batch, batch_idx=0):

@@ -140,6 +140,13 @@ def train_dropout_wanted():
     return os.environ.get("CCREC_FUSED_ENCODER_TRAIN_DROPOUT", "").strip() == "1"
 
 
+def train_packed_wanted():
+    """The opt-in of the training path's embedding block and packed pooling on kernels: CCREC_FUSED_ENCODER_TRAIN_PACKED=1, read at call
+    time (default off: _embed_train is the torch sum, the tower pools a padded tensor).  Honoured only together with
+    CCREC_FUSED_ENCODER_TRAIN=1."""
+    return train_wanted() and os.environ.get("CCREC_FUSED_ENCODER_TRAIN_PACKED", "").strip() == "1"
+
+
 SITE_PROBABILITIES, SITE_ATTENTION_OUTPUT, SITE_FFN_OUTPUT = 0, 1, 2
 EMBEDDINGS_STREAM = 0
 
@@ -480,10 +487,24 @@ class FusedBertEncoder:
 
     def _embed_train(self, token_ids, positions, token_types, dtype, drop=None):
         """_embed with gradients: F.embedding + F.layer_norm on the live tables (not a hot spot: one pass over T rows); drop (a
-        _DropoutDraw): then the embeddings' dropout from its keep bits (ops.dropout_train)."""
+        _DropoutDraw): then the embeddings' dropout from its keep bits (ops.dropout_train).
+        With CCREC_FUSED_ENCODER_TRAIN_PACKED=1 (train_packed_wanted) and plain contiguous fp32 tables: ops.embed_layernorm_train, the
+        block and its dropout in one kernel with the backward on kernels (no atomics in the table gradients); the same keep bits."""
         arch = _describe(self.model)
         e = arch.embeddings
         token_ids, positions = token_ids.long(), positions.long()
+        if train_packed_wanted():
+            word, pos, ln, types = e.word_embeddings.weight, e.position_embeddings.weight, e.LayerNorm, arch.type_table
+            if types is None:
+                assert token_types is None, "this architecture has no token types"
+                if self._no_types is None or self._no_types.device != word.device:
+                    self._no_types = torch.zeros(1, self.hidden, dtype=torch.float32, device=word.device)
+                types = self._no_types
+            if all(t.dtype == torch.float32 and t.is_contiguous() for t in (word, pos, types, ln.weight, ln.bias)):
+                bits, inv_keep = (None, 1.0) if drop is None else drop.rows(getattr(e, "dropout", None), EMBEDDINGS_STREAM,
+                                                                            token_ids.numel(), self.hidden, word.device)
+                return ops.embed_layernorm_train(word, pos, types, token_ids, positions, None if token_types is None else token_types.long(),
+                                                 ln.weight, ln.bias, ln.eps, keep_bits=bits, inv_keep=inv_keep, dtype=dtype)
         x = F.embedding(token_ids, e.word_embeddings.weight).float()
         if arch.type_table is not None:
             types = torch.zeros_like(token_ids) if token_types is None else token_types.long()
@@ -598,6 +619,28 @@ class FusedBertEncoder:
             if packed:
                 h = torch.zeros(B * L, self.hidden, dtype=torch.float32, device=dev).index_copy(0, keep, h)
         return h.view(B, L, self.hidden)
+
+    def forward_train_pooled(self, input_ids, lengths, token_type_ids=None, lengths_host=None, dtype=torch.bfloat16):
+        """forward_train followed by the tower's masked mean pooling (src/ccrec/models/item_tower.py:141-146), without the padded tensor in
+        between: the packed layers, then ops.meanpool_packed on the packed last hidden state -> [B, hidden] fp32 with gradients.  The
+        pooled rows have the bits ops.meanpool gives on forward_train(packed=True)'s [B, L, hidden]; no [B, L, hidden] tensor is built
+        and the backward writes no padding.  Same arguments as forward_train; the batch always runs packed."""
+        ops.require_gpu()
+        drop = self._check_train()
+        assert input_ids.is_cuda and input_ids.dim() == 2
+        B, L = input_ids.shape
+        assert L <= 512 and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.numel() == B
+        dev = input_ids.device
+        lens_h = lengths.cpu() if lengths_host is None else torch.as_tensor(lengths_host)
+        total, longest = int(lens_h.sum()), int(lens_h.max()) if B else 0
+        with torch.autocast("cuda", enabled=False):
+            keep = (torch.arange(L, device=dev)[None, :] < lengths[:, None]).flatten().nonzero().squeeze(1)   # rows of the real tokens
+            assert keep.numel() == total, "lengths_host does not match lengths"
+            h, hb = self._embed_train(input_ids.flatten()[keep], keep % L, None if token_type_ids is None else token_type_ids.flatten()[keep], dtype,
+                                      drop)
+            seq_start = (torch.cumsum(lengths, 0, dtype=torch.int32) - lengths).contiguous()
+            h = self._layers_forward_train(h, hb, seq_start, lengths, max(longest, 1), 0, None, drop)
+            return ops.meanpool_packed(h, seq_start, lengths.contiguous(), covers_all=True)
 
     @torch.no_grad()
     def forward_packed(self, token_ids, positions, seq_start, lengths, max_len, token_type_ids=None, cls_only=False, dtype=torch.bfloat16):

@@ -121,10 +121,9 @@ class NaiveItemTower(ItemTowerBase):
         enc.refresh(dtype)      # the weight copies follow the module's parameters (fine-tuning between two ranking steps)
         return enc.forward(inputs["input_ids"], lengths, inputs.get("token_type_ids"), cls_only=cls_only, dtype=dtype)
 
-    def _train_on_kernels(self, inputs, cls_only=False):
-        """Training forward (gradients on; bbpr.py:195-197, bert_mt.py:105-113 call the tower three times per step) on the layer kernels
-        and their backward -- only when CCREC_FUSED_ENCODER_TRAIN=1 asks for it, the caller's autocast type is fp16 or bf16, the encoder
-        is covered and has no active dropout, and the batch is plain right-padded token ids.  None = run the module."""
+    def _train_gate(self, inputs):
+        """-> (encoder, lengths, dtype) when a training forward of this batch may run on the layer kernels, else None (_train_on_kernels
+        says when)."""
         from . import fused_bert
         if not fused_bert.train_wanted():
             return None
@@ -141,7 +140,31 @@ class NaiveItemTower(ItemTowerBase):
         lengths = fused_bert.prefix_lengths(inputs["attention_mask"])
         if lengths is None:
             return None
+        return enc, lengths, dtype
+
+    def _train_on_kernels(self, inputs, cls_only=False):
+        """Training forward (gradients on; bbpr.py:195-197, bert_mt.py:105-113 call the tower three times per step) on the layer kernels
+        and their backward -- only when CCREC_FUSED_ENCODER_TRAIN=1 asks for it, the caller's autocast type is fp16 or bf16, the encoder
+        is covered and has no active dropout, and the batch is plain right-padded token ids.  None = run the module."""
+        gate = self._train_gate(inputs)
+        if gate is None:
+            return None
+        enc, lengths, dtype = gate
         return enc.forward_train(inputs["input_ids"], lengths, inputs.get("token_type_ids"), cls_only=cls_only, dtype=dtype)
+
+    def _train_pooled_on_kernels(self, inputs):
+        """The mean_pooling output step of a training forward in one packed pass (CCREC_FUSED_ENCODER_TRAIN_PACKED=1 on top of
+        CCREC_FUSED_ENCODER_TRAIN=1): the packed layers, then the pooling of the packed rows -- no [B, L, hidden] tensor in between
+        (item_tower.py:141-146).  None = whatever _train_on_kernels declines, or the variable is unset: the caller encodes and pools as ever."""
+        from . import fused_bert
+        if not torch.is_grad_enabled() or not fused_bert.train_packed_wanted():
+            return None
+        on_model = {name: value.to(self.cls_model.device) for name, value in inputs.items()}
+        gate = self._train_gate(on_model)
+        if gate is None:
+            return None
+        enc, lengths, dtype = gate
+        return enc.forward_train_pooled(on_model["input_ids"], lengths, on_model.get("token_type_ids"), dtype=dtype)
 
     def forward(self, cls=None, text=None, input_step="inputs", output_step="embedding", **inputs):
         if input_step == "text":
@@ -149,6 +172,11 @@ class NaiveItemTower(ItemTowerBase):
         hidden = None
         if input_step == "inputs":
             step = os.environ.get("CCREC_EMBEDDING_TYPE", "") if output_step == "embedding" else output_step
+            pooled = self._train_pooled_on_kernels(inputs) if step == "mean_pooling" else None
+            if pooled is not None:
+                if output_step == "embedding":
+                    warnings.warn(f"{self.__class__} inferring output_step from CCREC_EMBEDDING_TYPE as {step}")
+                return pooled
             hidden = self._encode(inputs, cls_only=step in _CLS_STEPS or step == "mean_layer_norm")
             cls = hidden[:, 0]
         else:

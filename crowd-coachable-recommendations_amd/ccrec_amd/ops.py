@@ -669,6 +669,191 @@ def dropout_train(x, bits, inv_keep, dtype=torch.bfloat16):
     return _DropoutTrain.apply(x.contiguous(), bits, inv_keep, dtype)
 
 
+# ---- the fine-tune step in one packed pass (library version 108): the embedding block with a backward (csrc/ccr_encoder.hip,
+# ccr_encoder_bwd.hip, ccr_embed_train.hip) and mean pooling of a packed token array with a backward (csrc/ccr_pack.hip).  The reference
+# encodes three times per step (src/ccrec/models/bbpr.py:195-197) and pools under the mask (item_tower.py:141-146) ------------------------
+_ENCODER_PACKED_TRAIN_CHECKED = False
+
+
+def _require_encoder_packed_train():
+    """require_gpu() + once: the loaded library has the embedding block's and the packed pooling's backward (ccr_version() >= 108)."""
+    global _ENCODER_PACKED_TRAIN_CHECKED
+    lib = require_gpu()
+    if not _ENCODER_PACKED_TRAIN_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.ENCODER_PACKED_TRAIN_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, the packed training ops need {_lib.ENCODER_PACKED_TRAIN_VERSION}: rebuild it "
+                                f"(python -c 'import __graft_entry__ as g; g.build()')")
+        _ENCODER_PACKED_TRAIN_CHECKED = True
+    return lib
+
+
+def _check_embed_args(word_table, position_table, type_table, token_ids, positions, token_types, gamma):
+    dim = word_table.shape[1]
+    for t in (word_table, position_table, type_table):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == dim and t.is_contiguous()
+    assert gamma.is_cuda and gamma.dtype == torch.float32 and tuple(gamma.shape) == (dim,) and gamma.is_contiguous()
+    T = token_ids.numel()
+    for t in (token_ids, positions) + ((token_types,) if token_types is not None else ()):
+        assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.numel() == T and t.is_contiguous()
+    return T, dim
+
+
+def embed_layernorm_drop(word_table, position_table, type_table, token_ids, positions, token_types, gamma, beta, eps, keep_bits=None,
+                         inv_keep=1.0, dtype=torch.bfloat16):
+    """embed_layernorm() followed by the block's dropout from keep bits [T, dim / 32] (ccr_embed_layernorm_train_half): one kernel,
+    the bits of dropout_apply(embed_layernorm(...)).  keep_bits None: no dropout.  -> (fp32 [T, dim], its copy in `dtype`)."""
+    lib = _require_encoder_packed_train()
+    code = _half_code(dtype)
+    T, dim = _check_embed_args(word_table, position_table, type_table, token_ids, positions, token_types, gamma)
+    assert beta.is_cuda and beta.dtype == torch.float32 and tuple(beta.shape) == (dim,) and beta.is_contiguous()
+    if keep_bits is not None:
+        _check_bits(keep_bits, (T, dim // 32))
+    f32 = torch.empty(T, dim, dtype=torch.float32, device=word_table.device)
+    b16 = torch.empty(T, dim, dtype=dtype, device=word_table.device)
+    with _on(word_table):
+        _lib.check(lib.ccr_embed_layernorm_train_half(_ptr(word_table), word_table.shape[0], _ptr(position_table), position_table.shape[0],
+                                                      _ptr(type_table), type_table.shape[0], _ptr(token_ids), _ptr(positions),
+                                                      _ptr(token_types), _ptr(gamma), _ptr(beta), float(eps), _ptr(keep_bits), float(inv_keep),
+                                                      _ptr(f32), _ptr(b16), T, dim, code, _stream(word_table)), "ccr_embed_layernorm_train_half")
+    return f32, b16
+
+
+def embed_layernorm_bwd(word_table, position_table, type_table, token_ids, positions, token_types, gamma, eps, d_y, keep_bits=None,
+                        inv_keep=1.0, want_x=True, want_gamma=True, want_beta=True):
+    """The backward of embed_layernorm_drop (ccr_embed_layernorm_bwd_half): d_y [T, dim] fp32 = the summed gradient of both outputs ->
+    (d_x fp32 [T, dim] = the gradient of every gathered table row, d_gamma, d_beta [dim] fp32); None where not wanted."""
+    lib = _require_encoder_packed_train()
+    T, dim = _check_embed_args(word_table, position_table, type_table, token_ids, positions, token_types, gamma)
+    assert d_y.is_cuda and d_y.dtype == torch.float32 and tuple(d_y.shape) == (T, dim) and d_y.is_contiguous()
+    if keep_bits is not None:
+        _check_bits(keep_bits, (T, dim // 32))
+    dev = word_table.device
+    d_x = torch.empty(T, dim, dtype=torch.float32, device=dev) if want_x else None
+    d_gamma = torch.empty(dim, dtype=torch.float32, device=dev) if want_gamma else None
+    d_beta = torch.empty(dim, dtype=torch.float32, device=dev) if want_beta else None
+    need = min((T + 3) // 4, 512) * 2 * dim * 4 if (want_gamma or want_beta) else 0      # per-workgroup column sums (include/ccr_retrieval.h)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with _on(word_table):
+        _lib.check(lib.ccr_embed_layernorm_bwd_half(_ptr(word_table), word_table.shape[0], _ptr(position_table), position_table.shape[0],
+                                                    _ptr(type_table), type_table.shape[0], _ptr(token_ids), _ptr(positions), _ptr(token_types),
+                                                    _ptr(gamma), float(eps), _ptr(keep_bits), float(inv_keep), _ptr(d_y), _ptr(d_x),
+                                                    _ptr(d_gamma), _ptr(d_beta), T, dim, _ptr(ws), need, _stream(word_table)),
+                   "ccr_embed_layernorm_bwd_half")
+    return d_x, d_gamma, d_beta
+
+
+def embedding_order(idx, n_rows):
+    """The permutation ccr_embedding_grad walks: token rows sorted by (clamped id, row) ascending.  One torch.sort of the unique keys
+    clamp(idx) * T + row on the device: no host wait, and the result does not depend on the sort being stable."""
+    T = idx.numel()
+    keys = idx.clamp(0, int(n_rows) - 1) * T + torch.arange(T, dtype=torch.int64, device=idx.device)
+    return torch.sort(keys)[1]
+
+
+def embedding_grad(idx, d_x, n_rows, order=None, out=None):
+    """The gradient [n_rows, dim] fp32 of an embedding table from d_x [T, dim] fp32, the gradient of its gathered rows table[idx]
+    (ccr_embedding_grad): no atomics, every row written (+0 where an id does not occur), the summation order of embed_grad_ref."""
+    lib = _require_encoder_packed_train()
+    assert idx.is_cuda and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()
+    T = idx.numel()
+    assert d_x.is_cuda and d_x.dtype == torch.float32 and d_x.dim() == 2 and d_x.shape[0] == T and d_x.is_contiguous()
+    dim = d_x.shape[1]
+    if order is None:
+        order = embedding_order(idx, n_rows)
+    assert order.is_cuda and order.dtype == torch.int64 and tuple(order.shape) == (T,) and order.is_contiguous()
+    if out is None:
+        out = torch.empty(int(n_rows), dim, dtype=torch.float32, device=d_x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (int(n_rows), dim) and out.is_contiguous()
+    with _on(d_x):
+        _lib.check(lib.ccr_embedding_grad(_ptr(idx), _ptr(order), _ptr(d_x), T, dim, _ptr(out), int(n_rows), _stream(d_x)), "ccr_embedding_grad")
+    return out
+
+
+class _EmbedLayerNormTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, word, pos, types, token_ids, positions, token_types, gamma, beta, eps, bits, inv_keep, dtype):
+        f32, b16 = embed_layernorm_drop(word, pos, types, token_ids, positions, token_types, gamma, beta, eps, bits, inv_keep, dtype)
+        ctx.save_for_backward(word, pos, types, token_ids, positions, token_types, gamma, bits)
+        ctx.eps, ctx.inv_keep = float(eps), float(inv_keep)
+        return f32, b16
+
+    @staticmethod
+    def backward(ctx, d_f32, d_b16):
+        word, pos, types, token_ids, positions, token_types, gamma, bits = ctx.saved_tensors
+        # the two outputs are one value in two precisions: their gradients add up (fp32) before the kernel runs
+        if d_f32 is None:
+            d_y = d_b16.float()
+        elif d_b16 is None:
+            d_y = d_f32.float()
+        else:
+            d_y = d_f32.float() + d_b16
+        need = ctx.needs_input_grad
+        d_x, d_gamma, d_beta = embed_layernorm_bwd(word, pos, types, token_ids, positions, token_types, gamma, ctx.eps, d_y.contiguous(), bits,
+                                                   ctx.inv_keep, want_x=any(need[:3]), want_gamma=need[6], want_beta=need[7])
+        d_word = embedding_grad(token_ids, d_x, word.shape[0]) if need[0] else None
+        d_pos = embedding_grad(positions, d_x, pos.shape[0]) if need[1] else None
+        d_types = None
+        if need[2] and token_types is not None:
+            d_types = embedding_grad(token_types, d_x, types.shape[0])
+        elif need[2]:      # every token is type 0: one run in row order, nothing to sort
+            rows = torch.arange(token_ids.numel(), dtype=torch.int64, device=token_ids.device)
+            d_types = embedding_grad(torch.zeros_like(token_ids), d_x, types.shape[0], order=rows)
+        return d_word, d_pos, d_types, None, None, None, d_gamma, d_beta, None, None, None, None
+
+
+def embed_layernorm_train(word_table, position_table, type_table, token_ids, positions, token_types, gamma, beta, eps, keep_bits=None,
+                          inv_keep=1.0, dtype=torch.bfloat16):
+    """The embedding block with a backward: dropout(LayerNorm((word[ids] + type[types]) + position[positions])) -> (fp32 [T, dim], its copy
+    in `dtype`), both differentiable.  Forward = embed_layernorm_drop (embed_layernorm's bits without keep_bits); backward =
+    embed_layernorm_bwd, then one embedding_grad per table that needs a gradient (needs_input_grad is honoured: a frozen table costs
+    nothing).  Tables, gamma, beta: contiguous fp32; index vectors int64 [T], token_types may be None = type 0."""
+    return _EmbedLayerNormTrain.apply(word_table, position_table, type_table, token_ids.contiguous(), positions.contiguous(),
+                                      None if token_types is None else token_types.contiguous(), gamma, beta, eps, keep_bits, inv_keep, dtype)
+
+
+def meanpool_bwd_packed(grad, seq_start, seq_len, out):
+    """Rows seq_start[s] .. + seq_len[s] - 1 of out [T, dim] receive grad[s] / len (ccr_meanpool_bwd_packed); every other row of out
+    keeps its bytes.  Returns out."""
+    lib = _require_encoder_packed_train()
+    assert grad.is_cuda and grad.dtype == torch.float32 and grad.dim() == 2 and grad.is_contiguous()
+    n_seq, dim = grad.shape
+    for t in (seq_start, seq_len):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n_seq
+    assert out.is_cuda and out.dtype in _DTYPES and out.dim() == 2 and out.shape[1] == dim and out.is_contiguous()
+    with _on(grad):
+        _lib.check(lib.ccr_meanpool_bwd_packed(_ptr(grad), _ptr(seq_start), _ptr(seq_len), _ptr(out), _DTYPES[out.dtype], n_seq, dim,
+                                               _stream(grad)), "ccr_meanpool_bwd_packed")
+    return out
+
+
+class _MeanPoolPacked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hidden, seq_start, seq_len, covers_all):
+        pooled = torch.empty(seq_len.numel(), hidden.shape[1], dtype=torch.float32, device=hidden.device)
+        meanpool_pack_packed(hidden.detach(), seq_start, seq_len, out_f32=pooled)
+        ctx.save_for_backward(seq_start, seq_len)
+        ctx.shape, ctx.dtype, ctx.covers_all = tuple(hidden.shape), hidden.dtype, bool(covers_all)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, grad):
+        seq_start, seq_len = ctx.saved_tensors
+        make = torch.empty if ctx.covers_all else torch.zeros      # rows of no sequence carry no gradient
+        dh = make(ctx.shape, dtype=ctx.dtype, device=grad.device)
+        meanpool_bwd_packed(grad.detach().to(torch.float32).contiguous(), seq_start, seq_len, dh)
+        return dh, None, None, None
+
+
+def meanpool_packed(hidden, seq_start, seq_len, covers_all=False):
+    """Mean pooling of a packed token array that autograd can differentiate: hidden [T, dim], sequence s = rows seq_start[s] .. +
+    seq_len[s] - 1 (int32 cuda) -> fp32 [n_seq, dim], with the bits of meanpool() on the zero-padded form of the same rows, forward and
+    backward; no [B, L, dim] tensor exists.  covers_all: the caller vouches that every row of hidden belongs to a sequence (the gradient
+    buffer then needs no zero fill)."""
+    _require_encoder_packed_train()
+    return _MeanPoolPacked.apply(hidden.contiguous(), seq_start, seq_len, covers_all)
+
+
 class CorpusIndex:
     """A resident bf16 corpus shard + its search state (ccr_index).  Build once per AL step, query many.
 

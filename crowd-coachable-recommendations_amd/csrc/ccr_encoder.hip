@@ -376,14 +376,17 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const uint16_t *__re
 
 // The embedding block of the encoder (transformers BertEmbeddings.forward): (word[id] + type[t]) + position[p] in that order, fp32,
 // then LayerNorm -> the fp32 residual stream and its bf16 copy.  One wave per token; ids outside a table are clamped (memory safety).
-template <int C, int DT>
+// DROP = true (ccr_embed_layernorm_train_half with bits): the block's dropout on the way out, y * (keep ? inv_keep : 0) as
+// dropout_apply_kernel forms it, from the lane's nibble of its row of bits [rows][DIM / 32].
+template <int C, int DT, bool DROP = false>
 __global__ __launch_bounds__(256) void embed_layernorm_kernel(const float *__restrict__ word, int64_t vocab,
                                                              const float *__restrict__ pos_tab, int64_t n_pos,
                                                              const float *__restrict__ type_tab, int64_t n_types,
                                                              const int64_t *__restrict__ ids, const int64_t *__restrict__ pos,
                                                              const int64_t *__restrict__ types, const float *__restrict__ gamma,
                                                              const float *__restrict__ beta, float eps, float *__restrict__ out_f32,
-                                                             uint16_t *__restrict__ out_bf16, int64_t rows) {
+                                                             uint16_t *__restrict__ out_bf16, int64_t rows,
+                                                             typename KeepArg<DROP>::type keep = {}) {
     constexpr int DIM = 256 * C;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -430,6 +433,11 @@ __global__ __launch_bounds__(256) void embed_layernorm_kernel(const float *__res
         y.y = fmaf((v[c][1] - mean) * rstd, gm.y, bt.y);
         y.z = fmaf((v[c][2] - mean) * rstd, gm.z, bt.z);
         y.w = fmaf((v[c][3] - mean) * rstd, gm.w, bt.w);
+        if constexpr (DROP) {
+            float mk[4];
+            keep_nibble(keep, row * (DIM / 32), 64 * c + lane, mk);
+            y.x *= mk[0], y.y *= mk[1], y.z *= mk[2], y.w *= mk[3];
+        }
         if (out_f32) *reinterpret_cast<float4 *>(out_f32 + row * DIM + col) = y;
         if (out_bf16) *reinterpret_cast<uint2 *>(out_bf16 + row * DIM + col) = round4<typename Half16<DT>::elem>(y.x, y.y, y.z, y.w);
     }
@@ -480,16 +488,16 @@ static int add_layernorm_any(const uint16_t *x, const float *res, const float *g
     }
 }
 
-template <int DT>
+template <int DT, bool DROP = false>
 static int embed_layernorm_any(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
                                const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
                                const int64_t *token_types, const float *gamma, const float *beta, float eps, float *out_f32,
-                               uint16_t *out_half, int64_t rows, int dim, hipStream_t s) {
+                               uint16_t *out_half, int64_t rows, int dim, hipStream_t s, typename KeepArg<DROP>::type keep = {}) {
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
 #define CCR_EMBED_CASE(C)                                                                                                              \
     case C:                                                                                                                            \
-        hipLaunchKernelGGL((embed_layernorm_kernel<C, DT>), grid, block, 0, s, word_table, vocab, position_table, n_positions,         \
-                           type_table, n_types, token_ids, positions, token_types, gamma, beta, eps, out_f32, out_half, rows);         \
+        hipLaunchKernelGGL((embed_layernorm_kernel<C, DT, DROP>), grid, block, 0, s, word_table, vocab, position_table, n_positions,   \
+                           type_table, n_types, token_ids, positions, token_types, gamma, beta, eps, out_f32, out_half, rows, keep);   \
         break;
     switch (dim / 256) {
         CCR_EMBED_CASE(1)
@@ -500,8 +508,8 @@ static int embed_layernorm_any(const float *word_table, int64_t vocab, const flo
         CCR_EMBED_CASE(6)
         CCR_EMBED_CASE(7)
         default:
-            hipLaunchKernelGGL((embed_layernorm_kernel<8, DT>), grid, block, 0, s, word_table, vocab, position_table, n_positions,
-                               type_table, n_types, token_ids, positions, token_types, gamma, beta, eps, out_f32, out_half, rows);
+            hipLaunchKernelGGL((embed_layernorm_kernel<8, DT, DROP>), grid, block, 0, s, word_table, vocab, position_table, n_positions,
+                               type_table, n_types, token_ids, positions, token_types, gamma, beta, eps, out_f32, out_half, rows, keep);
     }
 #undef CCR_EMBED_CASE
     CCR_LAUNCH_CHECK();
@@ -660,6 +668,34 @@ extern "C" int ccr_embed_layernorm_half(const float *word_table, int64_t vocab, 
                                                     positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s)
                : embed_layernorm_any<CCR_DTYPE_BF16>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
                                                      positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s);
+}
+
+extern "C" int ccr_embed_layernorm_train_half(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
+                                              const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
+                                              const int64_t *token_types, const float *gamma, const float *beta, float eps,
+                                              const uint32_t *bits, float inv_keep, float *out_f32, uint16_t *out_half, int64_t rows, int dim,
+                                              int half_dtype, void *stream) {
+    CCR_REQUIRE(word_table && position_table && type_table && token_ids && positions && gamma && beta && (out_f32 || out_half),
+                "ccr_embed_layernorm_train_half: null pointer");
+    CCR_REQUIRE_HALF(half_dtype, "ccr_embed_layernorm_train_half");
+    CCR_REQUIRE(vocab > 0 && n_positions > 0 && n_types > 0, "ccr_embed_layernorm_train_half: empty table");
+    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
+                "ccr_embed_layernorm_train_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
+    CCR_REQUIRE(!bits || (inv_keep >= 1.f && inv_keep <= 65536.f), "ccr_embed_layernorm_train_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
+    if (rows == 0) return CCR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (!bits)   // no dropout: the inference kernel, no extra loads
+        return half_dtype == CCR_DTYPE_F16
+                   ? embed_layernorm_any<CCR_DTYPE_F16>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
+                                                        positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s)
+                   : embed_layernorm_any<CCR_DTYPE_BF16>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
+                                                         positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s);
+    const KeepBits keep = {bits, inv_keep, 0};
+    return half_dtype == CCR_DTYPE_F16
+               ? embed_layernorm_any<CCR_DTYPE_F16, true>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
+                                                          positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s, keep)
+               : embed_layernorm_any<CCR_DTYPE_BF16, true>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
+                                                           positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s, keep);
 }
 
 extern "C" int ccr_embed_layernorm(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,

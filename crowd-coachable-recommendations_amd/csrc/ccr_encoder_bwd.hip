@@ -448,6 +448,131 @@ __global__ __launch_bounds__(256) void layernorm_bwd_reduce_kernel(const float *
     }
 }
 
+// ---- Embedding block backward (ccr_embed_layernorm_bwd_half): add_layernorm_bwd_kernel's row arithmetic on v = (word[id] + type[t]) +
+// position[p], gathered and summed as embed_layernorm_kernel does, so mean and rstd are the forward's.  DROP = true: the block's dropout
+// sits AFTER the LayerNorm, so the gradient that enters it is d_v = d_y * (keep ? inv_keep : 0); d gamma and d beta sum d_v.  d_x stays
+// fp32 (it feeds ccr_embedding_grad).  The row body is written out here, not shared with add_layernorm_bwd_kernel: that kernel's operand
+// loads, dropout site (before the sum) and 16-bit output differ, and its instantiations keep their code.
+template <int C, bool DROP = false>
+__global__ __launch_bounds__(256) void embed_layernorm_bwd_kernel(const float *__restrict__ word, int64_t vocab,
+                                                                 const float *__restrict__ pos_tab, int64_t n_pos,
+                                                                 const float *__restrict__ type_tab, int64_t n_types,
+                                                                 const int64_t *__restrict__ ids, const int64_t *__restrict__ pos,
+                                                                 const int64_t *__restrict__ types, const float *__restrict__ gamma, float eps,
+                                                                 const float *__restrict__ dy, float *__restrict__ d_x,
+                                                                 float *__restrict__ partial, int64_t rows,
+                                                                 typename KeepArg<DROP>::type keep = {}) {
+    constexpr int DIM = 256 * C;
+    __shared__ float red[3][DIM];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto clamp = [](int64_t v, int64_t n) { return v < 0 ? (int64_t)0 : (v >= n ? n - 1 : v); };
+    float gm[C][4], ag[C][4], ab[C][4];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float4 t = *reinterpret_cast<const float4 *>(gamma + 4 * (64 * c + lane));
+        gm[c][0] = t.x, gm[c][1] = t.y, gm[c][2] = t.z, gm[c][3] = t.w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ag[c][j] = ab[c][j] = 0.f;
+    }
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
+        const float *w = word + clamp(ids[row], vocab) * DIM;
+        const float *p = pos_tab + clamp(pos[row], n_pos) * DIM;
+        const float *t = type_tab + clamp(types ? types[row] : 0, n_types) * DIM;
+        float v[C][4], d[C][4];
+        float sum = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int col = 4 * (64 * c + lane);
+            const float4 a = *reinterpret_cast<const float4 *>(w + col);
+            const float4 b = *reinterpret_cast<const float4 *>(t + col);
+            const float4 e = *reinterpret_cast<const float4 *>(p + col);
+            const float4 g = *reinterpret_cast<const float4 *>(dy + row * DIM + col);
+            v[c][0] = (a.x + b.x) + e.x;
+            v[c][1] = (a.y + b.y) + e.y;
+            v[c][2] = (a.z + b.z) + e.z;
+            v[c][3] = (a.w + b.w) + e.w;
+            d[c][0] = g.x, d[c][1] = g.y, d[c][2] = g.z, d[c][3] = g.w;
+            if constexpr (DROP) {
+                float mk[4];
+                keep_nibble(keep, row * (DIM / 32), 64 * c + lane, mk);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) d[c][j] *= mk[j];
+            }
+            sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        const float mean = refined_mean<C>(v, sum * (1.f / DIM));
+        float sq = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float dd = v[c][j] - mean;
+                sq = fmaf(dd, dd, sq);
+            }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+        const float rstd = rsqrtf(sq * (1.f / DIM) + eps);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float xh = (v[c][j] - mean) * rstd;
+                const float gy = d[c][j] * gm[c][j];
+                v[c][j] = xh;
+                s1 += gy;
+                s2 = fmaf(gy, xh, s2);
+                ag[c][j] = fmaf(d[c][j], xh, ag[c][j]);
+                ab[c][j] += d[c][j];
+            }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            s1 += __shfl_xor(s1, o);
+            s2 += __shfl_xor(s2, o);
+        }
+        const float m1 = s1 * (1.f / DIM), m2 = s2 * (1.f / DIM);
+        if (d_x) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int col = 4 * (64 * c + lane);
+                float4 y;
+                y.x = rstd * ((d[c][0] * gm[c][0] - m1) - v[c][0] * m2);
+                y.y = rstd * ((d[c][1] * gm[c][1] - m1) - v[c][1] * m2);
+                y.z = rstd * ((d[c][2] * gm[c][2] - m1) - v[c][2] * m2);
+                y.w = rstd * ((d[c][3] * gm[c][3] - m1) - v[c][3] * m2);
+                *reinterpret_cast<float4 *>(d_x + row * DIM + col) = y;
+            }
+        }
+    }
+    if (!partial) return;   // (workgroup-uniform)
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+        if (which) __syncthreads();
+        if (wave > 0) {
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                *reinterpret_cast<float4 *>(&red[wave - 1][4 * (64 * c + lane)]) =
+                    which ? make_float4(ab[c][0], ab[c][1], ab[c][2], ab[c][3]) : make_float4(ag[c][0], ag[c][1], ag[c][2], ag[c][3]);
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int col = 4 * (64 * c + lane);
+                float4 t = which ? make_float4(ab[c][0], ab[c][1], ab[c][2], ab[c][3]) : make_float4(ag[c][0], ag[c][1], ag[c][2], ag[c][3]);
+#pragma unroll
+                for (int w = 0; w < 3; ++w) {
+                    const float4 u = *reinterpret_cast<const float4 *>(&red[w][col]);
+                    t.x += u.x, t.y += u.y, t.z += u.z, t.w += u.w;
+                }
+                *reinterpret_cast<float4 *>(partial + ((int64_t)blockIdx.x * 2 + which) * DIM + col) = t;
+            }
+        }
+    }
+}
+
 // d_x = d_y (Phi(x) + x phi(x)) of the exact GELU, from the pre-activation: fp32, rounded once, 16 bytes per lane per access.
 template <int DT>
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const uint4 *__restrict__ x, const uint4 *__restrict__ dy, uint4 *__restrict__ dx,
@@ -521,6 +646,34 @@ static int add_layernorm_bwd_any(const uint16_t *x, const float *res, const floa
         case 7: return launch_add_layernorm_bwd<7, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
         default: return launch_add_layernorm_bwd<8, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
     }
+}
+
+template <bool DROP>
+static int embed_layernorm_bwd_any(const float *word, int64_t vocab, const float *pos_tab, int64_t n_pos, const float *type_tab, int64_t n_types,
+                                   const int64_t *ids, const int64_t *pos, const int64_t *types, const float *gamma, float eps, const float *dy,
+                                   float *d_x, float *partial, int nblk, int64_t rows, int dim, hipStream_t s,
+                                   typename KeepArg<DROP>::type keep = {}) {
+    const dim3 grid((unsigned)nblk), block(256);
+#define CCR_EMBED_BWD_CASE(C)                                                                                                             \
+    case C:                                                                                                                               \
+        hipLaunchKernelGGL((embed_layernorm_bwd_kernel<C, DROP>), grid, block, 0, s, word, vocab, pos_tab, n_pos, type_tab, n_types, ids, \
+                           pos, types, gamma, eps, dy, d_x, partial, rows, keep);                                                         \
+        break;
+    switch (dim / 256) {
+        CCR_EMBED_BWD_CASE(1)
+        CCR_EMBED_BWD_CASE(2)
+        CCR_EMBED_BWD_CASE(3)
+        CCR_EMBED_BWD_CASE(4)
+        CCR_EMBED_BWD_CASE(5)
+        CCR_EMBED_BWD_CASE(6)
+        CCR_EMBED_BWD_CASE(7)
+        default:
+            hipLaunchKernelGGL((embed_layernorm_bwd_kernel<8, DROP>), grid, block, 0, s, word, vocab, pos_tab, n_pos, type_tab, n_types, ids,
+                               pos, types, gamma, eps, dy, d_x, partial, rows, keep);
+    }
+#undef CCR_EMBED_BWD_CASE
+    CCR_LAUNCH_CHECK();
+    return CCR_OK;
 }
 
 template <int DT>
@@ -666,6 +819,49 @@ extern "C" int ccr_add_layernorm_bwd_half(const uint16_t *x_half, const float *r
     const int rc = half_dtype == CCR_DTYPE_F16
                        ? add_layernorm_bwd_any<CCR_DTYPE_F16>(x_half, residual, gamma, eps, d_y, d_res, d_x, partial, (int)nblk, rows, dim, s)
                        : add_layernorm_bwd_any<CCR_DTYPE_BF16>(x_half, residual, gamma, eps, d_y, d_res, d_x, partial, (int)nblk, rows, dim, s);
+    if (rc != CCR_OK || !params) return rc;
+    hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((unsigned)(2 * dim / 64)), dim3(256), 0, s, partial, (int)nblk, dim, d_gamma, d_beta);
+    CCR_LAUNCH_CHECK();
+    return CCR_OK;
+}
+
+extern "C" int ccr_embed_layernorm_bwd_half(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
+                                            const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
+                                            const int64_t *token_types, const float *gamma, float eps, const uint32_t *bits, float inv_keep,
+                                            const float *d_y, float *d_x, float *d_gamma, float *d_beta, int64_t rows, int dim,
+                                            void *workspace, size_t workspace_bytes, void *stream) {
+    CCR_REQUIRE(word_table && position_table && type_table && token_ids && positions && gamma && d_y,
+                "ccr_embed_layernorm_bwd_half: null pointer");
+    CCR_REQUIRE(vocab > 0 && n_positions > 0 && n_types > 0, "ccr_embed_layernorm_bwd_half: empty table");
+    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
+                "ccr_embed_layernorm_bwd_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
+    CCR_REQUIRE(!bits || (inv_keep >= 1.f && inv_keep <= 65536.f), "ccr_embed_layernorm_bwd_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
+    const bool params = d_gamma || d_beta;
+    int64_t nblk = (rows + 3) / 4;
+    if (nblk > LN_BWD_MAX_BLOCKS) nblk = LN_BWD_MAX_BLOCKS;
+    const size_t need = params ? (size_t)nblk * 2 * dim * sizeof(float) : 0;
+    if (need && (!workspace || workspace_bytes < need)) {
+        set_error("ccr_embed_layernorm_bwd_half: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+        return CCR_ERR_WORKSPACE;
+    }
+    CCR_REQUIRE(!need || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ccr_embed_layernorm_bwd_half: 16-byte aligned workspace");
+    if (!d_x && !params) return CCR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (rows == 0) {   // sums over no rows
+        if (d_gamma) CCR_HIP_CHECK(hipMemsetAsync(d_gamma, 0, (size_t)dim * sizeof(float), s));
+        if (d_beta) CCR_HIP_CHECK(hipMemsetAsync(d_beta, 0, (size_t)dim * sizeof(float), s));
+        return CCR_OK;
+    }
+    float *partial = params ? static_cast<float *>(workspace) : nullptr;
+    int rc;
+    if (bits) {
+        const KeepBits keep = {bits, inv_keep, 0};
+        rc = embed_layernorm_bwd_any<true>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids, positions, token_types,
+                                           gamma, eps, d_y, d_x, partial, (int)nblk, rows, dim, s, keep);
+    } else {
+        rc = embed_layernorm_bwd_any<false>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids, positions, token_types,
+                                            gamma, eps, d_y, d_x, partial, (int)nblk, rows, dim, s);
+    }
     if (rc != CCR_OK || !params) return rc;
     hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((unsigned)(2 * dim / 64)), dim3(256), 0, s, partial, (int)nblk, dim, d_gamma, d_beta);
     CCR_LAUNCH_CHECK();

@@ -370,9 +370,56 @@ __global__ __launch_bounds__(256) void meanpool_bwd_kernel(const float *__restri
     }
 }
 
+// The same backward over a packed token array: rows seq_start[b] .. + seq_len[b] - 1 of dhidden [T][dim] receive grad[b] / (float)len --
+// meanpool_bwd_kernel's division, hence the bits of the padded form's real rows.  There is no padding to zero: rows of no sequence are
+// not touched.  blockIdx.y strides over the sequence's rows.
+template <typename T>
+__global__ __launch_bounds__(256) void meanpool_bwd_packed_kernel(const float *__restrict__ grad, const int32_t *__restrict__ seq_start,
+                                                                 const int32_t *__restrict__ seq_len, T *__restrict__ dhidden, int dim) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int L = seq_len[b];
+    if (L <= 0) return;
+    const float den = (float)L;
+    const int nchunk = dim >> 2;
+    for (int ch = tid; ch < nchunk; ch += blockDim.x) {
+        float4 g = reinterpret_cast<const float4 *>(grad + (int64_t)b * dim)[ch];
+        g.x /= den;
+        g.y /= den;
+        g.z /= den;
+        g.w /= den;
+        T *o = dhidden + (int64_t)seq_start[b] * dim + 4 * ch;
+        for (int l = blockIdx.y; l < L; l += gridDim.y) store4<T>(o + (int64_t)l * dim, g);
+    }
+}
+
 }  // namespace ccr
 
 using namespace ccr;
+
+extern "C" int ccr_meanpool_bwd_packed(const float *grad, const int32_t *seq_start, const int32_t *seq_len, void *dhidden, int hidden_dtype,
+                                       int n_seq, int dim, void *stream) {
+    CCR_REQUIRE(grad && seq_start && seq_len && dhidden, "ccr_meanpool_bwd_packed: null pointer");
+    CCR_REQUIRE(n_seq >= 0 && dim > 0 && dim % 4 == 0, "ccr_meanpool_bwd_packed: bad shape n_seq=%d dim=%d (dim %% 4 == 0)", n_seq, dim);
+    CCR_REQUIRE(hidden_dtype == CCR_DTYPE_F32 || hidden_dtype == CCR_DTYPE_F16 || hidden_dtype == CCR_DTYPE_BF16,
+                "ccr_meanpool_bwd_packed: unknown hidden_dtype %d", hidden_dtype);
+    if (n_seq == 0) return CCR_OK;
+    hipStream_t s = (hipStream_t)stream;
+    int threads = ((dim / 4 + 63) / 64) * 64;
+    if (threads > 256) threads = 256;
+    const dim3 grid(n_seq, 8);
+    switch (hidden_dtype) {
+        case CCR_DTYPE_F32:
+            hipLaunchKernelGGL(meanpool_bwd_packed_kernel<float>, grid, dim3(threads), 0, s, grad, seq_start, seq_len, (float *)dhidden, dim);
+            break;
+        case CCR_DTYPE_F16:
+            hipLaunchKernelGGL(meanpool_bwd_packed_kernel<_Float16>, grid, dim3(threads), 0, s, grad, seq_start, seq_len, (_Float16 *)dhidden, dim);
+            break;
+        default:
+            hipLaunchKernelGGL(meanpool_bwd_packed_kernel<__bf16>, grid, dim3(threads), 0, s, grad, seq_start, seq_len, (__bf16 *)dhidden, dim);
+    }
+    CCR_LAUNCH_CHECK();
+    return CCR_OK;
+}
 
 extern "C" int ccr_meanpool_bwd(const float *grad, const int64_t *mask, void *dhidden, int hidden_dtype, int B, int L, int dim,
                                 void *stream) {

@@ -650,6 +650,53 @@ typedef struct ccr_adamw_segment {
 int ccr_adamw_step(const ccr_adamw_segment *segments, int n_segments, float one_minus_beta1, float beta2, float one_minus_beta2,
                    float eps, void *stream);
 
+/*
+ * The fine-tune step in one packed pass (library version 108): the embedding block with a backward, and mean pooling over a packed token
+ * array with a backward.  The reference encodes queries, positives and negatives in three tower calls per step
+ * (src/ccrec/models/bbpr.py:195-197) and pools the last hidden state under its mask (src/ccrec/models/item_tower.py:141-146); with these
+ * four entry points no piece of that step runs outside the library's kernels, and every gradient is bit-identical from run to run (no
+ * atomics on floating-point data).
+ * ccr_embed_layernorm_train_half (bbpr.py:195-197: BertEmbeddings.forward in train()): ccr_embed_layernorm_half's arguments and
+ *   arithmetic -- (word + type) + position, the two-step mean, one fma with gamma and beta -- followed by the block's dropout,
+ *   y * (keep ? inv_keep : 0) exactly as ccr_dropout_apply forms it, from bits [rows][dim / 32] (ccr_dropout_bits_rows' layout).
+ *   bits == NULL: no dropout (inv_keep is ignored) and the outputs are ccr_embed_layernorm_half's; with all-ones bits and inv_keep = 1
+ *   likewise.  Either output may be NULL.  Ids outside a table are clamped.
+ * ccr_embed_layernorm_bwd_half (bbpr.py:195-197: loss.backward() through BertEmbeddings): from the forward's tables, index vectors,
+ *   gamma, eps, bits and inv_keep, and d_y [rows][dim] fp32 = the summed gradient of both outputs: d_v = d_y * keep * inv_keep; v, mean
+ *   and rstd are recomputed with the forward's bits; d_x [rows][dim] fp32 = rstd * (g - mean(g) - xhat * mean(g * xhat)) with
+ *   g = d_v * gamma is the gradient of every gathered table row; d_gamma = sum_rows d_v * xhat and d_beta = sum_rows d_v, [dim] fp32.
+ *   Any of the three may be NULL.  Nothing 16-bit is read or written (the name pairs it with its forward).
+ *   workspace (DEVICE, 16-byte aligned), needed when d_gamma or d_beta is asked for: min((rows + 3) / 4, 512) * 2 * dim * 4 bytes
+ *   (per-workgroup column sums, at most 512 rows of them, added up by a second kernel in a fixed order); NULL / 0 otherwise;
+ *   CCR_ERR_WORKSPACE if it is smaller.
+ * ccr_embedding_grad (bbpr.py:195-197: the gradient of word_embeddings / position_embeddings / token_type_embeddings .weight):
+ *   grad [n_rows][dim] fp32 from d_x [T][dim] fp32 and idx [T]: grad[r] = the sum of d_x[row] over the rows whose id, clamped to
+ *   0 .. n_rows - 1 as the forward clamps it, is r.  order [T] = the permutation that sorts (clamped idx, row) ascending (DEVICE; values
+ *   outside 0 .. T - 1 are clamped, an order that does not sort gives unspecified sums).  EVERY row of grad is written: ids that do not
+ *   occur get +0, so the caller needs no memset.  The summation order is normative: the rows of one id, in ascending row order, are cut
+ *   into chunks of CCR_EMBED_GRAD_CHUNK consecutive entries; a chunk is summed sequentially in fp32 starting from its first entry; the
+ *   chunk sums are then added sequentially, in order.  ccrec_amd/embed_grad_ref.py restates it in numpy, bit for bit.  Long runs (type 0
+ *   holds every token) are spread over many workgroups.  dim % 4 == 0, 16-byte aligned d_x and grad, T < 2^31; T == 0 gives all +0.
+ * ccr_meanpool_bwd_packed (item_tower.py:141-146 under autograd, over a packed token array): rows seq_start[s] .. + seq_len[s] - 1 of
+ *   d_hidden [T][dim] (hidden_dtype: CCR_DTYPE_F32 / F16 / BF16) receive grad[s] / (float)seq_len[s], grad [n_seq][dim] fp32 -- the
+ *   division of ccr_meanpool_bwd, hence the bits of the padded form's real rows.  Rows that belong to no sequence are LEFT ALONE (there
+ *   is no padding to zero); a sequence of length <= 0 writes nothing.  dim % 4 == 0.
+ */
+#define CCR_EMBED_GRAD_CHUNK 64
+int ccr_embed_layernorm_train_half(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
+                                   const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
+                                   const int64_t *token_types, const float *gamma, const float *beta, float eps, const uint32_t *bits,
+                                   float inv_keep, float *out_f32, uint16_t *out_half, int64_t rows, int dim, int half_dtype, void *stream);
+int ccr_embed_layernorm_bwd_half(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
+                                 const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
+                                 const int64_t *token_types, const float *gamma, float eps, const uint32_t *bits, float inv_keep,
+                                 const float *d_y, float *d_x, float *d_gamma, float *d_beta, int64_t rows, int dim, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int ccr_embedding_grad(const int64_t *idx, const int64_t *order, const float *d_x, int64_t T, int dim, float *grad, int64_t n_rows,
+                       void *stream);
+int ccr_meanpool_bwd_packed(const float *grad, const int32_t *seq_start, const int32_t *seq_len, void *d_hidden, int hidden_dtype, int n_seq,
+                            int dim, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
