@@ -20,6 +20,7 @@ the CPU in dropout_ref); without that opt-in such a model is refused and keeps t
 Only what the kernels cover is accepted (unsupported_reason): a BertModel or DistilBertModel encoder (post-LayerNorm layers, absolute
 positions, exact GELU), head width 64, hidden size a multiple of 256, at most 512 tokens, right-padded batches.  Every other encoder keeps
 running as its own torch module -- LengthSortedEncoder picks per model."""
+import collections
 import os
 import threading
 
@@ -184,13 +185,18 @@ class _DropoutDraw:
         return ops.dropout_bits_attention(seq_start, lengths, n_tokens, heads, max_len, self.seed, stream, p), self._ref.inv_keep(p)
 
 
+def _autocast_dtype():
+    """Inside a CUDA autocast context: the context's own type; outside one: None."""
+    if torch.cuda.is_available() and torch.is_autocast_enabled("cuda"):
+        return torch.get_autocast_dtype("cuda")
+    return None
+
+
 def train_dtype():
     """The 16-bit operand type of a training forward on the kernels = the CUDA autocast context's own type when that is fp16 or bf16;
     None (the module trains) outside autocast or under any other type."""
-    if torch.cuda.is_available() and torch.is_autocast_enabled("cuda"):
-        dtype = torch.get_autocast_dtype("cuda")
-        return dtype if dtype in (torch.float16, torch.bfloat16) else None
-    return None
+    dtype = _autocast_dtype()
+    return dtype if dtype in (torch.float16, torch.bfloat16) else None
 
 
 _ENV_DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp16": torch.float16, "float16": torch.float16, "half": torch.float16}
@@ -207,8 +213,8 @@ def kernel_dtype(explicit="auto"):
     env = os.environ.get("CCREC_FUSED_ENCODER", "").strip()
     if explicit is False or (explicit is not True and env == "0"):
         return None
-    if torch.cuda.is_available() and torch.is_autocast_enabled("cuda"):
-        dtype = torch.get_autocast_dtype("cuda")
+    dtype = _autocast_dtype()
+    if dtype is not None:
         return dtype if dtype in (torch.float16, torch.bfloat16) else None
     if explicit is True or env == "1":
         name = os.environ.get("CCREC_FUSED_ENCODER_DTYPE", "bf16").strip().lower()
@@ -250,6 +256,9 @@ def prefix_lengths(attention_mask):
     L = m.shape[1]
     ok = ((m != 0) == (torch.arange(L, device=m.device)[None, :] < lengths[:, None])).all() & (lengths > 0).all()
     return lengths.to(torch.int32) if bool(ok) else None
+
+
+_Batch = collections.namedtuple("_Batch", "B L ids positions types seq_start max_len pad_len keep")      # FusedBertEncoder._layout
 
 
 class _Layer:
@@ -438,24 +447,30 @@ class FusedBertEncoder:
                 layers.append(l)
         return layers
 
-    def _embed(self, token_ids, positions, token_types, dtype):
-        """The embedding block (BertEmbeddings.forward: (word + type) + position, LayerNorm; DistilBERT's Embeddings: word + position,
-        LayerNorm) over flat int64 index vectors [T] -> (fp32 [T, hidden], its copy in `dtype`): one kernel on the module's own fp32
-        tables (ccr_embed_layernorm; an all-zero type row stands in where the architecture has no token types), or the same sum
-        in torch when the tables are not plain fp32 (a half-precision checkpoint)."""
+    def _embedding_tables(self, token_types):
+        """-> (word table, position table, type table, the block's LayerNorm, plain): the module's own tables, an all-zero type row
+        standing in where the architecture has no token types; plain = all of them (and the LayerNorm's parameters) are contiguous fp32,
+        what the embedding kernels read (a half-precision checkpoint is not)."""
         arch = _describe(self.model)
         e = arch.embeddings
-        token_ids, positions = token_ids.long(), positions.long()          # (tokenizers may hand over int32 ids)
-        token_types = None if token_types is None else token_types.long()
-        word, pos, ln = e.word_embeddings.weight, e.position_embeddings.weight, e.LayerNorm
-        types = arch.type_table
+        word, pos, ln, types = e.word_embeddings.weight, e.position_embeddings.weight, e.LayerNorm, arch.type_table
         if types is None:
             assert token_types is None, "this architecture has no token types"
             if self._no_types is None or self._no_types.device != word.device:
                 self._no_types = torch.zeros(1, self.hidden, dtype=torch.float32, device=word.device)
             types = self._no_types
-        tables = (word, pos, types, ln.weight, ln.bias)
-        if all(t.dtype == torch.float32 and t.is_contiguous() for t in tables):
+        plain = all(t.dtype == torch.float32 and t.is_contiguous() for t in (word, pos, types, ln.weight, ln.bias))
+        return word, pos, types, ln, plain
+
+    def _embed(self, token_ids, positions, token_types, dtype):
+        """The embedding block (BertEmbeddings.forward: (word + type) + position, LayerNorm; DistilBERT's Embeddings: word + position,
+        LayerNorm) over flat int64 index vectors [T] -> (fp32 [T, hidden], its copy in `dtype`): one kernel on the module's own fp32
+        tables (ccr_embed_layernorm; an all-zero type row stands in where the architecture has no token types), or the same sum
+        in torch when the tables are not plain fp32 (a half-precision checkpoint)."""
+        token_ids, positions = token_ids.long(), positions.long()          # (tokenizers may hand over int32 ids)
+        token_types = None if token_types is None else token_types.long()
+        word, pos, types, ln, plain = self._embedding_tables(token_types)
+        if plain:
             return ops.embed_layernorm(word, pos, types, token_ids.contiguous(), positions.contiguous(),
                                        None if token_types is None else token_types.contiguous(), ln.weight, ln.bias, ln.eps, dtype=dtype)
         x = word[token_ids].float() + types[token_types if token_types is not None else torch.zeros_like(token_ids)].float()
@@ -494,13 +509,8 @@ class FusedBertEncoder:
         e = arch.embeddings
         token_ids, positions = token_ids.long(), positions.long()
         if train_packed_wanted():
-            word, pos, ln, types = e.word_embeddings.weight, e.position_embeddings.weight, e.LayerNorm, arch.type_table
-            if types is None:
-                assert token_types is None, "this architecture has no token types"
-                if self._no_types is None or self._no_types.device != word.device:
-                    self._no_types = torch.zeros(1, self.hidden, dtype=torch.float32, device=word.device)
-                types = self._no_types
-            if all(t.dtype == torch.float32 and t.is_contiguous() for t in (word, pos, types, ln.weight, ln.bias)):
+            word, pos, types, ln, plain = self._embedding_tables(token_types)
+            if plain:
                 bits, inv_keep = (None, 1.0) if drop is None else drop.rows(getattr(e, "dropout", None), EMBEDDINGS_STREAM,
                                                                             token_ids.numel(), self.hidden, word.device)
                 return ops.embed_layernorm_train(word, pos, types, token_ids, positions, None if token_types is None else token_types.long(),
@@ -565,6 +575,41 @@ class FusedBertEncoder:
             h = h[cls_rows]
         return h
 
+    @staticmethod
+    def _check_batch(input_ids, lengths):
+        """What every forward over a right-padded batch asks of its arguments, before anything else runs."""
+        assert input_ids.is_cuda and input_ids.dim() == 2
+        B, L = input_ids.shape
+        assert L <= 512 and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.numel() == B
+
+    def _layout(self, input_ids, lengths, token_type_ids, packed, lengths_host):
+        """The token array of a right-padded batch input_ids [B, L] with lengths [B] int32 -> a _Batch: the flat token ids, positions and
+        types, seq_start, max_len and pad_len as the layer kernels take them, and keep.
+        packed: only the real tokens (keep = their int64 rows of the flattened batch; pad_len 0, max_len = the longest sequence); not
+        packed: every row of the batch (keep None; pad_len = max_len = L).  packed None: packed when more than a tenth of the batch is
+        padding.  A packed layout needs the lengths on the host: `lengths_host`, or one device read.  (The caller has run _check_batch.)"""
+        B, L = input_ids.shape
+        dev = input_ids.device
+        if packed is None or packed:
+            lens_h = lengths.cpu() if lengths_host is None else torch.as_tensor(lengths_host)
+            total, longest = int(lens_h.sum()), int(lens_h.max()) if B else 0
+            if packed is None:
+                packed = total < 0.9 * B * L
+        if packed:
+            keep = (torch.arange(L, device=dev)[None, :] < lengths[:, None]).flatten().nonzero().squeeze(1)   # rows of the real tokens
+            assert keep.numel() == total, "lengths_host does not match lengths"
+            return _Batch(B, L, input_ids.flatten()[keep], keep % L, None if token_type_ids is None else token_type_ids.flatten()[keep],
+                          (torch.cumsum(lengths, 0, dtype=torch.int32) - lengths).contiguous(), max(longest, 1), 0, keep)
+        return _Batch(B, L, input_ids.flatten(), torch.arange(L, device=dev).repeat(B), None if token_type_ids is None else token_type_ids.flatten(),
+                      torch.arange(B, dtype=torch.int32, device=dev) * L, L, L, None)
+
+    def _padded(self, h, batch):
+        """The layers' result h over batch's token rows -> [B, L, hidden]: a packed result goes back to its rows of a zero-filled batch
+        (written in place into the fresh tensor; autograd follows index_copy_, padding rows carry no gradient)."""
+        if batch.keep is not None:
+            h = torch.zeros(batch.B * batch.L, self.hidden, dtype=torch.float32, device=h.device).index_copy_(0, batch.keep, h)
+        return h.view(batch.B, batch.L, self.hidden)
+
     def _check_train(self):
         """Refuse what train_unsupported_reason refuses; -> the call's _DropoutDraw (one fresh seed, kept in last_seed) when the model is
         in training mode with live dropout, else None (the dropout-free kernels run)."""
@@ -591,34 +636,12 @@ class FusedBertEncoder:
         (packed) or finite values nobody reads, and carry no gradient into the parameters."""
         ops.require_gpu()
         drop = self._check_train()
-        assert input_ids.is_cuda and input_ids.dim() == 2
-        B, L = input_ids.shape
-        assert L <= 512 and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.numel() == B
-        dev = input_ids.device
-        if packed is None or packed:
-            lens_h = lengths.cpu() if lengths_host is None else torch.as_tensor(lengths_host)
-            total, longest = int(lens_h.sum()), int(lens_h.max()) if B else 0
-            if packed is None:
-                packed = total < 0.9 * B * L
+        self._check_batch(input_ids, lengths)
         with torch.autocast("cuda", enabled=False):
-            if packed:
-                keep = (torch.arange(L, device=dev)[None, :] < lengths[:, None]).flatten().nonzero().squeeze(1)   # rows of the real tokens
-                assert keep.numel() == total, "lengths_host does not match lengths"
-                h, hb = self._embed_train(input_ids.flatten()[keep], keep % L, None if token_type_ids is None else token_type_ids.flatten()[keep], dtype,
-                                          drop)
-                max_len, pad_len = max(longest, 1), 0
-                seq_start = (torch.cumsum(lengths, 0, dtype=torch.int32) - lengths).contiguous()
-            else:
-                h, hb = self._embed_train(input_ids.flatten(), torch.arange(L, device=dev).repeat(B),
-                                          None if token_type_ids is None else token_type_ids.flatten(), dtype, drop)
-                max_len, pad_len = L, L
-                seq_start = torch.arange(B, dtype=torch.int32, device=dev) * L
-            h = self._layers_forward_train(h, hb, seq_start, lengths, max_len, pad_len, seq_start.long() if cls_only else None, drop)
-            if cls_only:
-                return h.view(B, 1, self.hidden)
-            if packed:
-                h = torch.zeros(B * L, self.hidden, dtype=torch.float32, device=dev).index_copy(0, keep, h)
-        return h.view(B, L, self.hidden)
+            b = self._layout(input_ids, lengths, token_type_ids, packed, lengths_host)
+            h, hb = self._embed_train(b.ids, b.positions, b.types, dtype, drop)
+            h = self._layers_forward_train(h, hb, b.seq_start, lengths, b.max_len, b.pad_len, b.seq_start.long() if cls_only else None, drop)
+            return h.view(b.B, 1, self.hidden) if cls_only else self._padded(h, b)
 
     def forward_train_pooled(self, input_ids, lengths, token_type_ids=None, lengths_host=None, dtype=torch.bfloat16):
         """forward_train followed by the tower's masked mean pooling (src/ccrec/models/item_tower.py:141-146), without the padded tensor in
@@ -627,20 +650,12 @@ class FusedBertEncoder:
         and the backward writes no padding.  Same arguments as forward_train; the batch always runs packed."""
         ops.require_gpu()
         drop = self._check_train()
-        assert input_ids.is_cuda and input_ids.dim() == 2
-        B, L = input_ids.shape
-        assert L <= 512 and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.numel() == B
-        dev = input_ids.device
-        lens_h = lengths.cpu() if lengths_host is None else torch.as_tensor(lengths_host)
-        total, longest = int(lens_h.sum()), int(lens_h.max()) if B else 0
+        self._check_batch(input_ids, lengths)
         with torch.autocast("cuda", enabled=False):
-            keep = (torch.arange(L, device=dev)[None, :] < lengths[:, None]).flatten().nonzero().squeeze(1)   # rows of the real tokens
-            assert keep.numel() == total, "lengths_host does not match lengths"
-            h, hb = self._embed_train(input_ids.flatten()[keep], keep % L, None if token_type_ids is None else token_type_ids.flatten()[keep], dtype,
-                                      drop)
-            seq_start = (torch.cumsum(lengths, 0, dtype=torch.int32) - lengths).contiguous()
-            h = self._layers_forward_train(h, hb, seq_start, lengths, max(longest, 1), 0, None, drop)
-            return ops.meanpool_packed(h, seq_start, lengths.contiguous(), covers_all=True)
+            b = self._layout(input_ids, lengths, token_type_ids, True, lengths_host)
+            h, hb = self._embed_train(b.ids, b.positions, b.types, dtype, drop)
+            h = self._layers_forward_train(h, hb, b.seq_start, lengths, b.max_len, 0, None, drop)
+            return ops.meanpool_packed(h, b.seq_start, lengths.contiguous(), covers_all=True)
 
     @torch.no_grad()
     def forward_packed(self, token_ids, positions, seq_start, lengths, max_len, token_type_ids=None, cls_only=False, dtype=torch.bfloat16):
@@ -672,34 +687,11 @@ class FusedBertEncoder:
         ops.require_gpu()
         model = self.model
         assert not model.training, "FusedBertEncoder is an inference forward: call model.eval() first"
-        assert input_ids.is_cuda and input_ids.dim() == 2
-        B, L = input_ids.shape
-        assert L <= 512 and lengths.dtype == torch.int32 and lengths.is_cuda and lengths.numel() == B
+        self._check_batch(input_ids, lengths)
         if dtype not in self._layers:
             self.refresh(dtype)
-        dev = input_ids.device
-        if packed is None or packed:
-            lens_h = lengths.cpu() if lengths_host is None else torch.as_tensor(lengths_host)
-            total, longest = int(lens_h.sum()), int(lens_h.max()) if B else 0
-            if packed is None:
-                packed = total < 0.9 * B * L
         with torch.autocast("cuda", enabled=False):
-            if packed:
-                keep = (torch.arange(L, device=dev)[None, :] < lengths[:, None]).flatten().nonzero().squeeze(1)   # rows of the real tokens
-                assert keep.numel() == total, "lengths_host does not match lengths"
-                h, hb = self._embed(input_ids.flatten()[keep], keep % L, None if token_type_ids is None else token_type_ids.flatten()[keep], dtype)
-                max_len, pad_len = max(longest, 1), 0
-                seq_start = (torch.cumsum(lengths, 0, dtype=torch.int32) - lengths).contiguous()
-            else:
-                h, hb = self._embed(input_ids.flatten(), torch.arange(L, device=dev).repeat(B),
-                                    None if token_type_ids is None else token_type_ids.flatten(), dtype)
-                max_len, pad_len = L, L
-                seq_start = torch.arange(B, dtype=torch.int32, device=dev) * L
-            h = self._layers_forward(h, hb, seq_start, lengths, max_len, pad_len, seq_start.long() if cls_only else None)
-            if cls_only:
-                return h.view(B, 1, self.hidden)
-            if packed:
-                full = torch.zeros(B * L, self.hidden, dtype=torch.float32, device=dev)
-                full[keep] = h
-                h = full
-        return h.view(B, L, self.hidden)
+            b = self._layout(input_ids, lengths, token_type_ids, packed, lengths_host)
+            h, hb = self._embed(b.ids, b.positions, b.types, dtype)
+            h = self._layers_forward(h, hb, b.seq_start, lengths, b.max_len, b.pad_len, b.seq_start.long() if cls_only else None)
+            return h.view(b.B, 1, self.hidden) if cls_only else self._padded(h, b)

@@ -176,6 +176,31 @@ def _half_code(dtype):
     return _HALF_DTYPES[dtype]
 
 
+def _check_qkv(qkv, seq_start, seq_len, n_heads):
+    """The token array and sequence table every attention op takes: qkv [T, 3 * n_heads * 64] contiguous on the GPU, seq_start / seq_len
+    [n_seq] contiguous int32 on the GPU.  -> T"""
+    assert qkv.is_cuda and qkv.dim() == 2 and qkv.is_contiguous()
+    T, width = qkv.shape
+    assert width == 3 * n_heads * 64, f"qkv rows are {width} wide, expected 3 x {n_heads} heads x 64"
+    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
+    assert seq_start.is_contiguous() and seq_len.is_contiguous() and seq_start.numel() == seq_len.numel()
+    return T
+
+
+def _check_rows(x, residual, *vectors, keep_bits=None):
+    """The operands of a row kernel: x [rows, dim] contiguous on the GPU, residual fp32 [rows, dim] or None, fp32 [dim] vectors (gamma,
+    beta), keep bits int32 [rows, dim / 32] or None.  -> (rows, dim)"""
+    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
+    rows, dim = x.shape
+    if keep_bits is not None:
+        _check_bits(keep_bits, (rows, dim // 32))
+    if residual is not None:
+        assert residual.is_cuda and residual.dtype == torch.float32 and tuple(residual.shape) == (rows, dim) and residual.is_contiguous()
+    for t in vectors:
+        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (dim,) and t.is_contiguous()
+    return rows, dim
+
+
 def attention(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, out=None):
     """Multi-head self-attention of a token array (ccr_attention_half; head width 64): qkv [T, 3 * n_heads * 64] bf16 or fp16 = the
     stacked query | key | value projection of every token, seq_start / seq_len [n_seq] int32 = each sequence's first row and real tokens,
@@ -183,11 +208,7 @@ def attention(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125,
     zeros) or 0 for a packed array.  -> context rows [T, n_heads * 64] of qkv's dtype."""
     lib = require_gpu()
     code = _half_code(qkv.dtype)
-    assert qkv.is_cuda and qkv.dim() == 2 and qkv.is_contiguous()
-    T, width = qkv.shape
-    assert width == 3 * n_heads * 64, f"qkv rows are {width} wide, expected 3 x {n_heads} heads x 64"
-    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
-    assert seq_start.is_contiguous() and seq_len.is_contiguous() and seq_start.numel() == seq_len.numel()
+    T = _check_qkv(qkv, seq_start, seq_len, n_heads)
     if out is None:
         out = torch.empty(T, n_heads * 64, dtype=qkv.dtype, device=qkv.device)
     assert out.is_cuda and out.dtype == qkv.dtype and tuple(out.shape) == (T, n_heads * 64) and out.is_contiguous()
@@ -197,26 +218,39 @@ def attention(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125,
     return out
 
 
-def embed_layernorm(word_table, position_table, type_table, token_ids, positions, token_types, gamma, beta, eps, dtype=torch.bfloat16):
-    """LayerNorm((word_table[ids] + type_table[types]) + position_table[positions]) per token (ccr_embed_layernorm_half): fp32 tables
-    [n, dim], int64 index vectors [T] (token_types may be None = type 0).  -> (fp32 [T, dim], its copy in `dtype` (bf16 / fp16) [T, dim])."""
-    lib = require_gpu()
-    code = _half_code(dtype)
+def _check_embed_args(word_table, position_table, type_table, token_ids, positions, token_types, gamma):
     dim = word_table.shape[1]
     for t in (word_table, position_table, type_table):
         assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == dim and t.is_contiguous()
-    for t in (gamma, beta):
-        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (dim,) and t.is_contiguous()
+    assert gamma.is_cuda and gamma.dtype == torch.float32 and tuple(gamma.shape) == (dim,) and gamma.is_contiguous()
     T = token_ids.numel()
     for t in (token_ids, positions) + ((token_types,) if token_types is not None else ()):
         assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.numel() == T and t.is_contiguous()
+    return T, dim
+
+
+def embed_layernorm(word_table, position_table, type_table, token_ids, positions, token_types, gamma, beta, eps, dtype=torch.bfloat16,
+                    keep_bits=None, inv_keep=1.0):
+    """LayerNorm((word_table[ids] + type_table[types]) + position_table[positions]) per token (ccr_embed_layernorm_half): fp32 tables
+    [n, dim], int64 index vectors [T] (token_types may be None = type 0).  -> (fp32 [T, dim], its copy in `dtype` (bf16 / fp16) [T, dim]).
+    keep_bits [T, dim / 32] (dropout_bits_rows): the block's dropout follows in the same kernel (ccr_embed_layernorm_train_half), with the
+    bits of dropout_apply(embed_layernorm(...))."""
+    lib = require_gpu() if keep_bits is None else _require_encoder_packed_train()
+    code = _half_code(dtype)
+    T, dim = _check_embed_args(word_table, position_table, type_table, token_ids, positions, token_types, gamma)
+    assert beta.is_cuda and beta.dtype == torch.float32 and tuple(beta.shape) == (dim,) and beta.is_contiguous()
+    if keep_bits is not None:
+        _check_bits(keep_bits, (T, dim // 32))
     f32 = torch.empty(T, dim, dtype=torch.float32, device=word_table.device)
     b16 = torch.empty(T, dim, dtype=dtype, device=word_table.device)
+    tables = (_ptr(word_table), word_table.shape[0], _ptr(position_table), position_table.shape[0], _ptr(type_table), type_table.shape[0],
+              _ptr(token_ids), _ptr(positions), _ptr(token_types), _ptr(gamma), _ptr(beta), float(eps))
     with _on(word_table):
-        _lib.check(lib.ccr_embed_layernorm_half(_ptr(word_table), word_table.shape[0], _ptr(position_table), position_table.shape[0],
-                                                _ptr(type_table), type_table.shape[0], _ptr(token_ids), _ptr(positions),
-                                                _ptr(token_types), _ptr(gamma), _ptr(beta), float(eps), _ptr(f32), _ptr(b16), T, dim,
-                                                code, _stream(word_table)), "ccr_embed_layernorm_half")
+        if keep_bits is None:
+            _lib.check(lib.ccr_embed_layernorm_half(*tables, _ptr(f32), _ptr(b16), T, dim, code, _stream(word_table)), "ccr_embed_layernorm_half")
+        else:
+            _lib.check(lib.ccr_embed_layernorm_train_half(*tables, _ptr(keep_bits), float(inv_keep), _ptr(f32), _ptr(b16), T, dim, code,
+                                                          _stream(word_table)), "ccr_embed_layernorm_train_half")
     return f32, b16
 
 
@@ -230,24 +264,23 @@ def gelu_(x):
     return x
 
 
-def add_layernorm(x, residual, gamma, beta, eps, want_f32=True, want_bf16=True):
+def add_layernorm(x, residual, gamma, beta, eps, want_f32=True, want_bf16=True, keep_bits=None, inv_keep=1.0):
     """LayerNorm(x + residual) * gamma + beta per row (ccr_add_layernorm_half): x [rows, dim] bf16 or fp16, residual [rows, dim] fp32 or
     None, gamma / beta [dim] fp32, dim a multiple of 256 (<= 2048).  -> (fp32 rows or None, their copy in x's dtype or None:
-    want_bf16 asks for that 16-bit copy whichever of the two types x has)."""
-    lib = require_gpu()
+    want_bf16 asks for that 16-bit copy whichever of the two types x has).
+    keep_bits int32 [rows, dim / 32] (dropout_bits_rows): LayerNorm(x * keep * inv_keep + residual) (ccr_add_layernorm_drop_half)."""
+    lib = require_gpu() if keep_bits is None else _require_encoder_dropout()
     code = _half_code(x.dtype)
-    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
-    rows, dim = x.shape
-    if residual is not None:
-        assert residual.is_cuda and residual.dtype == torch.float32 and tuple(residual.shape) == (rows, dim) and residual.is_contiguous()
-    for t in (gamma, beta):
-        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (dim,) and t.is_contiguous()
+    rows, dim = _check_rows(x, residual, gamma, beta, keep_bits=keep_bits)
     assert want_f32 or want_bf16
     f32 = torch.empty(rows, dim, dtype=torch.float32, device=x.device) if want_f32 else None
     b16 = torch.empty(rows, dim, dtype=x.dtype, device=x.device) if want_bf16 else None
+    tail = (_ptr(residual), _ptr(gamma), _ptr(beta), float(eps), _ptr(f32), _ptr(b16), rows, dim, code, _stream(x))
     with _on(x):
-        _lib.check(lib.ccr_add_layernorm_half(_ptr(x), _ptr(residual), _ptr(gamma), _ptr(beta), float(eps), _ptr(f32), _ptr(b16),
-                                              rows, dim, code, _stream(x)), "ccr_add_layernorm_half")
+        if keep_bits is None:
+            _lib.check(lib.ccr_add_layernorm_half(_ptr(x), *tail), "ccr_add_layernorm_half")
+        else:
+            _lib.check(lib.ccr_add_layernorm_drop_half(_ptr(x), _ptr(keep_bits), float(inv_keep), *tail), "ccr_add_layernorm_drop_half")
     return f32, b16
 
 
@@ -269,71 +302,87 @@ def _require_encoder_train():
     return lib
 
 
-def attention_fwd_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125):
+def attention_fwd_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, keep_q=None, inv_keep=1.0):
     """attention() that also returns lse [T, n_heads] fp32, the log-sum-exp of every real query row's scaled scores (0 on padding
-    rows): what attention_bwd rebuilds the probabilities from (ccr_attention_fwd_train_half).  -> (out, lse); out has attention()'s bits."""
-    lib = _require_encoder_train()
+    rows): what attention_bwd rebuilds the probabilities from (ccr_attention_fwd_train_half).  -> (out, lse); out has attention()'s bits.
+    keep_q (dropout_bits_attention): dropout on the probabilities (ccr_attention_fwd_train_drop_half): the value rounded for the P V
+    product is p * keep * inv_keep; lse stays that of the undropped scores."""
+    lib = _require_encoder_train() if keep_q is None else _require_encoder_dropout()
     code = _half_code(qkv.dtype)
-    assert qkv.is_cuda and qkv.dim() == 2 and qkv.is_contiguous()
-    T, width = qkv.shape
-    assert width == 3 * n_heads * 64, f"qkv rows are {width} wide, expected 3 x {n_heads} heads x 64"
-    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
-    assert seq_start.is_contiguous() and seq_len.is_contiguous() and seq_start.numel() == seq_len.numel()
+    T = _check_qkv(qkv, seq_start, seq_len, n_heads)
+    if keep_q is not None:
+        _check_bits(keep_q, (T, n_heads, (int(max_len) + 31) // 32))
     out = torch.empty(T, n_heads * 64, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(T, n_heads, dtype=torch.float32, device=qkv.device)
+    shape = (seq_len.numel(), int(n_heads), int(max_len), int(pad_len), float(scale), code, _stream(qkv))
     with _on(qkv):
-        _lib.check(lib.ccr_attention_fwd_train_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), _ptr(lse), seq_len.numel(),
-                                                    int(n_heads), int(max_len), int(pad_len), float(scale), code, _stream(qkv)),
-                   "ccr_attention_fwd_train_half")
+        if keep_q is None:
+            _lib.check(lib.ccr_attention_fwd_train_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), _ptr(lse), *shape),
+                       "ccr_attention_fwd_train_half")
+        else:
+            _lib.check(lib.ccr_attention_fwd_train_drop_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), _ptr(lse), _ptr(keep_q),
+                                                             float(inv_keep), *shape), "ccr_attention_fwd_train_drop_half")
     return out, lse
 
 
-def attention_bwd(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125):
+def attention_bwd(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, keep_q=None, keep_k=None, inv_keep=1.0):
     """d_qkv [T, 3 * n_heads * 64] (qkv's dtype and layout) from attention_fwd_train's (out, lse) and d_out [T, n_heads * 64]
-    (ccr_attention_bwd_half).  Rows of the sequences' padding get zeros; so do rows that belong to no sequence."""
-    lib = _require_encoder_train()
+    (ccr_attention_bwd_half).  Rows of the sequences' padding get zeros; so do rows that belong to no sequence.
+    keep_q, keep_k: the forward's bits, both or neither (ccr_attention_bwd_drop_half)."""
+    assert (keep_q is None) == (keep_k is None), "attention_bwd: keep_q and keep_k come together"
+    lib = _require_encoder_train() if keep_q is None else _require_encoder_dropout()
     code = _half_code(qkv.dtype)
-    T = qkv.shape[0]
-    assert qkv.is_cuda and qkv.is_contiguous() and tuple(qkv.shape) == (T, 3 * n_heads * 64)
+    T = _check_qkv(qkv, seq_start, seq_len, n_heads)
     for t in (out, d_out):
         assert t.is_cuda and t.dtype == qkv.dtype and tuple(t.shape) == (T, n_heads * 64) and t.is_contiguous()
     assert lse.is_cuda and lse.dtype == torch.float32 and tuple(lse.shape) == (T, n_heads) and lse.is_contiguous()
-    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_contiguous() and seq_len.is_contiguous()
+    if keep_q is not None:
+        for bits in (keep_q, keep_k):
+            _check_bits(bits, (T, n_heads, (int(max_len) + 31) // 32))
     n_seq = seq_len.numel()
     need = int(lib.ccr_attention_bwd_workspace_bytes(n_seq, int(n_heads), int(max_len)))
     if need == 0:
         _lib.check(_lib.CCR_ERR_INVALID, "ccr_attention_bwd_workspace_bytes")
     ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
     d_qkv = torch.zeros_like(qkv)
+    head = (_ptr(qkv), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(seq_start), _ptr(seq_len))
+    tail = (_ptr(d_qkv), n_seq, int(n_heads), int(max_len), int(pad_len), float(scale), code, _ptr(ws), need, _stream(qkv))
     with _on(qkv):
-        _lib.check(lib.ccr_attention_bwd_half(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(seq_start), _ptr(seq_len), _ptr(d_qkv),
-                                              n_seq, int(n_heads), int(max_len), int(pad_len), float(scale), code, _ptr(ws), need,
-                                              _stream(qkv)), "ccr_attention_bwd_half")
+        if keep_q is None:
+            _lib.check(lib.ccr_attention_bwd_half(*head, *tail), "ccr_attention_bwd_half")
+        else:
+            _lib.check(lib.ccr_attention_bwd_drop_half(*head, _ptr(keep_q), _ptr(keep_k), float(inv_keep), *tail), "ccr_attention_bwd_drop_half")
     return d_qkv
 
 
-def add_layernorm_bwd(x, residual, gamma, eps, d_y, want_res=True, want_x=True, want_gamma=True, want_beta=True):
+def _layernorm_bwd_workspace(rows, dim, want_params, device):
+    """(workspace, its bytes) of a LayerNorm backward that returns d_gamma or d_beta: the per-workgroup column sums of at most 512
+    workgroups of four rows (include/ccr_retrieval.h); (None, 0) when neither is wanted."""
+    need = min((rows + 3) // 4, 512) * 2 * dim * 4 if want_params else 0
+    return (torch.empty(need, dtype=torch.uint8, device=device) if need else None), need
+
+
+def add_layernorm_bwd(x, residual, gamma, eps, d_y, want_res=True, want_x=True, want_gamma=True, want_beta=True, keep_bits=None, inv_keep=1.0):
     """The backward of add_layernorm (ccr_add_layernorm_bwd_half): d_y [rows, dim] fp32 = the summed gradient of the LayerNorm output
-    -> (d_res fp32 = the gradient of x + residual, d_x = the same rounded to x's dtype, d_gamma, d_beta [dim] fp32); None where not wanted."""
-    lib = _require_encoder_train()
+    -> (d_res fp32 = the gradient of x + residual, d_x = the same rounded to x's dtype, d_gamma, d_beta [dim] fp32); None where not wanted.
+    keep_bits: the forward's (ccr_add_layernorm_bwd_drop_half): d_res is the gradient of the summed input, d_x = d_res * keep * inv_keep."""
+    lib = _require_encoder_train() if keep_bits is None else _require_encoder_dropout()
     code = _half_code(x.dtype)
-    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
-    rows, dim = x.shape
-    if residual is not None:
-        assert residual.is_cuda and residual.dtype == torch.float32 and tuple(residual.shape) == (rows, dim) and residual.is_contiguous()
-    assert gamma.is_cuda and gamma.dtype == torch.float32 and tuple(gamma.shape) == (dim,) and gamma.is_contiguous()
+    rows, dim = _check_rows(x, residual, gamma, keep_bits=keep_bits)
     assert d_y.is_cuda and d_y.dtype == torch.float32 and tuple(d_y.shape) == (rows, dim) and d_y.is_contiguous()
     dev = x.device
     d_res = torch.empty(rows, dim, dtype=torch.float32, device=dev) if want_res else None
     d_x = torch.empty(rows, dim, dtype=x.dtype, device=dev) if want_x else None
     d_gamma = torch.empty(dim, dtype=torch.float32, device=dev) if want_gamma else None
     d_beta = torch.empty(dim, dtype=torch.float32, device=dev) if want_beta else None
-    need = min((rows + 3) // 4, 512) * 2 * dim * 4 if (want_gamma or want_beta) else 0      # per-workgroup column sums (include/ccr_retrieval.h)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    ws, need = _layernorm_bwd_workspace(rows, dim, want_gamma or want_beta, dev)
+    tail = (_ptr(residual), _ptr(gamma), float(eps), _ptr(d_y), _ptr(d_res), _ptr(d_x), _ptr(d_gamma), _ptr(d_beta), rows, dim, code, _ptr(ws),
+            need, _stream(x))
     with _on(x):
-        _lib.check(lib.ccr_add_layernorm_bwd_half(_ptr(x), _ptr(residual), _ptr(gamma), float(eps), _ptr(d_y), _ptr(d_res), _ptr(d_x),
-                                                  _ptr(d_gamma), _ptr(d_beta), rows, dim, code, _ptr(ws), need, _stream(x)),
-                   "ccr_add_layernorm_bwd_half")
+        if keep_bits is None:
+            _lib.check(lib.ccr_add_layernorm_bwd_half(_ptr(x), *tail), "ccr_add_layernorm_bwd_half")
+        else:
+            _lib.check(lib.ccr_add_layernorm_bwd_drop_half(_ptr(x), _ptr(keep_bits), float(inv_keep), *tail), "ccr_add_layernorm_bwd_drop_half")
     return d_res, d_x, d_gamma, d_beta
 
 
@@ -349,61 +398,62 @@ def gelu_bwd(x, d_y):
     return d_x
 
 
+def _sum_output_grads(d_f32, d_b16):
+    """A row op returns one value in two precisions: the gradients of the two outputs add up (fp32) before the backward kernel runs."""
+    if d_f32 is None:
+        return d_b16.float()
+    if d_b16 is None:
+        return d_f32.float()
+    return d_f32.float() + d_b16
+
+
 class _AttentionTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale):
-        out, lse = attention_fwd_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale)
-        ctx.save_for_backward(qkv, out, lse, seq_start, seq_len)
-        ctx.shape = (int(n_heads), int(max_len), int(pad_len), float(scale))
+    def forward(ctx, qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q, keep_k, inv_keep):
+        out, lse = attention_fwd_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q, inv_keep)
+        ctx.save_for_backward(qkv, out, lse, seq_start, seq_len, keep_q, keep_k)
+        ctx.shape = (int(n_heads), int(max_len), int(pad_len), float(scale), float(inv_keep))
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        qkv, out, lse, seq_start, seq_len = ctx.saved_tensors
-        n_heads, max_len, pad_len, scale = ctx.shape
-        d_qkv = attention_bwd(qkv, out, lse, d_out.to(qkv.dtype).contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale)
-        return d_qkv, None, None, None, None, None, None
+        qkv, out, lse, seq_start, seq_len, keep_q, keep_k = ctx.saved_tensors
+        n_heads, max_len, pad_len, scale, inv_keep = ctx.shape
+        d_qkv = attention_bwd(qkv, out, lse, d_out.to(qkv.dtype).contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q,
+                              keep_k, inv_keep)
+        return (d_qkv,) + (None,) * 9
 
 
 def attention_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, keep_bits=None, inv_keep=1.0):
     """attention() with a backward: the same context rows, bit for bit; the gradient reaches qkv (the stacked projection's output).
     keep_bits = (keep_q, keep_k) of dropout_bits_attention: dropout on the probabilities, scaled by inv_keep, the bits saved for the backward."""
-    if keep_bits is None:
-        return _AttentionTrain.apply(qkv.contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale)
-    return _AttentionTrainDrop.apply(qkv.contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_bits[0], keep_bits[1], inv_keep)
+    keep_q, keep_k = (None, None) if keep_bits is None else keep_bits
+    return _AttentionTrain.apply(qkv.contiguous(), seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q, keep_k, inv_keep)
 
 
 class _AddLayerNormTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, residual, gamma, beta, eps):
-        f32, b16 = add_layernorm(x, residual, gamma, beta, eps)
-        ctx.save_for_backward(x, residual, gamma)
-        ctx.eps = float(eps)
+    def forward(ctx, x, residual, gamma, beta, eps, bits, inv_keep):
+        f32, b16 = add_layernorm(x, residual, gamma, beta, eps, keep_bits=bits, inv_keep=inv_keep)
+        ctx.save_for_backward(x, residual, gamma, bits)
+        ctx.eps, ctx.inv_keep = float(eps), float(inv_keep)
         return f32, b16
 
     @staticmethod
     def backward(ctx, d_f32, d_b16):
-        x, residual, gamma = ctx.saved_tensors
-        # the two outputs are one value in two precisions: their gradients add up (fp32) before the kernel runs
-        if d_f32 is None:
-            d_y = d_b16.float()
-        elif d_b16 is None:
-            d_y = d_f32.float()
-        else:
-            d_y = d_f32.float() + d_b16
+        x, residual, gamma, bits = ctx.saved_tensors
         need = ctx.needs_input_grad
-        d_res, d_x, d_gamma, d_beta = add_layernorm_bwd(x, residual, gamma, ctx.eps, d_y.contiguous(), want_res=residual is not None and need[1],
-                                                        want_x=need[0], want_gamma=need[2], want_beta=need[3])
-        return d_x, d_res, d_gamma, d_beta, None
+        d_res, d_x, d_gamma, d_beta = add_layernorm_bwd(x, residual, gamma, ctx.eps, _sum_output_grads(d_f32, d_b16).contiguous(),
+                                                        want_res=residual is not None and need[1], want_x=need[0], want_gamma=need[2],
+                                                        want_beta=need[3], keep_bits=bits, inv_keep=ctx.inv_keep)
+        return d_x, d_res, d_gamma, d_beta, None, None, None
 
 
 def add_layernorm_train(x, residual, gamma, beta, eps, keep_bits=None, inv_keep=1.0):
     """add_layernorm() with a backward -> (fp32 rows, their copy in x's dtype).  Both outputs are differentiable; the gradient reaches x
     (in its dtype), residual, gamma and beta.  keep_bits (dropout_bits_rows): LayerNorm(x * keep * inv_keep + residual)."""
-    if keep_bits is not None:
-        return _AddLayerNormTrainDrop.apply(x.contiguous(), None if residual is None else residual.contiguous(), gamma.contiguous(),
-                                            beta.contiguous(), eps, keep_bits, inv_keep)
-    return _AddLayerNormTrain.apply(x.contiguous(), None if residual is None else residual.contiguous(), gamma.contiguous(), beta.contiguous(), eps)
+    return _AddLayerNormTrain.apply(x.contiguous(), None if residual is None else residual.contiguous(), gamma.contiguous(), beta.contiguous(),
+                                    eps, keep_bits, inv_keep)
 
 
 class _GeluTrain(torch.autograd.Function):
@@ -510,138 +560,6 @@ def dropout_apply(x, bits, inv_keep, dtype=torch.bfloat16, want_f32=True, want_h
     return f32, b16
 
 
-def attention_fwd_train_drop(qkv, seq_start, seq_len, n_heads, max_len, keep_q, inv_keep, pad_len=0, scale=0.125):
-    """attention_fwd_train with dropout on the probabilities (ccr_attention_fwd_train_drop_half): the value rounded for the P V product is
-    p * keep * inv_keep; lse is that of the undropped scores.  -> (out, lse)."""
-    lib = _require_encoder_dropout()
-    code = _half_code(qkv.dtype)
-    assert qkv.is_cuda and qkv.dim() == 2 and qkv.is_contiguous()
-    T, width = qkv.shape
-    assert width == 3 * n_heads * 64, f"qkv rows are {width} wide, expected 3 x {n_heads} heads x 64"
-    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
-    assert seq_start.is_contiguous() and seq_len.is_contiguous() and seq_start.numel() == seq_len.numel()
-    _check_bits(keep_q, (T, n_heads, (int(max_len) + 31) // 32))
-    out = torch.empty(T, n_heads * 64, dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty(T, n_heads, dtype=torch.float32, device=qkv.device)
-    with _on(qkv):
-        _lib.check(lib.ccr_attention_fwd_train_drop_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), _ptr(lse), _ptr(keep_q),
-                                                         float(inv_keep), seq_len.numel(), int(n_heads), int(max_len), int(pad_len),
-                                                         float(scale), code, _stream(qkv)), "ccr_attention_fwd_train_drop_half")
-    return out, lse
-
-
-def attention_bwd_drop(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, keep_q, keep_k, inv_keep, pad_len=0, scale=0.125):
-    """attention_bwd for attention_fwd_train_drop's (out, lse) and the same bits (ccr_attention_bwd_drop_half)."""
-    lib = _require_encoder_dropout()
-    code = _half_code(qkv.dtype)
-    T = qkv.shape[0]
-    assert qkv.is_cuda and qkv.is_contiguous() and tuple(qkv.shape) == (T, 3 * n_heads * 64)
-    for t in (out, d_out):
-        assert t.is_cuda and t.dtype == qkv.dtype and tuple(t.shape) == (T, n_heads * 64) and t.is_contiguous()
-    assert lse.is_cuda and lse.dtype == torch.float32 and tuple(lse.shape) == (T, n_heads) and lse.is_contiguous()
-    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_contiguous() and seq_len.is_contiguous()
-    for bits in (keep_q, keep_k):
-        _check_bits(bits, (T, n_heads, (int(max_len) + 31) // 32))
-    n_seq = seq_len.numel()
-    need = int(lib.ccr_attention_bwd_workspace_bytes(n_seq, int(n_heads), int(max_len)))
-    if need == 0:
-        _lib.check(_lib.CCR_ERR_INVALID, "ccr_attention_bwd_workspace_bytes")
-    ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
-    d_qkv = torch.zeros_like(qkv)
-    with _on(qkv):
-        _lib.check(lib.ccr_attention_bwd_drop_half(_ptr(qkv), _ptr(out), _ptr(lse), _ptr(d_out), _ptr(seq_start), _ptr(seq_len), _ptr(keep_q),
-                                                   _ptr(keep_k), float(inv_keep), _ptr(d_qkv), n_seq, int(n_heads), int(max_len), int(pad_len),
-                                                   float(scale), code, _ptr(ws), need, _stream(qkv)), "ccr_attention_bwd_drop_half")
-    return d_qkv
-
-
-def add_layernorm_drop(x, bits, inv_keep, residual, gamma, beta, eps, want_f32=True, want_bf16=True):
-    """add_layernorm on x * keep * inv_keep + residual (ccr_add_layernorm_drop_half); bits int32 [rows, dim / 32]."""
-    lib = _require_encoder_dropout()
-    code = _half_code(x.dtype)
-    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
-    rows, dim = x.shape
-    _check_bits(bits, (rows, dim // 32))
-    if residual is not None:
-        assert residual.is_cuda and residual.dtype == torch.float32 and tuple(residual.shape) == (rows, dim) and residual.is_contiguous()
-    for t in (gamma, beta):
-        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (dim,) and t.is_contiguous()
-    assert want_f32 or want_bf16
-    f32 = torch.empty(rows, dim, dtype=torch.float32, device=x.device) if want_f32 else None
-    b16 = torch.empty(rows, dim, dtype=x.dtype, device=x.device) if want_bf16 else None
-    with _on(x):
-        _lib.check(lib.ccr_add_layernorm_drop_half(_ptr(x), _ptr(bits), float(inv_keep), _ptr(residual), _ptr(gamma), _ptr(beta), float(eps),
-                                                   _ptr(f32), _ptr(b16), rows, dim, code, _stream(x)), "ccr_add_layernorm_drop_half")
-    return f32, b16
-
-
-def add_layernorm_bwd_drop(x, bits, inv_keep, residual, gamma, eps, d_y, want_res=True, want_x=True, want_gamma=True, want_beta=True):
-    """add_layernorm_bwd for add_layernorm_drop (ccr_add_layernorm_bwd_drop_half): d_res = the gradient of the summed input, d_x = d_res *
-    keep * inv_keep rounded to x's dtype, d_gamma, d_beta; None where not wanted."""
-    lib = _require_encoder_dropout()
-    code = _half_code(x.dtype)
-    assert x.is_cuda and x.dim() == 2 and x.is_contiguous()
-    rows, dim = x.shape
-    _check_bits(bits, (rows, dim // 32))
-    if residual is not None:
-        assert residual.is_cuda and residual.dtype == torch.float32 and tuple(residual.shape) == (rows, dim) and residual.is_contiguous()
-    assert gamma.is_cuda and gamma.dtype == torch.float32 and tuple(gamma.shape) == (dim,) and gamma.is_contiguous()
-    assert d_y.is_cuda and d_y.dtype == torch.float32 and tuple(d_y.shape) == (rows, dim) and d_y.is_contiguous()
-    dev = x.device
-    d_res = torch.empty(rows, dim, dtype=torch.float32, device=dev) if want_res else None
-    d_x = torch.empty(rows, dim, dtype=x.dtype, device=dev) if want_x else None
-    d_gamma = torch.empty(dim, dtype=torch.float32, device=dev) if want_gamma else None
-    d_beta = torch.empty(dim, dtype=torch.float32, device=dev) if want_beta else None
-    need = min((rows + 3) // 4, 512) * 2 * dim * 4 if (want_gamma or want_beta) else 0
-    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-    with _on(x):
-        _lib.check(lib.ccr_add_layernorm_bwd_drop_half(_ptr(x), _ptr(bits), float(inv_keep), _ptr(residual), _ptr(gamma), float(eps), _ptr(d_y),
-                                                       _ptr(d_res), _ptr(d_x), _ptr(d_gamma), _ptr(d_beta), rows, dim, code, _ptr(ws), need,
-                                                       _stream(x)), "ccr_add_layernorm_bwd_drop_half")
-    return d_res, d_x, d_gamma, d_beta
-
-
-class _AttentionTrainDrop(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q, keep_k, inv_keep):
-        out, lse = attention_fwd_train_drop(qkv, seq_start, seq_len, n_heads, max_len, keep_q, inv_keep, pad_len, scale)
-        ctx.save_for_backward(qkv, out, lse, seq_start, seq_len, keep_q, keep_k)
-        ctx.shape = (int(n_heads), int(max_len), int(pad_len), float(scale), float(inv_keep))
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        qkv, out, lse, seq_start, seq_len, keep_q, keep_k = ctx.saved_tensors
-        n_heads, max_len, pad_len, scale, inv_keep = ctx.shape
-        d_qkv = attention_bwd_drop(qkv, out, lse, d_out.to(qkv.dtype).contiguous(), seq_start, seq_len, n_heads, max_len, keep_q, keep_k, inv_keep,
-                                   pad_len, scale)
-        return (d_qkv,) + (None,) * 9
-
-
-class _AddLayerNormTrainDrop(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, residual, gamma, beta, eps, bits, inv_keep):
-        f32, b16 = add_layernorm_drop(x, bits, inv_keep, residual, gamma, beta, eps)
-        ctx.save_for_backward(x, residual, gamma, bits)
-        ctx.eps, ctx.inv_keep = float(eps), float(inv_keep)
-        return f32, b16
-
-    @staticmethod
-    def backward(ctx, d_f32, d_b16):
-        x, residual, gamma, bits = ctx.saved_tensors
-        if d_f32 is None:
-            d_y = d_b16.float()
-        elif d_b16 is None:
-            d_y = d_f32.float()
-        else:
-            d_y = d_f32.float() + d_b16
-        need = ctx.needs_input_grad
-        d_res, d_x, d_gamma, d_beta = add_layernorm_bwd_drop(x, bits, ctx.inv_keep, residual, gamma, ctx.eps, d_y.contiguous(),
-                                                             want_res=residual is not None and need[1], want_x=need[0], want_gamma=need[2],
-                                                             want_beta=need[3])
-        return d_x, d_res, d_gamma, d_beta, None, None, None
-
-
 class _DropoutTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bits, inv_keep, dtype):
@@ -653,13 +571,7 @@ class _DropoutTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_f32, d_b16):
         (bits,) = ctx.saved_tensors
-        if d_f32 is None:
-            d_y = d_b16.float()
-        elif d_b16 is None:
-            d_y = d_f32.float()
-        else:
-            d_y = d_f32.float() + d_b16
-        d_x, _ = dropout_apply(d_y.contiguous(), bits, ctx.inv_keep, ctx.dtype, want_half=False)
+        d_x, _ = dropout_apply(_sum_output_grads(d_f32, d_b16).contiguous(), bits, ctx.inv_keep, ctx.dtype, want_half=False)
         return d_x, None, None, None
 
 
@@ -667,6 +579,30 @@ def dropout_train(x, bits, inv_keep, dtype=torch.bfloat16):
     """Dropout of fp32 rows [rows, dim] from explicit keep bits, with a backward (the same operation on the gradient) -> (fp32 rows, their
     copy in `dtype`); both outputs are differentiable.  The site after the embedding LayerNorm."""
     return _DropoutTrain.apply(x.contiguous(), bits, inv_keep, dtype)
+
+
+# ---- the earlier spelling of the ops with keep bits, for callers written against it: each forwards to the one function of its op (the
+# positional order of these differs from the keyword form's, so they stay functions of their own) --------------------------------------
+def attention_fwd_train_drop(qkv, seq_start, seq_len, n_heads, max_len, keep_q, inv_keep, pad_len=0, scale=0.125):
+    return attention_fwd_train(qkv, seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q=keep_q, inv_keep=inv_keep)
+
+
+def attention_bwd_drop(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, keep_q, keep_k, inv_keep, pad_len=0, scale=0.125):
+    return attention_bwd(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q=keep_q, keep_k=keep_k, inv_keep=inv_keep)
+
+
+def add_layernorm_drop(x, bits, inv_keep, residual, gamma, beta, eps, want_f32=True, want_bf16=True):
+    return add_layernorm(x, residual, gamma, beta, eps, want_f32, want_bf16, keep_bits=bits, inv_keep=inv_keep)
+
+
+def add_layernorm_bwd_drop(x, bits, inv_keep, residual, gamma, eps, d_y, want_res=True, want_x=True, want_gamma=True, want_beta=True):
+    return add_layernorm_bwd(x, residual, gamma, eps, d_y, want_res, want_x, want_gamma, want_beta, keep_bits=bits, inv_keep=inv_keep)
+
+
+def embed_layernorm_drop(word_table, position_table, type_table, token_ids, positions, token_types, gamma, beta, eps, keep_bits=None,
+                         inv_keep=1.0, dtype=torch.bfloat16):
+    _require_encoder_packed_train()      # (as it always asked, with or without bits)
+    return embed_layernorm(word_table, position_table, type_table, token_ids, positions, token_types, gamma, beta, eps, dtype, keep_bits, inv_keep)
 
 
 # ---- the fine-tune step in one packed pass (library version 108): the embedding block with a backward (csrc/ccr_encoder.hip,
@@ -688,40 +624,9 @@ def _require_encoder_packed_train():
     return lib
 
 
-def _check_embed_args(word_table, position_table, type_table, token_ids, positions, token_types, gamma):
-    dim = word_table.shape[1]
-    for t in (word_table, position_table, type_table):
-        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == dim and t.is_contiguous()
-    assert gamma.is_cuda and gamma.dtype == torch.float32 and tuple(gamma.shape) == (dim,) and gamma.is_contiguous()
-    T = token_ids.numel()
-    for t in (token_ids, positions) + ((token_types,) if token_types is not None else ()):
-        assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 1 and t.numel() == T and t.is_contiguous()
-    return T, dim
-
-
-def embed_layernorm_drop(word_table, position_table, type_table, token_ids, positions, token_types, gamma, beta, eps, keep_bits=None,
-                         inv_keep=1.0, dtype=torch.bfloat16):
-    """embed_layernorm() followed by the block's dropout from keep bits [T, dim / 32] (ccr_embed_layernorm_train_half): one kernel,
-    the bits of dropout_apply(embed_layernorm(...)).  keep_bits None: no dropout.  -> (fp32 [T, dim], its copy in `dtype`)."""
-    lib = _require_encoder_packed_train()
-    code = _half_code(dtype)
-    T, dim = _check_embed_args(word_table, position_table, type_table, token_ids, positions, token_types, gamma)
-    assert beta.is_cuda and beta.dtype == torch.float32 and tuple(beta.shape) == (dim,) and beta.is_contiguous()
-    if keep_bits is not None:
-        _check_bits(keep_bits, (T, dim // 32))
-    f32 = torch.empty(T, dim, dtype=torch.float32, device=word_table.device)
-    b16 = torch.empty(T, dim, dtype=dtype, device=word_table.device)
-    with _on(word_table):
-        _lib.check(lib.ccr_embed_layernorm_train_half(_ptr(word_table), word_table.shape[0], _ptr(position_table), position_table.shape[0],
-                                                      _ptr(type_table), type_table.shape[0], _ptr(token_ids), _ptr(positions),
-                                                      _ptr(token_types), _ptr(gamma), _ptr(beta), float(eps), _ptr(keep_bits), float(inv_keep),
-                                                      _ptr(f32), _ptr(b16), T, dim, code, _stream(word_table)), "ccr_embed_layernorm_train_half")
-    return f32, b16
-
-
 def embed_layernorm_bwd(word_table, position_table, type_table, token_ids, positions, token_types, gamma, eps, d_y, keep_bits=None,
                         inv_keep=1.0, want_x=True, want_gamma=True, want_beta=True):
-    """The backward of embed_layernorm_drop (ccr_embed_layernorm_bwd_half): d_y [T, dim] fp32 = the summed gradient of both outputs ->
+    """The backward of embed_layernorm, with or without keep bits (ccr_embed_layernorm_bwd_half): d_y [T, dim] fp32 = the summed gradient of both outputs ->
     (d_x fp32 [T, dim] = the gradient of every gathered table row, d_gamma, d_beta [dim] fp32); None where not wanted."""
     lib = _require_encoder_packed_train()
     T, dim = _check_embed_args(word_table, position_table, type_table, token_ids, positions, token_types, gamma)
@@ -732,8 +637,7 @@ def embed_layernorm_bwd(word_table, position_table, type_table, token_ids, posit
     d_x = torch.empty(T, dim, dtype=torch.float32, device=dev) if want_x else None
     d_gamma = torch.empty(dim, dtype=torch.float32, device=dev) if want_gamma else None
     d_beta = torch.empty(dim, dtype=torch.float32, device=dev) if want_beta else None
-    need = min((T + 3) // 4, 512) * 2 * dim * 4 if (want_gamma or want_beta) else 0      # per-workgroup column sums (include/ccr_retrieval.h)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    ws, need = _layernorm_bwd_workspace(T, dim, want_gamma or want_beta, dev)
     with _on(word_table):
         _lib.check(lib.ccr_embed_layernorm_bwd_half(_ptr(word_table), word_table.shape[0], _ptr(position_table), position_table.shape[0],
                                                     _ptr(type_table), type_table.shape[0], _ptr(token_ids), _ptr(positions), _ptr(token_types),
@@ -773,7 +677,8 @@ def embedding_grad(idx, d_x, n_rows, order=None, out=None):
 class _EmbedLayerNormTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, word, pos, types, token_ids, positions, token_types, gamma, beta, eps, bits, inv_keep, dtype):
-        f32, b16 = embed_layernorm_drop(word, pos, types, token_ids, positions, token_types, gamma, beta, eps, bits, inv_keep, dtype)
+        _require_encoder_packed_train()      # (its backward needs it: fail before the forward runs, not in the middle of a step)
+        f32, b16 = embed_layernorm(word, pos, types, token_ids, positions, token_types, gamma, beta, eps, dtype, bits, inv_keep)
         ctx.save_for_backward(word, pos, types, token_ids, positions, token_types, gamma, bits)
         ctx.eps, ctx.inv_keep = float(eps), float(inv_keep)
         return f32, b16
@@ -781,16 +686,9 @@ class _EmbedLayerNormTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_f32, d_b16):
         word, pos, types, token_ids, positions, token_types, gamma, bits = ctx.saved_tensors
-        # the two outputs are one value in two precisions: their gradients add up (fp32) before the kernel runs
-        if d_f32 is None:
-            d_y = d_b16.float()
-        elif d_b16 is None:
-            d_y = d_f32.float()
-        else:
-            d_y = d_f32.float() + d_b16
         need = ctx.needs_input_grad
-        d_x, d_gamma, d_beta = embed_layernorm_bwd(word, pos, types, token_ids, positions, token_types, gamma, ctx.eps, d_y.contiguous(), bits,
-                                                   ctx.inv_keep, want_x=any(need[:3]), want_gamma=need[6], want_beta=need[7])
+        d_x, d_gamma, d_beta = embed_layernorm_bwd(word, pos, types, token_ids, positions, token_types, gamma, ctx.eps,
+                                                   _sum_output_grads(d_f32, d_b16).contiguous(), bits, ctx.inv_keep, want_x=any(need[:3]), want_gamma=need[6], want_beta=need[7])
         d_word = embedding_grad(token_ids, d_x, word.shape[0]) if need[0] else None
         d_pos = embedding_grad(positions, d_x, pos.shape[0]) if need[1] else None
         d_types = None
@@ -805,7 +703,7 @@ class _EmbedLayerNormTrain(torch.autograd.Function):
 def embed_layernorm_train(word_table, position_table, type_table, token_ids, positions, token_types, gamma, beta, eps, keep_bits=None,
                           inv_keep=1.0, dtype=torch.bfloat16):
     """The embedding block with a backward: dropout(LayerNorm((word[ids] + type[types]) + position[positions])) -> (fp32 [T, dim], its copy
-    in `dtype`), both differentiable.  Forward = embed_layernorm_drop (embed_layernorm's bits without keep_bits); backward =
+    in `dtype`), both differentiable.  Forward = embed_layernorm (the inference kernel's bits without keep_bits); backward =
     embed_layernorm_bwd, then one embedding_grad per table that needs a gradient (needs_input_grad is honoured: a frozen table costs
     nothing).  Tables, gamma, beta: contiguous fp32; index vectors int64 [T], token_types may be None = type 0."""
     return _EmbedLayerNormTrain.apply(word_table, position_table, type_table, token_ids.contiguous(), positions.contiguous(),

@@ -345,30 +345,14 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const uint16_t *__re
         }
         sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = refined_mean<C>(v, sum * (1.f / DIM));
-    float sq = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float d = v[c][j] - mean;
-            sq = fmaf(d, d, sq);
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-    const float rstd = rsqrtf(sq * (1.f / DIM) + eps);
+    float mean, rstd;
+    row_mean_rstd<C>(v, sum, eps, mean, rstd);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const int col = 4 * (64 * c + lane);
         const float4 gm = *reinterpret_cast<const float4 *>(gamma + col);
         const float4 bt = *reinterpret_cast<const float4 *>(beta + col);
-        float4 y;
-        y.x = fmaf((v[c][0] - mean) * rstd, gm.x, bt.x);
-        y.y = fmaf((v[c][1] - mean) * rstd, gm.y, bt.y);
-        y.z = fmaf((v[c][2] - mean) * rstd, gm.z, bt.z);
-        y.w = fmaf((v[c][3] - mean) * rstd, gm.w, bt.w);
+        float4 y = layernorm_row_out<C>(v, c, mean, rstd, gm, bt);
         if (out_f32) *reinterpret_cast<float4 *>(out_f32 + row * DIM + col) = y;
         if (out_bf16) *reinterpret_cast<uint2 *>(out_bf16 + row * DIM + col) = round4<typename Half16<DT>::elem>(y.x, y.y, y.z, y.w);
     }
@@ -409,30 +393,14 @@ __global__ __launch_bounds__(256) void embed_layernorm_kernel(const float *__res
         v[c][3] = (a.w + b.w) + d.w;
         sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = refined_mean<C>(v, sum * (1.f / DIM));
-    float sq = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float d = v[c][j] - mean;
-            sq = fmaf(d, d, sq);
-        }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-    const float rstd = rsqrtf(sq * (1.f / DIM) + eps);
+    float mean, rstd;
+    row_mean_rstd<C>(v, sum, eps, mean, rstd);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const int col = 4 * (64 * c + lane);
         const float4 gm = *reinterpret_cast<const float4 *>(gamma + col);
         const float4 bt = *reinterpret_cast<const float4 *>(beta + col);
-        float4 y;
-        y.x = fmaf((v[c][0] - mean) * rstd, gm.x, bt.x);
-        y.y = fmaf((v[c][1] - mean) * rstd, gm.y, bt.y);
-        y.z = fmaf((v[c][2] - mean) * rstd, gm.z, bt.z);
-        y.w = fmaf((v[c][3] - mean) * rstd, gm.w, bt.w);
+        float4 y = layernorm_row_out<C>(v, c, mean, rstd, gm, bt);
         if constexpr (DROP) {
             float mk[4];
             keep_nibble(keep, row * (DIM / 32), 64 * c + lane, mk);
@@ -462,58 +430,6 @@ __global__ __launch_bounds__(256) void gelu_kernel(const uint4 *__restrict__ x, 
         const uint2 r0 = round4<typename HT::elem>(g[0], g[1], g[2], g[3]), r1 = round4<typename HT::elem>(g[4], g[5], g[6], g[7]);
         y[i] = make_uint4(r0.x, r0.y, r1.x, r1.y);
     }
-}
-
-template <int C, int DT, bool DROP>
-static int launch_add_layernorm(const uint16_t *x, const float *res, const float *gamma, const float *beta, float eps,
-                                float *out_f32, uint16_t *out_half, int64_t rows, hipStream_t s, typename KeepArg<DROP>::type keep) {
-    hipLaunchKernelGGL((add_layernorm_kernel<C, DT, DROP>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, res, gamma, beta, eps,
-                       out_f32, out_half, rows, keep);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
-}
-
-template <int DT, bool DROP = false>
-static int add_layernorm_any(const uint16_t *x, const float *res, const float *gamma, const float *beta, float eps, float *out_f32,
-                             uint16_t *out_half, int64_t rows, int dim, hipStream_t s, typename KeepArg<DROP>::type keep = {}) {
-    switch (dim / 256) {
-        case 1: return launch_add_layernorm<1, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
-        case 2: return launch_add_layernorm<2, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
-        case 3: return launch_add_layernorm<3, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
-        case 4: return launch_add_layernorm<4, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
-        case 5: return launch_add_layernorm<5, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
-        case 6: return launch_add_layernorm<6, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
-        case 7: return launch_add_layernorm<7, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
-        default: return launch_add_layernorm<8, DT, DROP>(x, res, gamma, beta, eps, out_f32, out_half, rows, s, keep);
-    }
-}
-
-template <int DT, bool DROP = false>
-static int embed_layernorm_any(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
-                               const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
-                               const int64_t *token_types, const float *gamma, const float *beta, float eps, float *out_f32,
-                               uint16_t *out_half, int64_t rows, int dim, hipStream_t s, typename KeepArg<DROP>::type keep = {}) {
-    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define CCR_EMBED_CASE(C)                                                                                                              \
-    case C:                                                                                                                            \
-        hipLaunchKernelGGL((embed_layernorm_kernel<C, DT, DROP>), grid, block, 0, s, word_table, vocab, position_table, n_positions,   \
-                           type_table, n_types, token_ids, positions, token_types, gamma, beta, eps, out_f32, out_half, rows, keep);   \
-        break;
-    switch (dim / 256) {
-        CCR_EMBED_CASE(1)
-        CCR_EMBED_CASE(2)
-        CCR_EMBED_CASE(3)
-        CCR_EMBED_CASE(4)
-        CCR_EMBED_CASE(5)
-        CCR_EMBED_CASE(6)
-        CCR_EMBED_CASE(7)
-        default:
-            hipLaunchKernelGGL((embed_layernorm_kernel<8, DT, DROP>), grid, block, 0, s, word_table, vocab, position_table, n_positions,
-                               type_table, n_types, token_ids, positions, token_types, gamma, beta, eps, out_f32, out_half, rows, keep);
-    }
-#undef CCR_EMBED_CASE
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
 }
 
 template <int DT, bool LSE = false, bool DROP = false>
@@ -564,53 +480,91 @@ static int gelu_any(const uint16_t *x, uint16_t *y, int64_t n, hipStream_t strea
 
 using namespace ccr;
 
+// ---- The implementations behind the exported pairs (plain / _drop_half, inference / _train_half): a null bits pointer means no dropout.
+// Each reports its errors under the exported function's name `who`; every check runs before any launch.
+
+static int attention_fwd_train(const char *who, const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, float *lse,
+                               const uint32_t *keep_q, float inv_keep, int n_seq, int n_heads, int max_len, int pad_len, float scale,
+                               int half_dtype, hipStream_t s) {
+    if (const int rc = check_attention_shape(who, half_dtype, n_seq, n_heads, max_len, pad_len, scale)) return rc;
+    if (keep_q)
+        if (const int rc = check_inv_keep(who, inv_keep)) return rc;
+    if (n_seq == 0) return CCR_OK;
+    return dispatch_half(half_dtype, [&](auto dt) {
+        return dispatch_drop(keep_q != nullptr, [&](auto drop) {
+            constexpr bool DROP = decltype(drop)::value;
+            return attention_any<decltype(dt)::value, true, DROP>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, s, lse,
+                                                                  keep_arg<DROP>(keep_q, inv_keep, (max_len + 31) / 32));
+        });
+    });
+}
+
+static int add_layernorm(const char *who, const uint16_t *x, const uint32_t *bits, float inv_keep, const float *res, const float *gamma,
+                         const float *beta, float eps, float *out_f32, uint16_t *out_half, int64_t rows, int dim, int half_dtype,
+                         hipStream_t s) {
+    if (const int rc = check_half(who, half_dtype)) return rc;
+    if (const int rc = check_rows_dim(who, rows, dim)) return rc;
+    if (bits)
+        if (const int rc = check_inv_keep(who, inv_keep)) return rc;
+    if (rows == 0) return CCR_OK;
+    return dispatch_width(dim, [&](auto c) {
+        return dispatch_half(half_dtype, [&](auto dt) {
+            return dispatch_drop(bits != nullptr, [&](auto drop) {
+                constexpr bool DROP = decltype(drop)::value;
+                return launch_row_kernel(add_layernorm_kernel<decltype(c)::value, decltype(dt)::value, DROP>, (rows + 3) / 4, s, x, res, gamma, beta, eps,
+                                   out_f32, out_half, rows, keep_arg<DROP>(bits, inv_keep, 0));
+            });
+        });
+    });
+}
+
+static int embed_layernorm(const char *who, const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
+                           const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
+                           const int64_t *token_types, const float *gamma, const float *beta, float eps, const uint32_t *bits, float inv_keep,
+                           float *out_f32, uint16_t *out_half, int64_t rows, int dim, int half_dtype, hipStream_t s) {
+    CCR_REQUIRE(word_table && position_table && type_table && token_ids && positions && gamma && beta && (out_f32 || out_half),
+                "%s: null pointer", who);
+    if (const int rc = check_half(who, half_dtype)) return rc;
+    CCR_REQUIRE(vocab > 0 && n_positions > 0 && n_types > 0, "%s: empty table", who);
+    if (const int rc = check_rows_dim(who, rows, dim)) return rc;
+    if (bits)
+        if (const int rc = check_inv_keep(who, inv_keep)) return rc;
+    if (rows == 0) return CCR_OK;
+    return dispatch_width(dim, [&](auto c) {
+        return dispatch_half(half_dtype, [&](auto dt) {
+            return dispatch_drop(bits != nullptr, [&](auto drop) {   // no bits: the inference kernel, no extra loads
+                constexpr bool DROP = decltype(drop)::value;
+                return launch_row_kernel(embed_layernorm_kernel<decltype(c)::value, decltype(dt)::value, DROP>, (rows + 3) / 4, s, word_table, vocab,
+                                   position_table, n_positions, type_table, n_types, token_ids, positions, token_types, gamma, beta, eps,
+                                   out_f32, out_half, rows, keep_arg<DROP>(bits, inv_keep, 0));
+            });
+        });
+    });
+}
+
 extern "C" int ccr_attention_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, int n_seq,
                                   int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *stream) {
     CCR_REQUIRE(qkv && seq_start && seq_len && out, "ccr_attention_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_attention_half");
-    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024, "ccr_attention_half: bad shape n_seq=%d n_heads=%d",
-                n_seq, n_heads);
-    CCR_REQUIRE(max_len > 0 && max_len <= 512 && pad_len >= 0 && pad_len <= 512,
-                "ccr_attention_half: max_len=%d pad_len=%d (1..512 tokens per sequence)", max_len, pad_len);
-    CCR_REQUIRE(scale > 0.f, "ccr_attention_half: scale must be positive");
+    if (const int rc = check_attention_shape("ccr_attention_half", half_dtype, n_seq, n_heads, max_len, pad_len, scale)) return rc;
     if (n_seq == 0) return CCR_OK;
-    return half_dtype == CCR_DTYPE_F16
-               ? attention_any<CCR_DTYPE_F16>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream)
-               : attention_any<CCR_DTYPE_BF16>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream);
+    return dispatch_half(half_dtype, [&](auto dt) {
+        return attention_any<decltype(dt)::value>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream);
+    });
 }
 
 extern "C" int ccr_attention_fwd_train_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, float *lse,
                                             int n_seq, int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *stream) {
     CCR_REQUIRE(qkv && seq_start && seq_len && out && lse, "ccr_attention_fwd_train_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_attention_fwd_train_half");
-    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024, "ccr_attention_fwd_train_half: bad shape n_seq=%d n_heads=%d",
-                n_seq, n_heads);
-    CCR_REQUIRE(max_len > 0 && max_len <= 512 && pad_len >= 0 && pad_len <= 512,
-                "ccr_attention_fwd_train_half: max_len=%d pad_len=%d (1..512 tokens per sequence)", max_len, pad_len);
-    CCR_REQUIRE(scale > 0.f, "ccr_attention_fwd_train_half: scale must be positive");
-    if (n_seq == 0) return CCR_OK;
-    return half_dtype == CCR_DTYPE_F16
-               ? attention_any<CCR_DTYPE_F16, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream, lse)
-               : attention_any<CCR_DTYPE_BF16, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream, lse);
+    return attention_fwd_train("ccr_attention_fwd_train_half", qkv, seq_start, seq_len, out, lse, nullptr, 1.f, n_seq, n_heads, max_len, pad_len,
+                               scale, half_dtype, (hipStream_t)stream);
 }
 
 extern "C" int ccr_attention_fwd_train_drop_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out,
                                                  float *lse, const uint32_t *keep_q, float inv_keep, int n_seq, int n_heads, int max_len,
                                                  int pad_len, float scale, int half_dtype, void *stream) {
     CCR_REQUIRE(qkv && seq_start && seq_len && out && lse && keep_q, "ccr_attention_fwd_train_drop_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_attention_fwd_train_drop_half");
-    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024,
-                "ccr_attention_fwd_train_drop_half: bad shape n_seq=%d n_heads=%d", n_seq, n_heads);
-    CCR_REQUIRE(max_len > 0 && max_len <= 512 && pad_len >= 0 && pad_len <= 512,
-                "ccr_attention_fwd_train_drop_half: max_len=%d pad_len=%d (1..512 tokens per sequence)", max_len, pad_len);
-    CCR_REQUIRE(scale > 0.f, "ccr_attention_fwd_train_drop_half: scale must be positive");
-    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "ccr_attention_fwd_train_drop_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
-    if (n_seq == 0) return CCR_OK;
-    const KeepBits keep = {keep_q, inv_keep, (max_len + 31) / 32};
-    return half_dtype == CCR_DTYPE_F16 ? attention_any<CCR_DTYPE_F16, true, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len,
-                                                                                  scale, (hipStream_t)stream, lse, keep)
-                                       : attention_any<CCR_DTYPE_BF16, true, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len,
-                                                                                   scale, (hipStream_t)stream, lse, keep);
+    return attention_fwd_train("ccr_attention_fwd_train_drop_half", qkv, seq_start, seq_len, out, lse, keep_q, inv_keep, n_seq, n_heads, max_len,
+                               pad_len, scale, half_dtype, (hipStream_t)stream);
 }
 
 extern "C" int ccr_attention_bf16(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out,
@@ -621,29 +575,16 @@ extern "C" int ccr_attention_bf16(const uint16_t *qkv, const int32_t *seq_start,
 extern "C" int ccr_add_layernorm_half(const uint16_t *x_half, const float *residual, const float *gamma, const float *beta, float eps,
                                       float *out_f32, uint16_t *out_half, int64_t rows, int dim, int half_dtype, void *stream) {
     CCR_REQUIRE(x_half && gamma && beta && (out_f32 || out_half), "ccr_add_layernorm_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_add_layernorm_half");
-    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
-                "ccr_add_layernorm_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
-    if (rows == 0) return CCR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    return half_dtype == CCR_DTYPE_F16 ? add_layernorm_any<CCR_DTYPE_F16>(x_half, residual, gamma, beta, eps, out_f32, out_half, rows, dim, s)
-                                       : add_layernorm_any<CCR_DTYPE_BF16>(x_half, residual, gamma, beta, eps, out_f32, out_half, rows, dim, s);
+    return add_layernorm("ccr_add_layernorm_half", x_half, nullptr, 1.f, residual, gamma, beta, eps, out_f32, out_half, rows, dim, half_dtype,
+                         (hipStream_t)stream);
 }
 
 extern "C" int ccr_add_layernorm_drop_half(const uint16_t *x_half, const uint32_t *bits, float inv_keep, const float *residual,
                                            const float *gamma, const float *beta, float eps, float *out_f32, uint16_t *out_half, int64_t rows,
                                            int dim, int half_dtype, void *stream) {
     CCR_REQUIRE(x_half && bits && gamma && beta && (out_f32 || out_half), "ccr_add_layernorm_drop_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_add_layernorm_drop_half");
-    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
-                "ccr_add_layernorm_drop_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
-    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "ccr_add_layernorm_drop_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
-    if (rows == 0) return CCR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const KeepBits keep = {bits, inv_keep, 0};
-    return half_dtype == CCR_DTYPE_F16
-               ? add_layernorm_any<CCR_DTYPE_F16, true>(x_half, residual, gamma, beta, eps, out_f32, out_half, rows, dim, s, keep)
-               : add_layernorm_any<CCR_DTYPE_BF16, true>(x_half, residual, gamma, beta, eps, out_f32, out_half, rows, dim, s, keep);
+    return add_layernorm("ccr_add_layernorm_drop_half", x_half, bits, inv_keep, residual, gamma, beta, eps, out_f32, out_half, rows, dim,
+                         half_dtype, (hipStream_t)stream);
 }
 
 extern "C" int ccr_add_layernorm(const uint16_t *x_bf16, const float *residual, const float *gamma, const float *beta, float eps,
@@ -655,19 +596,8 @@ extern "C" int ccr_embed_layernorm_half(const float *word_table, int64_t vocab, 
                                         const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
                                         const int64_t *token_types, const float *gamma, const float *beta, float eps, float *out_f32,
                                         uint16_t *out_half, int64_t rows, int dim, int half_dtype, void *stream) {
-    CCR_REQUIRE(word_table && position_table && type_table && token_ids && positions && gamma && beta && (out_f32 || out_half),
-                "ccr_embed_layernorm_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_embed_layernorm_half");
-    CCR_REQUIRE(vocab > 0 && n_positions > 0 && n_types > 0, "ccr_embed_layernorm_half: empty table");
-    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
-                "ccr_embed_layernorm_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
-    if (rows == 0) return CCR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    return half_dtype == CCR_DTYPE_F16
-               ? embed_layernorm_any<CCR_DTYPE_F16>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
-                                                    positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s)
-               : embed_layernorm_any<CCR_DTYPE_BF16>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
-                                                     positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s);
+    return embed_layernorm("ccr_embed_layernorm_half", word_table, vocab, position_table, n_positions, type_table, n_types, token_ids, positions,
+                           token_types, gamma, beta, eps, nullptr, 1.f, out_f32, out_half, rows, dim, half_dtype, (hipStream_t)stream);
 }
 
 extern "C" int ccr_embed_layernorm_train_half(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
@@ -675,27 +605,9 @@ extern "C" int ccr_embed_layernorm_train_half(const float *word_table, int64_t v
                                               const int64_t *token_types, const float *gamma, const float *beta, float eps,
                                               const uint32_t *bits, float inv_keep, float *out_f32, uint16_t *out_half, int64_t rows, int dim,
                                               int half_dtype, void *stream) {
-    CCR_REQUIRE(word_table && position_table && type_table && token_ids && positions && gamma && beta && (out_f32 || out_half),
-                "ccr_embed_layernorm_train_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_embed_layernorm_train_half");
-    CCR_REQUIRE(vocab > 0 && n_positions > 0 && n_types > 0, "ccr_embed_layernorm_train_half: empty table");
-    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
-                "ccr_embed_layernorm_train_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
-    CCR_REQUIRE(!bits || (inv_keep >= 1.f && inv_keep <= 65536.f), "ccr_embed_layernorm_train_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
-    if (rows == 0) return CCR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (!bits)   // no dropout: the inference kernel, no extra loads
-        return half_dtype == CCR_DTYPE_F16
-                   ? embed_layernorm_any<CCR_DTYPE_F16>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
-                                                        positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s)
-                   : embed_layernorm_any<CCR_DTYPE_BF16>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
-                                                         positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s);
-    const KeepBits keep = {bits, inv_keep, 0};
-    return half_dtype == CCR_DTYPE_F16
-               ? embed_layernorm_any<CCR_DTYPE_F16, true>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
-                                                          positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s, keep)
-               : embed_layernorm_any<CCR_DTYPE_BF16, true>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
-                                                           positions, token_types, gamma, beta, eps, out_f32, out_half, rows, dim, s, keep);
+    return embed_layernorm("ccr_embed_layernorm_train_half", word_table, vocab, position_table, n_positions, type_table, n_types, token_ids,
+                           positions, token_types, gamma, beta, eps, bits, inv_keep, out_f32, out_half, rows, dim, half_dtype,
+                           (hipStream_t)stream);
 }
 
 extern "C" int ccr_embed_layernorm(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
@@ -708,12 +620,11 @@ extern "C" int ccr_embed_layernorm(const float *word_table, int64_t vocab, const
 
 extern "C" int ccr_gelu_half(const uint16_t *x, uint16_t *y, int64_t n, int half_dtype, void *stream) {
     CCR_REQUIRE(x && y, "ccr_gelu_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_gelu_half");
+    if (const int rc = check_half("ccr_gelu_half", half_dtype)) return rc;
     CCR_REQUIRE(n >= 0 && n % 8 == 0, "ccr_gelu_half: n=%lld (a multiple of 8 elements)", (long long)n);
     CCR_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0, "ccr_gelu_half: 16-byte aligned arrays");
     if (n == 0) return CCR_OK;
-    return half_dtype == CCR_DTYPE_F16 ? gelu_any<CCR_DTYPE_F16>(x, y, n, (hipStream_t)stream)
-                                       : gelu_any<CCR_DTYPE_BF16>(x, y, n, (hipStream_t)stream);
+    return dispatch_half(half_dtype, [&](auto dt) { return gelu_any<decltype(dt)::value>(x, y, n, (hipStream_t)stream); });
 }
 
 extern "C" int ccr_gelu_bf16(const uint16_t *x, uint16_t *y, int64_t n, void *stream) {

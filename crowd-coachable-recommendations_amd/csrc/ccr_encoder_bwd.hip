@@ -308,8 +308,9 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const uint16_t *
                                                                float *__restrict__ partial, int64_t rows,
                                                                typename KeepArg<DROP>::type keep = {}) {
     constexpr int DIM = 256 * C;
-    __shared__ float red[3][DIM];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // gamma and the zeroed column sums stay written out in the two backward kernels: as a shared function these eight lines cost every
+    // instantiation two VGPRs (ccr_encoder_common.h holds the rest of the row body)
     float gm[C][4], ag[C][4], ab[C][4];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -344,47 +345,13 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const uint16_t *
             }
             sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        const float mean = refined_mean<C>(v, sum * (1.f / DIM));
-        float sq = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float dd = v[c][j] - mean;
-                sq = fmaf(dd, dd, sq);
-            }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-        const float rstd = rsqrtf(sq * (1.f / DIM) + eps);
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float xh = (v[c][j] - mean) * rstd;
-                const float gy = d[c][j] * gm[c][j];
-                v[c][j] = xh;
-                s1 += gy;
-                s2 = fmaf(gy, xh, s2);
-                ag[c][j] = fmaf(d[c][j], xh, ag[c][j]);
-                ab[c][j] += d[c][j];
-            }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s1 += __shfl_xor(s1, o);
-            s2 += __shfl_xor(s2, o);
-        }
-        const float m1 = s1 * (1.f / DIM), m2 = s2 * (1.f / DIM);
+        float mean, rstd, m1, m2;
+        row_mean_rstd<C>(v, sum, eps, mean, rstd);
+        layernorm_bwd_row<C>(v, d, gm, mean, rstd, ag, ab, m1, m2);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const int col = 4 * (64 * c + lane);
-            float4 y;
-            y.x = rstd * ((d[c][0] * gm[c][0] - m1) - v[c][0] * m2);
-            y.y = rstd * ((d[c][1] * gm[c][1] - m1) - v[c][1] * m2);
-            y.z = rstd * ((d[c][2] * gm[c][2] - m1) - v[c][2] * m2);
-            y.w = rstd * ((d[c][3] * gm[c][3] - m1) - v[c][3] * m2);
+            const float4 y = layernorm_bwd_dv<C>(v, d, gm, c, rstd, m1, m2);
             if (d_res) *reinterpret_cast<float4 *>(d_res + row * DIM + col) = y;
             if constexpr (DROP) {
                 if (d_x) {
@@ -399,30 +366,7 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const uint16_t *
         }
     }
     if (!partial) return;   // (workgroup-uniform)
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-        if (which) __syncthreads();
-        if (wave > 0) {
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-                *reinterpret_cast<float4 *>(&red[wave - 1][4 * (64 * c + lane)]) =
-                    which ? make_float4(ab[c][0], ab[c][1], ab[c][2], ab[c][3]) : make_float4(ag[c][0], ag[c][1], ag[c][2], ag[c][3]);
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int col = 4 * (64 * c + lane);
-                float4 t = which ? make_float4(ab[c][0], ab[c][1], ab[c][2], ab[c][3]) : make_float4(ag[c][0], ag[c][1], ag[c][2], ag[c][3]);
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    const float4 u = *reinterpret_cast<const float4 *>(&red[w][col]);
-                    t.x += u.x, t.y += u.y, t.z += u.z, t.w += u.w;
-                }
-                *reinterpret_cast<float4 *>(partial + ((int64_t)blockIdx.x * 2 + which) * DIM + col) = t;
-            }
-        }
-    }
+    layernorm_bwd_flush<C>(ag, ab, partial, lane, wave);
 }
 
 // Second stage: column vc of partial [nblk][2 * dim] (gamma sums | beta sums) summed over the workgroups in a fixed order: four thread
@@ -451,8 +395,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_reduce_kernel(const float *
 // ---- Embedding block backward (ccr_embed_layernorm_bwd_half): add_layernorm_bwd_kernel's row arithmetic on v = (word[id] + type[t]) +
 // position[p], gathered and summed as embed_layernorm_kernel does, so mean and rstd are the forward's.  DROP = true: the block's dropout
 // sits AFTER the LayerNorm, so the gradient that enters it is d_v = d_y * (keep ? inv_keep : 0); d gamma and d beta sum d_v.  d_x stays
-// fp32 (it feeds ccr_embedding_grad).  The row body is written out here, not shared with add_layernorm_bwd_kernel: that kernel's operand
-// loads, dropout site (before the sum) and 16-bit output differ, and its instantiations keep their code.
+// fp32 (it feeds ccr_embedding_grad).
 template <int C, bool DROP = false>
 __global__ __launch_bounds__(256) void embed_layernorm_bwd_kernel(const float *__restrict__ word, int64_t vocab,
                                                                  const float *__restrict__ pos_tab, int64_t n_pos,
@@ -463,7 +406,6 @@ __global__ __launch_bounds__(256) void embed_layernorm_bwd_kernel(const float *_
                                                                  float *__restrict__ partial, int64_t rows,
                                                                  typename KeepArg<DROP>::type keep = {}) {
     constexpr int DIM = 256 * C;
-    __shared__ float red[3][DIM];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     auto clamp = [](int64_t v, int64_t n) { return v < 0 ? (int64_t)0 : (v >= n ? n - 1 : v); };
     float gm[C][4], ag[C][4], ab[C][4];
@@ -500,77 +442,20 @@ __global__ __launch_bounds__(256) void embed_layernorm_bwd_kernel(const float *_
             }
             sum += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        const float mean = refined_mean<C>(v, sum * (1.f / DIM));
-        float sq = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float dd = v[c][j] - mean;
-                sq = fmaf(dd, dd, sq);
-            }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-        const float rstd = rsqrtf(sq * (1.f / DIM) + eps);
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float xh = (v[c][j] - mean) * rstd;
-                const float gy = d[c][j] * gm[c][j];
-                v[c][j] = xh;
-                s1 += gy;
-                s2 = fmaf(gy, xh, s2);
-                ag[c][j] = fmaf(d[c][j], xh, ag[c][j]);
-                ab[c][j] += d[c][j];
-            }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s1 += __shfl_xor(s1, o);
-            s2 += __shfl_xor(s2, o);
-        }
-        const float m1 = s1 * (1.f / DIM), m2 = s2 * (1.f / DIM);
+        float mean, rstd, m1, m2;
+        row_mean_rstd<C>(v, sum, eps, mean, rstd);
+        layernorm_bwd_row<C>(v, d, gm, mean, rstd, ag, ab, m1, m2);
         if (d_x) {
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 const int col = 4 * (64 * c + lane);
-                float4 y;
-                y.x = rstd * ((d[c][0] * gm[c][0] - m1) - v[c][0] * m2);
-                y.y = rstd * ((d[c][1] * gm[c][1] - m1) - v[c][1] * m2);
-                y.z = rstd * ((d[c][2] * gm[c][2] - m1) - v[c][2] * m2);
-                y.w = rstd * ((d[c][3] * gm[c][3] - m1) - v[c][3] * m2);
+                const float4 y = layernorm_bwd_dv<C>(v, d, gm, c, rstd, m1, m2);
                 *reinterpret_cast<float4 *>(d_x + row * DIM + col) = y;
             }
         }
     }
     if (!partial) return;   // (workgroup-uniform)
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-        if (which) __syncthreads();
-        if (wave > 0) {
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-                *reinterpret_cast<float4 *>(&red[wave - 1][4 * (64 * c + lane)]) =
-                    which ? make_float4(ab[c][0], ab[c][1], ab[c][2], ab[c][3]) : make_float4(ag[c][0], ag[c][1], ag[c][2], ag[c][3]);
-        }
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int col = 4 * (64 * c + lane);
-                float4 t = which ? make_float4(ab[c][0], ab[c][1], ab[c][2], ab[c][3]) : make_float4(ag[c][0], ag[c][1], ag[c][2], ag[c][3]);
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    const float4 u = *reinterpret_cast<const float4 *>(&red[w][col]);
-                    t.x += u.x, t.y += u.y, t.z += u.z, t.w += u.w;
-                }
-                *reinterpret_cast<float4 *>(partial + ((int64_t)blockIdx.x * 2 + which) * DIM + col) = t;
-            }
-        }
-    }
+    layernorm_bwd_flush<C>(ag, ab, partial, lane, wave);
 }
 
 // d_x = d_y (Phi(x) + x phi(x)) of the exact GELU, from the pre-activation: fp32, rounded once, 16 bytes per lane per access.
@@ -623,59 +508,6 @@ static int attention_bwd_any(const uint16_t *qkv, const uint16_t *out, const flo
     return CCR_OK;
 }
 
-template <int C, int DT, bool DROP>
-static int launch_add_layernorm_bwd(const uint16_t *x, const float *res, const float *gamma, float eps, const float *dy, float *d_res,
-                                    uint16_t *d_x, float *partial, int nblk, int64_t rows, hipStream_t s, typename KeepArg<DROP>::type keep) {
-    hipLaunchKernelGGL((add_layernorm_bwd_kernel<C, DT, DROP>), dim3((unsigned)nblk), dim3(256), 0, s, x, res, gamma, eps, dy, d_res, d_x, partial,
-                       rows, keep);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
-}
-
-template <int DT, bool DROP = false>
-static int add_layernorm_bwd_any(const uint16_t *x, const float *res, const float *gamma, float eps, const float *dy, float *d_res,
-                                 uint16_t *d_x, float *partial, int nblk, int64_t rows, int dim, hipStream_t s,
-                                 typename KeepArg<DROP>::type keep = {}) {
-    switch (dim / 256) {
-        case 1: return launch_add_layernorm_bwd<1, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
-        case 2: return launch_add_layernorm_bwd<2, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
-        case 3: return launch_add_layernorm_bwd<3, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
-        case 4: return launch_add_layernorm_bwd<4, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
-        case 5: return launch_add_layernorm_bwd<5, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
-        case 6: return launch_add_layernorm_bwd<6, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
-        case 7: return launch_add_layernorm_bwd<7, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
-        default: return launch_add_layernorm_bwd<8, DT, DROP>(x, res, gamma, eps, dy, d_res, d_x, partial, nblk, rows, s, keep);
-    }
-}
-
-template <bool DROP>
-static int embed_layernorm_bwd_any(const float *word, int64_t vocab, const float *pos_tab, int64_t n_pos, const float *type_tab, int64_t n_types,
-                                   const int64_t *ids, const int64_t *pos, const int64_t *types, const float *gamma, float eps, const float *dy,
-                                   float *d_x, float *partial, int nblk, int64_t rows, int dim, hipStream_t s,
-                                   typename KeepArg<DROP>::type keep = {}) {
-    const dim3 grid((unsigned)nblk), block(256);
-#define CCR_EMBED_BWD_CASE(C)                                                                                                             \
-    case C:                                                                                                                               \
-        hipLaunchKernelGGL((embed_layernorm_bwd_kernel<C, DROP>), grid, block, 0, s, word, vocab, pos_tab, n_pos, type_tab, n_types, ids, \
-                           pos, types, gamma, eps, dy, d_x, partial, rows, keep);                                                         \
-        break;
-    switch (dim / 256) {
-        CCR_EMBED_BWD_CASE(1)
-        CCR_EMBED_BWD_CASE(2)
-        CCR_EMBED_BWD_CASE(3)
-        CCR_EMBED_BWD_CASE(4)
-        CCR_EMBED_BWD_CASE(5)
-        CCR_EMBED_BWD_CASE(6)
-        CCR_EMBED_BWD_CASE(7)
-        default:
-            hipLaunchKernelGGL((embed_layernorm_bwd_kernel<8, DROP>), grid, block, 0, s, word, vocab, pos_tab, n_pos, type_tab, n_types, ids,
-                               pos, types, gamma, eps, dy, d_x, partial, rows, keep);
-    }
-#undef CCR_EMBED_BWD_CASE
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
-}
-
 template <int DT>
 static int gelu_bwd_any(const uint16_t *x, const uint16_t *dy, uint16_t *dx, int64_t n, hipStream_t stream) {
     const int64_t n16 = n / 8;
@@ -700,29 +532,91 @@ extern "C" size_t ccr_attention_bwd_workspace_bytes(int n_seq, int n_heads, int 
     return need ? need : sizeof(float);
 }
 
+// ---- The implementations behind the exported pairs: null bits pointers mean no dropout.  Each reports its errors under the exported
+// function's name `who`; every check runs before any launch.
+
+static int attention_bwd(const char *who, const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *d_out,
+                         const int32_t *seq_start, const int32_t *seq_len, const uint32_t *keep_q, const uint32_t *keep_k, float inv_keep,
+                         uint16_t *d_qkv, int n_seq, int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *workspace,
+                         size_t workspace_bytes, hipStream_t s) {
+    if (const int rc = check_attention_shape(who, half_dtype, n_seq, n_heads, max_len, pad_len, scale)) return rc;
+    if (keep_q)
+        if (const int rc = check_inv_keep(who, inv_keep)) return rc;
+    const size_t need = ccr_attention_bwd_workspace_bytes(n_seq, n_heads, max_len);
+    if (workspace_bytes < need) {
+        set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+        return CCR_ERR_WORKSPACE;
+    }
+    CCR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "%s: 4-byte aligned workspace", who);
+    if (n_seq == 0) return CCR_OK;
+    float *delta = static_cast<float *>(workspace);
+    const int W = (max_len + 31) / 32;
+    return dispatch_half(half_dtype, [&](auto dt) {
+        return dispatch_drop(keep_q != nullptr, [&](auto drop) {
+            constexpr bool DROP = decltype(drop)::value;
+            return attention_bwd_any<decltype(dt)::value, DROP>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads, max_len, pad_len,
+                                                               scale, delta, s, keep_arg<DROP>(keep_q, inv_keep, W),
+                                                               keep_arg<DROP>(keep_k, inv_keep, W));
+        });
+    });
+}
+
+// The plan of a LayerNorm backward, for its three entry points: at most LN_BWD_MAX_BLOCKS workgroups walk the rows; when d gamma or d beta
+// is wanted, the workgroups' sums go through the workspace partial [nblk][2][dim] and layernorm_bwd_reduce_kernel adds them up.
+// launch(partial, nblk) starts the row kernel (partial is null when no parameter gradient is wanted).
+template <class Launch>
+static int layernorm_bwd_run(const char *who, bool wants_dx, float *d_gamma, float *d_beta, int64_t rows, int dim, void *workspace,
+                             size_t workspace_bytes, hipStream_t s, Launch &&launch) {
+    const bool params = d_gamma || d_beta;
+    int64_t nblk = (rows + 3) / 4;
+    if (nblk > LN_BWD_MAX_BLOCKS) nblk = LN_BWD_MAX_BLOCKS;
+    const size_t need = params ? (size_t)nblk * 2 * dim * sizeof(float) : 0;
+    if (need && (!workspace || workspace_bytes < need)) {
+        set_error("%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
+        return CCR_ERR_WORKSPACE;
+    }
+    CCR_REQUIRE(!need || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "%s: 16-byte aligned workspace", who);
+    if (!wants_dx && !params) return CCR_OK;
+    if (rows == 0) {   // sums over no rows
+        if (d_gamma) CCR_HIP_CHECK(hipMemsetAsync(d_gamma, 0, (size_t)dim * sizeof(float), s));
+        if (d_beta) CCR_HIP_CHECK(hipMemsetAsync(d_beta, 0, (size_t)dim * sizeof(float), s));
+        return CCR_OK;
+    }
+    float *partial = params ? static_cast<float *>(workspace) : nullptr;
+    const int rc = launch(partial, (int)nblk);
+    if (rc != CCR_OK || !params) return rc;
+    hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((unsigned)(2 * dim / 64)), dim3(256), 0, s, partial, (int)nblk, dim, d_gamma, d_beta);
+    CCR_LAUNCH_CHECK();
+    return CCR_OK;
+}
+
+static int add_layernorm_bwd(const char *who, const uint16_t *x, const uint32_t *bits, float inv_keep, const float *res, const float *gamma,
+                             float eps, const float *dy, float *d_res, uint16_t *d_x, float *d_gamma, float *d_beta, int64_t rows, int dim,
+                             int half_dtype, void *workspace, size_t workspace_bytes, hipStream_t s) {
+    if (const int rc = check_half(who, half_dtype)) return rc;
+    if (const int rc = check_rows_dim(who, rows, dim)) return rc;
+    if (bits)
+        if (const int rc = check_inv_keep(who, inv_keep)) return rc;
+    return layernorm_bwd_run(who, d_res || d_x, d_gamma, d_beta, rows, dim, workspace, workspace_bytes, s, [&](float *partial, int nblk) {
+        return dispatch_width(dim, [&](auto c) {
+            return dispatch_half(half_dtype, [&](auto dt) {
+                return dispatch_drop(bits != nullptr, [&](auto drop) {
+                    constexpr bool DROP = decltype(drop)::value;
+                    return launch_row_kernel(add_layernorm_bwd_kernel<decltype(c)::value, decltype(dt)::value, DROP>, nblk, s, x, res, gamma, eps, dy,
+                                         d_res, d_x, partial, rows, keep_arg<DROP>(bits, inv_keep, 0));
+                });
+            });
+        });
+    });
+}
+
 extern "C" int ccr_attention_bwd_half(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *d_out,
                                       const int32_t *seq_start, const int32_t *seq_len, uint16_t *d_qkv, int n_seq, int n_heads,
                                       int max_len, int pad_len, float scale, int half_dtype, void *workspace, size_t workspace_bytes,
                                       void *stream) {
     CCR_REQUIRE(qkv && out && lse && d_out && seq_start && seq_len && d_qkv && workspace, "ccr_attention_bwd_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_attention_bwd_half");
-    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024, "ccr_attention_bwd_half: bad shape n_seq=%d n_heads=%d",
-                n_seq, n_heads);
-    CCR_REQUIRE(max_len > 0 && max_len <= BWD_MAX_LEN && pad_len >= 0 && pad_len <= BWD_MAX_LEN,
-                "ccr_attention_bwd_half: max_len=%d pad_len=%d (1..512 tokens per sequence)", max_len, pad_len);
-    CCR_REQUIRE(scale > 0.f, "ccr_attention_bwd_half: scale must be positive");
-    const size_t need = ccr_attention_bwd_workspace_bytes(n_seq, n_heads, max_len);
-    if (workspace_bytes < need) {
-        set_error("ccr_attention_bwd_half: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-        return CCR_ERR_WORKSPACE;
-    }
-    CCR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "ccr_attention_bwd_half: 4-byte aligned workspace");
-    if (n_seq == 0) return CCR_OK;
-    float *delta = static_cast<float *>(workspace);
-    hipStream_t s = (hipStream_t)stream;
-    return half_dtype == CCR_DTYPE_F16
-               ? attention_bwd_any<CCR_DTYPE_F16>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads, max_len, pad_len, scale, delta, s)
-               : attention_bwd_any<CCR_DTYPE_BF16>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads, max_len, pad_len, scale, delta, s);
+    return attention_bwd("ccr_attention_bwd_half", qkv, out, lse, d_out, seq_start, seq_len, nullptr, nullptr, 1.f, d_qkv, n_seq, n_heads, max_len,
+                         pad_len, scale, half_dtype, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ccr_attention_bwd_drop_half(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *d_out,
@@ -731,28 +625,8 @@ extern "C" int ccr_attention_bwd_drop_half(const uint16_t *qkv, const uint16_t *
                                            int half_dtype, void *workspace, size_t workspace_bytes, void *stream) {
     CCR_REQUIRE(qkv && out && lse && d_out && seq_start && seq_len && keep_q && keep_k && d_qkv && workspace,
                 "ccr_attention_bwd_drop_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_attention_bwd_drop_half");
-    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024, "ccr_attention_bwd_drop_half: bad shape n_seq=%d n_heads=%d",
-                n_seq, n_heads);
-    CCR_REQUIRE(max_len > 0 && max_len <= BWD_MAX_LEN && pad_len >= 0 && pad_len <= BWD_MAX_LEN,
-                "ccr_attention_bwd_drop_half: max_len=%d pad_len=%d (1..512 tokens per sequence)", max_len, pad_len);
-    CCR_REQUIRE(scale > 0.f, "ccr_attention_bwd_drop_half: scale must be positive");
-    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "ccr_attention_bwd_drop_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
-    const size_t need = ccr_attention_bwd_workspace_bytes(n_seq, n_heads, max_len);
-    if (workspace_bytes < need) {
-        set_error("ccr_attention_bwd_drop_half: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-        return CCR_ERR_WORKSPACE;
-    }
-    CCR_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "ccr_attention_bwd_drop_half: 4-byte aligned workspace");
-    if (n_seq == 0) return CCR_OK;
-    float *delta = static_cast<float *>(workspace);
-    hipStream_t s = (hipStream_t)stream;
-    const int W = (max_len + 31) / 32;
-    const KeepBits kq = {keep_q, inv_keep, W}, kk = {keep_k, inv_keep, W};
-    return half_dtype == CCR_DTYPE_F16 ? attention_bwd_any<CCR_DTYPE_F16, true>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads,
-                                                                                max_len, pad_len, scale, delta, s, kq, kk)
-                                       : attention_bwd_any<CCR_DTYPE_BF16, true>(qkv, out, lse, d_out, seq_start, seq_len, d_qkv, n_seq, n_heads,
-                                                                                 max_len, pad_len, scale, delta, s, kq, kk);
+    return attention_bwd("ccr_attention_bwd_drop_half", qkv, out, lse, d_out, seq_start, seq_len, keep_q, keep_k, inv_keep, d_qkv, n_seq, n_heads,
+                         max_len, pad_len, scale, half_dtype, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ccr_add_layernorm_bwd_drop_half(const uint16_t *x_half, const uint32_t *bits, float inv_keep, const float *residual,
@@ -760,69 +634,16 @@ extern "C" int ccr_add_layernorm_bwd_drop_half(const uint16_t *x_half, const uin
                                                float *d_beta, int64_t rows, int dim, int half_dtype, void *workspace, size_t workspace_bytes,
                                                void *stream) {
     CCR_REQUIRE(x_half && bits && gamma && d_y, "ccr_add_layernorm_bwd_drop_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_add_layernorm_bwd_drop_half");
-    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
-                "ccr_add_layernorm_bwd_drop_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
-    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "ccr_add_layernorm_bwd_drop_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
-    const bool params = d_gamma || d_beta;
-    int64_t nblk = (rows + 3) / 4;
-    if (nblk > LN_BWD_MAX_BLOCKS) nblk = LN_BWD_MAX_BLOCKS;
-    const size_t need = params ? (size_t)nblk * 2 * dim * sizeof(float) : 0;
-    if (need && (!workspace || workspace_bytes < need)) {
-        set_error("ccr_add_layernorm_bwd_drop_half: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-        return CCR_ERR_WORKSPACE;
-    }
-    CCR_REQUIRE(!need || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ccr_add_layernorm_bwd_drop_half: 16-byte aligned workspace");
-    if (!d_res && !d_x && !params) return CCR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (rows == 0) {   // sums over no rows
-        if (d_gamma) CCR_HIP_CHECK(hipMemsetAsync(d_gamma, 0, (size_t)dim * sizeof(float), s));
-        if (d_beta) CCR_HIP_CHECK(hipMemsetAsync(d_beta, 0, (size_t)dim * sizeof(float), s));
-        return CCR_OK;
-    }
-    float *partial = params ? static_cast<float *>(workspace) : nullptr;
-    const KeepBits keep = {bits, inv_keep, 0};
-    const int rc = half_dtype == CCR_DTYPE_F16 ? add_layernorm_bwd_any<CCR_DTYPE_F16, true>(x_half, residual, gamma, eps, d_y, d_res, d_x, partial,
-                                                                                            (int)nblk, rows, dim, s, keep)
-                                               : add_layernorm_bwd_any<CCR_DTYPE_BF16, true>(x_half, residual, gamma, eps, d_y, d_res, d_x, partial,
-                                                                                             (int)nblk, rows, dim, s, keep);
-    if (rc != CCR_OK || !params) return rc;
-    hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((unsigned)(2 * dim / 64)), dim3(256), 0, s, partial, (int)nblk, dim, d_gamma, d_beta);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return add_layernorm_bwd("ccr_add_layernorm_bwd_drop_half", x_half, bits, inv_keep, residual, gamma, eps, d_y, d_res, d_x, d_gamma, d_beta, rows,
+                             dim, half_dtype, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ccr_add_layernorm_bwd_half(const uint16_t *x_half, const float *residual, const float *gamma, float eps, const float *d_y,
                                           float *d_res, uint16_t *d_x, float *d_gamma, float *d_beta, int64_t rows, int dim,
                                           int half_dtype, void *workspace, size_t workspace_bytes, void *stream) {
     CCR_REQUIRE(x_half && gamma && d_y, "ccr_add_layernorm_bwd_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_add_layernorm_bwd_half");
-    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
-                "ccr_add_layernorm_bwd_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
-    const bool params = d_gamma || d_beta;
-    int64_t nblk = (rows + 3) / 4;
-    if (nblk > LN_BWD_MAX_BLOCKS) nblk = LN_BWD_MAX_BLOCKS;
-    const size_t need = params ? (size_t)nblk * 2 * dim * sizeof(float) : 0;
-    if (need && (!workspace || workspace_bytes < need)) {
-        set_error("ccr_add_layernorm_bwd_half: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-        return CCR_ERR_WORKSPACE;
-    }
-    CCR_REQUIRE(!need || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ccr_add_layernorm_bwd_half: 16-byte aligned workspace");
-    if (!d_res && !d_x && !params) return CCR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (rows == 0) {   // sums over no rows
-        if (d_gamma) CCR_HIP_CHECK(hipMemsetAsync(d_gamma, 0, (size_t)dim * sizeof(float), s));
-        if (d_beta) CCR_HIP_CHECK(hipMemsetAsync(d_beta, 0, (size_t)dim * sizeof(float), s));
-        return CCR_OK;
-    }
-    float *partial = params ? static_cast<float *>(workspace) : nullptr;
-    const int rc = half_dtype == CCR_DTYPE_F16
-                       ? add_layernorm_bwd_any<CCR_DTYPE_F16>(x_half, residual, gamma, eps, d_y, d_res, d_x, partial, (int)nblk, rows, dim, s)
-                       : add_layernorm_bwd_any<CCR_DTYPE_BF16>(x_half, residual, gamma, eps, d_y, d_res, d_x, partial, (int)nblk, rows, dim, s);
-    if (rc != CCR_OK || !params) return rc;
-    hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((unsigned)(2 * dim / 64)), dim3(256), 0, s, partial, (int)nblk, dim, d_gamma, d_beta);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return add_layernorm_bwd("ccr_add_layernorm_bwd_half", x_half, nullptr, 1.f, residual, gamma, eps, d_y, d_res, d_x, d_gamma, d_beta, rows, dim,
+                             half_dtype, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ccr_embed_layernorm_bwd_half(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
@@ -830,51 +651,32 @@ extern "C" int ccr_embed_layernorm_bwd_half(const float *word_table, int64_t voc
                                             const int64_t *token_types, const float *gamma, float eps, const uint32_t *bits, float inv_keep,
                                             const float *d_y, float *d_x, float *d_gamma, float *d_beta, int64_t rows, int dim,
                                             void *workspace, size_t workspace_bytes, void *stream) {
+    static const char who[] = "ccr_embed_layernorm_bwd_half";
     CCR_REQUIRE(word_table && position_table && type_table && token_ids && positions && gamma && d_y,
                 "ccr_embed_layernorm_bwd_half: null pointer");
     CCR_REQUIRE(vocab > 0 && n_positions > 0 && n_types > 0, "ccr_embed_layernorm_bwd_half: empty table");
-    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
-                "ccr_embed_layernorm_bwd_half: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", (long long)rows, dim);
-    CCR_REQUIRE(!bits || (inv_keep >= 1.f && inv_keep <= 65536.f), "ccr_embed_layernorm_bwd_half: inv_keep=%g (1 .. 65536)", (double)inv_keep);
-    const bool params = d_gamma || d_beta;
-    int64_t nblk = (rows + 3) / 4;
-    if (nblk > LN_BWD_MAX_BLOCKS) nblk = LN_BWD_MAX_BLOCKS;
-    const size_t need = params ? (size_t)nblk * 2 * dim * sizeof(float) : 0;
-    if (need && (!workspace || workspace_bytes < need)) {
-        set_error("ccr_embed_layernorm_bwd_half: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-        return CCR_ERR_WORKSPACE;
-    }
-    CCR_REQUIRE(!need || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ccr_embed_layernorm_bwd_half: 16-byte aligned workspace");
-    if (!d_x && !params) return CCR_OK;
+    if (const int rc = check_rows_dim(who, rows, dim)) return rc;
+    if (bits)
+        if (const int rc = check_inv_keep(who, inv_keep)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (rows == 0) {   // sums over no rows
-        if (d_gamma) CCR_HIP_CHECK(hipMemsetAsync(d_gamma, 0, (size_t)dim * sizeof(float), s));
-        if (d_beta) CCR_HIP_CHECK(hipMemsetAsync(d_beta, 0, (size_t)dim * sizeof(float), s));
-        return CCR_OK;
-    }
-    float *partial = params ? static_cast<float *>(workspace) : nullptr;
-    int rc;
-    if (bits) {
-        const KeepBits keep = {bits, inv_keep, 0};
-        rc = embed_layernorm_bwd_any<true>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids, positions, token_types,
-                                           gamma, eps, d_y, d_x, partial, (int)nblk, rows, dim, s, keep);
-    } else {
-        rc = embed_layernorm_bwd_any<false>(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids, positions, token_types,
-                                            gamma, eps, d_y, d_x, partial, (int)nblk, rows, dim, s);
-    }
-    if (rc != CCR_OK || !params) return rc;
-    hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((unsigned)(2 * dim / 64)), dim3(256), 0, s, partial, (int)nblk, dim, d_gamma, d_beta);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return layernorm_bwd_run(who, d_x != nullptr, d_gamma, d_beta, rows, dim, workspace, workspace_bytes, s, [&](float *partial, int nblk) {
+        return dispatch_width(dim, [&](auto c) {
+            return dispatch_drop(bits != nullptr, [&](auto drop) {
+                constexpr bool DROP = decltype(drop)::value;
+                return launch_row_kernel(embed_layernorm_bwd_kernel<decltype(c)::value, DROP>, nblk, s, word_table, vocab, position_table, n_positions,
+                                     type_table, n_types, token_ids, positions, token_types, gamma, eps, d_y, d_x, partial, rows,
+                                     keep_arg<DROP>(bits, inv_keep, 0));
+            });
+        });
+    });
 }
 
 extern "C" int ccr_gelu_bwd_half(const uint16_t *x, const uint16_t *d_y, uint16_t *d_x, int64_t n, int half_dtype, void *stream) {
     CCR_REQUIRE(x && d_y && d_x, "ccr_gelu_bwd_half: null pointer");
-    CCR_REQUIRE_HALF(half_dtype, "ccr_gelu_bwd_half");
+    if (const int rc = check_half("ccr_gelu_bwd_half", half_dtype)) return rc;
     CCR_REQUIRE(n >= 0 && n % 8 == 0, "ccr_gelu_bwd_half: n=%lld (a multiple of 8 elements)", (long long)n);
     CCR_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(d_y) | reinterpret_cast<uintptr_t>(d_x)) & 15) == 0,
                 "ccr_gelu_bwd_half: 16-byte aligned arrays");
     if (n == 0) return CCR_OK;
-    return half_dtype == CCR_DTYPE_F16 ? gelu_bwd_any<CCR_DTYPE_F16>(x, d_y, d_x, n, (hipStream_t)stream)
-                                       : gelu_bwd_any<CCR_DTYPE_BF16>(x, d_y, d_x, n, (hipStream_t)stream);
+    return dispatch_half(half_dtype, [&](auto dt) { return gelu_bwd_any<decltype(dt)::value>(x, d_y, d_x, n, (hipStream_t)stream); });
 }

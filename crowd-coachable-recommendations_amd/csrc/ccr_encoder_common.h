@@ -1,6 +1,9 @@
 // ccr_encoder_common.h -- what the encoder layer's forward (ccr_encoder.hip) and backward (ccr_encoder_bwd.hip) kernels share:
-// the two 16-bit operand types, the rounding of four fp32 values, and the LayerNorm's two-step mean.
+// the two 16-bit operand types, the rounding of four fp32 values, the LayerNorm row body (statistics, backward row step, partial-sum
+// flush) that the add_ and embed_ kernels of both files run on a row held in registers, and the host side's dispatchers and checks.
 #pragma once
+
+#include <type_traits>
 
 #include "ccr_common.h"
 
@@ -79,6 +82,113 @@ __device__ __forceinline__ float refined_mean(const float (&v)[C][4], float m0) 
     return m0 + sd * (1.f / (256 * C));
 }
 
+// ---- The LayerNorm row body.  A wave holds one row of DIM = 256 C elements, v[c][j] = element 4 (64 c + lane) + j.  Each kernel loads its
+// own operands into v (and d = d_y), applies its own dropout and stores its own outputs; what lies between is the same arithmetic, in the
+// same order, for all four row kernels -- written once here, so that the forward's and the backward's mean and rstd cannot drift apart.
+
+// mean and rstd of the row from the lane's partial sum of its elements: butterfly sum, refined mean, squared deviations, rsqrt
+template <int C>
+__device__ __forceinline__ void row_mean_rstd(const float (&v)[C][4], float sum, float eps, float &mean, float &rstd) {
+    constexpr int DIM = 256 * C;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    mean = refined_mean<C>(v, sum * (1.f / DIM));
+    float sq = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float d = v[c][j] - mean;
+            sq = fmaf(d, d, sq);
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+    rstd = rsqrtf(sq * (1.f / DIM) + eps);
+}
+
+// slice c of y = xhat gamma + beta
+template <int C>
+__device__ __forceinline__ float4 layernorm_row_out(const float (&v)[C][4], int c, float mean, float rstd, float4 gm, float4 bt) {
+    float4 y;
+    y.x = fmaf((v[c][0] - mean) * rstd, gm.x, bt.x);
+    y.y = fmaf((v[c][1] - mean) * rstd, gm.y, bt.y);
+    y.z = fmaf((v[c][2] - mean) * rstd, gm.z, bt.z);
+    y.w = fmaf((v[c][3] - mean) * rstd, gm.w, bt.w);
+    return y;
+}
+
+// One row of the backward: v (the summed input) becomes xhat = (v - mean) rstd, the row's d_y (d) joins ag / ab, and m1 = mean(d gamma),
+// m2 = mean(d gamma xhat) come back for layernorm_bwd_dv.
+template <int C>
+__device__ __forceinline__ void layernorm_bwd_row(float (&v)[C][4], const float (&d)[C][4], const float (&gm)[C][4], float mean, float rstd,
+                                                  float (&ag)[C][4], float (&ab)[C][4], float &m1, float &m2) {
+    constexpr int DIM = 256 * C;
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float xh = (v[c][j] - mean) * rstd;
+            const float gy = d[c][j] * gm[c][j];
+            v[c][j] = xh;
+            s1 += gy;
+            s2 = fmaf(gy, xh, s2);
+            ag[c][j] = fmaf(d[c][j], xh, ag[c][j]);
+            ab[c][j] += d[c][j];
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_xor(s1, o);
+        s2 += __shfl_xor(s2, o);
+    }
+    m1 = s1 * (1.f / DIM), m2 = s2 * (1.f / DIM);
+}
+
+// slice c of d_v = rstd (d gamma - m1 - xhat m2), xhat as layernorm_bwd_row left it
+template <int C>
+__device__ __forceinline__ float4 layernorm_bwd_dv(const float (&xhat)[C][4], const float (&d)[C][4], const float (&gm)[C][4], int c,
+                                                   float rstd, float m1, float m2) {
+    float4 y;
+    y.x = rstd * ((d[c][0] * gm[c][0] - m1) - xhat[c][0] * m2);
+    y.y = rstd * ((d[c][1] * gm[c][1] - m1) - xhat[c][1] * m2);
+    y.z = rstd * ((d[c][2] * gm[c][2] - m1) - xhat[c][2] * m2);
+    y.w = rstd * ((d[c][3] * gm[c][3] - m1) - xhat[c][3] * m2);
+    return y;
+}
+
+// The workgroup's four waves add their ag, then their ab, through LDS in a fixed order (wave 0 adds waves 1, 2, 3), and the sums go to
+// partial [gridDim.x][2][DIM].  Every wave of the workgroup calls this (it holds barriers).  red is declared here, not handed in by the
+// kernel: with the array as a parameter add_layernorm_bwd_kernel<3, *, true> went from 128 to 130 VGPRs and lost an occupancy step.
+template <int C>
+__device__ __forceinline__ void layernorm_bwd_flush(const float (&ag)[C][4], const float (&ab)[C][4], float *partial, int lane, int wave) {
+    constexpr int DIM = 256 * C;
+    __shared__ float red[3][DIM];
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+        if (which) __syncthreads();
+        if (wave > 0) {
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+                *reinterpret_cast<float4 *>(&red[wave - 1][4 * (64 * c + lane)]) =
+                    which ? make_float4(ab[c][0], ab[c][1], ab[c][2], ab[c][3]) : make_float4(ag[c][0], ag[c][1], ag[c][2], ag[c][3]);
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int col = 4 * (64 * c + lane);
+                float4 t = which ? make_float4(ab[c][0], ab[c][1], ab[c][2], ab[c][3]) : make_float4(ag[c][0], ag[c][1], ag[c][2], ag[c][3]);
+#pragma unroll
+                for (int w = 0; w < 3; ++w) {
+                    const float4 u = *reinterpret_cast<const float4 *>(&red[w][col]);
+                    t.x += u.x, t.y += u.y, t.z += u.z, t.w += u.w;
+                }
+                *reinterpret_cast<float4 *>(partial + ((int64_t)blockIdx.x * 2 + which) * DIM + col) = t;
+            }
+        }
+    }
+}
+
 // Training dropout (ccr_dropout.hip writes the bits): a kernel instantiated with DROP = true takes the packed keep bits of its site and
 // the scale 1 / (1 - p_eff) of a kept element; DROP = false takes an empty struct in their place, as NoLse does for lse -- the
 // dropout-free instantiations keep their argument layout and their code.
@@ -104,7 +214,71 @@ __device__ __forceinline__ void keep_nibble(const KeepBits &keep, int64_t word0,
     for (int j = 0; j < 4; ++j) mk[j] = (nib >> j) & 1u ? keep.inv_keep : 0.f;
 }
 
+// the argument a <.., DROP> kernel takes for a site whose bits pointer may be null (DROP = false: nothing)
+template <bool DROP>
+inline typename KeepArg<DROP>::type keep_arg(const uint32_t *bits, float inv_keep, int W) {
+    if constexpr (DROP)
+        return KeepBits{bits, inv_keep, W};
+    else
+        return NoKeep{};
+}
+
+// (ccr_dropout.hip spells its 16-bit type check with this macro; the encoder files use check_half below: one text, two callers)
 #define CCR_REQUIRE_HALF(dtype, who) \
     CCR_REQUIRE((dtype) == CCR_DTYPE_BF16 || (dtype) == CCR_DTYPE_F16, who ": half_dtype=%d (CCR_DTYPE_F16 or CCR_DTYPE_BF16)", (int)(dtype))
+
+// ---- Host side: a run-time width, 16-bit type or dropout flag becomes a template argument in ONE place each.  f is a generic lambda
+// whose parameter is a std::integral_constant (read its ::value); it returns the launch's status.
+template <class F>
+inline int dispatch_width(int dim, F &&f) {   // dim = 256 C, C = 1 .. 8 (the caller has checked)
+    switch (dim / 256) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        default: return f(std::integral_constant<int, 8>{});
+    }
+}
+template <class F>
+inline int dispatch_half(int half_dtype, F &&f) {   // CCR_DTYPE_F16 or CCR_DTYPE_BF16 (the caller has checked)
+    return half_dtype == CCR_DTYPE_F16 ? f(std::integral_constant<int, CCR_DTYPE_F16>{}) : f(std::integral_constant<int, CCR_DTYPE_BF16>{});
+}
+template <class F>
+inline int dispatch_drop(bool drop, F &&f) {
+    return drop ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// the launch of a row kernel: nblk workgroups of four waves, one row per wave at a time
+template <class K, class... A>
+inline int launch_row_kernel(K kernel, int64_t nblk, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), 0, s, args...);
+    CCR_LAUNCH_CHECK();
+    return CCR_OK;
+}
+
+// The argument checks that entry points share, reported under the caller's name `who`.
+inline int check_half(const char *who, int half_dtype) {
+    CCR_REQUIRE(half_dtype == CCR_DTYPE_BF16 || half_dtype == CCR_DTYPE_F16, "%s: half_dtype=%d (CCR_DTYPE_F16 or CCR_DTYPE_BF16)", who, half_dtype);
+    return CCR_OK;
+}
+inline int check_inv_keep(const char *who, float inv_keep) {
+    CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "%s: inv_keep=%g (1 .. 65536)", who, (double)inv_keep);
+    return CCR_OK;
+}
+inline int check_rows_dim(const char *who, int64_t rows, int dim) {   // the row kernels: one wave per row of 256 C elements
+    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048, "%s: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", who, (long long)rows, dim);
+    return CCR_OK;
+}
+inline int check_attention_shape(const char *who, int half_dtype, int n_seq, int n_heads, int max_len, int pad_len, float scale) {
+    if (const int rc = check_half(who, half_dtype)) return rc;
+    CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024, "%s: bad shape n_seq=%d n_heads=%d", who, n_seq, n_heads);
+    CCR_REQUIRE(max_len > 0 && max_len <= 512 && pad_len >= 0 && pad_len <= 512, "%s: max_len=%d pad_len=%d (1..512 tokens per sequence)", who,
+                max_len, pad_len);
+    CCR_REQUIRE(scale > 0.f, "%s: scale must be positive", who);
+    return CCR_OK;
+}
 
 }  // namespace ccr

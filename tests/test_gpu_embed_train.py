@@ -73,10 +73,10 @@ def test_forward_has_the_bits_of_embed_layernorm_then_dropout_apply(C, dtype):
     c = _block(11, 256 * C)
     f32, b16 = ops.embed_layernorm(*_fwd_args(c), dtype=dtype)
     ones = torch.full((11, 8 * C), -1, dtype=torch.int32, device="cuda")
-    for got in (ops.embed_layernorm_drop(*_fwd_args(c), dtype=dtype), ops.embed_layernorm_drop(*_fwd_args(c), keep_bits=ones, inv_keep=1.0, dtype=dtype)):
+    for got in (ops.embed_layernorm(*_fwd_args(c), dtype=dtype), ops.embed_layernorm(*_fwd_args(c), keep_bits=ones, inv_keep=1.0, dtype=dtype)):
         assert _same(got[0], f32) and _same(got[1], b16)
     want = ops.dropout_apply(f32, c["bits"], c["inv_keep"], dtype)
-    got = ops.embed_layernorm_drop(*_fwd_args(c), keep_bits=c["bits"], inv_keep=c["inv_keep"], dtype=dtype)
+    got = ops.embed_layernorm(*_fwd_args(c), keep_bits=c["bits"], inv_keep=c["inv_keep"], dtype=dtype)
     assert _same(got[0], want[0]) and _same(got[1], want[1])
     assert (got[0] == 0).any() and (got[0] != 0).any()
     got = ops.embed_layernorm_train(*_fwd_args(c), keep_bits=c["bits"], inv_keep=c["inv_keep"], dtype=dtype)

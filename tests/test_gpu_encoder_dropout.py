@@ -119,12 +119,12 @@ def _ones_bits(case):
 
 def _run_drop(case, keep_q, keep_k, inv_keep, d_out=None):
     from ccrec_amd import ops
-    out, lse = ops.attention_fwd_train_drop(case["qkv"], case["seq_start"], case["seq_len"], case["H"], case["max_len"], keep_q, inv_keep,
-                                            case["pad_len"])
+    out, lse = ops.attention_fwd_train(case["qkv"], case["seq_start"], case["seq_len"], case["H"], case["max_len"], case["pad_len"],
+                                       keep_q=keep_q, inv_keep=inv_keep)
     out_nan = out.clone()
     out_nan[~case["live"]] = float("nan")                 # the backward must not read the forward's padding rows
-    d_qkv = ops.attention_bwd_drop(case["qkv"], out_nan, lse, case["d_out"] if d_out is None else d_out, case["seq_start"], case["seq_len"],
-                                   case["H"], case["max_len"], keep_q, keep_k, inv_keep, case["pad_len"])
+    d_qkv = ops.attention_bwd(case["qkv"], out_nan, lse, case["d_out"] if d_out is None else d_out, case["seq_start"], case["seq_len"],
+                              case["H"], case["max_len"], case["pad_len"], keep_q=keep_q, keep_k=keep_k, inv_keep=inv_keep)
     return out, lse, d_qkv
 
 
@@ -192,22 +192,54 @@ def test_all_ones_bits_and_scale_one_are_the_dropout_free_attention(name, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=_IDS)
-@pytest.mark.parametrize("rows,dim", [(1, 256), (7, 768), (1031, 768), (4, 2048)])
+@pytest.mark.parametrize("rows,dim", [(1, 256), (7, 768), (1031, 768), (4, 2048)] + [(7, 256 * C) for C in (2, 4, 5, 6, 7)])
 def test_all_ones_bits_and_scale_one_are_the_dropout_free_layernorm_and_cast(rows, dim, dtype):
     from ccrec_amd import ops
     x, res, gamma, d_y = ln_inputs(rows, dim, dtype, True, seed=rows + dim)
     beta = torch.linspace(-1, 1, dim, device="cuda")
     ones = torch.full((rows, dim // 32), -1, dtype=torch.int32, device="cuda")
     for r in (res, None):
-        want, got = ops.add_layernorm(x, r, gamma, beta, LN_EPS), ops.add_layernorm_drop(x, ones, 1.0, r, gamma, beta, LN_EPS)
+        want, got = ops.add_layernorm(x, r, gamma, beta, LN_EPS), ops.add_layernorm(x, r, gamma, beta, LN_EPS, keep_bits=ones, inv_keep=1.0)
         assert torch.equal(got[0], want[0]) and torch.equal(_bits32(got[1]), _bits32(want[1]))
-        want, got = ops.add_layernorm_bwd(x, r, gamma, LN_EPS, d_y), ops.add_layernorm_bwd_drop(x, ones, 1.0, r, gamma, LN_EPS, d_y)
+        want, got = ops.add_layernorm_bwd(x, r, gamma, LN_EPS, d_y), ops.add_layernorm_bwd(x, r, gamma, LN_EPS, d_y, keep_bits=ones, inv_keep=1.0)
         for w, g in zip(want, got):
             assert (w is None) == (g is None)
             if w is not None:
                 assert torch.equal(_bits32(g), _bits32(w))
     f32, b16 = ops.dropout_apply(res, ones, 1.0, dtype)
     assert torch.equal(_bits32(f32), _bits32(res)) and torch.equal(_bits32(b16), _bits32(res.to(dtype)))
+
+
+def test_the_earlier_drop_names_are_the_keyword_form():
+    """ops.*_drop (the spelling before each op became one function with optional bits) forward to the keyword form: the same bits out of
+    both, at one small shape per op, random bits."""
+    from ccrec_amd import dropout_ref, ops
+    dtype, p = torch.bfloat16, 0.1
+    inv = dropout_ref.inv_keep(p)
+    case = _case("padded_edges", dtype)
+    a = (case["qkv"], case["seq_start"], case["seq_len"], case["H"], case["max_len"])
+    kq, kk = ops.dropout_bits_attention(case["seq_start"], case["seq_len"], case["T"], case["H"], case["max_len"], 7, 3, p)
+    out, lse = ops.attention_fwd_train(*a, case["pad_len"], keep_q=kq, inv_keep=inv)
+    old = ops.attention_fwd_train_drop(*a, kq, inv, case["pad_len"])
+    assert torch.equal(_bits32(old[0]), _bits32(out)) and torch.equal(_bits32(old[1]), _bits32(lse))
+    out = torch.where(case["live"][:, None], out, torch.zeros_like(out))
+    b = (case["qkv"], out, lse, case["d_out"], case["seq_start"], case["seq_len"], case["H"], case["max_len"])
+    assert torch.equal(_bits32(ops.attention_bwd_drop(*b, kq, kk, inv, case["pad_len"])),
+                       _bits32(ops.attention_bwd(*b, case["pad_len"], keep_q=kq, keep_k=kk, inv_keep=inv)))
+    x, res, gamma, d_y = ln_inputs(7, 256, dtype, True, seed=5)
+    beta = torch.linspace(-1, 1, 256, device="cuda")
+    bits = ops.dropout_bits_rows(7, 256, 7, 4, p)
+    pairs = list(zip(ops.add_layernorm_drop(x, bits, inv, res, gamma, beta, LN_EPS), ops.add_layernorm(x, res, gamma, beta, LN_EPS, keep_bits=bits, inv_keep=inv)))
+    pairs += zip(ops.add_layernorm_bwd_drop(x, bits, inv, res, gamma, LN_EPS, d_y), ops.add_layernorm_bwd(x, res, gamma, LN_EPS, d_y, keep_bits=bits, inv_keep=inv))
+    g = torch.Generator().manual_seed(6)
+    word, pos, typ = (torch.randn(n, 256, generator=g).cuda() for n in (50, 16, 2))
+    ids, ps = (torch.randint(0, n, (7,), generator=g).cuda() for n in (50, 16))
+    e = (word, pos, typ, ids, ps, None, gamma, beta, LN_EPS)
+    pairs += zip(ops.embed_layernorm_drop(*e, keep_bits=bits, inv_keep=inv, dtype=dtype), ops.embed_layernorm(*e, dtype=dtype, keep_bits=bits, inv_keep=inv))
+    pairs += zip(ops.embed_layernorm_drop(*e, dtype=dtype), ops.embed_layernorm(*e, dtype=dtype))
+    assert len(pairs) == 10
+    for was, now in pairs:
+        assert torch.equal(_bits32(was), _bits32(now))
 
 
 # ---------------------------------------------------------------------------------------------------------------------- exact structure
@@ -225,7 +257,7 @@ def test_scale_two_doubles_the_output_exactly_and_leaves_lse(name, dtype):
         case["qkv"][:, :2 * case["H"] * 64] *= 0.25
     out0, lse0 = ops.attention_fwd_train(case["qkv"], case["seq_start"], case["seq_len"], case["H"], case["max_len"], case["pad_len"])
     ones = _ones_bits(case)
-    out, lse = ops.attention_fwd_train_drop(case["qkv"], case["seq_start"], case["seq_len"], case["H"], case["max_len"], ones, 2.0, case["pad_len"])
+    out, lse = ops.attention_fwd_train(case["qkv"], case["seq_start"], case["seq_len"], case["H"], case["max_len"], case["pad_len"], keep_q=ones, inv_keep=2.0)
     assert torch.equal(_bits32(lse), _bits32(lse0))
     tiny = torch.finfo(dtype).tiny
     normal = (out0.float().abs() >= tiny) | (out0 == 0)
@@ -287,7 +319,7 @@ def test_canaries_behind_the_gradient_and_the_workspace_survive():
     case = _case("packed_12_heads", dtype)
     m = _masked_case("packed_12_heads", dtype, 0.1)
     H, T, n_seq = case["H"], case["T"], len(case["lens"])
-    out, lse = ops.attention_fwd_train_drop(case["qkv"], case["seq_start"], case["seq_len"], H, case["max_len"], m["keep_q"], m["inv_keep"])
+    out, lse = ops.attention_fwd_train(case["qkv"], case["seq_start"], case["seq_len"], H, case["max_len"], keep_q=m["keep_q"], inv_keep=m["inv_keep"])
     need = lib.ccr_attention_bwd_workspace_bytes(n_seq, H, case["max_len"])
     pad = 4096
     ws = torch.full((need + pad,), 0x5a, dtype=torch.uint8, device="cuda")
@@ -297,8 +329,8 @@ def test_canaries_behind_the_gradient_and_the_workspace_survive():
                                                p(m["keep_q"]), p(m["keep_k"]), m["inv_keep"], p(d_buf), n_seq, H, case["max_len"], 0, 0.125,
                                                _lib.DTYPE_BF16, p(ws), need, ops._stream(ws)))
     assert (ws[need:] == 0x5a).all() and (d_buf[T * 3 * H * 64:] == 7).all()
-    want = ops.attention_bwd_drop(case["qkv"], out, lse, case["d_out"], case["seq_start"], case["seq_len"], H, case["max_len"], m["keep_q"],
-                                  m["keep_k"], m["inv_keep"])
+    want = ops.attention_bwd(case["qkv"], out, lse, case["d_out"], case["seq_start"], case["seq_len"], H, case["max_len"], keep_q=m["keep_q"],
+                             keep_k=m["keep_k"], inv_keep=m["inv_keep"])
     assert torch.equal(_bits32(d_buf[:T * 3 * H * 64].view(T, 3 * H * 64)), _bits32(want))
     # bad arguments launch nothing
     d_buf.fill_(7.0)
@@ -362,7 +394,7 @@ def test_one_flipped_bit_of_keep_k_alone_fails_the_comparison(dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=_IDS)
 @pytest.mark.parametrize("p", [0.1, 0.5])
-@pytest.mark.parametrize("rows,dim", [(1, 256), (7, 256), (1031, 256), (1, 768), (7, 768), (1031, 768)])
+@pytest.mark.parametrize("rows,dim", [(1, 256), (7, 256), (1031, 256), (1, 768), (7, 768), (1031, 768)] + [(7, 256 * C) for C in (2, 4, 5, 6, 7, 8)])
 def test_layernorm_with_bits_against_fp64(rows, dim, p, dtype):
     """d_res, d_x, d_gamma, d_beta of LayerNorm(x * M * inv_keep + residual) vs fp64 torch: at most 2 x the error of torch's fp32 path
     (the same formula in fp32, F.layer_norm backward; d_x rounded to the type), floor 1e-6 max |ref| -- test_gpu_encoder_train.py's bar.
@@ -378,12 +410,12 @@ def test_layernorm_with_bits_against_fp64(rows, dim, p, dtype):
     v64, v32 = x.double() * m64 + res.double(), x.float() * m32 + res
     ref = ln_torch_backward(v64, gamma, d_y, torch.float64)
     yard = ln_torch_backward(v32, gamma, d_y, torch.float32)
-    d_res, d_x, d_gamma, d_beta = ops.add_layernorm_bwd_drop(x, bits, inv_keep, res, gamma, LN_EPS, d_y)
+    d_res, d_x, d_gamma, d_beta = ops.add_layernorm_bwd(x, res, gamma, LN_EPS, d_y, keep_bits=bits, inv_keep=inv_keep)
     pieces = [("d_res", d_res, ref[0], yard[0]), ("d_x", d_x, ref[0] * m64, (yard[0] * m32).to(dtype)), ("d_gamma", d_gamma, ref[1], yard[1]),
               ("d_beta", d_beta, ref[2], yard[2])]
     y64 = F.layer_norm(v64, (dim,), gamma.double(), beta.double(), LN_EPS)
     y32 = F.layer_norm(v32, (dim,), gamma, beta, LN_EPS)
-    f32, b16 = ops.add_layernorm_drop(x, bits, inv_keep, res, gamma, beta, LN_EPS)
+    f32, b16 = ops.add_layernorm(x, res, gamma, beta, LN_EPS, keep_bits=bits, inv_keep=inv_keep)
     pieces += [("y_f32", f32, y64, y32), ("y_half", b16, y64, y32.to(dtype))]
     for label, mine, r, y in pieces:
         assert torch.isfinite(mine).all()
@@ -568,10 +600,10 @@ def test_fine_tune_step_with_dropout_through_the_layer_kernels(kind, dtype, monk
     monkeypatch.setattr(ops, "attention_train", lambda *a, **k: (calls.append(k.get("keep_bits") is not None), real_att(*a, **k))[1])
     monkeypatch.setattr(fused_bert, "draw_seed", lambda: (seeds.append(real_seed()), seeds[-1])[1])
     variance = []      # per attention backward call: the modelled variance of the key bias's rounding residue (see the key-bias branch below)
-    real_bwd = ops.attention_bwd_drop
+    real_bwd = ops.attention_bwd
     ebits = MANTISSA[dtype]
 
-    def bwd_spy(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, keep_q, keep_k, inv_keep, pad_len=0, scale=0.125):
+    def bwd_spy(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, keep_q=None, keep_k=None, inv_keep=1.0):
         T = qkv.shape[0]
         q2 = qkv[:, :n_heads * 64].double().view(T, n_heads, 64).pow(2).sum(-1)                       # ||Q_qh||^2
         vmax = qkv[:, 2 * n_heads * 64:].double().view(T, n_heads, 64).abs().amax(0)                  # max_k |V_khd| (over all rows: an upper estimate)
@@ -580,9 +612,9 @@ def test_fine_tune_step_with_dropout_through_the_layer_kernels(kind, dtype, monk
         var_o = ulp.pow(2) / 12 + (2.0 ** -ebits * inv_keep * vmax).pow(2) / 12                          # O's own rounding + its P m operands'
         var_r = (d_out.double().view(T, n_heads, 64).pow(2) * var_o).sum(-1)                            # of dO . (O_stored - O)
         variance.append((scale ** 2 * (q2 * var_r).sum()).item())
-        return real_bwd(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, keep_q, keep_k, inv_keep, pad_len, scale)
+        return real_bwd(qkv, out, lse, d_out, seq_start, seq_len, n_heads, max_len, pad_len, scale, keep_q, keep_k, inv_keep)
 
-    monkeypatch.setattr(ops, "attention_bwd_drop", bwd_spy)
+    monkeypatch.setattr(ops, "attention_bwd", bwd_spy)
 
     monkeypatch.setenv("CCREC_FUSED_ENCODER_TRAIN", "1")
     monkeypatch.delenv("CCREC_FUSED_ENCODER_TRAIN_DROPOUT", raising=False)

@@ -151,7 +151,7 @@ def test_attention_rejects_bad_shapes():
         ops.attention(qkv, s, n, 2, max_len=16)     # rows are 192 wide, not 3 x 2 x 64
 
 
-@pytest.mark.parametrize("rows,dim", [(1, 256), (7, 768), (1000, 768), (333, 1024), (5, 2048)])
+@pytest.mark.parametrize("rows,dim", [(1, 256), (7, 768), (1000, 768), (333, 1024), (5, 2048)] + [(7, 256 * C) for C in (2, 5, 6, 7)])
 @pytest.mark.parametrize("half", HALVES)
 def test_add_layernorm_matches_torch(rows, dim, half):
     from ccrec_amd import ops

@@ -138,18 +138,18 @@ def bench_kernels_dropout(dtype, p, runs, warmup, rows):
     keep_q, keep_k = ops.dropout_bits_attention(seq_start, seq_len, T, H, L, 1, 1, p)
     bits = ops.dropout_bits_rows(T, hidden, 1, 2, p)
     out, lse = ops.attention_fwd_train(qkv, seq_start, seq_len, H, L)
-    out_d, lse_d = ops.attention_fwd_train_drop(qkv, seq_start, seq_len, H, L, keep_q, inv)
+    out_d, lse_d = ops.attention_fwd_train(qkv, seq_start, seq_len, H, L, keep_q=keep_q, inv_keep=inv)
     cases = [
         ("ccr_dropout_bits_attention", lambda: ops.dropout_bits_attention(seq_start, seq_len, T, H, L, 1, 1, p)),
         ("ccr_dropout_bits_rows", lambda: ops.dropout_bits_rows(T, hidden, 1, 2, p)),
         ("ccr_attention_fwd_train_half", lambda: ops.attention_fwd_train(qkv, seq_start, seq_len, H, L)),
-        ("ccr_attention_fwd_train_drop_half", lambda: ops.attention_fwd_train_drop(qkv, seq_start, seq_len, H, L, keep_q, inv)),
+        ("ccr_attention_fwd_train_drop_half", lambda: ops.attention_fwd_train(qkv, seq_start, seq_len, H, L, keep_q=keep_q, inv_keep=inv)),
         ("ccr_attention_bwd_half", lambda: ops.attention_bwd(qkv, out, lse, d_out, seq_start, seq_len, H, L)),
-        ("ccr_attention_bwd_drop_half", lambda: ops.attention_bwd_drop(qkv, out_d, lse_d, d_out, seq_start, seq_len, H, L, keep_q, keep_k, inv)),
+        ("ccr_attention_bwd_drop_half", lambda: ops.attention_bwd(qkv, out_d, lse_d, d_out, seq_start, seq_len, H, L, keep_q=keep_q, keep_k=keep_k, inv_keep=inv)),
         ("ccr_add_layernorm_half", lambda: ops.add_layernorm(x, res, gamma, beta, 1e-12)),
-        ("ccr_add_layernorm_drop_half", lambda: ops.add_layernorm_drop(x, bits, inv, res, gamma, beta, 1e-12)),
+        ("ccr_add_layernorm_drop_half", lambda: ops.add_layernorm(x, res, gamma, beta, 1e-12, keep_bits=bits, inv_keep=inv)),
         ("ccr_add_layernorm_bwd_half", lambda: ops.add_layernorm_bwd(x, res, gamma, 1e-12, d_y)),
-        ("ccr_add_layernorm_bwd_drop_half", lambda: ops.add_layernorm_bwd_drop(x, bits, inv, res, gamma, 1e-12, d_y)),
+        ("ccr_add_layernorm_bwd_drop_half", lambda: ops.add_layernorm_bwd(x, res, gamma, 1e-12, d_y, keep_bits=bits, inv_keep=inv)),
         ("ccr_dropout_apply", lambda: ops.dropout_apply(res, bits, inv, dtype)),
     ]
     for name, fn in cases:
