@@ -1,4 +1,4 @@
-// ccr_api.hip -- host side of the C ABI: index object, planner, ccr_search orchestration.
+// ccr_api.hip -- host side of the C ABI: index object, ccr_search orchestration (the planner: ccr_plan.hip).
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -22,551 +22,6 @@ void set_error(const char *fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
-}
-
-// ------------------------------------------------------------------ planner
-// Query-block groups per XCD set (pick_qgroups): the smallest divisor of qblocks among {1,2,4,8} that keeps one XCD's
-// query rows (qblocks / groups blocks of tile_q rows) within ~3 MiB of its 4-MiB L2.  These are the EQUAL groups every launch
-// knows; a block count they cannot cut small enough (nine = 3 x 3, a prime) gets unequal groups in a single-launch main pass
-// (pick_qsplit).
-static int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
-Knobs read_knobs() {
-    Knobs kn;
-    kn.qgroups = env_int("CCR_QGROUPS", 0);
-    kn.progressive = env_int("CCR_PROGRESSIVE", 1);
-    kn.max_phases = env_int("CCR_PHASES", 3);
-    kn.mfma16 = env_int("CCR_MFMA16", -1);
-    kn.sample_div = env_int("CCR_SAMPLE_DIV", 0);
-    kn.max_lists = env_int("CCR_MAX_LISTS", 0);
-    kn.ranges = env_int("CCR_RANGES", 0);
-    kn.optimistic = env_int("CCR_OPTIMISTIC", -1);
-    kn.opt_rank = env_int("CCR_OPT_RANK", 0);
-    kn.narrow = env_int("CCR_NARROW", -1);
-    kn.wide = env_int("CCR_WIDE", -1);
-    kn.skip_sampled = env_int("CCR_SKIP_SAMPLED", -1);
-    kn.skip_list = env_int("CCR_SKIP_LIST", 1);
-    kn.qsplit = env_int("CCR_QSPLIT", -1);
-    kn.thr_phases = env_int("CCR_THR_PHASES", 0);
-    kn.narrow_grid = env_int("CCR_NARROW_GRID", 0);
-    kn.narrow_groups = env_int("CCR_NARROW_GROUPS", NARROW_MAX_GROUPS);
-    return kn;
-}
-
-static int pick_qgroups(int qblocks, int dim, const Knobs &kn, int tile_q = TILE_Q) {
-    {
-        const int v = kn.qgroups;
-        if ((v == 1 || v == 2 || v == 4 || v == 8) && qblocks % v == 0) return v;
-    }
-    const size_t block_bytes = (size_t)tile_q * dim * 2;
-    int best = 1;
-    for (int gq = 1; gq <= NUM_XCD; gq *= 2) {
-        if (qblocks % gq) continue;
-        best = gq;
-        if ((size_t)(qblocks / gq) * block_bytes <= (size_t)3 << 20) break;
-    }
-    return best;
-}
-
-// Price class of the query bytes one XCD walks in a main pass (the per-flop table of the wide tile): they stay in its 4-MiB L2
-// beside the corpus stream (0), mostly (1), or stream past it (2).
-static int footprint_class(double bytes) { return bytes <= 3.2 * 1048576.0 ? 0 : (bytes <= 5.5 * 1048576.0 ? 1 : 2); }
-
-// Unequal query groups of a single-launch main pass (main_item() in ccr_common.h): G in {2, 4, 8} that does NOT divide the block
-// count, each group base = qblocks / G whole blocks, the qblocks % G left-over blocks shared range row by range row, so that an XCD
-// walks base + rem blocks.  0 = keep the equal groups.  The planner's own choice: the smallest G whose footprint reaches a better
-// price class than the equal groups' (NQ on the wide tile: nine blocks = 5.06 MiB in one group, five = 2.81 MiB with G = 2).
-// CCR_QSPLIT=1: any block count that has a split gets one; a CCR_QGROUPS that does not divide the block count names G.
-static int pick_qsplit(int qblocks, int equal_groups, int dim, int tile_q, const Knobs &kn) {
-    if (kn.qsplit == 0) return 0;
-    const int v = kn.qgroups;
-    if (v == 2 || v == 4 || v == 8) return qblocks % v ? v : 0;
-    const double block_bytes = (double)tile_q * dim * 2.0;
-    const int equal_class = footprint_class((double)(qblocks / equal_groups) * block_bytes);
-    for (int G = 2; G <= NUM_XCD; G *= 2)
-        if (qblocks % G && footprint_class((double)(qblocks / G + qblocks % G) * block_bytes) < equal_class) return G;
-    if (kn.qsplit == 1)
-        for (int G = 2; G <= NUM_XCD; G *= 2)
-            if (qblocks % G) return G;
-    return 0;
-}
-
-static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-// Range count of the SAMPLE pass: its few tiles (1/16 ... 1/64 of the corpus) are cut into (range, query block) items like the main
-// pass's, and with so few tiles per item the rounding decides the time: 82 sample tiles x 14 query blocks in 24 ranges are 42 items per XCD
-// set = two rounds of 4- and 3-tile items, in 16 ranges one round of 6- and 5-tile items (1/8 NQ shard: 0.145 -> 0.115 ms).  The kernel's
-// static assignment is simulated exactly (workgroup j of an XCD set takes items j, j + per_x, ...; item = range-row * blocks + block).
-static int best_sample_ranges(int64_t n_vt, int qblocks, int qgroups, int grid) {
-    const int nrc = NUM_XCD / qgroups, qb_per = qblocks / qgroups, per_x = std::max(1, grid / NUM_XCD);
-    int best_r = NUM_XCD;
-    double best = 1e300;
-    const int64_t r_max = round_up(std::min<int64_t>(n_vt, 1024), NUM_XCD);
-    std::vector<double> load((size_t)per_x);
-    for (int64_t R = NUM_XCD; R <= r_max; R += NUM_XCD) {
-        double worst = 0.0;
-        for (int rc = 0; rc < nrc; ++rc) {   // the XCD sets of one query group differ only in their range class
-            std::fill(load.begin(), load.end(), 0.0);
-            const int64_t items = R / nrc * qb_per;
-            for (int64_t item = 0; item < items; ++item) {
-                const int64_t r = rc + nrc * (item / qb_per);
-                const int64_t ntile = (n_vt - r + R - 1) / R;
-                if (ntile > 0) load[(size_t)(item % per_x)] += (double)ntile + 0.15;   // + pipeline fill per item
-            }
-            worst = std::max(worst, *std::max_element(load.begin(), load.end()));
-        }
-        if (worst < best - 1e-9) {
-            best = worst;
-            best_r = (int)R;
-        }
-    }
-    return best_r;
-}
-
-constexpr size_t DENSE_SCRATCH_TARGET = (size_t)1 << 30;  // ~1 GiB of score rows per dense chunk
-
-// ------------------------------------------------------------------ main-pass planner
-// Work items of the main pass are (range, query block); range r owns the tiles r, r + R, ...  An XCD set of per_x
-// workgroups walks (R / nrc) * qb_per items round-robin, so R (a multiple of 8, near 6 items per workgroup, items of at
-// least 8 tiles) is chosen to make that count sit just below a multiple of per_x -- NQ: 128 ranges give exactly 7 items per
-// workgroup where 112 left the last round 1/8 full.  The launches: phase A = one round of items with the sample
-// thresholds, a re-tightening (threshold_update_kernel), optionally a second re-tightening after whole rounds, the rest.
-//
-// Every candidate (sample size, R, phase split) is priced in TILE UNITS of one workgroup (one 256 x 256 x dim tile ~ 22 us):
-//   makespan of each launch    simulated static item assignment (+ 0.15 tile of pipeline fill per item)
-//   sample pass                its tiles spread over the grid + the threshold kernel's passes over the group maxima
-//   select stage               0.1 per range (it walks R x sublists sub-lists per query)
-//   surviving candidates       0.014 each (filter hit path + select), a phase that covers the corpus fraction f with
-//                              thresholds taken from a fraction g seen before lets through k * f / g rows per query
-//                              (measured: 3 280 from a 1/32 sample alone, 1 180 with one re-tightening at k = 100)
-//   launch boundary            3 per extra phase
-// The per-query terms were measured at 3 452 queries (14 query blocks) and scale with the query count.
-struct MainPassChoice {
-    int64_t sample, ranges;
-    int item_a, item_b;   // phase ends in work items of one XCD set (0 = absent)
-    int opt_rank;         // > 0: ESTIMATED thresholds (the opt_rank-th largest sampled group maximum), single launch, verified by the select
-    int skip;             // 1: that launch leaves out the sampled tiles (the select joins their rows from the group maxima)
-};
-
-// May a single-launch estimated-threshold main pass leave out the `sample` sampled tiles?  Only a tile kernel (not the streaming
-// kernel of small batches), only when unsampled tiles lie between the sampled ones (stride >= 2) and every sampled tile is a full
-// tile.  Every other plan -- conservative, phased, streaming -- and the retry, margin and dense paths score every tile.
-static bool may_skip_sampled(const Plan &p, int64_t sample, bool streaming, const Knobs &kn) {
-    if (kn.skip_sampled == 0 || streaming || sample < 1) return false;
-    const int64_t stride = std::max<int64_t>(1, p.full_tiles / sample);
-    return stride >= 2 && (sample - 1) * stride < p.full_tiles && sample < p.tiles;
-}
-
-// Estimated ("optimistic") thresholds.  The conservative threshold -- the k-th largest group maximum of a sample of the corpus
-// fraction fs -- lets k / fs rows per query through the first phase, so large k needs a big sample (1/16 at k = 1001: 1/16 of the
-// corpus scored twice) and two re-tightenings.  But the filter does not need a BOUND: any threshold tau works if at least k rows
-// turn out to pass it with their lower bounds (then the k-th largest exact score is >= tau and every row that could reach it was
-// recorded) -- which the select stage checks (L >= tau; a query that fails is retried under a valid bound).  So tau is set to
-// the r-th largest sampled group maximum: about r / fs rows pass over the WHOLE corpus in ONE launch.  Given r, the pass count is
-// (r / fs) x Gamma(r) / r: fewer than k rows pass iff Gamma(r) < k fs.  r is the smallest rank whose 1e-7 lower quantile
-// (Wilson-Hilferty: r (1 - 1/(9r) - 5.2 sqrt(1/(9r)))^3) reaches k fs, and at least 40 -- k = 1001 on a 1/64 sample: r = 41,
-// 2 700 rows pass.  Why the floor: a corpus in topical order can fool the estimate when the sample holds a query's whole
-// cluster tile; with r <= 16 that ONE tile's 16 group maxima set tau (measured with r = 13 at k = 100 on the topically sorted
-// bench corpus: one query in 3 452 fails the check, and its retry costs 5 ms of an 18-ms step), with r >= 40 at least three
-// tiles contribute (k = 1001, same corpus: nobody fails).  With the floor the planner keeps the conservative plan at small k
-// (2 560 rows would pass at k = 100 against 1 296), where the phased plan is cheap anyway.  Exact either way.
-// (skip: the main pass leaves out the sampled tiles, so the k rows must pass among the unsampled fraction 1 - fs: k fs / (1 - fs))
-static int optimistic_rank(int k, int64_t sample, int64_t tiles, const Knobs &kn, bool skip = false) {
-    if (kn.opt_rank > 0) return kn.opt_rank;   // tests: a small rank makes most queries fail the check
-    const double need = (double)k * (double)sample / (double)(skip ? tiles - sample : tiles);
-    int r = 40;
-    for (; r < 1 << 20; ++r) {
-        const double a = 1.0 / (9.0 * r), t = 1.0 - a - 5.2 * sqrt(a);
-        if (t > 0.0 && (double)r * t * t * t >= need) break;
-    }
-    return r;
-}
-
-// skip_only > 0: the second call for a plan whose first choice was a single launch under estimated thresholds on the sample
-// skip_only and which may leave out the sampled tiles -- only that kind of plan on that sample is priced, now over the
-// tiles - sample virtual tiles its launch walks (ranges, rounds, item cost).  The sample size and the kind of plan stay chosen on the
-// price of scoring every tile: the re-priced model prefers twice the sample at NQ by less than its own error (the sample pass's
-// tiles count as main-pass tiles that need not be walked), and the select's walk over the group maxima grows with the sample.
-static MainPassChoice choose_main_pass(const Plan &p, int k, int64_t sample_a, int64_t sample_b, int64_t sample_c, const Knobs &kn,
-                                       bool single_only = false, int64_t skip_only = 0) {
-    const int nrc = NUM_XCD / p.main_qgroups, qb_per = p.main_qblocks / p.main_qgroups, per_x = p.grid / NUM_XCD;
-    // a 256 x 384 tile in units of the 256 x 256 tile the other terms were measured in (1.5x the multiply-adds at ~1.09x the rate)
-    const double tile_cost = p.tile_q == WIDE_Q ? 1.37 : 1.0;
-    // the select stage walks ranges x sublists sub-lists per query: 1 024 with its 256-thread form, 2 048 with the 1 024-thread
-    // form large k uses anyway (rescore_cap > 512)
-    int64_t max_lists = p.rescore_cap > 512 ? 2048 : 1024;
-    // one or two query blocks: 128 ranges x 8 sub-lists would leave half of the workgroups without a work item (n_q = 1: main pass
-    // 1.34 ms instead of 0.7) -- the select stage's wide form walks 2 048 sub-lists, and its cost does not matter for so few queries
-    if ((max_lists / p.sublists) * p.main_qblocks < p.grid) max_lists = 2048;
-    if (kn.max_lists >= 64 && kn.max_lists < max_lists) max_lists = kn.max_lists;
-    const int64_t r_hi = std::min<int64_t>(max_lists / p.sublists, round_up(std::max<int64_t>(1, p.tiles / 8), NUM_XCD));
-    const int64_t target = std::min<int64_t>(r_hi, round_up(std::max<int64_t>(NUM_XCD, (int64_t)p.grid * 6 / p.main_qblocks), NUM_XCD));
-    const bool prog_on = kn.progressive != 0 && !single_only;   // 0: single launch (the streaming kernel of small batches has no phases)
-    const int max_phases = kn.max_phases;        // 2: at most one re-tightening
-    const double qscale = (double)p.nq_pad / 3584.0;
-    const double select_per_range = 0.1 * qscale, hit_w = 0.014 * qscale, phase_w = 3.0;
-    // 0.11 ms = 4.9 units of threshold kernel for 328 sample tiles x 3 584 queries
-    // (the threshold kernel's time follows the number of sampled groups, not the number of queries, below ~3 500 queries: it runs
-    // nq_pad / 16 workgroups of four latency-bound passes -- 0.21 ms for 655 sample tiles at n_q = 1)
-    auto sample_cost = [&](int64_t smp) -> double {
-        return (double)((smp * p.qblocks + p.grid - 1) / p.grid) + 0.015 * (double)smp * std::max(1.0, qscale);
-    };
-
-    MainPassChoice best_choice = {sample_a, target, 0, 0, 0, 0};
-    double best = 1e300;
-    for (int pass = 0; pass < 3; ++pass) {
-        const int64_t smp = pass == 0 ? sample_a : (pass == 1 ? sample_b : sample_c);
-        if ((pass >= 1 && smp == sample_a) || (pass == 2 && smp == sample_b)) continue;
-        if (skip_only && smp != skip_only) continue;
-        const double fs = (double)smp / (double)p.tiles;
-        const double smp_cost = sample_cost(smp);
-        auto survivors = [&](double fa, double fb) -> double {   // fa, fb: corpus fractions of phases A and B1 (0 = absent)
-            if (fa <= 0.0) return (double)k / fs;
-            if (fb <= 0.0) return (double)k * (fa / fs + (1.0 - fa) / fa);
-            return (double)k * (fa / fs + fb / fa + (1.0 - fa - fb) / (fa + fb));
-        };
-        // Every XCD set holds the same items = (R / classes) * blocks_per_group, all of ceil(tiles / R) tiles at most, dealt
-        // round-robin to its per_x workgroups: a launch over n items takes ceil(n / per_x) rounds.  Phases end at ITEM
-        // indices, so phase A is exactly one full round (and the middle phase whole rounds) for any R.
-        // R stays a multiple of the XCD count (not just of the range classes): the retry pass of flagged queries re-uses the
-        // ranges with its own, possibly different, query grouping
-        const int64_t r_lo = std::max<int64_t>(NUM_XCD, target / 2 / NUM_XCD * NUM_XCD);
-        for (int64_t R = r_lo; R <= std::min(r_hi, target * 2); R += NUM_XCD) {
-            if (kn.ranges > 0 && R != std::min<int64_t>(r_hi, std::max<int64_t>(r_lo, round_up(kn.ranges, NUM_XCD)))) continue;
-            const int64_t items = R / nrc * qb_per;
-            const double item_cost = ((double)((p.tiles + R - 1) / R) + 0.15) * tile_cost;   // + pipeline fill per item
-            auto rounds = [&](int64_t n) { return (double)((n + per_x - 1) / per_x); };
-            const double common = smp_cost + select_per_range * (double)R + 1e-3 * std::abs((double)(R - target));
-            const double single = rounds(items) * item_cost + hit_w * survivors(0.0, 0.0) + common;
-            if (single < best && kn.optimistic != 1 && !skip_only) {
-                best = single;
-                best_choice = {smp, R, 0, 0, 0, 0};
-            }
-            if (kn.optimistic != 0 && smp * GROUPS_PER_TILE >= 4 * 40) {   // estimated thresholds: one launch, ~rank / fs rows pass
-                // (a main pass that leaves out the sampled tiles walks tiles - smp virtual tiles)
-                const bool skip = skip_only && may_skip_sampled(p, smp, single_only, kn);
-                const int rank = optimistic_rank(k, smp, p.tiles, kn, skip);
-                if ((int64_t)rank * 4 <= smp * GROUPS_PER_TILE) {
-                    const double pass = std::max((double)rank / fs, (double)k);
-                    const double opt_item = skip ? ((double)((p.tiles - smp + R - 1) / R) + 0.15) * tile_cost : item_cost;
-                    const double opt = rounds(items) * opt_item + hit_w * pass + common - (kn.optimistic == 1 ? 1e9 : 0.0);
-                    if (opt < best) {
-                        best = opt;
-                        best_choice = {smp, R, 0, 0, rank, skip ? 1 : 0};
-                    }
-                }
-            }
-            if (skip_only || !(prog_on && items > per_x && (double)p.tiles / (double)R >= 8.0)) continue;
-            // the thresholds after phase A come from the ranges it completed (+ the started one for part of the queries)
-            const double fa = (double)per_x / (double)items;
-            const double two = (1.0 + rounds(items - per_x)) * item_cost + phase_w + hit_w * survivors(fa, 0.0) + common;
-            if (two < best) {
-                best = two;
-                best_choice = {smp, R, per_x, 0, 0, 0};
-            }
-            if (max_phases < 3) continue;
-            for (int m = 1; m <= 3; ++m) {   // a second re-tightening after m more rounds
-                const int64_t ib = (int64_t)per_x * (1 + m);
-                if (ib >= items) break;
-                const double fb = (double)m * per_x / (double)items;
-                const double three = (1.0 + m + rounds(items - ib)) * item_cost + 2.0 * phase_w + hit_w * survivors(fa, fb) + common;
-                if (three < best) {
-                    best = three;
-                    best_choice = {smp, R, per_x, (int)ib, 0, 0};
-                }
-            }
-        }
-    }
-    return best_choice;
-}
-
-// candidate layout of one segment over every range
-static CandLayout one_segment(int cap) {
-    CandLayout L;
-    memset(&L, 0, sizeof(L));
-    L.nseg = 1;
-    L.seg_end[0] = L.seg_end[1] = L.seg_end[2] = INT32_MAX;
-    L.cap[0] = L.cap[1] = L.cap[2] = cap;
-    return L;
-}
-
-static Plan make_plan_for(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn, int mfma16) {
-    Plan p;
-    memset(&p, 0, sizeof(p));
-    p.nq_pad = (int)round_up(n_q, TILE_Q);
-    p.qblocks = p.nq_pad / TILE_Q;
-    p.tile_q = TILE_Q;
-    p.main_qblocks = p.qblocks;
-    p.main_qgroups = 1;
-    p.tiles = (n_rows + TILE_DOCS - 1) / TILE_DOCS;
-    p.full_tiles = n_rows / TILE_DOCS;
-    p.grid = std::max(NUM_XCD, num_cu / NUM_XCD * NUM_XCD);
-    {
-        p.mfma16 = mfma16;   // main pass on v_mfma_f32_16x16x32_bf16 (8 sub-lists per (range, query)) or 32x32x16 (4)
-        p.sublists = p.mfma16 ? 8 : 4;
-    }
-    p.rescore_cap = p.rescore_regular = std::min(8192, std::max(256, 2 * pow2_ceil(k)));
-
-    // sample pass: group maxima of 16 rows; need comfortably more groups than k
-    const int64_t min_sample = (2 * (int64_t)k + GROUPS_PER_TILE - 1) / GROUPS_PER_TILE;
-    int64_t sample_div = 32;   // fraction of the tiles scored by the threshold pass; the planner also prices 1/64
-    bool sample_div_forced = false;   // CCR_SAMPLE_DIV pins it
-    {
-        if (kn.sample_div >= 4 && kn.sample_div <= 256) {
-            sample_div = kn.sample_div;
-            sample_div_forced = true;
-        }
-    }
-    auto sample_for = [&](int64_t div) { return std::max<int64_t>({(p.tiles + div - 1) / div, min_sample, 4}); };
-    int64_t sample = sample_for(sample_div);
-    // any dim the index accepts (a multiple of 8): the fused kernels zero-fill the last 32-element K sub-stage when dim % 32 != 0
-    bool fused = (dim % 8 == 0) && dim >= 8 && (sample * 4 <= p.full_tiles) && k <= MAX_K;
-    if ((flags & CCR_SEARCH_FORCE_FUSED) && (dim % 8 == 0) && p.full_tiles >= 1) {
-        // honour the request where at all possible: the sample may be the whole corpus
-        if (!fused) sample = std::min<int64_t>(std::max<int64_t>(sample, 1), p.full_tiles);
-        fused = sample * GROUPS_PER_TILE >= k;
-    }
-    if (flags & CCR_SEARCH_FORCE_DENSE) fused = false;
-    p.fused = fused ? 1 : 0;
-
-    if (p.fused) {
-        p.qgroups = pick_qgroups(p.qblocks, dim, kn);
-        // the planner prices three sample sizes: 1/32 of the tiles, 1/64 (cheaper pass, twice the survivors of phase A) and 1/16
-        // (large k: phase A's survivors cost more than the second half of the sample)
-        const bool pinned = sample_div_forced || (flags & CCR_SEARCH_FORCE_FUSED);
-        const int64_t sample_alt = pinned ? sample : sample_for(2 * sample_div);
-        int64_t sample_big = pinned ? sample : sample_for(sample_div / 2);
-        if (sample_big * 4 > p.full_tiles) sample_big = sample;
-        // small batches: the first main pass is the streaming kernel (ccr_narrow.hip) when the query rows fit its LDS image
-        // (65 .. 128 queries: two groups of <= 64 on paired workgroups that walk the same rows)
-        int nqt = n_q <= 16 ? 1 : (n_q <= 32 ? 2 : 4);
-        int ngroups = n_q <= NARROW_MAX_Q ? 1 : 2;
-        // 65 .. 96 queries: ONE group of six query tiles where their rows fit the LDS (dim <= 768) -- every corpus row is pulled once
-        if (n_q > NARROW_MAX_Q && n_q <= 96 && kn.narrow_groups >= 2 && dim % TILE_K == 0 && narrow_lds_bytes(6, dim) <= (size_t)160 * 1024)
-            nqt = 6, ngroups = 1;
-        const bool narrow = kn.narrow != 0 && n_q <= NARROW_MAX_Q * std::min(std::max(kn.narrow_groups, 1), NARROW_MAX_GROUPS) && dim % TILE_K == 0 &&
-                            narrow_lds_bytes(nqt, dim) <= (size_t)160 * 1024 && (ngroups == 1 || num_cu >= 16);
-        p.narrow = narrow ? nqt : 0;
-        p.narrow_groups = narrow ? ngroups : 1;
-        // the main pass's tile: 256 x 384 (gemm_topk16w_kernel: -17 % bytes per flop through the L1 miss path that bounds the 256 x 256
-        // kernel) where it pays.  Measured at the NQ corpus (profiles/r06_wide_*.txt), per padded multiply-add against the 256 x 256
-        // kernel: 0.92-0.96 while the query rows one XCD walks stay L2-resident (300 and 1 100 queries: main pass -31 % / -14 %, most
-        // of it the padding: one block instead of two, three instead of five), 0.97 at 5 MiB per XCD (3 452 queries: nine blocks =
-        // 3 456 columns against fourteen = 3 584: -6.5 %), and SLOWER beyond -- 4 096 queries = eleven blocks, 6 980 = nineteen: a prime
-        // block count has no equal groups over the XCDs, every XCD streams all the query rows past its 4-MiB L2 (L2 hit rate 0.71 against
-        // 0.91, +3.4 % main pass) while sixteen / twenty-eight 256-blocks split into groups that fit.
-        // (The tile is priced on its EQUAL groups: the unequal ones of pick_qsplit exist for a single-launch plan only, which is not
-        // known yet, and they have been measured at nine blocks alone -- eleven and nineteen blocks stay on the 256 x 256 tile.)
-        p.tile_q = TILE_Q;
-        p.main_qblocks = p.qblocks;
-        if (!narrow && p.mfma16 && dim % 32 == 0 && kn.wide != 0) {
-            const int wb = (n_q + WIDE_Q - 1) / WIDE_Q;
-            const double per_xcd = (double)(wb / pick_qgroups(wb, dim, kn, WIDE_Q)) * WIDE_Q * dim * 2.0;   // query bytes one XCD walks
-            const double per_flop = per_xcd <= 3.2 * 1048576.0 ? 0.95 : (per_xcd <= 5.5 * 1048576.0 ? 0.97 : 1.04);
-            if (kn.wide == 1 || (double)wb * WIDE_Q * per_flop < (double)p.qblocks * TILE_Q) {
-                p.tile_q = WIDE_Q;
-                p.main_qblocks = wb;
-                p.nq_pad = (int)round_up(std::max<int64_t>(n_q, (int64_t)wb * WIDE_Q), TILE_Q);   // the counters of every block's columns exist
-                p.qblocks = p.nq_pad / TILE_Q;
-                p.qgroups = pick_qgroups(p.qblocks, dim, kn);
-            }
-        }
-        p.main_qgroups = pick_qgroups(p.main_qblocks, dim, kn, p.tile_q);
-        MainPassChoice choice = choose_main_pass(p, k, sample, sample_alt, sample_big, kn, narrow);
-        if (choice.opt_rank > 0 && may_skip_sampled(p, choice.sample, narrow, kn)) {
-            const MainPassChoice skipped = choose_main_pass(p, k, sample, sample_alt, sample_big, kn, narrow, choice.sample);
-            if (skipped.skip) choice = skipped;   // (else: the rank the unsampled fraction needs does not fit the sample)
-        }
-        sample = choice.sample;
-        const int64_t R = choice.ranges;
-        p.sample_tiles = (int)sample;
-        p.sample_stride = std::max<int64_t>(1, p.full_tiles / sample);
-        p.sample_ranges = best_sample_ranges(sample, p.qblocks, p.qgroups, p.grid);
-        p.ranges = (int)R;
-        p.item_a = choice.item_a;
-        p.item_b = choice.item_b;
-        p.opt_rank = choice.opt_rank;
-        p.skip_sampled = (p.opt_rank > 0 && !p.narrow) ? choice.skip : 0;
-        // unequal query groups: a single launch of a tile kernel only (phase ends are item indices of the equal groups' map, and
-        // the re-tightening between two phases takes a query's finished ranges from its block's place in an equal group)
-        p.main_qsplit = (!p.narrow && p.item_a == 0 && p.item_b == 0) ? pick_qsplit(p.main_qblocks, p.main_qgroups, dim, p.tile_q, kn) : 0;
-        // the join can add a whole sampled tile to a query's collected rows (a corpus in topical order): room for one beside the
-        // regular rows (about k, and ties around the cut) -- 512 at k = 100, which keeps the select's 256-thread form.  On iid rows a
-        // sampled group of 16 holds a row of the top k with probability 1 - (1 - k / n)^16 and joins whole: J rows per query (50 at NQ,
-        // k = 100; 1 700 for k = 1001 of 300 000 rows with a tenth of them sampled: measured, every query overflowed 2 048) -- room
-        // for 1.5 J of them; where even 8 192 do not hold that, every tile is scored
-        if (p.skip_sampled) {
-            const double join_rows = 256.0 * (double)choice.sample * (1.0 - pow(1.0 - std::min(1.0, (double)k / (double)n_rows), 16.0));
-            const double need = (double)k + (double)(k / 4) + 1.5 * join_rows + TILE_DOCS + 16;
-            // the planner's own choice prices the join: a joined row costs the select 0.065 tile units (measured at NQ: + 0.06 ms for
-            // 50 rows per query at k = 100, + 0.42 ms for 250 at k = 1001), the main pass saves sample x blocks / grid tiles per
-            // workgroup of which the item rounding returns about half (0.29 of 0.35 ms at k = 100, 0.08 of 0.17 at k = 1001: there the
-            // search got SLOWER, 13.46 against 13.10 ms) -- CCR_SKIP_SAMPLED=1 skips wherever the plan allows.
-            // The three constants (0.065, the 3 584-query scale of the planner's other per-query terms, the half) are fitted to
-            // those TWO measured points: at NQ the rule switches the skip off above k of about 240; nothing between the points and
-            // no other query count has been measured.
-            const double saved = 0.5 * (double)choice.sample * p.main_qblocks * (p.tile_q == WIDE_Q ? 1.37 : 1.0) / (double)p.grid;
-            const bool pays = 0.065 * join_rows * ((double)p.nq_pad / 3584.0) < saved;
-            if (need > 8192.0 || (kn.skip_sampled < 0 && !pays))
-                p.skip_sampled = 0;
-            else
-                p.rescore_cap = std::min(8192, std::max(p.rescore_cap, pow2_ceil((int)need)));
-        }
-        // ranges that hold items of a phase: the candidate segments (a range started in phase A keeps phase A's capacity)
-        const int nrc_p = NUM_XCD / p.main_qgroups, qb_per_p = p.main_qblocks / p.main_qgroups;
-        const int64_t RA = p.item_a ? std::min<int64_t>(R, (int64_t)nrc_p * ((p.item_a + qb_per_p - 1) / qb_per_p)) : 0;
-        const int64_t RB = p.item_b ? std::min<int64_t>(R, (int64_t)nrc_p * ((p.item_b + qb_per_p - 1) / qb_per_p)) : 0;
-        const double ratio = (double)p.tiles / (double)sample;
-        const double expect = (double)k * ratio * 1.3 + 64.0;  // survivors per query under the sample thresholds alone
-        // Sub-list capacities, one per phase (segment).  A phase whose thresholds were taken from a corpus fraction g lets
-        // k / g rows per query through, spread over R * sublists sub-lists.  Two noise terms on top of that mean:
-        //   the threshold itself is the k-th order statistic of what was seen: its pass rate is Gamma(k)-distributed, an
-        //     upper quantile of it is (k + 4.75 sqrt(k) + 8) / k times the mean (15 x at k = 1, 1.6 x at k = 100, 1.16 x at
-        //     k = 1000) -- times 1.25 for uneven data;
-        //   the count of one sub-list is Poisson around its share: + 6 sigma + 16.
-        // An overflowing sub-list only flags its query for the exact path, so the model needs to be safe, not a bound.
-        const double fs = 1.0 / ratio, nlists = (double)R * p.sublists;
-        const double xk = 1.25 * ((double)k + 4.75 * sqrt((double)k) + 8.0) / (double)k;
-        // Allowance: one WHOLE tile may pass for a query (a corpus in topical order: all 256 rows of a tile belong to the
-        // query's cluster); that is TILE_DOCS / sublists rows for one sub-list on top of its regular share.
-        const int64_t tile_rows = TILE_DOCS / p.sublists;
-        // estimated thresholds: about opt_rank / fs rows pass, Gamma(opt_rank)-distributed
-        const double xr = p.opt_rank ? 1.25 * ((double)p.opt_rank + 4.75 * sqrt((double)p.opt_rank) + 8.0) / (double)p.opt_rank : 0.0;
-        auto cap_for = [&](double g) -> int {
-            const double mean = p.opt_rank ? xr * std::max((double)p.opt_rank / fs, (double)k) / nlists : xk * (double)k / (g * nlists);
-            const int64_t c = (int64_t)(mean + 6.0 * sqrt(mean)) + 16 + tile_rows;   // the model's share PLUS one whole tile
-            return (int)round_up(std::min<int64_t>(std::max<int64_t>(c, 16), 8192), 4);
-        };
-        // corpus fractions the re-tightenings have SEEN: the ranges completed by then
-        const double fa = p.item_a ? (double)(p.item_a / qb_per_p) * nrc_p / (double)R : 0.0;
-        const double fb = p.item_b ? std::max(0.0, (double)(p.item_b / qb_per_p) * nrc_p / (double)R - fa) : 0.0;
-        // the re-tightening selects among at most `compact` of the candidates found so far (launch_threshold_update): when
-        // phase A is expected to leave more than that, the bound is the k-th of a subset and passes proportionally more
-        const double upd_compact = std::min(32768.0, std::max(4096.0, 8.0 * pow2_ceil(k)));
-        auto seen = [&](double g, double found) { return found > upd_compact ? g * upd_compact / found : g; };
-        const double found_a = (double)k * fa / fs;
-        CandLayout &L = p.cand;
-        memset(&L, 0, sizeof(L));
-        const int seg_end_v[3] = {RA ? (int)RA : (int)R, RB > RA ? (int)RB : (int)R, (int)R};
-        int64_t recs = 0;
-        L.nseg = 0;
-        int prev_end = 0;
-        for (int g = 0; g < 3; ++g) {
-            L.seg_end[g] = INT32_MAX;
-            L.cap[g] = 16;
-            L.base[g] = recs;
-        }
-        for (int g = 0; g < 3; ++g) {
-            if (seg_end_v[g] <= prev_end) continue;
-            const int sg = L.nseg++;
-            double frac_seen = fs;                                  // phase A: the sample
-            if (sg == 1) frac_seen = fa >= 2.0 * fs ? seen(fa, found_a) : fs;
-            if (sg == 2) frac_seen = fa >= 2.0 * fs ? seen(fa + fb, found_a + (double)k * fb / fa) : fs;
-            L.seg_end[sg] = seg_end_v[g];
-            L.cap[sg] = cap_for(std::min(1.0, std::max(frac_seen, fs)));
-            L.base[sg] = recs;
-            recs += (int64_t)(seg_end_v[g] - prev_end) * p.nq_pad * p.sublists * L.cap[sg];
-            recs = round_up(recs, 32);
-            prev_end = seg_end_v[g];
-        }
-        L.seg_end[L.nseg - 1] = INT32_MAX;   // the last segment is open-ended (sub-list lookups never fall off the table)
-        p.cap = L.cap[0];
-        // survivors per query reaching the select stage: ~12 k after the progressive re-tightening, `expect` without it
-        // (estimated thresholds leave fewer candidates, but the select's staged re-score borrows this area: about 1.15 k rows are
-        // re-scored per query and a 64-byte slice of each needs 80 bytes = 10 entries -- a smaller area sends the re-score down its
-        // unstaged path: measured 2.41 instead of 2.06 ms at k = 1001)
-        const double want_opt = std::max(xr * std::max((double)p.opt_rank / fs, (double)k) + 512.0, k > 256 ? 18.0 * k : 0.0);   // (18 entries per re-scored row: the 128-byte slices, where the LDS budget allows)
-        p.select_compact = select_compact_entries(dim, p.ranges * p.sublists, p.rescore_cap,
-                                                  (int64_t)((p.opt_rank ? want_opt : (RA ? 16.0 * k + 512.0 : expect)) * 1.25));
-        // what the FIRST main pass fills: the tile kernels' (range, query) cells -- or, for the streaming kernel, one cell of two
-        // sub-lists per query with whatever the candidate area gives each of them (at least 8 x the model's expectation)
-        p.first_nsub = p.ranges * p.sublists;
-        p.first_sp = p.sublists;
-        p.first_lay = p.cand;
-        if (p.narrow) {
-            const double pass = p.opt_rank ? xr * std::max((double)p.opt_rank / fs, (double)k) : expect;
-            int64_t capn = std::max<int64_t>(recs / ((int64_t)NARROW_SUBLISTS * std::max(1, n_q)), (int64_t)(8.0 * pass) + 4096);
-            capn = std::min<int64_t>(capn, (int64_t)1 << 22) / 4 * 4;
-            recs = std::max<int64_t>(recs, capn * NARROW_SUBLISTS * n_q);
-            p.first_lay = one_segment((int)capn);
-            p.first_nsub = NARROW_SUBLISTS;
-            p.first_sp = NARROW_SUBLISTS;
-        }
-        p.cand_recs = recs;
-        p.dense_rows_per_chunk = FALLBACK_ROWS;
-    } else {
-        int64_t rows = (int64_t)(DENSE_SCRATCH_TARGET / ((size_t)n_rows * 4));
-        rows = std::min<int64_t>(std::max<int64_t>(rows, 1), n_q);
-        if (rows >= 64) rows = rows / 64 * 64;
-        p.dense_rows_per_chunk = rows;
-    }
-    const SearchWs w = search_ws(p, n_rows, dim, n_q, k, nullptr);   // no base: the pointers are the byte offsets
-    p.off_qnorm = (size_t)w.qnorm, p.off_thr = (size_t)w.thr, p.off_gmax = (size_t)w.gmax, p.off_cnt = (size_t)w.cnt, p.off_cand = (size_t)w.cand;
-    p.off_flag = (size_t)w.flag_count, p.off_dense = (size_t)w.dense, p.off_retry = (size_t)w.Q2, p.off_top = (size_t)w.top, p.off_safe = (size_t)w.thr_safe;
-    p.total = w.total;
-    return p;
-}
-
-SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char *base) {
-    SearchWs w;
-    memset(&w, 0, sizeof(w));
-    Bump b = {0};
-    auto at = [&](size_t off) { return (char *)((uintptr_t)base + off); };
-    auto take = [&](size_t bytes) { return at(b.take(bytes)); };
-    if (!p.fused) {
-        w.flag_count = (uint32_t *)take(64 + (size_t)n_q * 4);   // queries the margin select hands to the fp64 path
-        w.flag_list = w.flag_count + 16;
-        w.dense_bytes = (size_t)p.dense_rows_per_chunk * (n_rows + 3) * 4;
-        w.dense = (float *)take(w.dense_bytes);
-        w.total = b.off;
-        return w;
-    }
-    const size_t nq_pad = p.nq_pad;
-    w.qnorm = (float *)take(nq_pad * 4);
-    w.thr = (float *)take(nq_pad * 8);
-    w.cq = w.thr + nq_pad;
-    w.gmax = (float *)take((size_t)p.sample_tiles * GROUPS_PER_TILE * nq_pad * 4);
-    w.cnt = (uint32_t *)take((size_t)p.ranges * nq_pad * p.sublists * 4);
-    w.cand = (uint2 *)take((size_t)p.cand_recs * 8);
-    w.flag_count = (uint32_t *)take(64 + (size_t)n_q * 4);
-    w.stat_cand = (unsigned long long *)(w.flag_count + 2);
-    w.flag_list = w.flag_count + 16;
-    w.cand_bytes = (char *)w.flag_count - (char *)w.cand;
-    w.top = (uint32_t *)take(p.item_b ? (nq_pad + (size_t)n_q * k) * 4 : 0);
-    w.thr_safe = (float *)take(p.opt_rank ? nq_pad * 8 : 0);
-    w.cq_safe = w.thr_safe + nq_pad;
-    w.glist = (uint32_t *)take(p.skip_sampled ? nq_pad * (size_t)(skip_list_cap(p.opt_rank) + 1) * 4 : 0);
-    w.dense_bytes = (size_t)p.dense_rows_per_chunk * n_rows * 4;
-    w.dense = (float *)take(w.dense_bytes);
-    // the retry area keeps its reserved size: its nine sub-buffers plus up to 255 bytes of rounding each
-    w.retry_bytes = nq_pad * dim * 2 + nq_pad * 8 + (size_t)n_q * 16 + 64 + 64 + (size_t)n_q * 4 + 256 * 10;
-    Bump r = {b.take(w.retry_bytes)};
-    w.Q2 = (uint16_t *)at(r.take(nq_pad * dim * 2));
-    w.thr2 = (float *)at(r.take(nq_pad * 4));
-    w.cq2 = (float *)at(r.take(nq_pad * 4));
-    w.retry_list = (uint32_t *)at(r.take((size_t)n_q * 4));
-    w.dense_list = (uint32_t *)at(r.take((size_t)n_q * 4));
-    w.counts = (uint32_t *)at(r.take(64));
-    w.flag2 = (uint32_t *)at(r.take(64 + (size_t)n_q * 4));
-    w.list_b = (uint32_t *)at(r.take((size_t)n_q * 4));
-    w.list_c = (uint32_t *)at(r.take((size_t)n_q * 4));
-    w.total = b.off;
-    return w;
-}
-
-// Which main-pass kernel: CCR_MFMA16 pins it.  Otherwise the 16x16x32 kernel (the chip holds a higher clock on that MFMA shape)
-// whenever its eight sub-lists per (range, query) do not force FEWER ranges than the 32x32x16 plan wants: up to k = 512 always
-// (measured), above that when the four-sub-list plan's range count times 8 stays within the select stage's 2 048
-// sub-lists (config-4 shard, k = 1000, 62 ranges: main pass 111 vs 120 ms, select 8.9 vs 9.4 ms).
-Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn) {
-    if (kn.mfma16 >= 0) return make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, kn.mfma16 ? 1 : 0);
-    if (k <= 512) return make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, 1);
-    const Plan p32 = make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, 0);
-    if (p32.fused && p32.ranges * 8 <= 2048) return make_plan_for(n_rows, dim, n_q, k, flags, num_cu, kn, 1);
-    return p32;
 }
 
 }  // namespace ccr

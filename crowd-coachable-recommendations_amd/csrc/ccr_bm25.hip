@@ -482,7 +482,7 @@ __global__ __launch_bounds__(256) void bm25_check_postings_kernel(const int32_t 
 }
 
 // rank of the sample whose value at most k documents fail to reach with probability < 1e-7 (the planner's rule for estimated
-// thresholds, ccr_api.hip: Wilson-Hilferty lower quantile of Gamma(r) >= k x sample fraction; at least 40)
+// thresholds, ccr_plan.hip: Wilson-Hilferty lower quantile of Gamma(r) >= k x sample fraction; at least 40)
 static int bm25_sample_rank(int k, double fs) {
     const double need = (double)k * fs;
     int r = 40;

@@ -74,46 +74,6 @@ __host__ __device__ __forceinline__ long long cand_sublist(const CandLayout &L, 
     return L.base[g] + (((long long)(r - r0) * nq_pad + q) * sp) * (long long)cap + s;
 }
 
-struct Plan {
-    int fused;            // 1 = fused MFMA path usable
-    int nq_pad;           // n_q rounded up to TILE_Q (256 x 384 main pass: at least main_qblocks * 384)
-    int qblocks;          // nq_pad / TILE_Q: the query blocks of the sample pass (and of every 256 x 256 kernel)
-    int tile_q;           // queries per tile of the MAIN pass: TILE_Q, or 384 (gemm_topk16w_kernel)
-    int main_qblocks;     // query blocks of the main pass: ceil(n_q / tile_q)
-    int main_qgroups;     // ... and their groups over the XCDs (divides main_qblocks)
-    int main_qsplit;      // 0, or the UNEQUAL groups (2, 4, 8; do not divide main_qblocks) of a single-launch main pass: main_item()
-    int64_t tiles;        // ceil(n_rows / TILE_DOCS)
-    int64_t full_tiles;   // floor(n_rows / TILE_DOCS)
-    int sample_tiles;     // tiles scored by the threshold pass
-    int64_t sample_stride;
-    int sample_ranges;    // range count of the sample pass (chosen by simulating its item assignment)
-    int ranges;           // corpus ranges of the main pass (multiple of NUM_XCD)
-    int item_a;           // phase A = work items [0, item_a) of every XCD set (0 = single phase); thresholds are re-tightened after it
-    int item_b;           // end of the second phase in items (0: two phases)
-    int opt_rank;         // > 0: estimated thresholds = the opt_rank-th largest sampled group maximum (single launch; the select verifies)
-    int skip_sampled;     // 1: the main pass does not score the sample_tiles sampled tiles again; the select joins their rows from gmax
-    int qgroups;          // query-block groups over the XCDs
-    int cap;              // candidate slots per sub-list (the largest segment's: statistics)
-    CandLayout cand;      // per-phase segments of the candidate area
-    int grid;             // persistent workgroups (multiple of NUM_XCD)
-    int rescore_cap;      // max rows re-scored per query (power of two)
-    int rescore_regular;  // ... of them recorded candidates (skip_sampled: rescore_cap also holds the joined rows of the sampled tiles)
-    int select_compact;   // candidates per query the select kernel gathers into LDS
-    int mfma16;           // 1: main pass on the 16x16x32 MFMA kernel
-    int sublists;         // candidate sub-lists per (range, query): 4 (32x32x16 kernel) or 8 (16x16x32 kernel)
-    // small query batches (n_q <= 64, query rows resident in LDS): the FIRST main pass is the streaming kernel (ccr_narrow.hip) with
-    // its own list layout -- one range, two sub-lists per query; the retry pass of flagged queries keeps the tile kernels' layout above
-    int narrow;           // 0, or the query tiles of 16 the streaming kernel computes (1, 2, 4)
-    int narrow_groups;    // 1, or 2: 65 .. 128 queries as two groups of <= 64, each streamed by half of the workgroups (pairs on one XCD)
-    int first_nsub;       // sub-lists per query the first main pass fills (ranges * sublists, or 2) ...
-    int first_sp;         // ... per cell (sublists, or 2) ...
-    CandLayout first_lay; // ... and where they are (cand, or one segment of narrow capacity)
-    int64_t cand_recs;    // 8-byte records of the candidate area
-    // workspace layout (byte offsets, as search_ws lays it out)
-    size_t off_qnorm, off_thr, off_gmax, off_cnt, off_cand, off_flag, off_dense, off_retry, off_top, off_safe, total;
-    int64_t dense_rows_per_chunk;  // queries per dense chunk
-};
-
 // The sample pass scores the tiles j * s, j < n (s = sample stride, n = sample tiles).  The v-th of the OTHER tiles in ascending
 // order: below n * (s - 1) every run of s - 1 unsampled tiles sits behind one sampled tile, beyond the last sampled tile the shift
 // is n.  s = 0: no tile is left out.  Tile counts fit 32 bits (n_rows < 2^32).

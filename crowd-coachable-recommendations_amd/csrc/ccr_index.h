@@ -1,63 +1,10 @@
 // ccr_index.h -- the index object and the launchers shared by the host-side translation units
-// (ccr_api.hip: planner + ccr_search; ccr_special.hip: blocked / sparse-prior searches).
+// (ccr_api.hip: ccr_search; ccr_special.hip: blocked / sparse-prior searches).  The planner's interface is ccr_plan.h.
 #pragma once
 #include "ccr_common.h"
+#include "ccr_plan.h"
 
 namespace ccr {
-
-// Tuning knobs from the environment, read ONCE when an index is created (never inside a search).
-struct Knobs {
-    int qgroups;       // CCR_QGROUPS      0 = planner's choice, else 1/2/4/8
-    int progressive;   // CCR_PROGRESSIVE  0 = single main-pass launch
-    int max_phases;    // CCR_PHASES       2 = at most one re-tightening (default 3)
-    int mfma16;        // CCR_MFMA16       -1 = planner's choice, 0 = 32x32x16 kernel, 1 = 16x16x32 kernel
-    int sample_div;    // CCR_SAMPLE_DIV   0 = planner's choice, else the pinned sample fraction 1/div
-    int ranges;        // CCR_RANGES       0 = planner's choice, else the pinned range count (rounded to a multiple of 8)
-    int optimistic;    // CCR_OPTIMISTIC   -1 = planner's choice, 0 = conservative thresholds only, 1 = estimated thresholds wherever the sample allows
-    int opt_rank;      // CCR_OPT_RANK     0 = max(48, 3 k fs), else the pinned rank (tests: a small rank makes the verification fail)
-    int max_lists;     // CCR_MAX_LISTS    0 = planner's limit, else a cap on ranges x sublists (A/B of the select stage's walk)
-    int narrow;        // CCR_NARROW       -1 = planner's choice (n_q <= 64 whose rows fit the LDS), 0 = tile kernels only (the A/B knob)
-    int narrow_grid;   // CCR_NARROW_GRID  0 = planner's choice, else workgroups of the streaming kernel
-    int skip_sampled;  // CCR_SKIP_SAMPLED -1 = planner's choice, 0 = the main pass scores every tile (the A/B knob), 1 = it leaves out the sampled tiles wherever the plan allows
-    int skip_list;     // CCR_SKIP_LIST    1 = the select's join reads the threshold kernel's short list of sampled groups (default), 0 = it walks the query's column of group maxima (the A/B knob)
-    int qsplit;        // CCR_QSPLIT       -1 = planner's choice, 0 = equal query groups only (the A/B knob), 1 = unequal groups (left-over blocks shared) wherever a single-launch main pass has a block count they apply to; a CCR_QGROUPS that does not divide the block count names their number
-    int wide;          // CCR_WIDE         -1 = planner's choice, 0 = 256 x 256 main-pass tiles only (the A/B knob), 1 = 256 x 384 wherever the kernel applies
-    int thr_phases;    // CCR_THR_PHASES   0 = launcher's choice by the sample's size, 16 / 64 = the threshold kernel's group phases per query, pinned (tests, the A/B)
-    int narrow_groups; // CCR_NARROW_GROUPS 2 = batches of 65 .. 128 queries stream as two query groups (default), 1 = tile kernels above 64 queries (the A/B knob)
-};
-Knobs read_knobs();
-
-constexpr int FALLBACK_ROWS = 16;   // dense score rows reserved for flagged queries (one on-stream chunk)
-
-Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn);
-
-// Workspace layouts: take() places a buffer at the current offset and moves on to the next 256-byte boundary.
-struct Bump {
-    size_t off;
-    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) / 256 * 256; return o; }
-};
-
-// The workspace of one search, typed: search_ws() is the one description of its layout (with a null base the pointers are byte
-// offsets; the planner takes `total` from there).  A dense plan has the flag area and the dense scratch only.
-struct SearchWs {
-    float *qnorm, *thr, *cq, *gmax;     // thr, cq (margin coefficients gamma ||q||): [nq_pad] each, cq right after thr
-    uint32_t *cnt;                      // sub-list counters
-    uint2 *cand;                        // candidate area (cand_bytes): free once the select stage has run
-    uint32_t *flag_count, *flag_list;   // flag area: flag count at +0, candidate count (stat_cand) at +8, flagged queries at +64
-    unsigned long long *stat_cand;
-    uint32_t *top;                      // the k best lower bounds per query between two re-tightenings (three-phase plans)
-    float *thr_safe, *cq_safe, *dense;  // estimated thresholds: the conservative bounds of a failing search; dense scratch (dense_bytes)
-    uint32_t *glist;                    // skip_sampled: [nq_pad][skip_list_cap(opt_rank) + 1] short lists of sampled groups for the select's join
-    // retry area (retry_bytes from Q2 on): compact query rows, their thresholds and margin coefficients, the retry and dense
-    // lists, two partition counts, a second flag area, and the two lists the rounds of a group alternate on
-    uint16_t *Q2;
-    float *thr2, *cq2;
-    uint32_t *retry_list, *dense_list, *counts, *flag2, *list_b, *list_c;
-    size_t cand_bytes, dense_bytes, retry_bytes, total;
-};
-SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char *base);
-// entries of a query's short list: about opt_rank groups reach tau (it IS the opt_rank-th largest lower bound), a few more inside the margin
-inline int skip_list_cap(int opt_rank) { return 2 * opt_rank + 30; }
 
 // kernels implemented in the other translation units
 // the fused GEMM + top-k kernels: 256 x 256 tiles on the 32x32x16 MFMA (every epi) or the 16x16x32 MFMA (no EPI_GMAX), or

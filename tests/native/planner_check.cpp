@@ -5,8 +5,7 @@
 
 #include <vector>
 
-#include "ccr_index.h"
-#include "ccr_narrow.h"
+#include "ccr_plan.h"
 
 using namespace ccr;
 
@@ -17,15 +16,12 @@ static int fail(const char *what, long long n, int d, int nq, int k) {
 
 static size_t at(const void *p) { return (size_t)(uintptr_t)p; }   // search_ws without a base: the pointers are byte offsets
 
-// the plan's offsets are search_ws's; every buffer of the search workspace ends at or before `total`, every sub-buffer of the
+// the plan's total is search_ws's; every buffer of the search workspace ends at or before `total`, every sub-buffer of the
 // retry area inside that area
 static int check_layout(const Plan &p, long long n, int d, int nq, int k) {
     const SearchWs w = search_ws(p, n, d, nq, k, nullptr);
     int bad = 0;
-    if (p.off_qnorm != at(w.qnorm) || p.off_thr != at(w.thr) || p.off_gmax != at(w.gmax) || p.off_cnt != at(w.cnt) || p.off_cand != at(w.cand) ||
-        p.off_flag != at(w.flag_count) || p.off_dense != at(w.dense) || p.off_retry != at(w.Q2) || p.off_top != at(w.top) ||
-        p.off_safe != at(w.thr_safe) || p.total != w.total)
-        bad += fail("plan offsets differ from search_ws", n, d, nq, k);
+    if (p.total != w.total) bad += fail("plan total differs from search_ws", n, d, nq, k);
     const size_t pad = p.nq_pad, q4 = (size_t)nq * 4;
     struct Buf {
         const void *p;
@@ -49,13 +45,14 @@ static int check_layout(const Plan &p, long long n, int d, int nq, int k) {
 }
 
 int main() {
-    Knobs kn;
-    memset(&kn, 0, sizeof(kn));
-    kn.progressive = 1;
-    kn.max_phases = 3;
-    kn.mfma16 = -1;
-    kn.optimistic = -1;   // the planner's choice, as in production
-    kn.wide = -1;         // 256 x 384 main-pass tiles where the planner prices them in
+    // the default knobs (estimated thresholds and the 256 x 384 tile where the planner prices them in), except for the A/B legs this
+    // check has always walked: tile kernels only (the second loop below turns the streaming kernel on), every tile scored, equal query groups
+    Knobs kn = default_knobs();
+    kn.narrow = 0;
+    kn.skip_sampled = 0;
+    kn.skip_list = 0;
+    kn.qsplit = 0;
+    kn.narrow_groups = 0;
     const long long rows[] = {300, 9862, 70000, 335184, 1105228, 2681468, 8841823, 6250000};
     const int dims[] = {64, 768, 1024};
     const int nqs[] = {1, 40, 300, 3452, 6980, 10000};
@@ -67,6 +64,7 @@ int main() {
                 for (int k : ks) {
                     if (k > n) continue;
                     const Plan p = make_plan(n, d, nq, k, CCR_SEARCH_DEFAULT, 256, kn);
+                    const SearchWs w = search_ws(p, n, d, nq, k, nullptr);
                     ++total;
                     if (p.total == 0) bad += fail("empty workspace", n, d, nq, k);
                     bad += check_layout(p, n, d, nq, k);
@@ -118,9 +116,9 @@ int main() {
                         end = L.base[g] + (long long)(seg_end - prev) * p.nq_pad * p.sublists * L.cap[g];
                         prev = seg_end;
                     }
-                    if (p.off_cand + (size_t)end * 8 > p.off_flag) bad += fail("candidate area overruns the flag area", n, d, nq, k);
-                    if (!(p.off_qnorm < p.off_thr && p.off_thr < p.off_gmax && p.off_gmax < p.off_cnt && p.off_cnt < p.off_cand &&
-                          p.off_cand < p.off_flag && p.off_flag < p.off_dense && p.off_dense < p.off_retry && p.off_retry < p.total))
+                    if (at(w.cand) + (size_t)end * 8 > at(w.flag_count)) bad += fail("candidate area overruns the flag area", n, d, nq, k);
+                    if (!(at(w.qnorm) < at(w.thr) && at(w.thr) < at(w.gmax) && at(w.gmax) < at(w.cnt) && at(w.cnt) < at(w.cand) &&
+                          at(w.cand) < at(w.flag_count) && at(w.flag_count) < at(w.dense) && at(w.dense) < at(w.Q2) && at(w.Q2) < p.total))
                         bad += fail("workspace layout order", n, d, nq, k);
                     if ((n == 2681468 && d == 768 && nq == 3452 && (k == 100 || k == 1001)) || (n == 8841823 && d == 768 && nq == 6980 && k == 100) ||
                         (n == 6250000 && d == 1024 && nq == 10000 && k == 1001))
@@ -138,6 +136,7 @@ int main() {
                 for (int k : ks) {
                     if (k > n) continue;
                     const Plan p = make_plan(n, d, nq, k, CCR_SEARCH_DEFAULT, 256, kn);
+                    const SearchWs w = search_ws(p, n, d, nq, k, nullptr);
                     bad += check_layout(p, n, d, nq, k);
                     if (!p.fused) {
                         if (p.narrow) bad += fail("narrow without the fused path", n, d, nq, k);
@@ -155,8 +154,8 @@ int main() {
                     if (p.item_a || p.item_b) bad += fail("narrow plan with phases", n, d, nq, k);
                     if (p.first_nsub != NARROW_SUBLISTS || p.first_sp != NARROW_SUBLISTS || p.first_lay.nseg != 1) bad += fail("narrow layout", n, d, nq, k);
                     const long long capn = p.first_lay.cap[0];
-                    if (capn % 4 || capn < 4096 || p.off_cand + (size_t)capn * NARROW_SUBLISTS * nq * 8 > p.off_flag) bad += fail("narrow capacity", n, d, nq, k);
-                    if ((size_t)nq * NARROW_SUBLISTS * 4 > p.off_cand - p.off_cnt) bad += fail("narrow counters", n, d, nq, k);
+                    if (capn % 4 || capn < 4096 || at(w.cand) + (size_t)capn * NARROW_SUBLISTS * nq * 8 > at(w.flag_count)) bad += fail("narrow capacity", n, d, nq, k);
+                    if ((size_t)nq * NARROW_SUBLISTS * 4 > at(w.cand) - at(w.cnt)) bad += fail("narrow counters", n, d, nq, k);
                     if (p.ranges % NUM_XCD || p.ranges * p.sublists > 2048) bad += fail("retry layout of a narrow plan", n, d, nq, k);
                 }
     printf("%d narrow plans\n", narrow);

@@ -8,7 +8,7 @@
 #include <set>
 #include <vector>
 
-#include "ccr_index.h"
+#include "ccr_plan.h"
 
 using namespace ccr;
 
@@ -77,22 +77,6 @@ static int check_launch(int B, int G, bool split, int R, long long n_vt, int gri
     return bad ? 1 : 0;
 }
 
-static Knobs default_knobs() {   // what read_knobs() gives with an empty environment
-    Knobs kn;
-    memset(&kn, 0, sizeof(kn));
-    kn.progressive = 1;
-    kn.max_phases = 3;
-    kn.mfma16 = -1;
-    kn.optimistic = -1;
-    kn.narrow = -1;
-    kn.wide = -1;
-    kn.skip_sampled = -1;
-    kn.skip_list = 1;
-    kn.narrow_groups = 2;
-    kn.qsplit = -1;
-    return kn;
-}
-
 static int expect_plan(const char *what, const Plan &p, int want_split, int want_tile) {
     printf("%s: fused %d tile_q %d blocks %d groups %d opt_rank %d phases %d/%d narrow %d ranges %d, split %d\n", what, p.fused, p.tile_q, p.main_qblocks,
            p.main_qgroups, p.opt_rank, p.item_a, p.item_b, p.narrow, p.ranges, p.main_qsplit);
@@ -127,7 +111,7 @@ int main() {
                 }
         }
 
-    // plans at the default knobs
+    // plans at the default knobs (default_knobs() in ccr_plan.h: what read_knobs() gives with an empty environment)
     const Knobs kn = default_knobs();
     bad += expect_plan("NQ k=100", make_plan(2681468, 768, 3452, 100, CCR_SEARCH_DEFAULT, 256, kn), 2, WIDE_Q);
     bad += expect_plan("NQ k=1001", make_plan(2681468, 768, 3452, 1001, CCR_SEARCH_DEFAULT, 256, kn), 2, WIDE_Q);

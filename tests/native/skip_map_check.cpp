@@ -5,7 +5,7 @@
 
 #include <vector>
 
-#include "ccr_index.h"
+#include "ccr_plan.h"
 
 using namespace ccr;
 
@@ -33,20 +33,6 @@ static int check_map(long long tiles, int s, int n) {
     if (bad) printf("FAIL map tiles=%lld s=%d n=%d: %s%s%s%s%s\n", tiles, s, n, bad & 1 ? "not ascending; " : "", bad & 2 ? "out of range; " : "",
                     bad & 4 ? "hits a sampled tile; " : "", bad & 8 ? "a tile twice; " : "", bad & 16 ? "an unsampled tile missed; " : "");
     return bad ? 1 : 0;
-}
-
-static Knobs default_knobs() {   // what read_knobs() gives with an empty environment
-    Knobs kn;
-    memset(&kn, 0, sizeof(kn));
-    kn.progressive = 1;
-    kn.max_phases = 3;
-    kn.mfma16 = -1;
-    kn.optimistic = -1;
-    kn.narrow = -1;
-    kn.wide = -1;
-    kn.skip_sampled = -1;
-    kn.narrow_groups = 2;
-    return kn;
 }
 
 static int expect_skip(const char *what, const Plan &p, int want) {
@@ -89,7 +75,7 @@ int main() {
     bad += check_map(63, 2, 32);
     maps += 4;
 
-    // plans at the default knobs
+    // plans at the default knobs (default_knobs() in ccr_plan.h: what read_knobs() gives with an empty environment)
     const Knobs kn = default_knobs();
     bad += expect_skip("NQ k=100", make_plan(2681468, 768, 3452, 100, CCR_SEARCH_DEFAULT, 256, kn), 1);
     // (k = 1001: measured, the 250 joined rows per query cost the select more than the main pass saves -- the planner's own choice

@@ -55,7 +55,7 @@ def test_header_is_plain_c_and_links_against_the_library(tmp_path):
 
 
 def test_planner_invariants_on_cpu(tmp_path):
-    """The search planner is host code (ccr::make_plan in the library): tests/native/planner_check.cpp walks 800+ shapes --
+    """The search planner is host code (ccr::make_plan, csrc/ccr_plan.hip, in the library): tests/native/planner_check.cpp walks 800+ shapes --
     every BASELINE config among them -- and checks range / phase / sample / candidate-segment / workspace-layout invariants
     (phases are whole rounds of work items, capacities hold one whole tile, segments do not overlap ...).  No GPU call."""
     import shutil

@@ -1,5 +1,5 @@
-"""Unequal query groups of the main pass (CCR_QSPLIT): the item map (ccr::main_item) and the plans that choose it are host code --
-tests/native/qsplit_map_check.cpp checks both.  No GPU call."""
+"""Unequal query groups of the main pass (CCR_QSPLIT): the item map (ccr::main_item) and the plans that choose it (ccr::make_plan,
+csrc/ccr_plan.hip) are host code -- tests/native/qsplit_map_check.cpp checks both.  No GPU call."""
 import os
 import shutil
 import subprocess

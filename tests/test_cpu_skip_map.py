@@ -1,5 +1,5 @@
 """The main pass that leaves out the sampled tiles (CCR_SKIP_SAMPLED): its map from virtual to real tiles (ccr::unsampled_tile) and
-the plans that switch it on are host code -- tests/native/skip_map_check.cpp checks both.  No GPU call."""
+the plans that switch it on (ccr::make_plan, csrc/ccr_plan.hip) are host code -- tests/native/skip_map_check.cpp checks both.  No GPU call."""
 import os
 import shutil
 import subprocess
