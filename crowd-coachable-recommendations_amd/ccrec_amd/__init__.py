@@ -59,6 +59,6 @@ init_env_defaults()
 
 from . import _lib  # noqa: E402
 from .ops import (  # noqa: E402,F401
-    CorpusIndex, apply_block, colsum_bf16, inbatch_ce, meanpool, meanpool_pack, merge_topk, pack_bf16, require_gpu,
+    CorpusIndex, apply_block, colsum_bf16, inbatch_ce, index_dtype, meanpool, meanpool_pack, merge_topk, pack_bf16, pack_half, require_gpu,
 )
 from .bbpr_loss import BprStep, item_proposal  # noqa: E402,F401

@@ -30,6 +30,8 @@ EXPORTS = [
     "ccr_add_layernorm_drop_half", "ccr_add_layernorm_bwd_drop_half", "ccr_search_last_main_split",
     "ccr_search_last_threshold_phases", "ccr_adamw_step",
     "ccr_embed_layernorm_train_half", "ccr_embed_layernorm_bwd_half", "ccr_embedding_grad", "ccr_meanpool_bwd_packed",
+    "ccr_pack_half_ex", "ccr_pack_half_padded", "ccr_meanpool_pack_half_ex", "ccr_meanpool_pack_half_packed", "ccr_index_create_half",
+    "ccr_index_create_with_norms_half", "ccr_index_dtype", "ccr_colsum_half",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
@@ -40,6 +42,7 @@ QSPLIT_VERSION = 105   # ... and the main pass's unequal query groups with their
 THR_PHASES_VERSION = 106   # ... and the threshold kernel's 64-phase form with its getter (ccr_search_last_threshold_phases)
 OPTIM_VERSION = 107   # ... and the multi-tensor AdamW step that keeps the encoder's 16-bit weights current (ccr_adamw_step)
 ENCODER_PACKED_TRAIN_VERSION = 108   # ... and the embedding block's and the packed pooling's backward (ccr_embed_layernorm_bwd_half and its kin)
+HALF_INDEX_VERSION = 109   # ... and the pack, index and search on either 16-bit element type (ccr_index_create_half and its kin)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -182,6 +185,14 @@ def load():
     lib.ccr_embedding_grad.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp]
     lib.ccr_meanpool_bwd_packed.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.ccr_meanpool_pack_bf16_packed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.ccr_pack_half_ex.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp]
+    lib.ccr_pack_half_padded.argtypes = [vp, i64, i32, vp, i32, vp, vp, i32, i32, vp, vp]
+    lib.ccr_meanpool_pack_half_ex.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.ccr_meanpool_pack_half_packed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    lib.ccr_index_create_half.argtypes = [vp, i64, i32, i32, i64, vp, ctypes.POINTER(vp)]
+    lib.ccr_index_create_with_norms_half.argtypes = [vp, i64, i32, i32, i64, vp, vp, ctypes.POINTER(vp)]
+    lib.ccr_index_dtype.argtypes = [vp]
+    lib.ccr_colsum_half.argtypes = [vp, i64, i32, i32, vp, vp]
     lib.ccr_shard_message_bytes.argtypes = [i32, i32]
     lib.ccr_shard_message_bytes.restype = sz
     lib.ccr_search_shard.argtypes = [vp, vp, i32, i32, vp, vp, sz, i32, vp]
@@ -190,7 +201,7 @@ def load():
     lib.ccr_merge_short_lists.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if fn.restype is ctypes.c_int and name not in ("ccr_version", "ccr_index_dim"):
+        if fn.restype is ctypes.c_int and name not in ("ccr_version", "ccr_index_dim", "ccr_index_dtype"):
             fn.restype = i32
     _lib = lib
     return lib

@@ -18,8 +18,11 @@ from . import ops
 
 def get_all_embeddings(item_titles, tokenizer, tokenizer_kw, model, batch_size, output_step="embedding", sim_type=None):
     """bbpr.py:466-483: encode all titles in batches of `batch_size` -> packed bf16 [n_items, dim] on device
-    (cos: rows L2-normalised by the pack kernel)."""
+    (cos: rows L2-normalised by the pack kernel).  Under CCREC_INDEX_DTYPE=fp16 (ops.index_dtype()) the rows are fp16; the elements
+    that left fp16's range are counted over all batches and checked once, here, before anything searches the rows (OverflowError)."""
     ops.require_gpu()
+    half = ops.index_dtype()
+    overflow = ops.IndexOverflow(half, "cuda")
     if sim_type is None:
         sim_type = os.environ["CCREC_SIM_TYPE"]
     if output_step == "embedding":
@@ -36,8 +39,13 @@ def get_all_embeddings(item_titles, tokenizer, tokenizer_kw, model, batch_size, 
             tokens = tokenizer(text_batch, **tokenizer_kw)
             emb = torch.as_tensor(model(**tokens, output_step=output_step)).cuda()
             if out is None:
-                out = torch.empty(num, ops.padded_dim(emb.shape[1]), dtype=torch.bfloat16, device=emb.device)
-            ops.pack_bf16(emb, normalize=(sim_type == "cos"), out=out[step * batch_size:step * batch_size + len(text_batch)])
+                out = torch.empty(num, ops.padded_dim(emb.shape[1]), dtype=half, device=emb.device)
+            rows = out[step * batch_size:step * batch_size + len(text_batch)]
+            if half == torch.bfloat16:
+                ops.pack_bf16(emb, normalize=(sim_type == "cos"), out=rows)
+            else:
+                ops.pack_half(emb, half, normalize=(sim_type == "cos"), out=rows, overflow=overflow.counter)
+    overflow.check()
     return out
 
 
@@ -49,11 +57,12 @@ def _row_index(key, n, device):
 
 
 class LowRankScore:
-    """Lazy [n_users, n_items] score = U V^T over packed bf16 rows (duck-types the .shape / .T / as_tensor
-    surface of rime_lite's LazyScoreBase that the evaluation code touches)."""
+    """Lazy [n_users, n_items] score = U V^T over packed bf16 rows -- or fp16 rows: both factors of one type, the index and every
+    search follow it -- (duck-types the .shape / .T / as_tensor surface of rime_lite's LazyScoreBase that the evaluation code touches)."""
 
     def __init__(self, user_bf16, item_bf16):
-        assert user_bf16.dtype == torch.bfloat16 and item_bf16.dtype == torch.bfloat16
+        assert user_bf16.dtype in ops.INDEX_DTYPES and item_bf16.dtype == user_bf16.dtype, \
+            f"user rows are {user_bf16.dtype}, item rows {item_bf16.dtype}: both torch.bfloat16 or both torch.float16"
         self.user, self.item = user_bf16.contiguous(), item_bf16.contiguous()
         self.shape = (self.user.shape[0], self.item.shape[0])
         self._index = None

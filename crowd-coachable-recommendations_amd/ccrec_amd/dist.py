@@ -90,6 +90,23 @@ def agreed_cuts(n_rows, world_size, weights=None, group=None, device=None):
     return cuts
 
 
+def agreed_index_dtype(dtype, world_size, group=None):
+    """The element type of a sharded index (ops.index_dtype(): the CCREC_INDEX_DTYPE switch of THIS rank), checked across the ranks:
+    one tiny all-reduce of (code, -code) by maximum gives every rank the largest and the smallest code, so a rank whose environment
+    differs makes ALL ranks raise ValueError -- none is left waiting in the next collective, and no rank's queries meet a shard of
+    the other type.  Returns dtype."""
+    if world_size <= 1 or not (dist.is_available() and dist.is_initialized()):
+        return dtype
+    code = 1 if dtype == torch.float16 else 2   # ccr_retrieval.h: CCR_DTYPE_F16 / CCR_DTYPE_BF16
+    device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else "cpu"
+    t = torch.tensor([code, -code], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    hi, lo = int(t[0]), -int(t[1])
+    if hi != lo:
+        raise ValueError("CCREC_INDEX_DTYPE differs between the ranks (bf16 on some, fp16 on others): set one value for all of them")
+    return dtype
+
+
 def largest_share(cuts):
     """Largest fraction of the corpus rows one rank holds (1 / world for equal row counts)."""
     n = int(cuts[-1])

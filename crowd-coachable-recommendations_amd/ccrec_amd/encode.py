@@ -260,16 +260,22 @@ class LengthSortedEncoder:
         return batches, int(lengths.sum()), int(sum(len(idx) * pl for idx, pl in plan)), time.perf_counter() - t0
 
     @torch.no_grad()
-    def encode(self, texts, sim="dot", out=None, row_offset=0, norm_bounds=None, out_f32=None):
+    def encode(self, texts, sim="dot", out=None, row_offset=0, norm_bounds=None, out_f32=None, dtype=None, overflow=None):
         """Encode `texts` into rows [row_offset, row_offset + len(texts)) of `out` (bf16 [>=N, dim] cuda; allocated if
         None).  sim "cos" L2-normalises before rounding.  norm_bounds: fp32 [>=N] tensor indexed like `out`'s rows, see
-        ops.pack_bf16.  out_f32: optional fp32
+        ops.pack_bf16.  dtype: element type of the packed rows, torch.bfloat16 or torch.float16 (None: ops.index_dtype(), the
+        CCREC_INDEX_DTYPE switch); overflow: the ops.IndexOverflow of the index build these rows belong to (fp16: counts the elements
+        that left the type's range; the caller checks it once before its first search).  out_f32: optional fp32
         [>=N, dim] tensor that also receives the un-rounded pooled rows (tests / the cls|mean_layer_norm consumers).
         Returns the bf16 tensor.  self.stats afterwards: texts, batches, real / padded tokens, host seconds of the
         tokenise + plan thread, seconds the GPU loop waited for it, GPU seconds of the batches (events) and the wall time."""
         import time
         from concurrent.futures import ThreadPoolExecutor
         ops.require_gpu()
+        dtype = ops.index_dtype() if dtype is None else dtype
+        assert overflow is None or overflow.dtype == dtype, "overflow: an IndexOverflow of the packed element type"
+        # (bf16: the arguments of the calls below are the ones they always had)
+        pack_kw = {} if dtype == torch.bfloat16 else {"dtype": dtype, "overflow": None if overflow is None else overflow.counter}
         tower = self.tower
         tower.eval()
         device = tower.cls_model.device
@@ -326,10 +332,10 @@ class LengthSortedEncoder:
                                                       seq_start, seq_len, longest,                       # [T, dim] fp32, or the CLS rows [B, dim]
                                                       cls_only=self.output_step != "mean_pooling", dtype=half)
                         if out is None:
-                            out = torch.empty(n + row_offset, hidden.shape[-1], dtype=torch.bfloat16, device=hidden.device)
+                            out = torch.empty(n + row_offset, hidden.shape[-1], dtype=dtype, device=hidden.device)
                         if self.output_step == "mean_pooling":
                             ops.meanpool_pack_packed(hidden, seq_start, seq_len, normalize=(sim == "cos"), out_bf16=out, out_f32=out_f32,
-                                                     dst_rows=rows, norm_bounds=norm_bounds)
+                                                     dst_rows=rows, norm_bounds=norm_bounds, **pack_kw)
                             continue
                         first = hidden                                                                     # the CLS rows
                         mask = torch.ones(len(idx), 1, dtype=torch.int64, device=device)
@@ -338,7 +344,7 @@ class LengthSortedEncoder:
                         inputs = {"input_ids": ids_t.to(device, non_blocking=True), "attention_mask": mask_t.to(device, non_blocking=True)}
                         hidden = tower.cls_model(**inputs).last_hidden_state
                         if out is None:
-                            out = torch.empty(n + row_offset, hidden.shape[-1], dtype=torch.bfloat16, device=hidden.device)
+                            out = torch.empty(n + row_offset, hidden.shape[-1], dtype=dtype, device=hidden.device)
                         mask = inputs["attention_mask"]
                         first = hidden[:, 0]
                     if self.output_step != "mean_pooling":
@@ -348,11 +354,11 @@ class LengthSortedEncoder:
                             first = tower.standard_layer_norm(first)
                         hidden, mask = first.unsqueeze(1).contiguous(), mask[:, :1]
                     ops.meanpool_pack(hidden, mask, normalize=(sim == "cos"), want_f32=False, out_bf16=out,
-                                      out_f32=out_f32, dst_rows=rows, norm_bounds=norm_bounds)
+                                      out_f32=out_f32, dst_rows=rows, norm_bounds=norm_bounds, **pack_kw)
                 e1.record()
                 spans.append((e0, e1))
         if out is None:   # no texts
-            out = torch.empty(row_offset, 0, dtype=torch.bfloat16, device=device)
+            out = torch.empty(row_offset, 0, dtype=dtype, device=device)
         if spans:
             spans[-1][1].synchronize()
             st["gpu_busy_s"] = sum(a.elapsed_time(b) for a, b in spans) * 1e-3
@@ -361,11 +367,13 @@ class LengthSortedEncoder:
         return out
 
 
-def encode_local_shard(encoder, corpus_ids, corpus, sim, rank, world, norm_bounds=None, weights=None, cuts=None):
+def encode_local_shard(encoder, corpus_ids, corpus, sim, rank, world, norm_bounds=None, weights=None, cuts=None, dtype=None, overflow=None):
     """This rank's contiguous block of the corpus (dist.shard_bounds; weights: equal-weight blocks; cuts: the world + 1 boundaries every
-    rank agreed on -- dist.agreed_cuts -- take precedence) -> (bf16 shard [hi-lo, dim], lo, hi)."""
+    rank agreed on -- dist.agreed_cuts -- take precedence) -> (bf16 shard [hi-lo, dim], lo, hi).  dtype / overflow: as
+    LengthSortedEncoder.encode (an fp16 shard under CCREC_INDEX_DTYPE=fp16)."""
     lo, hi = (int(cuts[rank]), int(cuts[rank + 1])) if cuts is not None else shard_bounds(len(corpus_ids), world, rank, weights)
-    shard = encoder.encode([corpus[c] for c in corpus_ids[lo:hi]], sim=sim, norm_bounds=norm_bounds)
+    half_kw = {} if dtype is None and overflow is None else {"dtype": dtype, "overflow": overflow}
+    shard = encoder.encode([corpus[c] for c in corpus_ids[lo:hi]], sim=sim, norm_bounds=norm_bounds, **half_kw)
     return shard, lo, hi
 
 
@@ -409,7 +417,13 @@ def ranking_sharded(corpus, queries, encoder, block_dict=None, rank=0, world=1, 
     queries_ids, corpus_ids = list(queries.keys()), list(corpus.keys())
     sim = "cos" if os.environ["CCREC_SIM_TYPE"] == "cos" else "dot"
     keep = KEEP if keep is None else keep
-    q_bf16 = encoder.encode([queries[q] for q in queries_ids], sim=sim)
+    # the index's element type (CCREC_INDEX_DTYPE): the ranks must agree -- a mismatch fails on ALL of them, before any rank encodes --,
+    # and ONE overflow counter serves this index build: queries and shard rows add to it, it is read once before the search
+    from .dist import agreed_index_dtype
+    half = agreed_index_dtype(ops.index_dtype(), world, group=group)
+    overflow = ops.IndexOverflow(half, "cuda") if half != torch.bfloat16 else None
+    half_kw = {} if overflow is None else {"dtype": half, "overflow": overflow}
+    q_bf16 = encoder.encode([queries[q] for q in queries_ids], sim=sim, **half_kw)
     weights = None
     if world > 1 and not (isinstance(balance, str) and balance == "rows"):
         weights = (token_weights([corpus[c] for c in corpus_ids], encoder.max_length, tokenizer=encoder.tokenizer)
@@ -420,8 +434,10 @@ def ranking_sharded(corpus, queries, encoder, block_dict=None, rank=0, world=1, 
     cuts = agreed_cuts(len(corpus_ids), world, weights, group=group, device=q_bf16.device if q_bf16.is_cuda else None)
     lo0, hi0 = cuts[rank], cuts[rank + 1]
     bounds = torch.empty(max(hi0 - lo0, 1), dtype=torch.float32, device=q_bf16.device)   # norm bound of every packed row
-    shard, lo, hi = encode_local_shard(encoder, corpus_ids, corpus, sim, rank, world, norm_bounds=bounds, cuts=cuts)
+    shard, lo, hi = encode_local_shard(encoder, corpus_ids, corpus, sim, rank, world, norm_bounds=bounds, cuts=cuts, **half_kw)
     bounds = bounds if hi > lo else None
+    if overflow is not None:
+        overflow.check()
     if world == 1:
         return Retriever(corpus_ids, shard, norm_bounds=bounds).ranking_profile(queries_ids, q_bf16, block_dict, keep, with_tensors, lazy)
     index = ops.CorpusIndex(shard, global_row_offset=lo, norm_bounds=bounds)

@@ -26,11 +26,14 @@ CANONICAL_COS_SIM_MACS = 4e9   # above this many multiply-adds cos_sim() switche
 
 
 def generate_embeddings(data_indices, data_dic, embedding_func, batch_size, embedding_size=768, name=None, pack=None,
-                        device=None, norm_bounds=None):
+                        device=None, norm_bounds=None, overflow=None):
     """scripts/ms_marco_eval.py:123-152.  Same batching, progress lines and return value (a [num, dim]
     tensor), but the result stays on the GPU.  pack=None -> fp32; pack="dot"/"cos" -> bf16 shard packed
-    batch by batch (cos = L2-normalised first)."""
+    batch by batch (cos = L2-normalised first) -- an fp16 shard under CCREC_INDEX_DTYPE=fp16 (ops.index_dtype()), with
+    overflow (an ops.IndexOverflow of that type, optional) counting the elements that left fp16's range."""
     ops.require_gpu()
+    half = ops.index_dtype() if pack is not None else None   # read once per call
+    assert overflow is None or overflow.dtype == half, "overflow: an IndexOverflow of the index's element type"
     num = len(data_indices)
     num_batches = math.ceil(num / batch_size)
     device = torch.device(device if device is not None else "cuda")
@@ -47,18 +50,22 @@ def generate_embeddings(data_indices, data_dic, embedding_func, batch_size, embe
                 device, non_blocking=bool(int(os.environ.get("CCREC_NON_BLOCKING", "1"))))
             if out is None:
                 dim = emb.shape[1] if pack is None else ops.padded_dim(emb.shape[1])   # packed rows: zero-padded to a multiple of 8
-                out = torch.empty(num, dim, device=device, dtype=torch.float32 if pack is None else torch.bfloat16)
+                out = torch.empty(num, dim, device=device, dtype=torch.float32 if pack is None else half)
             lo = step * batch_size
             if pack is None:
                 out[lo:lo + emb.shape[0]] = emb
-            else:
+            elif half == torch.bfloat16:
                 ops.pack_bf16(emb, normalize=(pack == "cos"), out=out[lo:lo + emb.shape[0]],
                               norm_bounds=None if norm_bounds is None else norm_bounds[lo:lo + emb.shape[0]])
+            else:
+                ops.pack_half(emb, half, normalize=(pack == "cos"), out=out[lo:lo + emb.shape[0]],
+                              norm_bounds=None if norm_bounds is None else norm_bounds[lo:lo + emb.shape[0]],
+                              overflow=None if overflow is None else overflow.counter)
     torch.cuda.synchronize()
     print(f"Processed total {num} t={time.time() - tic:.1f}s")
     if out is None:
         out = torch.empty(0, embedding_size if pack is None else ops.padded_dim(embedding_size), device=device,
-                          dtype=torch.float32 if pack is None else torch.bfloat16)
+                          dtype=torch.float32 if pack is None else half)
     if name is not None:
         torch.save(out, name)
     return out
@@ -95,7 +102,7 @@ def block_csr(block_lists, n_rows):
 class Retriever:
     """Build the index once per active-learning step, query many times.
 
-    corpus_ids: list of passage ids in corpus row order; corpus_bf16: packed shard [N, dim]."""
+    corpus_ids: list of passage ids in corpus row order; corpus_bf16: packed shard [N, dim], bf16 or fp16 (queries follow it)."""
 
     def __init__(self, corpus_ids, corpus_bf16, global_row_offset=0, norm_bounds=None):
         self.corpus_ids = list(corpus_ids)
@@ -155,9 +162,13 @@ def ranking(corpus, queries, embedding_func, batch_size, block_dict=None, lazy=F
     ops.require_gpu()
     queries_ids, corpus_ids = list(queries.keys()), list(corpus.keys())
     sim = "cos" if os.environ["CCREC_SIM_TYPE"] == "cos" else "dot"
-    queries_embeddings = generate_embeddings(queries_ids, queries, embedding_func, batch_size, pack=sim)
+    # one overflow counter for this index build (fp16 only): queries and passages add to it, it is read once before the search
+    overflow = ops.IndexOverflow(ops.index_dtype(), "cuda")
+    queries_embeddings = generate_embeddings(queries_ids, queries, embedding_func, batch_size, pack=sim, overflow=overflow)
     # the pack kernel leaves a norm bound per packed row, batch by batch: the index build then needs no pass over the shard
     bounds = torch.empty(len(corpus_ids), dtype=torch.float32, device="cuda") if corpus_ids else None
-    passage_embeddings = generate_embeddings(corpus_ids, corpus, embedding_func, batch_size, pack=sim, norm_bounds=bounds)
+    passage_embeddings = generate_embeddings(corpus_ids, corpus, embedding_func, batch_size, pack=sim, norm_bounds=bounds,
+                                             overflow=overflow)
+    overflow.check()
     retriever = Retriever(corpus_ids, passage_embeddings, norm_bounds=bounds)
     return retriever.ranking_profile(queries_ids, queries_embeddings, block_dict, lazy=lazy)

@@ -2,6 +2,7 @@
 arithmetic step runs in libccr_hip.so.  All ops raise if there is no ROCm device."""
 import contextlib
 import ctypes
+import os
 
 import torch
 
@@ -46,6 +47,95 @@ def padded_dim(dim):
     return (int(dim) + 7) // 8 * 8
 
 
+# ---- the 16-bit element type of a search index: bf16 (the default) or fp16 (opt-in)
+INDEX_DTYPES = {torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+_INDEX_DTYPE_NAMES = {"bf16": torch.bfloat16, "fp16": torch.float16}
+_HALF_INDEX_CHECKED = False
+
+
+def _require_half_index():
+    """require_gpu() + once: the loaded library packs, indexes and searches either 16-bit type (ccr_version() >= 109)."""
+    global _HALF_INDEX_CHECKED
+    lib = require_gpu()
+    if not _HALF_INDEX_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.HALF_INDEX_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, an fp16 index needs {_lib.HALF_INDEX_VERSION}: rebuild it "
+                                f"(python -c 'import __graft_entry__ as g; g.build()')")
+        _HALF_INDEX_CHECKED = True
+    return lib
+
+
+def index_dtype():
+    """The element type the ranking paths pack and index with: os.environ["CCREC_INDEX_DTYPE"] = "bf16" (the default when unset) or
+    "fp16", read at call time like CCREC_SIM_TYPE.  fp16 is what the reference's autocast hands its `Q @ chunk.T`
+    (ms_marco_eval.py:215): unit roundoff 2^-11 instead of 2^-8, but a range that ends at 65 504 (see IndexOverflow)."""
+    name = os.environ.get("CCREC_INDEX_DTYPE", "bf16")
+    if name not in _INDEX_DTYPE_NAMES:
+        raise ValueError(f"CCREC_INDEX_DTYPE={name!r}: expected 'bf16' or 'fp16'")
+    return _INDEX_DTYPE_NAMES[name]
+
+
+def _check_index_dtype(dtype):
+    if dtype not in INDEX_DTYPES:
+        raise TypeError(f"{dtype}: an index holds torch.bfloat16 or torch.float16 rows")
+    return INDEX_DTYPES[dtype]
+
+
+class IndexOverflow:
+    """The overflow counter of ONE index build: every pack of the build adds the elements that were finite in fp32 and left fp16's
+    range (-> +-inf) to one device int32; check() reads it once -- before the first search, not per batch -- and raises OverflowError.
+    With bf16 there is nothing to count: `counter` is None and check() returns at once."""
+
+    def __init__(self, dtype, device):
+        self.dtype = dtype
+        self.counter = torch.zeros(1, dtype=torch.int32, device=device) if dtype == torch.float16 else None
+
+    def check(self):
+        if self.counter is None:
+            return
+        n = int(self.counter.item())
+        if n:
+            raise OverflowError(f"{n} embedding element(s) left fp16's range (|x| >= 65520 became inf) while the index was packed: use "
+                                f"CCREC_INDEX_DTYPE=bf16, or CCREC_SIM_TYPE=cos (normalised rows fit any type)")
+
+
+def _check_overflow(overflow, dev):
+    assert overflow.is_cuda and overflow.dtype == torch.int32 and overflow.numel() >= 1 and overflow.device == dev, \
+        "overflow: an int32 cuda counter on the packed tensor's device"
+
+
+def pack_half(x, dtype=torch.bfloat16, normalize=False, out=None, return_norms=False, norm_bounds=None, overflow=None):
+    """pack_bf16 into either 16-bit element type of an index: fp32 [rows, dim] (cuda) -> dtype [rows, padded_dim(dim)], round to nearest
+    even -- the bits of x.to(dtype), fp16 subnormals included; a finite value beyond +-65 504 becomes +-inf in fp16, as in torch.
+    overflow: optional int32 cuda counter (zeroed by the caller, shared by any number of packs) that receives the number of such
+    elements (fp16 only).  normalize / out / return_norms / norm_bounds: as pack_bf16."""
+    lib = _require_half_index()
+    code = _check_index_dtype(dtype)
+    assert x.is_cuda and x.dim() == 2, "pack_half expects a 2-d cuda tensor"
+    x = x.contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    rows, dim = x.shape
+    pdim = padded_dim(dim)
+    if out is None:
+        out = torch.empty(rows, pdim, dtype=dtype, device=x.device)
+    assert out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == (rows, pdim)
+    norms = torch.empty(rows, dtype=torch.float32, device=x.device) if return_norms else None
+    if norm_bounds is not None:
+        _check_bounds(norm_bounds, rows)
+    if overflow is not None:
+        _check_overflow(overflow, x.device)
+    with _on(x):
+        if pdim != dim:
+            _lib.check(lib.ccr_pack_half_padded(_ptr(x), rows, dim, _ptr(out), pdim, _ptr(norms), _ptr(norm_bounds),
+                                                int(bool(normalize)), code, _ptr(overflow), _stream(x)), "ccr_pack_half_padded")
+        else:
+            _lib.check(lib.ccr_pack_half_ex(_ptr(x), _ptr(out), _ptr(norms), _ptr(norm_bounds), rows, dim, int(bool(normalize)), code,
+                                            _ptr(overflow), _stream(x)), "ccr_pack_half")
+    return (out, norms) if return_norms else out
+
+
 def pack_bf16(x, normalize=False, out=None, return_norms=False, norm_bounds=None):
     """fp32 [rows, dim] (cuda) -> bf16 [rows, padded_dim(dim)]; normalize=True applies x / max(||x||, 1e-12) first
     (the cos_sim rule, ms_marco_eval.py:160-161).  `out` may be a slice of a preallocated shard.
@@ -78,22 +168,25 @@ def pack_bf16(x, normalize=False, out=None, return_norms=False, norm_bounds=None
 
 
 def meanpool_pack(hidden, mask, normalize=False, want_f32=True, want_bf16=True, out_bf16=None, out_f32=None, dst_rows=None,
-                  norm_bounds=None):
+                  norm_bounds=None, dtype=torch.bfloat16, overflow=None):
     """Fused masked mean pooling (item_tower.py:141-146) + bf16 pack of [B, L, dim] hidden states.
     Returns (pooled_f32 or None, packed_bf16 or None).
 
     out_bf16 / out_f32: write into these [rows, dim] tensors (e.g. the resident shard) instead of fresh [B, dim] ones;
     dst_rows: [B] int64 destination rows inside them (length-sorted batches scatter back to corpus order);
-    norm_bounds: fp32 cuda tensor indexed like the destination rows: bound of each packed row's norm (see pack_bf16)."""
-    lib = require_gpu()
+    norm_bounds: fp32 cuda tensor indexed like the destination rows: bound of each packed row's norm (see pack_bf16);
+    dtype: element type of the packed rows (`out_bf16` keeps its name): torch.bfloat16, or torch.float16 with `overflow` as pack_half."""
+    half = dtype != torch.bfloat16 or overflow is not None
+    lib = _require_half_index() if half else require_gpu()
+    code = _check_index_dtype(dtype)
     assert hidden.is_cuda and hidden.dim() == 3 and hidden.dtype in _DTYPES
     hidden = hidden.contiguous()
     mask = mask.to(device=hidden.device, dtype=torch.int64).contiguous()
     B, L, dim = hidden.shape
     assert tuple(mask.shape) == (B, L)
     f32 = out_f32 if out_f32 is not None else (torch.empty(B, dim, dtype=torch.float32, device=hidden.device) if want_f32 else None)
-    b16 = out_bf16 if out_bf16 is not None else (torch.empty(B, dim, dtype=torch.bfloat16, device=hidden.device) if want_bf16 else None)
-    for t, dt in ((f32, torch.float32), (b16, torch.bfloat16)):
+    b16 = out_bf16 if out_bf16 is not None else (torch.empty(B, dim, dtype=dtype, device=hidden.device) if want_bf16 else None)
+    for t, dt in ((f32, torch.float32), (b16, dtype)):
         if t is not None:
             assert t.is_cuda and t.dtype == dt and t.dim() == 2 and t.shape[1] == dim and t.is_contiguous()
             assert dst_rows is not None or t.shape[0] >= B
@@ -102,24 +195,35 @@ def meanpool_pack(hidden, mask, normalize=False, want_f32=True, want_bf16=True, 
         assert dst_rows.numel() == B
     if norm_bounds is not None:
         _check_bounds(norm_bounds, b16.shape[0] if (b16 is not None and dst_rows is not None) else B)
+    if overflow is not None:
+        _check_overflow(overflow, hidden.device)
     with _on(hidden):
-        _lib.check(lib.ccr_meanpool_pack_bf16_ex(_ptr(hidden), _DTYPES[hidden.dtype], _ptr(mask), _ptr(b16), _ptr(f32),
-                                                 _ptr(dst_rows), _ptr(norm_bounds), B, L, dim, int(bool(normalize)),
-                                                 _stream(hidden)), "ccr_meanpool_pack_bf16")
+        if half:
+            _lib.check(lib.ccr_meanpool_pack_half_ex(_ptr(hidden), _DTYPES[hidden.dtype], _ptr(mask), _ptr(b16), _ptr(f32),
+                                                     _ptr(dst_rows), _ptr(norm_bounds), B, L, dim, int(bool(normalize)), code,
+                                                     _ptr(overflow), _stream(hidden)), "ccr_meanpool_pack_half")
+        else:
+            _lib.check(lib.ccr_meanpool_pack_bf16_ex(_ptr(hidden), _DTYPES[hidden.dtype], _ptr(mask), _ptr(b16), _ptr(f32),
+                                                     _ptr(dst_rows), _ptr(norm_bounds), B, L, dim, int(bool(normalize)),
+                                                     _stream(hidden)), "ccr_meanpool_pack_bf16")
     return f32, b16
 
 
-def meanpool_pack_packed(hidden, seq_start, seq_len, normalize=False, out_bf16=None, out_f32=None, dst_rows=None, norm_bounds=None):
+def meanpool_pack_packed(hidden, seq_start, seq_len, normalize=False, out_bf16=None, out_f32=None, dst_rows=None, norm_bounds=None,
+                         dtype=torch.bfloat16, overflow=None):
     """meanpool_pack for a packed token array: hidden [T, dim], sequence s = rows seq_start[s] .. + seq_len[s] - 1 (int32 cuda
-    tensors).  Writes into out_bf16 / out_f32 ([rows, dim], at dst_rows or rows 0 .. n_seq - 1); returns (out_f32, out_bf16)."""
-    lib = require_gpu()
+    tensors).  Writes into out_bf16 / out_f32 ([rows, dim], at dst_rows or rows 0 .. n_seq - 1); returns (out_f32, out_bf16).
+    dtype / overflow: as meanpool_pack."""
+    half = dtype != torch.bfloat16 or overflow is not None
+    lib = _require_half_index() if half else require_gpu()
+    code = _check_index_dtype(dtype)
     assert hidden.is_cuda and hidden.dim() == 2 and hidden.dtype in _DTYPES and hidden.is_contiguous()
     n_seq, dim = seq_len.numel(), hidden.shape[1]
     for t in (seq_start, seq_len):
         assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n_seq
     if out_bf16 is None and out_f32 is None:
-        out_bf16 = torch.empty(n_seq, dim, dtype=torch.bfloat16, device=hidden.device)
-    for t, dt in ((out_f32, torch.float32), (out_bf16, torch.bfloat16)):
+        out_bf16 = torch.empty(n_seq, dim, dtype=dtype, device=hidden.device)
+    for t, dt in ((out_f32, torch.float32), (out_bf16, dtype)):
         if t is not None:
             assert t.is_cuda and t.dtype == dt and t.dim() == 2 and t.shape[1] == dim and t.is_contiguous()
             assert dst_rows is not None or t.shape[0] >= n_seq
@@ -128,10 +232,17 @@ def meanpool_pack_packed(hidden, seq_start, seq_len, normalize=False, out_bf16=N
         assert dst_rows.numel() == n_seq
     if norm_bounds is not None:
         _check_bounds(norm_bounds, out_bf16.shape[0] if (out_bf16 is not None and dst_rows is not None) else n_seq)
+    if overflow is not None:
+        _check_overflow(overflow, hidden.device)
     with _on(hidden):
-        _lib.check(lib.ccr_meanpool_pack_bf16_packed(_ptr(hidden), _DTYPES[hidden.dtype], _ptr(seq_start), _ptr(seq_len), _ptr(out_bf16),
-                                                     _ptr(out_f32), _ptr(dst_rows), _ptr(norm_bounds), n_seq, dim, int(bool(normalize)),
-                                                     _stream(hidden)), "ccr_meanpool_pack_bf16_packed")
+        if half:
+            _lib.check(lib.ccr_meanpool_pack_half_packed(_ptr(hidden), _DTYPES[hidden.dtype], _ptr(seq_start), _ptr(seq_len), _ptr(out_bf16),
+                                                         _ptr(out_f32), _ptr(dst_rows), _ptr(norm_bounds), n_seq, dim, int(bool(normalize)),
+                                                         code, _ptr(overflow), _stream(hidden)), "ccr_meanpool_pack_half_packed")
+        else:
+            _lib.check(lib.ccr_meanpool_pack_bf16_packed(_ptr(hidden), _DTYPES[hidden.dtype], _ptr(seq_start), _ptr(seq_len), _ptr(out_bf16),
+                                                         _ptr(out_f32), _ptr(dst_rows), _ptr(norm_bounds), n_seq, dim, int(bool(normalize)),
+                                                         _stream(hidden)), "ccr_meanpool_pack_bf16_packed")
     return out_f32, out_bf16
 
 
@@ -753,9 +864,10 @@ def meanpool_packed(hidden, seq_start, seq_len, covers_all=False):
 
 
 class CorpusIndex:
-    """A resident bf16 corpus shard + its search state (ccr_index).  Build once per AL step, query many.
+    """A resident 16-bit corpus shard + its search state (ccr_index).  Build once per AL step, query many.
 
-    corpus_bf16: [n_rows, dim] bf16 cuda tensor (kept alive by this object; the C index borrows it).
+    corpus_bf16: [n_rows, dim] bf16 -- or fp16: the argument keeps its name -- cuda tensor (kept alive by this object; the C index
+    borrows it).  `.dtype` is its element type; every search takes queries of that type (TypeError otherwise).
     global_row_offset: id of row 0 in the whole corpus (row-sharded multi-GPU search).
     norm_bounds: [n_rows] fp32 cuda tensor written by pack_bf16 / meanpool_pack(norm_bounds=...) for THESE rows (optional;
     kept alive by this object and not to be rewritten while the index is in use).
@@ -763,8 +875,11 @@ class CorpusIndex:
     """
 
     def __init__(self, corpus_bf16, global_row_offset=0, norm_bounds=None, workspace=None):
-        self._lib = require_gpu()
-        assert corpus_bf16.is_cuda and corpus_bf16.dtype == torch.bfloat16 and corpus_bf16.dim() == 2
+        assert corpus_bf16.is_cuda and corpus_bf16.dim() == 2
+        code = _check_index_dtype(corpus_bf16.dtype)
+        self.dtype = corpus_bf16.dtype
+        half = self.dtype != torch.bfloat16
+        self._lib = _require_half_index() if half else require_gpu()
         self.corpus = corpus_bf16.contiguous()
         self.n_rows, self.dim = self.corpus.shape
         self.offset = int(global_row_offset)
@@ -776,12 +891,20 @@ class CorpusIndex:
         self._ws_need = {}
         self._deferred = None
         with _on(self.corpus):
-            if norm_bounds is None:
+            if norm_bounds is not None:
+                _check_bounds(norm_bounds, self.n_rows)
+                self._norm_bounds = norm_bounds   # borrowed by the C index, like the corpus
+            if half and norm_bounds is None:
+                _lib.check(self._lib.ccr_index_create_half(_ptr(self.corpus), self.n_rows, self.dim, code, self.offset,
+                                                           _stream(self.corpus), ctypes.byref(self._h)), "ccr_index_create_half")
+            elif half:
+                _lib.check(self._lib.ccr_index_create_with_norms_half(_ptr(self.corpus), self.n_rows, self.dim, code, self.offset,
+                                                                      _ptr(norm_bounds), _stream(self.corpus),
+                                                                      ctypes.byref(self._h)), "ccr_index_create_with_norms_half")
+            elif norm_bounds is None:
                 _lib.check(self._lib.ccr_index_create(_ptr(self.corpus), self.n_rows, self.dim, self.offset,
                                                       _stream(self.corpus), ctypes.byref(self._h)), "ccr_index_create")
             else:  # row-norm bounds from ccr_pack_bf16_ex: no extra pass over the shard, no synchronisation
-                _check_bounds(norm_bounds, self.n_rows)
-                self._norm_bounds = norm_bounds   # borrowed by the C index, like the corpus
                 _lib.check(self._lib.ccr_index_create_with_norms(_ptr(self.corpus), self.n_rows, self.dim, self.offset,
                                                                  _ptr(norm_bounds), _stream(self.corpus),
                                                                  ctypes.byref(self._h)), "ccr_index_create_with_norms")
@@ -796,6 +919,19 @@ class CorpusIndex:
     @property
     def workspace(self):
         return self._ws
+
+    def _check_queries(self, q):
+        """The query matrix of a search: [n_q, dim] cuda rows of the index's element type."""
+        if q.dtype != self.dtype:
+            raise TypeError(f"queries are {q.dtype} but the index holds {self.dtype} rows: pack the queries with "
+                            f"pack_half(dtype={self.dtype})")
+        assert q.is_cuda and q.dim() == 2 and q.shape[1] == self.dim
+
+    def library_dtype(self):
+        """ccr_index_dtype of the C index, as a torch dtype."""
+        _require_half_index()
+        code = int(self._lib.ccr_index_dtype(self._h))
+        return {v: k for k, v in INDEX_DTYPES.items()}[code]
 
     def _grow_ws(self, need):
         """The workspace, at least `need` bytes.  A deferred search still owns the current one: complete it before the
@@ -819,7 +955,7 @@ class CorpusIndex:
         defer=True: CCR_SEARCH_ASYNC -- the call returns without synchronising the stream; call finish() before trusting
         the result (it completes the -- rare -- flagged queries and fills last_stats())."""
         q = queries_bf16
-        assert q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 2 and q.shape[1] == self.dim
+        self._check_queries(q)
         q = q.contiguous()
         n_q = q.shape[0]
         if out is None:
@@ -863,7 +999,7 @@ class CorpusIndex:
         moves (dist.ShardMessage.send).  `message`: uint8 cuda tensor of ccr_shard_message_bytes(n_q, k).  defer=True: no host
         synchronisation; the header's n_flagged is written on the stream, finish() completes the search."""
         q = queries_bf16
-        assert q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 2 and q.shape[1] == self.dim
+        self._check_queries(q)
         q = q.contiguous()
         n_q = q.shape[0]
         assert 0 < n_q <= MAX_QUERIES_PER_SEARCH and 1 <= k <= self.n_rows
@@ -880,7 +1016,7 @@ class CorpusIndex:
 
     def _special_args(self, queries_bf16, ptr, idx):
         q = queries_bf16
-        assert q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 2 and q.shape[1] == self.dim
+        self._check_queries(q)
         q = q.contiguous()
         ptr = torch.as_tensor(ptr, dtype=torch.int64).cpu().contiguous()
         assert ptr.numel() == q.shape[0] + 1
@@ -965,7 +1101,7 @@ class CorpusIndex:
         """Dense score matrix [n_q, n_rows] fp32 (ccr_scores).  mode "canonical": the fp64-ordered values the ranking
         reports; "mfma": the same bf16 rows through the MFMA tile kernel (fp32 accumulation)."""
         q = queries_bf16.contiguous()
-        assert q.is_cuda and q.dtype == torch.bfloat16 and q.dim() == 2 and q.shape[1] == self.dim
+        self._check_queries(q)
         out = torch.empty(q.shape[0], self.n_rows, dtype=torch.float32, device=q.device)
         if q.shape[0] == 0:
             return out
@@ -1074,13 +1210,18 @@ def apply_block(scores, ids, block_ptr, block_idx, k_out, n_rows_total):
 
 
 def colsum_bf16(x):
-    """Column sums of a bf16 [rows, dim] cuda matrix in fp64 (ccr_colsum_bf16) -> [dim] float64."""
-    lib = require_gpu()
-    assert x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2
+    """Column sums of a bf16 -- or fp16: it follows the tensor it is given -- [rows, dim] cuda matrix in fp64 (ccr_colsum_bf16 /
+    ccr_colsum_half) -> [dim] float64."""
+    assert x.is_cuda and x.dim() == 2
+    code = _check_index_dtype(x.dtype)
+    lib = require_gpu() if x.dtype == torch.bfloat16 else _require_half_index()
     x = x.contiguous()
     out = torch.empty(x.shape[1], dtype=torch.float64, device=x.device)
     with _on(x):
-        _lib.check(lib.ccr_colsum_bf16(_ptr(x), x.shape[0], x.shape[1], _ptr(out), _stream(x)), "ccr_colsum_bf16")
+        if x.dtype == torch.bfloat16:
+            _lib.check(lib.ccr_colsum_bf16(_ptr(x), x.shape[0], x.shape[1], _ptr(out), _stream(x)), "ccr_colsum_bf16")
+        else:
+            _lib.check(lib.ccr_colsum_half(_ptr(x), x.shape[0], x.shape[1], code, _ptr(out), _stream(x)), "ccr_colsum_half")
     return out
 
 

@@ -74,7 +74,7 @@ void slab_give(int device, uint32_t *p) {
 }  // namespace
 
 extern "C" const char *ccr_last_error(void) { return g_err; }
-extern "C" int ccr_version(void) { return 108; }
+extern "C" int ccr_version(void) { return 109; }
 
 extern "C" int ccr_index_destroy(ccr_index *ix);
 
@@ -127,9 +127,10 @@ void block_give(int device, void *p, size_t bytes) {
 
 // row_bounds (device, n_rows floats, or null): upper bounds of the packed rows' norms as ccr_pack_bf16_ex wrote them (borrowed for
 // the life of the index: the select stage reads them per candidate); without them the index makes its own pass over the shard.
-static int index_create_impl(const uint16_t *D_bf16, int64_t n_rows, int dim, int64_t global_row_offset, const float *row_bounds,
+static int index_create_impl(const uint16_t *D_bf16, int half_dtype, int64_t n_rows, int dim, int64_t global_row_offset, const float *row_bounds,
                              void *stream, ccr_index **out) {
     CCR_REQUIRE(D_bf16 && out, "ccr_index_create: null pointer");
+    if (const int rc = check_half("ccr_index_create", half_dtype)) return rc;
     CCR_REQUIRE(n_rows >= 1 && n_rows < ((int64_t)1 << 32), "ccr_index_create: n_rows=%lld out of range [1, 2^32)",
                 (long long)n_rows);
     CCR_REQUIRE(dim >= 8 && dim % 8 == 0 && dim <= 4096, "ccr_index_create: dim=%d must be a multiple of 8 in [8, 4096]", dim);
@@ -138,6 +139,7 @@ static int index_create_impl(const uint16_t *D_bf16, int64_t n_rows, int dim, in
     ccr_index *ix = new ccr_index();
     memset(ix, 0, sizeof(*ix));
     ix->D = D_bf16;
+    ix->dtype = half_dtype;
     ix->n_rows = n_rows;
     ix->dim = dim;
     ix->offset = ix->id_out = global_row_offset;
@@ -165,7 +167,7 @@ static int index_create_impl(const uint16_t *D_bf16, int64_t n_rows, int dim, in
             ix->row_norm = ix->row_norm_own = (float *)rn;
             CCR_HIP_CHECK(hipMemsetAsync(ix->dmax_bits, 0, 4, s));   // (this path max-accumulates with atomics)
             CCR_HIP_CHECK(hipMemsetAsync(tile_bits, 0, (size_t)tiles * 4, s));
-            rc = launch_row_norms_bf16(D_bf16, n_rows, dim, ix->row_norm_own, ix->dmax_bits, tile_bits, s);
+            rc = launch_row_norms(D_bf16, half_dtype, n_rows, dim, ix->row_norm_own, ix->dmax_bits, tile_bits, s);
             if (rc != CCR_OK) return rc;
             CCR_HIP_CHECK(hipStreamSynchronize(s));
         }
@@ -180,15 +182,25 @@ static int index_create_impl(const uint16_t *D_bf16, int64_t n_rows, int dim, in
     return CCR_OK;
 }
 
+extern "C" int ccr_index_create_half(const uint16_t *D, int64_t n_rows, int dim, int half_dtype, int64_t global_row_offset, void *stream,
+                                     ccr_index **out) {
+    return index_create_impl(D, half_dtype, n_rows, dim, global_row_offset, nullptr, stream, out);
+}
+
+extern "C" int ccr_index_create_with_norms_half(const uint16_t *D, int64_t n_rows, int dim, int half_dtype, int64_t global_row_offset,
+                                                const float *row_norm_bounds, void *stream, ccr_index **out) {
+    CCR_REQUIRE(row_norm_bounds, "ccr_index_create_with_norms: null row_norm_bounds");
+    return index_create_impl(D, half_dtype, n_rows, dim, global_row_offset, row_norm_bounds, stream, out);
+}
+
 extern "C" int ccr_index_create(const uint16_t *D_bf16, int64_t n_rows, int dim, int64_t global_row_offset, void *stream,
                                 ccr_index **out) {
-    return index_create_impl(D_bf16, n_rows, dim, global_row_offset, nullptr, stream, out);
+    return ccr_index_create_half(D_bf16, n_rows, dim, CCR_DTYPE_BF16, global_row_offset, stream, out);
 }
 
 extern "C" int ccr_index_create_with_norms(const uint16_t *D_bf16, int64_t n_rows, int dim, int64_t global_row_offset,
                                            const float *row_norm_bounds, void *stream, ccr_index **out) {
-    CCR_REQUIRE(row_norm_bounds, "ccr_index_create_with_norms: null row_norm_bounds");
-    return index_create_impl(D_bf16, n_rows, dim, global_row_offset, row_norm_bounds, stream, out);
+    return ccr_index_create_with_norms_half(D_bf16, n_rows, dim, CCR_DTYPE_BF16, global_row_offset, row_norm_bounds, stream, out);
 }
 
 extern "C" int ccr_index_destroy(ccr_index *ix) {
@@ -211,6 +223,7 @@ extern "C" int ccr_index_destroy(ccr_index *ix) {
 
 extern "C" int64_t ccr_index_rows(const ccr_index *ix) { return ix ? ix->n_rows : -1; }
 extern "C" int ccr_index_dim(const ccr_index *ix) { return ix ? ix->dim : -1; }
+extern "C" int ccr_index_dtype(const ccr_index *ix) { return ix ? ix->dtype : -1; }
 
 extern "C" size_t ccr_search_workspace_bytes(const ccr_index *ix, int n_q, int k) {
     if (!ix || n_q <= 0 || k <= 0) return 0;
@@ -250,7 +263,7 @@ static int dense_for_list(const ccr_index *ix, const uint16_t *Q, const uint32_t
                           float *out_scores, int64_t *out_ids, hipStream_t s) {
     for (int lo = 0; lo < n; lo += (int)rows_per_chunk) {
         const int m = std::min<int64_t>(rows_per_chunk, n - lo);
-        int rc = launch_dense_scores(ix->D, ix->n_rows, ix->dim, Q, d_qlist ? d_qlist + lo : nullptr, lo, m, nullptr, scratch, s);
+        int rc = launch_dense_scores(ix->D, ix->dtype, ix->n_rows, ix->dim, Q, d_qlist ? d_qlist + lo : nullptr, lo, m, nullptr, scratch, s);
         if (rc != CCR_OK) return rc;
         rc = launch_dense_select(scratch, ix->n_rows, k, d_qlist ? d_qlist + lo : nullptr, lo, m, nullptr, ix->id_out, out_scores, out_ids, s);
         if (rc != CCR_OK) return rc;
@@ -303,7 +316,7 @@ static int store_scores(const ccr_index *ix, const uint16_t *Q, int n_q, int ran
     g.qgroups = 1;
     g.store = out;
     g.store_pitch = pitch;
-    return launch_gemm(g, ix->knobs.mfma16 != 0 ? MAIN_16X16 : MAIN_32X32, EPI_STORE, std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD), s);
+    return launch_gemm(g, ix->dtype, ix->knobs.mfma16 != 0 ? MAIN_16X16 : MAIN_32X32, EPI_STORE, std::max(NUM_XCD, ix->num_cu / NUM_XCD * NUM_XCD), s);
 }
 
 // The same for inner-product scores the fast way: MFMA score rows of the chunk (EPI_STORE of the fused kernel) + margin select
@@ -321,7 +334,7 @@ static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float 
         const uint16_t *Q = Qc + (int64_t)lo * ix->dim;
         int rc = store_scores(ix, Q, m, ranges, scratch, pitch, s);
         if (rc != CCR_OK) return rc;
-        rc = launch_margin_select(scratch, pitch, ix->n_rows, k, ix->dim, Q, ix->D, ix->tile_norm, ix->row_norm, ix->dmax_bits,
+        rc = launch_margin_select(scratch, pitch, ix->n_rows, k, ix->dim, Q, ix->D, ix->dtype, ix->tile_norm, ix->row_norm, ix->dmax_bits,
                                   hint ? hint + lo : nullptr, out_rows ? out_rows + lo : nullptr, lo, m, ix->id_out, out_scores, out_ids, flag_count, flag_list, s);
         if (rc != CCR_OK) return rc;
     }
@@ -359,7 +372,7 @@ static int run_main_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, 
         gm.item_begin = done;
         gm.item_end = bounds[ph];
         const MainKernel kind = p.tile_q == WIDE_Q ? MAIN_WIDE : p.mfma16 ? MAIN_16X16 : MAIN_32X32;
-        const int rc = launch_gemm(gm, kind, EPI_FILTER, p.grid, s);
+        const int rc = launch_gemm(gm, ix->dtype, kind, EPI_FILTER, p.grid, s);
         if (rc != CCR_OK) return rc;
         done = bounds[ph];
     }
@@ -390,7 +403,7 @@ static int run_narrow_pass(const ccr_index *ix, const Plan &p, const SearchWs &w
     const int64_t blocks = (ix->n_rows + 16 * NARROW_WAVES - 1) / (16 * NARROW_WAVES);
     if ((int64_t)ngrid > blocks) ngrid = (int)std::max<int64_t>(1, blocks);
     if (p.narrow_groups == 2) ngrid = std::max(16, ngrid / 16 * 16);   // whole sets of eight (b, b + 8) pairs; a pair shares its row stream
-    return launch_narrow_filter(na, p.narrow, ngrid, s);
+    return launch_narrow_filter(na, ix->dtype, p.narrow, ngrid, s);
 }
 
 // n 32-bit words from the device to the host; synchronises the stream
@@ -464,10 +477,10 @@ static int retry_group(ccr_index *ix, const SearchWs &w, const uint32_t *cur, in
         CCR_HIP_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)nsub_all * pad2 * 4, s));
         CCR_HIP_CHECK(hipMemsetAsync(w.flag2, 0, 64, s));
         const GemmArgs g = filter_args(ix, p, w, w.Q2, n_cur, pad2, pad2 / TILE_Q, pick_qgroups(pad2 / TILE_Q, ix->dim, ix->knobs), w.thr2, w.cq2, lay2);
-        rc = launch_gemm(g, p.mfma16 ? MAIN_16X16 : MAIN_32X32, EPI_FILTER, p.grid, s);   // TILE_Q blocks: never the wide kernel
+        rc = launch_gemm(g, ix->dtype, p.mfma16 ? MAIN_16X16 : MAIN_32X32, EPI_FILTER, p.grid, s);   // TILE_Q blocks: never the wide kernel
         if (rc != CCR_OK) return rc;
         rc = launch_select_rescore(w.cand, w.cnt, nsub_all, p.sublists, n_cur, pad2, lay2, pd.k, p.rescore_cap, p.select_compact, ix->n_rows,
-                                   w.thr2, w.cq2, ix->tile_norm, ix->row_norm, ix->dmax_bits, w.Q2, ix->D, ix->dim, ix->id_out, pd.out_scores, pd.out_ids,
+                                   w.thr2, w.cq2, ix->tile_norm, ix->row_norm, ix->dmax_bits, w.Q2, ix->D, ix->dtype, ix->dim, ix->id_out, pd.out_scores, pd.out_ids,
                                    w.flag2, w.flag2 + 16, nullptr, cur, s, nullptr, 0, 0, 0, nullptr, 0, p.rescore_regular);
         if (rc != CCR_OK) return rc;
         ix->stats.n_retried += n_cur;
@@ -675,7 +688,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     // main_qblocks * tile_q (the 256 x 384 kernel leaves [main_qblocks * 384, nq_pad) unwritten: no reader goes past n_q);
     // only a plan with more ranges than tiles (forced fused searches of tiny corpora) leaves counters unwritten
     if ((int64_t)p.ranges > p.tiles - (p.skip_sampled ? p.sample_tiles : 0)) CCR_HIP_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)p.ranges * p.nq_pad * p.sublists * 4, s));
-    int rc = launch_row_norms_bf16(Q_bf16, n_q, ix->dim, w.qnorm, nullptr, nullptr, s);
+    int rc = launch_row_norms(Q_bf16, ix->dtype, n_q, ix->dim, w.qnorm, nullptr, nullptr, s);
     if (rc != CCR_OK) return rc;
 
     // sample pass -> group maxima -> thresholds
@@ -686,7 +699,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     gs.ranges = p.sample_ranges;
     gs.gmax = w.gmax;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SAMPLE_BEGIN], s));
-    rc = launch_gemm(gs, MAIN_32X32, EPI_GMAX, p.grid, s);
+    rc = launch_gemm(gs, ix->dtype, MAIN_32X32, EPI_GMAX, p.grid, s);
     if (rc != CCR_OK) return rc;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SAMPLE_END], s));
     // (small batches: the streaming pass's sub-list counters are cleared by the threshold launch)
@@ -702,7 +715,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_MAIN_END], s));
     ix->main_pass_recorded = true;
     rc = launch_select_rescore(w.cand, w.cnt, p.first_nsub, p.first_sp, n_q, p.nq_pad, p.first_lay, k, p.rescore_cap, p.select_compact, ix->n_rows, w.thr,
-                               w.cq, ix->tile_norm, ix->row_norm, ix->dmax_bits, Q_bf16, ix->D, ix->dim, ix->id_out, out_scores, out_ids,
+                               w.cq, ix->tile_norm, ix->row_norm, ix->dmax_bits, Q_bf16, ix->D, ix->dtype, ix->dim, ix->id_out, out_scores, out_ids,
                                w.flag_count, w.flag_list, w.stat_cand, nullptr, s, p.skip_sampled ? w.gmax : nullptr, p.sample_tiles,
                                (int)p.sample_stride, p.nq_pad, ix->knobs.skip_list ? w.glist : nullptr, skip_list_cap(p.opt_rank),
                                p.rescore_regular);
@@ -764,7 +777,7 @@ extern "C" int ccr_scores(const ccr_index *ix, const uint16_t *Q_bf16, int n_q, 
     CCR_REQUIRE(ix && Q_bf16 && out && n_q > 0, "ccr_scores: bad argument");
     CCR_REQUIRE((uintptr_t)Q_bf16 % 16 == 0, "ccr_scores: query pointer must be 16-byte aligned");
     if (mode == CCR_SCORES_CANONICAL)
-        return launch_dense_scores(ix->D, ix->n_rows, ix->dim, Q_bf16, nullptr, 0, n_q, nullptr, out, (hipStream_t)stream);
+        return launch_dense_scores(ix->D, ix->dtype, ix->n_rows, ix->dim, Q_bf16, nullptr, 0, n_q, nullptr, out, (hipStream_t)stream);
     CCR_REQUIRE(mode == CCR_SCORES_MFMA, "ccr_scores: unknown mode %d", mode);
     CCR_REQUIRE(ix->dim % 8 == 0, "ccr_scores: CCR_SCORES_MFMA needs dim %% 8 == 0 (dim=%d)", ix->dim);
     return store_scores(ix, Q_bf16, n_q, (int)round_up(std::min<int64_t>(64, tiles_of(ix)), NUM_XCD), out, 0, (hipStream_t)stream);

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "ccr_retrieval.h"
 
 namespace ccr {
@@ -159,8 +161,43 @@ struct GemmArgs {
 };
 
 
+// ---- the 16-bit element type of an index and its queries: CCR_DTYPE_BF16 or CCR_DTYPE_F16.  Every kernel that reads an element as a
+// NUMBER takes it as the template argument DT; what moves rows around (LDS-DMA, gathers, merges) is byte-level and has none.
+// Host side: a run-time type becomes the template argument in ONE place per launcher.  f is a generic lambda whose parameter is a
+// std::integral_constant (read its ::value); it returns the launch's status.
+template <class F>
+inline int dispatch_half(int half_dtype, F &&f) {   // CCR_DTYPE_F16 or CCR_DTYPE_BF16 (the caller has checked)
+    return half_dtype == CCR_DTYPE_F16 ? f(std::integral_constant<int, CCR_DTYPE_F16>{}) : f(std::integral_constant<int, CCR_DTYPE_BF16>{});
+}
+inline int check_half(const char *who, int half_dtype) {
+    CCR_REQUIRE(half_dtype == CCR_DTYPE_BF16 || half_dtype == CCR_DTYPE_F16, "%s: half_dtype=%d (CCR_DTYPE_F16 or CCR_DTYPE_BF16)", who, half_dtype);
+    return CCR_OK;
+}
+
 // ---- device helpers
-__device__ __forceinline__ float bf16_bits_to_f32(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
+// The value of a 16-bit element, exactly (both types embed in fp32; fp16 subnormals are kept: v_cvt_f32_f16 follows the kernel's
+// fp16/fp64 denormal mode, which hipcc leaves on).  elem_lo / elem_hi: the two elements of a 32-bit word, element 0 in the low half.
+template <int DT>
+__device__ __forceinline__ float elem_to_f32(uint16_t h) {
+    if constexpr (DT == CCR_DTYPE_F16)
+        return (float)__builtin_bit_cast(_Float16, h);
+    else
+        return __uint_as_float(((uint32_t)h) << 16);
+}
+template <int DT>
+__device__ __forceinline__ float elem_lo(uint32_t w) {
+    if constexpr (DT == CCR_DTYPE_F16)
+        return elem_to_f32<DT>((uint16_t)w);
+    else
+        return __uint_as_float(w << 16);
+}
+template <int DT>
+__device__ __forceinline__ float elem_hi(uint32_t w) {
+    if constexpr (DT == CCR_DTYPE_F16)
+        return elem_to_f32<DT>((uint16_t)(w >> 16));
+    else
+        return __uint_as_float(w & 0xffff0000u);
+}
 
 // monotone map float -> uint32 (larger float <-> larger uint); NaN maps above +inf (never produced here)
 __device__ __forceinline__ uint32_t f32_orderable(float f) {

@@ -16,6 +16,7 @@ constexpr int LDP = 68;  // padded leading dimension (floats)
 
 // scores[qi][j] = canonical(Q[qsel(qi)], D[j]);  qlist == nullptr -> qsel(qi) = q_begin + qi.
 // grid = (ceil(n_rows/DT), ceil(nq_chunk/QT)), block = 256 (thread = 4 queries x 4 docs).
+template <int ET>   // element type of D and Q
 __global__ __launch_bounds__(256) void dense_scores_kernel(const uint16_t *__restrict__ D, int64_t n_rows, int dim,
                                                           const uint16_t *__restrict__ Q, const uint32_t *__restrict__ qlist,
                                                           int q_begin, int nq_chunk, const uint32_t *__restrict__ count_dev,
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void dense_scores_kernel(const uint16_t *__res
     const int tid = threadIdx.x;
     const int64_t d0 = (int64_t)blockIdx.x * DT;
     const int q0 = blockIdx.y * QT;
-    // staging role: one 16-byte chunk (8 bf16) of one row per operand
+    // staging role: one 16-byte chunk (8 elements) of one row per operand
     const int srow = tid >> 2, schunk = tid & 3;
     int64_t drow = d0 + srow;
     if (drow > n_rows - 1) drow = n_rows - 1;
@@ -59,10 +60,10 @@ __global__ __launch_bounds__(256) void dense_scores_kernel(const uint16_t *__res
         const uint32_t qw[4] = {qv.x, qv.y, qv.z, qv.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            Ds[schunk * 8 + 2 * e][srow] = __uint_as_float(dw[e] << 16);
-            Ds[schunk * 8 + 2 * e + 1][srow] = __uint_as_float(dw[e] & 0xffff0000u);
-            Qs[schunk * 8 + 2 * e][srow] = __uint_as_float(qw[e] << 16);
-            Qs[schunk * 8 + 2 * e + 1][srow] = __uint_as_float(qw[e] & 0xffff0000u);
+            Ds[schunk * 8 + 2 * e][srow] = elem_lo<ET>(dw[e]);
+            Ds[schunk * 8 + 2 * e + 1][srow] = elem_hi<ET>(dw[e]);
+            Qs[schunk * 8 + 2 * e][srow] = elem_lo<ET>(qw[e]);
+            Qs[schunk * 8 + 2 * e + 1][srow] = elem_hi<ET>(qw[e]);
         }
         __syncthreads();
 #pragma unroll 8
@@ -176,12 +177,14 @@ __global__ __launch_bounds__(256) void dense_select_kernel(const float *__restri
     }
 }
 
-int launch_dense_scores(const uint16_t *D, int64_t n_rows, int dim, const uint16_t *Q, const uint32_t *qlist,
+int launch_dense_scores(const uint16_t *D, int dt, int64_t n_rows, int dim, const uint16_t *Q, const uint32_t *qlist,
                         int q_begin, int nq_chunk, const uint32_t *count_dev, float *out, hipStream_t s) {
     dim3 grid((unsigned)((n_rows + DT - 1) / DT), (unsigned)((nq_chunk + QT - 1) / QT));
-    hipLaunchKernelGGL(dense_scores_kernel, grid, dim3(256), 0, s, D, n_rows, dim, Q, qlist, q_begin, nq_chunk, count_dev, out);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return dispatch_half(dt, [&](auto et) {
+        hipLaunchKernelGGL(dense_scores_kernel<decltype(et)::value>, grid, dim3(256), 0, s, D, n_rows, dim, Q, qlist, q_begin, nq_chunk, count_dev, out);
+        CCR_LAUNCH_CHECK();
+        return CCR_OK;
+    });
 }
 
 int launch_dense_select(const float *scores, int64_t n_rows, int k, const uint32_t *out_rows, int q_begin, int nq_chunk,
@@ -210,6 +213,7 @@ int launch_dense_select(const float *scores, int64_t n_rows, int k, const uint32
 // re-scored canonically (fp64 ordered) and the k best of those, by (score desc, row asc), are the exact result.  A query
 // with more than `cap` such rows (mass ties) or non-finite margins is flagged for the fp64 path.
 // grid = chunk, block = 1024, dyn LDS = dim * 2 (query row) + cap * 8 (keys).
+template <int ET>
 __global__ __launch_bounds__(1024) void margin_select_kernel(const float *__restrict__ scores, int64_t pitch, int64_t n_rows, int k, int dim,
                                                             const uint16_t *__restrict__ Q, const uint16_t *__restrict__ D,
                                                             const float *__restrict__ tile_norm, const float *__restrict__ row_norm,
@@ -238,7 +242,7 @@ __global__ __launch_bounds__(1024) void margin_select_kernel(const float *__rest
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float lo = __uint_as_float(w[e] << 16), hi = __uint_as_float(w[e] & 0xffff0000u);
+            const float lo = elem_lo<ET>(w[e]), hi = elem_hi<ET>(w[e]);
             ss = fmaf(lo, lo, ss);
             ss = fmaf(hi, hi, ss);
         }
@@ -334,7 +338,7 @@ __global__ __launch_bounds__(1024) void margin_select_kernel(const float *__rest
         unsigned long long key = 0ull;
         if (i < n) {
             const uint32_t r = (uint32_t)s_keys[i];
-            key = make_key(canonical_dot(s_q, D + (int64_t)r * dim, dim), r);
+            key = make_key(canonical_dot<ET>(s_q, D + (int64_t)r * dim, dim), r);
         }
         s_keys[i] = key;
     }
@@ -349,17 +353,20 @@ __global__ __launch_bounds__(1024) void margin_select_kernel(const float *__rest
 constexpr int MARGIN_SELECT_CAP = 8192;   // rows re-scored per query at most (64 KiB of keys)
 static_assert(MARGIN_SELECT_CAP <= 8 * 1024, "margin_select_kernel: a thread keeps at most 8 list entries while the list is rebuilt in place");
 
-int launch_margin_select(const float *scores, int64_t pitch, int64_t n_rows, int k, int dim, const uint16_t *Q, const uint16_t *D,
+int launch_margin_select(const float *scores, int64_t pitch, int64_t n_rows, int k, int dim, const uint16_t *Q, const uint16_t *D, int dt,
                          const float *tile_norm, const float *row_norm, const uint32_t *dmax_bits, const float *hint, const uint32_t *out_rows, int q_begin,
                          int nq_chunk, int64_t id_offset, float *out_scores, int64_t *out_ids, uint32_t *flag_count, uint32_t *flag_list,
                          hipStream_t s) {
     const size_t lds = (((size_t)dim * 2 + 15) & ~(size_t)15) + (size_t)MARGIN_SELECT_CAP * 8;
-    const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&margin_select_kernel), 96 * 1024);
-    if (rc != CCR_OK) return rc;
-    hipLaunchKernelGGL(margin_select_kernel, dim3(nq_chunk), dim3(1024), lds, s, scores, pitch, n_rows, k, dim, Q, D, tile_norm, row_norm,
-                       dmax_bits, mfma_gamma(dim), MARGIN_SELECT_CAP, hint, out_rows, q_begin, id_offset, out_scores, out_ids, flag_count, flag_list);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return dispatch_half(dt, [&](auto et) {
+        constexpr int ET = decltype(et)::value;
+        const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&margin_select_kernel<ET>), 96 * 1024);
+        if (rc != CCR_OK) return rc;
+        hipLaunchKernelGGL(margin_select_kernel<ET>, dim3(nq_chunk), dim3(1024), lds, s, scores, pitch, n_rows, k, dim, Q, D, tile_norm, row_norm,
+                           dmax_bits, mfma_gamma(dim), MARGIN_SELECT_CAP, hint, out_rows, q_begin, id_offset, out_scores, out_ids, flag_count, flag_list);
+        CCR_LAUNCH_CHECK();
+        return CCR_OK;
+    });
 }
 
 }  // namespace ccr

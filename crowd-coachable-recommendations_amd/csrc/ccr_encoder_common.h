@@ -242,10 +242,7 @@ inline int dispatch_width(int dim, F &&f) {   // dim = 256 C, C = 1 .. 8 (the ca
         default: return f(std::integral_constant<int, 8>{});
     }
 }
-template <class F>
-inline int dispatch_half(int half_dtype, F &&f) {   // CCR_DTYPE_F16 or CCR_DTYPE_BF16 (the caller has checked)
-    return half_dtype == CCR_DTYPE_F16 ? f(std::integral_constant<int, CCR_DTYPE_F16>{}) : f(std::integral_constant<int, CCR_DTYPE_BF16>{});
-}
+// (dispatch_half: ccr_common.h -- the search kernels resolve their element type with it too)
 template <class F>
 inline int dispatch_drop(bool drop, F &&f) {
     return drop ? f(std::true_type{}) : f(std::false_type{});
@@ -260,10 +257,7 @@ inline int launch_row_kernel(K kernel, int64_t nblk, hipStream_t s, A... args) {
 }
 
 // The argument checks that entry points share, reported under the caller's name `who`.
-inline int check_half(const char *who, int half_dtype) {
-    CCR_REQUIRE(half_dtype == CCR_DTYPE_BF16 || half_dtype == CCR_DTYPE_F16, "%s: half_dtype=%d (CCR_DTYPE_F16 or CCR_DTYPE_BF16)", who, half_dtype);
-    return CCR_OK;
-}
+// (check_half: ccr_common.h)
 inline int check_inv_keep(const char *who, float inv_keep) {
     CCR_REQUIRE(inv_keep >= 1.f && inv_keep <= 65536.f, "%s: inv_keep=%g (1 .. 65536)", who, (double)inv_keep);
     return CCR_OK;

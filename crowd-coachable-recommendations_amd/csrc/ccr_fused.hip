@@ -18,9 +18,9 @@
 // query column).  Staging: global_load_lds_dwordx4 into a ring of four 32-KiB sub-stages (32 K
 // elements = 64-B rows), the 16-byte chunk index XOR-swizzled on the SOURCE address and on the
 // fragment read (conflict-free ds_read_b128).  One body, main_pass_256, serves two MFMA shapes:
-//   gemm_topk_kernel     v_mfma_f32_32x32x16_bf16 (Mfma32): the sample pass (EPI_GMAX), and EPI_FILTER / EPI_STORE where
+//   gemm_topk_kernel     v_mfma_f32_32x32x16_bf16 / _f16 (Mfma32): the sample pass (EPI_GMAX), and EPI_FILTER / EPI_STORE where
 //                        the plan or CCR_MFMA16=0 picks it
-//   gemm_topk16_kernel   v_mfma_f32_16x16x32_bf16 (Mfma16): the default 256 x 256 main pass (EPI_FILTER) and EPI_STORE
+//   gemm_topk16_kernel   v_mfma_f32_16x16x32_bf16 / _f16 (Mfma16): the default 256 x 256 main pass (EPI_FILTER) and EPI_STORE
 // gemm_topk16w_kernel is the 256 x 384 form of the 16x16 main pass (EPI_FILTER, dim % 32 == 0) on a body of its own.
 #include <stdlib.h>
 
@@ -105,6 +105,7 @@ struct ItemWalk {
 //   C layout: lane -> query column (lane & 31); register e -> corpus row (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5) of the 32-row
 //   MFMA tile -> 4 candidate sub-lists per (range, query): (wave row, lane >> 5).
 //   LDS image: 16-byte chunk c of row r stored at chunk c ^ ((r >> 2) & 3).
+template <int ET>
 struct Mfma32 {
     typedef f32x16 Acc;
     static constexpr int TILE = 32, REGS = 16, DT = 4, QT = 2, SUBLISTS = 4;
@@ -136,17 +137,17 @@ struct Mfma32 {
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-                for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][dt], f.b[0][qt], z, 0, 0, 0);
+                for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = mfma_32x32x16<ET>(f.a[0][dt], f.b[0][qt], z);
         } else {
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-                for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][dt], f.b[0][qt], acc[dt][qt], 0, 0, 0);
+                for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = mfma_32x32x16<ET>(f.a[0][dt], f.b[0][qt], acc[dt][qt]);
         }
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-            for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1][dt], f.b[1][qt], acc[dt][qt], 0, 0, 0);
+            for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = mfma_32x32x16<ET>(f.a[1][dt], f.b[1][qt], acc[dt][qt]);
     }
 
     // maxima of query tile qt: per group of four registers, and per MFMA tile (two 16-row groups, one per lane half)
@@ -219,6 +220,7 @@ struct Mfma32 {
 //   -> a lane owns 4 query columns x 32 rows; 8 candidate sub-lists per (range, query): (wave row, lane >> 4).
 //   LDS image: 16-byte chunk c of row r stored at chunk c ^ (((r >> 2) & 1) << 1) (conflict-free for the 16x16 fragment read
 //   pattern; brute-forced over all xor tables).
+template <int ET>
 struct Mfma16 {
     typedef f32x4v Acc;
     static constexpr int TILE = 16, REGS = 4, DT = 8, QT = 4, SUBLISTS = 8;
@@ -244,13 +246,13 @@ struct Mfma16 {
 #pragma unroll
             for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
-                for (int qt = 0; qt < 4; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[dt], f.b[qt], z, 0, 0, 0);
+                for (int qt = 0; qt < 4; ++qt) acc[dt][qt] = mfma_16x16x32<ET>(f.a[dt], f.b[qt], z);
             return;
         }
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
-            for (int qt = 0; qt < 4; ++qt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[dt], f.b[qt], acc[dt][qt], 0, 0, 0);
+            for (int qt = 0; qt < 4; ++qt) acc[dt][qt] = mfma_16x16x32<ET>(f.a[dt], f.b[qt], acc[dt][qt]);
     }
 
     // EPI_FILTER of a finished wave tile (see Mfma32::filter; a query tile's column of this lane is q0 + wq * 64 + qt * 16 + (lane & 15))
@@ -302,7 +304,7 @@ struct Mfma16 {
 //        barrier instance precedes every mem(u).
 template <class S, int EPI, bool TAIL>
 __device__ __forceinline__ void main_pass_256(const GemmArgs &a) {
-    static_assert(EPI != EPI_GMAX || std::is_same<S, Mfma32>::value, "EPI_GMAX exists on the 32x32 shape only");
+    static_assert(EPI != EPI_GMAX || S::TILE == 32, "EPI_GMAX exists on the 32x32 shape only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     // (the mask costs nothing once inlined into a kernel with GEMM_THREADS threads, but tells hipcc the range of the thread id while it
@@ -516,10 +518,10 @@ __device__ __forceinline__ void main_pass_256(const GemmArgs &a) {
     }
 }
 
-template <int EPI, bool TAIL = false>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmArgs a) { main_pass_256<Mfma32, EPI, TAIL>(a); }
-template <int EPI, bool TAIL = false>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const GemmArgs a) { main_pass_256<Mfma16, EPI, TAIL>(a); }
+template <int ET, int EPI, bool TAIL = false>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk_kernel(const GemmArgs a) { main_pass_256<Mfma32<ET>, EPI, TAIL>(a); }
+template <int ET, int EPI, bool TAIL = false>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16_kernel(const GemmArgs a) { main_pass_256<Mfma16<ET>, EPI, TAIL>(a); }
 
 // =============================================================================================
 // WIDE form of the 16x16x32 main pass (round 6): a 256 x 384 tile on the same eight waves.
@@ -603,6 +605,7 @@ constexpr int WIDE_QT = 6;                                         // query tile
 constexpr int WIDE_RING_BYTES = WIDE_RING * WIDE_SUB_BYTES;        // 122880
 constexpr size_t WIDE_LDS = (size_t)WIDE_RING_BYTES + WIDE_Q * 8 + (size_t)(GEMM_THREADS / 64) * WIDE_QT * 64 * 4;   // 138240
 
+template <int ET>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *s_tc = reinterpret_cast<float2 *>(smem + WIDE_RING_BYTES);                     // [384] {tau_q, cq} of the item's query block
@@ -837,7 +840,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
 #pragma unroll
                 for (int qt = 0; qt < WIDE_QT; ++qt) {
 #pragma unroll
-                    for (int dt = 0; dt < 8; ++dt) acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], bfr[qt % WIDE_BFR], z, 0, 0, 0);
+                    for (int dt = 0; dt < 8; ++dt) acc[dt][qt] = mfma_16x16x32<ET>(af[dt], bfr[qt % WIDE_BFR], z);
                     if (WIDE_BFR == 3 && qt < 3) {
                         __builtin_amdgcn_sched_barrier(0);
                         bfr[qt] = *reinterpret_cast<const bf16x8 *>(bbuf + b_base + (qt + 3) * 1024);
@@ -849,7 +852,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
                 for (int qt = 0; qt < WIDE_QT; ++qt) {
 #pragma unroll
                     for (int dt = 0; dt < 8; ++dt)
-                        acc[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], bfr[qt % WIDE_BFR], acc[dt][qt], 0, 0, 0);
+                        acc[dt][qt] = mfma_16x16x32<ET>(af[dt], bfr[qt % WIDE_BFR], acc[dt][qt]);
                     if (WIDE_BFR == 3 && qt < 3) {
                         __builtin_amdgcn_sched_barrier(0);
                         bfr[qt] = *reinterpret_cast<const bf16x8 *>(bbuf + b_base + (qt + 3) * 1024);
@@ -889,11 +892,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
 }
 
 // ---------------------------------------------------------------------------------------------
-// bf16 row norms (fp32 accumulate; used only for error margins, inflated by the caller).  With tile_bits (the index's own
+// row norms of 16-bit rows (fp32 accumulate: an fp16 square is at most 2^32, at least 2^-48; used only for error margins, inflated by the caller).  With tile_bits (the index's own
 // pass over a shard it was given without norms) a wave takes 64 CONSECUTIVE rows at a time and max-accumulates their norms
 // into the word of their 256-row tile (four adds per tile); norms of non-negative floats order as unsigned bit patterns and a
 // NaN (row with a NaN) stays on top.
-__global__ __launch_bounds__(256) void row_norms_bf16_kernel(const uint16_t *__restrict__ X, int64_t rows, int dim,
+template <int ET>
+__global__ __launch_bounds__(256) void row_norms_kernel(const uint16_t *__restrict__ X, int64_t rows, int dim,
                                                             float *__restrict__ norms, uint32_t *__restrict__ max_bits,
                                                             uint32_t *__restrict__ tile_bits) {
     const int lane = threadIdx.x & 63;
@@ -912,7 +916,7 @@ __global__ __launch_bounds__(256) void row_norms_bf16_kernel(const uint16_t *__r
                 const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float lo = __uint_as_float(w[e] << 16), hi = __uint_as_float(w[e] & 0xffff0000u);
+                    const float lo = elem_lo<ET>(w[e]), hi = elem_hi<ET>(w[e]);
                     s = fmaf(lo, lo, s);
                     s = fmaf(hi, hi, s);
                 }
@@ -1290,7 +1294,7 @@ __global__ __launch_bounds__(256) void threshold_update_kernel(const uint2 *__re
 //   * so a group with gmax + c * tile_norm < L holds no result row, and a group at or above L is re-scored WHOLE (its 16 rows
 //     join the collected rows through the same counter and capacity check; an overflow takes the dense path);
 //   * ties are settled by the sort on (score, ~row) as before.
-template <int THREADS>
+template <int ET, int THREADS>
 __global__ __launch_bounds__(THREADS) void select_rescore_kernel(const uint2 *__restrict__ cand, const uint32_t *__restrict__ cnt,
                                                             int ranges, int sp, int nq_pad, const CandLayout lay, int k, int rescore_cap, int compact,
                                                             int64_t n_rows, float *__restrict__ thr, const float *__restrict__ cq,
@@ -1635,8 +1639,8 @@ __global__ __launch_bounds__(THREADS) void select_rescore_kernel(const uint2 *__
                         const uint32_t qw[4] = {qv.x, qv.y, qv.z, qv.w};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            a = fma((double)__uint_as_float(qw[e] << 16), (double)__uint_as_float(dw[e] << 16), a);
-                            a = fma((double)__uint_as_float(qw[e] & 0xffff0000u), (double)__uint_as_float(dw[e] & 0xffff0000u), a);
+                            a = fma((double)elem_lo<ET>(qw[e]), (double)elem_lo<ET>(dw[e]), a);
+                            a = fma((double)elem_hi<ET>(qw[e]), (double)elem_hi<ET>(dw[e]), a);
                         }
                     }
                     acc[j] = a;
@@ -1655,7 +1659,7 @@ __global__ __launch_bounds__(THREADS) void select_rescore_kernel(const uint2 *__
             unsigned long long key = 0ull;
             if (i < ncoll) {
                 const uint32_t row = (uint32_t)s_keys[i];
-                key = make_key(canonical_dot(s_q, D + (int64_t)row * dim, dim), row);
+                key = make_key(canonical_dot<ET>(s_q, D + (int64_t)row * dim, dim), row);
             }
             s_keys[i] = key;
         }
@@ -1749,7 +1753,9 @@ static int launch_kernel(K kernel, size_t lds, const GemmArgs &a, int grid, hipS
     return CCR_OK;
 }
 
-int launch_gemm(const GemmArgs &a, MainKernel kind, int epi, int grid, hipStream_t s) {
+// the kernel table of one element type
+template <int ET>
+static int launch_gemm_of(const GemmArgs &a, MainKernel kind, int epi, int grid, hipStream_t s) {
     if (epi != EPI_FILTER && epi != EPI_GMAX && epi != EPI_STORE) {
         set_error("launch_gemm: unknown epilogue %d", epi);
         return CCR_ERR_INVALID;
@@ -1759,16 +1765,16 @@ int launch_gemm(const GemmArgs &a, MainKernel kind, int epi, int grid, hipStream
             set_error("launch_gemm: the 256 x 384 kernel takes EPI_FILTER and dim %% %d == 0 only (epi %d, dim %d)", SUB_K, epi, a.dim);
             return CCR_ERR_INVALID;
         }
-        return launch_kernel(&gemm_topk16w_kernel, WIDE_LDS, a, grid, s);
+        return launch_kernel(&gemm_topk16w_kernel<ET>, WIDE_LDS, a, grid, s);
     }
     typedef void (*Kernel)(const GemmArgs);
     static const Kernel k256[2][3][2] = {   // [kind][epi][TAIL: dim % 32 != 0, the last K sub-stage zero-filled]
-        {{gemm_topk_kernel<EPI_FILTER>, gemm_topk_kernel<EPI_FILTER, true>},
-         {gemm_topk_kernel<EPI_GMAX>, gemm_topk_kernel<EPI_GMAX, true>},
-         {gemm_topk_kernel<EPI_STORE>, gemm_topk_kernel<EPI_STORE, true>}},
-        {{gemm_topk16_kernel<EPI_FILTER>, gemm_topk16_kernel<EPI_FILTER, true>},
+        {{gemm_topk_kernel<ET, EPI_FILTER>, gemm_topk_kernel<ET, EPI_FILTER, true>},
+         {gemm_topk_kernel<ET, EPI_GMAX>, gemm_topk_kernel<ET, EPI_GMAX, true>},
+         {gemm_topk_kernel<ET, EPI_STORE>, gemm_topk_kernel<ET, EPI_STORE, true>}},
+        {{gemm_topk16_kernel<ET, EPI_FILTER>, gemm_topk16_kernel<ET, EPI_FILTER, true>},
          {nullptr, nullptr},
-         {gemm_topk16_kernel<EPI_STORE>, gemm_topk16_kernel<EPI_STORE, true>}},
+         {gemm_topk16_kernel<ET, EPI_STORE>, gemm_topk16_kernel<ET, EPI_STORE, true>}},
     };
     const Kernel k = k256[kind == MAIN_16X16][epi][a.dim % SUB_K != 0];
     if (!k) {
@@ -1778,14 +1784,20 @@ int launch_gemm(const GemmArgs &a, MainKernel kind, int epi, int grid, hipStream
     return launch_kernel(k, RING * (size_t)SUB_BYTES, a, grid, s);
 }
 
-int launch_row_norms_bf16(const uint16_t *X, int64_t rows, int dim, float *norms, uint32_t *max_bits, uint32_t *tile_bits,
-                          hipStream_t s) {
+int launch_gemm(const GemmArgs &a, int dt, MainKernel kind, int epi, int grid, hipStream_t s) {
+    return dispatch_half(dt, [&](auto et) { return launch_gemm_of<decltype(et)::value>(a, kind, epi, grid, s); });
+}
+
+int launch_row_norms(const uint16_t *X, int dt, int64_t rows, int dim, float *norms, uint32_t *max_bits, uint32_t *tile_bits,
+                     hipStream_t s) {
     if (rows <= 0) return CCR_OK;
     int64_t blocks = tile_bits ? (rows + 255) / 256 : (rows + 3) / 4;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(row_norms_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X, rows, dim, norms, max_bits, tile_bits);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return dispatch_half(dt, [&](auto et) {
+        hipLaunchKernelGGL(row_norms_kernel<decltype(et)::value>, dim3((unsigned)blocks), dim3(256), 0, s, X, rows, dim, norms, max_bits, tile_bits);
+        CCR_LAUNCH_CHECK();
+        return CCR_OK;
+    });
 }
 
 int launch_tile_norms(const float *row_bounds, int64_t rows, uint32_t *tile_bits, uint32_t *max_bits, hipStream_t s) {
@@ -1952,7 +1964,7 @@ int launch_gather_queries(const uint16_t *Q, int dim, const uint32_t *list, int 
 int launch_select_rescore(const uint2 *cand, const uint32_t *cnt, int ranges, int sp, int n_q, int nq_pad, const CandLayout &lay, int k,
                           int rescore_cap, int compact, int64_t n_rows, float *thr, const float *cq, const float *tile_norm, const float *row_norm,
                           const uint32_t *dmax_bits, const uint16_t *Q,
-                          const uint16_t *D, int dim, int64_t id_offset, float *out_scores, int64_t *out_ids,
+                          const uint16_t *D, int dt, int dim, int64_t id_offset, float *out_scores, int64_t *out_ids,
                           uint32_t *flag_count, uint32_t *flag_list, unsigned long long *stat_cand, const uint32_t *out_rows,
                           hipStream_t s, const float *gmax, int sample_tiles, int sample_stride, int gmax_pitch, const uint32_t *glist, int list_cap,
                           int regular_cap) {
@@ -1970,8 +1982,11 @@ int launch_select_rescore(const uint2 *cand, const uint32_t *cnt, int ranges, in
         CCR_LAUNCH_CHECK();
         return CCR_OK;
     };
-    if (wide) return go(&select_rescore_kernel<1024>, 1024);
-    return go(&select_rescore_kernel<256>, 256);
+    return dispatch_half(dt, [&](auto et) {
+        constexpr int ET = decltype(et)::value;
+        if (wide) return go(&select_rescore_kernel<ET, 1024>, 1024);
+        return go(&select_rescore_kernel<ET, 256>, 256);
+    });
 }
 
 }  // namespace ccr

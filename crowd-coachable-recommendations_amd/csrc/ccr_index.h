@@ -10,12 +10,12 @@ namespace ccr {
 // the fused GEMM + top-k kernels: 256 x 256 tiles on the 32x32x16 MFMA (every epi) or the 16x16x32 MFMA (no EPI_GMAX), or
 // 256 x 384 tiles on the 16x16x32 MFMA (MAIN_WIDE: a.qblocks = blocks of 384 queries, EPI_FILTER and dim % 32 == 0 only)
 enum MainKernel { MAIN_32X32, MAIN_16X16, MAIN_WIDE };
-int launch_gemm(const GemmArgs &a, MainKernel kind, int epi, int grid, hipStream_t s);
+int launch_gemm(const GemmArgs &a, int dt, MainKernel kind, int epi, int grid, hipStream_t s);   // dt: element type of a.D and a.Q (CCR_DTYPE_BF16 / _F16), here and below
 int launch_shard_header(const ccr_shard_header &h, void *message, hipStream_t s);   // ccr_merge.hip: the 32-byte header, by value
 int ensure_dynamic_lds(const void *kernel, size_t lds);   // per (kernel, device) opt-in to > 64 KiB of dynamic LDS
 // tile_bits (optional): bit patterns of the largest row norm of every 256-row tile, max-accumulated (zeroed by the caller)
-int launch_row_norms_bf16(const uint16_t *X, int64_t rows, int dim, float *norms, uint32_t *max_bits, uint32_t *tile_bits,
-                          hipStream_t s);
+int launch_row_norms(const uint16_t *X, int dt, int64_t rows, int dim, float *norms, uint32_t *max_bits, uint32_t *tile_bits,
+                     hipStream_t s);
 int launch_tile_norms(const float *row_bounds, int64_t rows, uint32_t *tile_bits, uint32_t *max_bits, hipStream_t s);
 // thr[q] = tau_q (lower bound of the k-th largest exact score), cq[q] = gamma ||q|| (margin per unit of row norm)
 int launch_threshold(const float *gmax, int64_t n_groups, int n_q, int nq_pad, int k, const float *qnorm,
@@ -32,7 +32,7 @@ int select_compact_entries(int dim, int ranges, int rescore_cap, int64_t want);
 // glist / list_cap (may be null): launch_threshold's short lists of the groups to test; without one the query's column of gmax is walked.
 int launch_select_rescore(const uint2 *cand, const uint32_t *cnt, int ranges, int sp, int n_q, int nq_pad, const CandLayout &lay, int k,
                           int rescore_cap, int compact, int64_t n_rows, float *thr, const float *cq, const float *tile_norm, const float *row_norm,
-                          const uint32_t *dmax_bits, const uint16_t *Q, const uint16_t *D, int dim, int64_t id_offset, float *out_scores, int64_t *out_ids,
+                          const uint32_t *dmax_bits, const uint16_t *Q, const uint16_t *D, int dt, int dim, int64_t id_offset, float *out_scores, int64_t *out_ids,
                           uint32_t *flag_count, uint32_t *flag_list, unsigned long long *stat_cand, const uint32_t *out_rows,
                           hipStream_t s, const float *gmax = nullptr, int sample_tiles = 0, int sample_stride = 0, int gmax_pitch = 0,
                           const uint32_t *glist = nullptr, int list_cap = 0, int regular_cap = 0);   // regular_cap: limit of the recorded rows (0: rescore_cap)
@@ -52,7 +52,7 @@ int launch_threshold_update(const uint2 *cand, const uint32_t *cnt, int nsub, in
 // dense exact path.  qlist: query rows to score (nullptr: q_begin + qi); out_rows: destination rows of the select
 // (nullptr: q_begin + qi); count_dev (device, may be null): only the first *count_dev - q_begin entries of the list exist
 // (the on-stream fallback chunk of an asynchronous search -- the host does not know the count yet).
-int launch_dense_scores(const uint16_t *D, int64_t n_rows, int dim, const uint16_t *Q, const uint32_t *qlist,
+int launch_dense_scores(const uint16_t *D, int dt, int64_t n_rows, int dim, const uint16_t *Q, const uint32_t *qlist,
                         int q_begin, int nq_chunk, const uint32_t *count_dev, float *out, hipStream_t s);
 int launch_dense_select(const float *scores, int64_t n_rows, int k, const uint32_t *out_rows, int q_begin, int nq_chunk,
                         const uint32_t *count_dev, int64_t id_offset, float *out_scores, int64_t *out_ids, hipStream_t s,
@@ -63,7 +63,7 @@ int launch_dense_select(const float *scores, int64_t n_rows, int k, const uint32
 // Exact top-k from MFMA score rows [nq_chunk][pitch] + error margins (ccr_dense.hip); the chunk's query rows are contiguous at Q.
 // hint (per chunk query, or null): a valid lower bound of its k-th largest score -- one scan of the row instead of five.
 // Queries it cannot finish (more than 8 192 rows inside the margin, non-finite margins) are appended to flag_list with FLAG_DENSE.
-int launch_margin_select(const float *scores, int64_t pitch, int64_t n_rows, int k, int dim, const uint16_t *Q, const uint16_t *D,
+int launch_margin_select(const float *scores, int64_t pitch, int64_t n_rows, int k, int dim, const uint16_t *Q, const uint16_t *D, int dt,
                          const float *tile_norm, const float *row_norm, const uint32_t *dmax_bits, const float *hint, const uint32_t *out_rows,
                          int q_begin, int nq_chunk, int64_t id_offset, float *out_scores, int64_t *out_ids, uint32_t *flag_count, uint32_t *flag_list,
                          hipStream_t s);
@@ -76,6 +76,7 @@ enum SearchEvent { EV_BEGIN, EV_SAMPLE_BEGIN, EV_SAMPLE_END, EV_MAIN_BEGIN, EV_M
 
 struct ccr_index {
     const uint16_t *D;
+    int dtype;            // CCR_DTYPE_BF16 or CCR_DTYPE_F16: the element type of D and of every query matrix searched against it
     int64_t n_rows;
     int dim;
     int64_t offset;

@@ -38,6 +38,6 @@ struct NarrowArgs {
                              // blocks b and b + 8 -- one XCD -- walk the SAME rows, so the second reader finds them in that XCD's L2
 };
 
-int launch_narrow_filter(const NarrowArgs &a, int nqt, int grid, hipStream_t s);
+int launch_narrow_filter(const NarrowArgs &a, int dt, int nqt, int grid, hipStream_t s);   // dt: element type of a.D and a.Q
 
 }  // namespace ccr

@@ -39,7 +39,7 @@ __device__ __forceinline__ bf16x8 stream_load(const char *p) { return *reinterpr
 
 // NQT: query tiles of 16 (1, 2, 4; 6 = 65 .. 96 queries in one group, with a short staging list per query); P: loads in flight per wave =
 // K-steps per chunk (divides dim / 32)
-template <int NQT, int P>
+template <int ET, int NQT, int P>
 __global__ __launch_bounds__(NARROW_THREADS) void narrow_filter_kernel(const NarrowArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -134,10 +134,10 @@ __global__ __launch_bounds__(NARROW_THREADS) void narrow_filter_kernel(const Nar
             if (j == 0 && cc == 0) {
                 const f32x4n z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int qt = 0; qt < NQT; ++qt) acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(buf[j], bcur[qt], z, 0, 0, 0);
+                for (int qt = 0; qt < NQT; ++qt) acc[qt] = mfma_16x16x32<ET>(buf[j], bcur[qt], z);
             } else {
 #pragma unroll
-                for (int qt = 0; qt < NQT; ++qt) acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(buf[j], bcur[qt], acc[qt], 0, 0, 0);
+                for (int qt = 0; qt < NQT; ++qt) acc[qt] = mfma_16x16x32<ET>(buf[j], bcur[qt], acc[qt]);
             }
             // refill the slot just consumed (chunk c + 1, step j) RIGHT behind the MFMAs that read it: a rolling window of P loads.
             // UNCONDITIONAL (behind the last chunk `lp` names rows of the wave's first group again: P KiB read for nothing, once per
@@ -215,39 +215,42 @@ size_t narrow_lds_bytes(int nqt, int dim) {
     return (size_t)nqt * 16 * S + (size_t)nqt * 16 * 4 + (size_t)nqt * 16 * narrow_lds_cap(nqt) * 8;
 }
 
-template <int NQT, int P>
+template <int ET, int NQT, int P>
 static int launch_narrow_np(const NarrowArgs &a, int grid, hipStream_t s) {
-    const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&narrow_filter_kernel<NQT, P>), 160 * 1024);
+    const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&narrow_filter_kernel<ET, NQT, P>), 160 * 1024);
     if (rc != CCR_OK) return rc;
-    hipLaunchKernelGGL((narrow_filter_kernel<NQT, P>), dim3(grid), dim3(NARROW_THREADS), narrow_lds_bytes(NQT, a.dim), s, a);
+    hipLaunchKernelGGL((narrow_filter_kernel<ET, NQT, P>), dim3(grid), dim3(NARROW_THREADS), narrow_lds_bytes(NQT, a.dim), s, a);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
 
-template <int NQT>
+template <int ET, int NQT>
 static int launch_narrow_n(const NarrowArgs &a, int grid, hipStream_t s) {
     const int KS = a.dim / SUB_K;
     // two query groups: every corpus row is pulled by two CUs (one of them from the L2 / the Infinity Cache), i.e. a CU moves twice the
     // bytes of the one-group launch -- twice the window (24 KiB per wave in flight) keeps the pull rate per CU from binding
     if constexpr (NQT == 4) {
-        if (a.groups == 2 && KS % 24 == 0) return launch_narrow_np<NQT, 24>(a, grid, s);
+        if (a.groups == 2 && KS % 24 == 0) return launch_narrow_np<ET, NQT, 24>(a, grid, s);
     }
-    if (KS % 12 == 0) return launch_narrow_np<NQT, 12>(a, grid, s);
-    if (KS % 8 == 0) return launch_narrow_np<NQT, 8>(a, grid, s);
-    if (KS % 4 == 0) return launch_narrow_np<NQT, 4>(a, grid, s);
-    if (KS % 2 == 0) return launch_narrow_np<NQT, 2>(a, grid, s);
-    return launch_narrow_np<NQT, 1>(a, grid, s);
+    if (KS % 12 == 0) return launch_narrow_np<ET, NQT, 12>(a, grid, s);
+    if (KS % 8 == 0) return launch_narrow_np<ET, NQT, 8>(a, grid, s);
+    if (KS % 4 == 0) return launch_narrow_np<ET, NQT, 4>(a, grid, s);
+    if (KS % 2 == 0) return launch_narrow_np<ET, NQT, 2>(a, grid, s);
+    return launch_narrow_np<ET, NQT, 1>(a, grid, s);
 }
 
-int launch_narrow_filter(const NarrowArgs &a, int nqt, int grid, hipStream_t s) {
+int launch_narrow_filter(const NarrowArgs &a, int dt, int nqt, int grid, hipStream_t s) {
     CCR_REQUIRE(a.dim % SUB_K == 0 && a.n_q >= 1 && (nqt == 1 || nqt == 2 || nqt == 4 || nqt == 6) && (a.groups == 1 || a.groups == 2) &&
                     (a.groups == 1 ? a.n_q <= nqt * 16 : (nqt == 4 && a.n_q > NARROW_MAX_Q && a.n_q <= 2 * NARROW_MAX_Q && grid % 16 == 0)),
                 "narrow main pass: bad shape (internal)");
     CCR_REQUIRE(narrow_lds_bytes(nqt, a.dim) <= 160 * 1024, "narrow main pass: %zu bytes of LDS (internal)", narrow_lds_bytes(nqt, a.dim));
-    if (nqt == 1) return launch_narrow_n<1>(a, grid, s);
-    if (nqt == 2) return launch_narrow_n<2>(a, grid, s);
-    if (nqt == 6) return launch_narrow_n<6>(a, grid, s);
-    return launch_narrow_n<4>(a, grid, s);
+    return dispatch_half(dt, [&](auto et) {
+        constexpr int ET = decltype(et)::value;
+        if (nqt == 1) return launch_narrow_n<ET, 1>(a, grid, s);
+        if (nqt == 2) return launch_narrow_n<ET, 2>(a, grid, s);
+        if (nqt == 6) return launch_narrow_n<ET, 6>(a, grid, s);
+        return launch_narrow_n<ET, 4>(a, grid, s);
+    });
 }
 
 }  // namespace ccr

@@ -1,4 +1,4 @@
-// ccr_pack.hip -- fp32 -> bf16 pack of encoder outputs (+ L2 normalise, + fused masked mean pooling).
+// ccr_pack.hip -- fp32 -> bf16 / fp16 pack of encoder outputs (+ L2 normalise, + fused masked mean pooling).
 //
 // Pure HBM streaming kernels: 6 B per element (4 read + 2 written); the mean-pool variant reads
 // L * dim * sizeof(hidden) per row.  16 B per lane loads, 16 B per lane stores, one wave per row
@@ -9,25 +9,75 @@
 
 namespace ccr {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+// The packed element type E is __bf16 or _Float16 (elem_of<DT>).  Both conversions round to nearest even, as torch's .to() does; the
+// fp16 one keeps subnormals (hipcc leaves the fp16 denormal mode on) and turns a finite value of magnitude >= 65 520 into +-inf.
+template <class E>
+using vec4 = E __attribute__((ext_vector_type(4)));
+template <class E>
+using vec8 = E __attribute__((ext_vector_type(8)));
+typedef vec4<__bf16> bf16x4;
 typedef float f32x4n __attribute__((ext_vector_type(4)));
+template <int DT>
+using elem_of = typename std::conditional<DT == CCR_DTYPE_F16, _Float16, __bf16>::type;
 
-__device__ __forceinline__ bf16x4 cvt4(float4 v) {
-    bf16x4 r;
-    r[0] = (__bf16)v.x;
-    r[1] = (__bf16)v.y;
-    r[2] = (__bf16)v.z;
-    r[3] = (__bf16)v.w;
+template <class E>
+__device__ __forceinline__ vec4<E> cvt4(float4 v) {
+    vec4<E> r;
+    r[0] = (E)v.x;
+    r[1] = (E)v.y;
+    r[2] = (E)v.z;
+    r[3] = (E)v.w;
     return r;
+}
+
+// ---- the fp16 pack's overflow count: elements that are finite in fp32 and +-inf once packed (|x| >= 65 520: the tie 65 520 rounds to
+// the even neighbour 2^16).  A thread counts its own elements in a register; the workgroup adds them up in LDS and ONE thread sends
+// one atomic to the caller's counter, only where the workgroup saw any.  The bf16 instantiations contain none of this.
+template <class E>
+__device__ __forceinline__ int left_range(float x) {
+    if constexpr (std::is_same<E, _Float16>::value) {
+        const float a = fabsf(x);
+        return (a >= 65520.f && a < INFINITY) ? 1 : 0;
+    } else {
+        return 0;
+    }
+}
+template <class E>
+__device__ __forceinline__ int left_range4(float4 v) {
+    return left_range<E>(v.x) + left_range<E>(v.y) + left_range<E>(v.z) + left_range<E>(v.w);
+}
+// Upper bound of a packed row's norm from the fp32 row's norm v (a wave per row; mine: this lane's out-of-range elements of the row).
+// Rounding moves an element by at most 2^-8 (bf16) or 2^-11 (fp16) relative: 0.4 % covers both.  An fp16 element below the normal range
+// moves by up to 2^-25 absolute instead -- at most sqrt(dim) 2^-25 <= 1.9e-6 on the norm --, and a row with an element that left fp16's
+// range holds an inf: its bound is inf, as the bound of a row that was inf in fp32 already.
+template <class E>
+__device__ __forceinline__ float pack_row_bound(double v, int mine) {
+    if constexpr (std::is_same<E, _Float16>::value) {
+        if (__ballot(mine != 0) != 0ull) return INFINITY;
+        return (float)(v * 1.004 + 4e-6);
+    } else {
+        return (float)(v * 1.004);
+    }
+}
+// every thread of the workgroup calls this once, at the end of the kernel (overflow is a kernel argument: uniform)
+template <class E>
+__device__ __forceinline__ void flush_overflow(int mine, int32_t *overflow) {
+    if constexpr (std::is_same<E, _Float16>::value) {
+        if (!overflow) return;
+        __shared__ int s_overflow;
+        if (threadIdx.x == 0) s_overflow = 0;
+        __syncthreads();
+        if (mine) atomicAdd(&s_overflow, mine);   // (LDS; nothing is issued by a thread that saw none)
+        __syncthreads();
+        if (threadIdx.x == 0 && s_overflow) atomicAdd(overflow, s_overflow);
+    }
 }
 
 // ---------------------------------------------------------------- plain elementwise pack
 // n8 = number of 8-element groups; tail handled by the scalar kernel below.
-template <int UNROLL>
-__global__ __launch_bounds__(256) void pack_bf16_kernel(const float4 *__restrict__ src, bf16x8 *__restrict__ dst,
-                                                       int64_t n8) {
+template <class E, int UNROLL>
+__global__ __launch_bounds__(256) void pack_kernel(const float4 *__restrict__ src, vec8<E> *__restrict__ dst, int64_t n8,
+                                                  int32_t *__restrict__ overflow) {
     // one block = UNROLL x 256 output vectors: the 2 * UNROLL loads of a thread are issued before the first conversion,
     // consecutive lanes touch consecutive 32-byte segments
     const int64_t base = (int64_t)blockIdx.x * (256 * UNROLL) + threadIdx.x;
@@ -39,18 +89,29 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const float4 *__restrict
         a[u] = src[2 * ic];
         b[u] = src[2 * ic + 1];
     }
+    int nover = 0;
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
         const int64_t i = base + u * 256;
-        const bf16x4 lo = cvt4(a[u]), hi = cvt4(b[u]);
-        if (i < n8) dst[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        const vec4<E> lo = cvt4<E>(a[u]), hi = cvt4<E>(b[u]);
+        if (i < n8) {
+            dst[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            nover += left_range4<E>(a[u]) + left_range4<E>(b[u]);
+        }
     }
+    flush_overflow<E>(nover, overflow);
 }
 
-__global__ void pack_bf16_tail_kernel(const float *__restrict__ src, __bf16 *__restrict__ dst, int64_t begin,
-                                      int64_t n) {
+template <class E>
+__global__ void pack_tail_kernel(const float *__restrict__ src, E *__restrict__ dst, int64_t begin, int64_t n,
+                                 int32_t *__restrict__ overflow) {
     int64_t i = begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (__bf16)src[i];
+    int nover = 0;
+    if (i < n) {
+        dst[i] = (E)src[i];
+        nover = left_range<E>(src[i]);
+    }
+    flush_overflow<E>(nover, overflow);
 }
 
 
@@ -59,13 +120,15 @@ __global__ void pack_bf16_tail_kernel(const float *__restrict__ src, __bf16 *__r
 // squares of the bf16-ROUNDED values, wave reduce, one 4-byte store per row: bounds[r] >= ||packed row r|| (inflated by 2^-11
 // for the fp32 summation; a NaN / Inf row gives a NaN / Inf bound).  The index reduces the bounds to one per 256-row tile;
 // they are used only inside the filter's error margins.
-template <int ROWS>
-__global__ __launch_bounds__(256) void pack_rows_bound_kernel(const float *__restrict__ src, __bf16 *__restrict__ dst,
-                                                             int64_t rows, int dim, float *__restrict__ bounds) {
+template <class E, int ROWS>
+__global__ __launch_bounds__(256) void pack_rows_bound_kernel(const float *__restrict__ src, E *__restrict__ dst,
+                                                             int64_t rows, int dim, float *__restrict__ bounds,
+                                                             int32_t *__restrict__ overflow) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const int n8 = dim >> 3;
+    int nover = 0;
     // ROWS rows per iteration: 2*ROWS 16-byte loads in flight per lane (pure HBM stream, read once -> nontemporal)
     for (int64_t r = ROWS * wave; r < rows; r += ROWS * nwaves) {
         float ss[ROWS];
@@ -82,10 +145,14 @@ __global__ __launch_bounds__(256) void pack_rows_bound_kernel(const float *__res
             }
 #pragma unroll
             for (int j = 0; j < ROWS; ++j) {
-                const bf16x4 lo = cvt4(make_float4(a[j][0], a[j][1], a[j][2], a[j][3]));
-                const bf16x4 hi = cvt4(make_float4(b[j][0], b[j][1], b[j][2], b[j][3]));
-                const bf16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                if (r + j < rows) __builtin_nontemporal_store(v, reinterpret_cast<bf16x8 *>(dst + (r + j) * dim) + c);
+                const float4 af = make_float4(a[j][0], a[j][1], a[j][2], a[j][3]), bf = make_float4(b[j][0], b[j][1], b[j][2], b[j][3]);
+                const vec4<E> lo = cvt4<E>(af);
+                const vec4<E> hi = cvt4<E>(bf);
+                const vec8<E> v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                if (r + j < rows) {
+                    __builtin_nontemporal_store(v, reinterpret_cast<vec8<E> *>(dst + (r + j) * dim) + c);
+                    nover += left_range4<E>(af) + left_range4<E>(bf);
+                }
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float f = (float)v[e];
@@ -101,6 +168,7 @@ __global__ __launch_bounds__(256) void pack_rows_bound_kernel(const float *__res
             if (lane == 0 && r + j < rows) bounds[r + j] = sqrtf(t) * 1.00048828125f;
         }
     }
+    flush_overflow<E>(nover, overflow);
 }
 
 // ---------------------------------------------------------------- row-wise: norms / normalise + pack
@@ -122,20 +190,23 @@ __device__ __forceinline__ double wave_sumsq(const float *__restrict__ x, int di
     return p;
 }
 
-__global__ __launch_bounds__(256) void pack_rows_kernel(const float *__restrict__ src, __bf16 *__restrict__ dst,
+template <class E>
+__global__ __launch_bounds__(256) void pack_rows_kernel(const float *__restrict__ src, E *__restrict__ dst,
                                                        float *__restrict__ norms, int64_t rows, int dim,
-                                                       int normalize, float *__restrict__ bounds) {
+                                                       int normalize, float *__restrict__ bounds, int32_t *__restrict__ overflow) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const int nchunk = dim >> 2;
+    int nover = 0;
     for (int64_t r = wave; r < rows; r += nwaves) {
         const float *x = src + r * dim;
         const double ss = wave_sumsq(x, dim, lane);
         const double nrm = sqrt(ss);
         if (norms && lane == 0) norms[r] = (float)nrm;
         const double den = nrm > 1e-12 ? nrm : 1e-12;
-        bf16x4 *y = reinterpret_cast<bf16x4 *>(dst + r * dim);
+        vec4<E> *y = reinterpret_cast<vec4<E> *>(dst + r * dim);
+        int rover = 0;
         for (int c = lane; c < nchunk; c += 64) {
             float4 v = reinterpret_cast<const float4 *>(x)[c];
             if (normalize) {
@@ -144,26 +215,32 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float *__restrict_
                 v.z = (float)((double)v.z / den);
                 v.w = (float)((double)v.w / den);
             }
-            y[c] = cvt4(v);
+            y[c] = cvt4<E>(v);
+            rover += left_range4<E>(v);
         }
-        // upper bound of the packed row's norm: bf16 rounding moves each element by at most 2^-8 relative.  One plain store
+        // upper bound of the packed row's norm (pack_row_bound).  One plain store
         // per row (round 2 first did an atomicMax per row on ONE word: 2.7 M atomics on a single address took 30 ms at the NQ
         // shape -- the whole normalising pack ran at 0.4 TB/s)
-        if (bounds && lane == 0) bounds[r] = (float)((normalize ? nrm / den : nrm) * 1.004);
+        const float bound = pack_row_bound<E>(normalize ? nrm / den : nrm, rover);   // (all lanes: a ballot inside)
+        if (bounds && lane == 0) bounds[r] = bound;
+        nover += rover;
     }
+    flush_overflow<E>(nover, overflow);
 }
 
 // ---------------------------------------------------------------- rows of ANY width -> zero-padded rows of a multiple of 8
 // One wave per row, element-wise loads (source rows of an odd width are not 16-byte aligned).  The sum of squares keeps the
 // canonical order of wave_sumsq: element i belongs to "chunk" i / 4, lane (i / 4) % 64, accumulated in increasing index, then
 // the butterfly -- for dim % 4 == 0 the same bits as pack_rows_kernel, and appending zeros to a row changes nothing (p + 0.0 = p).
-__global__ __launch_bounds__(256) void pack_rows_padded_kernel(const float *__restrict__ src, int src_dim, __bf16 *__restrict__ dst,
+template <class E>
+__global__ __launch_bounds__(256) void pack_rows_padded_kernel(const float *__restrict__ src, int src_dim, E *__restrict__ dst,
                                                               int dst_dim, float *__restrict__ norms, int64_t rows, int normalize,
-                                                              float *__restrict__ bounds) {
+                                                              float *__restrict__ bounds, int32_t *__restrict__ overflow) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const int nchunk = (dst_dim + 3) >> 2;
+    int nover = 0;
     for (int64_t r = wave; r < rows; r += nwaves) {
         const float *x = src + r * src_dim;
         double p = 0.0;
@@ -180,7 +257,8 @@ __global__ __launch_bounds__(256) void pack_rows_padded_kernel(const float *__re
         const double nrm = sqrt(p);
         if (norms && lane == 0) norms[r] = (float)nrm;
         const double den = nrm > 1e-12 ? nrm : 1e-12;
-        __bf16 *y = dst + r * dst_dim;
+        E *y = dst + r * dst_dim;
+        int rover = 0;
         for (int c = lane; c < nchunk; c += 64) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -188,11 +266,15 @@ __global__ __launch_bounds__(256) void pack_rows_padded_kernel(const float *__re
                 if (i >= dst_dim) break;
                 float v = i < src_dim ? x[i] : 0.f;
                 if (normalize && i < src_dim) v = (float)((double)v / den);
-                y[i] = (__bf16)v;
+                y[i] = (E)v;
+                rover += left_range<E>(v);
             }
         }
-        if (bounds && lane == 0) bounds[r] = (float)((normalize ? nrm / den : nrm) * 1.004);
+        const float bound = pack_row_bound<E>(normalize ? nrm / den : nrm, rover);
+        if (bounds && lane == 0) bounds[r] = bound;
+        nover += rover;
     }
+    flush_overflow<E>(nover, overflow);
 }
 
 // ---------------------------------------------------------------- fused masked mean pooling + pack
@@ -218,15 +300,15 @@ __device__ __forceinline__ float4 load4<__bf16>(const __bf16 *p) {
     return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 
-template <typename T>
+template <typename T, class E>
 __global__ __launch_bounds__(256) void meanpool_pack_kernel(const T *__restrict__ hidden,
                                                            const int64_t *__restrict__ mask,
-                                                           __bf16 *__restrict__ dst_bf16,
+                                                           E *__restrict__ dst_bf16,
                                                            float *__restrict__ dst_f32, int L, int dim,
                                                            int normalize, const int64_t *__restrict__ dst_rows,
                                                            float *__restrict__ bounds,
                                                            const int32_t *__restrict__ seq_start,
-                                                           const int32_t *__restrict__ seq_len) {
+                                                           const int32_t *__restrict__ seq_len, int32_t *__restrict__ overflow) {
     __shared__ double red[4];
     __shared__ float redf[4];
     const int b = blockIdx.x;
@@ -290,6 +372,7 @@ __global__ __launch_bounds__(256) void meanpool_pack_kernel(const T *__restrict_
         den = nrm > 1e-12 ? nrm : 1e-12;
     }
     nown = 0;
+    int nover = 0;
     float pss = 0.f;   // squared norm of the PACKED row (what the index's filter margin needs a bound of)
     for (int c = tid; c < nchunk && nown < 4; c += blockDim.x, ++nown) {
         float4 a = acc[nown];
@@ -301,8 +384,9 @@ __global__ __launch_bounds__(256) void meanpool_pack_kernel(const T *__restrict_
                 a.z = (float)((double)a.z / den);
                 a.w = (float)((double)a.w / den);
             }
-            const bf16x4 v = cvt4(a);
-            reinterpret_cast<bf16x4 *>(dst_bf16 + ob * dim)[c] = v;
+            const vec4<E> v = cvt4<E>(a);
+            reinterpret_cast<vec4<E> *>(dst_bf16 + ob * dim)[c] = v;
+            nover += left_range4<E>(a);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float f = (float)v[e];
@@ -321,6 +405,7 @@ __global__ __launch_bounds__(256) void meanpool_pack_kernel(const T *__restrict_
             bounds[ob] = sqrtf(tot) * 1.0001f;   // norm bound of the packed row, at its destination row
         }
     }
+    flush_overflow<E>(nover, overflow);
 }
 
 // Backward of the masked mean pooling: d hidden[b][l][:] = mask[b][l] ? grad[b][:] / count_b : 0 (item_tower.py:141-146 under
@@ -339,7 +424,7 @@ __device__ __forceinline__ void store4<_Float16>(_Float16 *p, float4 v) {
 }
 template <>
 __device__ __forceinline__ void store4<__bf16>(__bf16 *p, float4 v) {
-    *reinterpret_cast<bf16x4 *>(p) = cvt4(v);
+    *reinterpret_cast<bf16x4 *>(p) = cvt4<__bf16>(v);
 }
 
 template <typename T>
@@ -447,17 +532,20 @@ extern "C" int ccr_meanpool_bwd(const float *grad, const int64_t *mask, void *dh
     return CCR_OK;
 }
 
-extern "C" int ccr_pack_bf16_ex(const float *src, uint16_t *dst, float *norms, float *row_norm_bounds, int64_t rows, int dim,
-                                int normalize, void *stream) {
-    CCR_REQUIRE(src && dst, "ccr_pack_bf16: null pointer");
-    CCR_REQUIRE(rows >= 0 && dim > 0, "ccr_pack_bf16: bad shape rows=%lld dim=%d", (long long)rows, dim);
+// ---- the pack entry points on the packed element type E; `who` names the caller in error messages
+template <class E>
+static int pack_ex(const char *who, const float *src, uint16_t *dst, float *norms, float *row_norm_bounds, int64_t rows, int dim, int normalize,
+                   int32_t *overflow, void *stream) {
+    CCR_REQUIRE(src && dst, "%s: null pointer", who);
+    CCR_REQUIRE(rows >= 0 && dim > 0, "%s: bad shape rows=%lld dim=%d", who, (long long)rows, dim);
     if (rows == 0) return CCR_OK;
     hipStream_t s = (hipStream_t)stream;
     float *bounds = row_norm_bounds;
+    E *dp = reinterpret_cast<E *>(dst);
     if (!normalize && !norms) {
-        CCR_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0), "ccr_pack_bf16: buffers must be 16-byte aligned");
+        CCR_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0), "%s: buffers must be 16-byte aligned", who);
         if (bounds) {
-            CCR_REQUIRE(dim % 8 == 0, "ccr_pack_bf16: row_norm_bounds needs dim %% 8 == 0 (dim=%d)", dim);
+            CCR_REQUIRE(dim % 8 == 0, "%s: row_norm_bounds needs dim %% 8 == 0 (dim=%d)", who, dim);
             static int rows_per = -1;
             if (rows_per < 0) {
                 const char *e = getenv("CCR_PACK_ROWS");
@@ -465,13 +553,12 @@ extern "C" int ccr_pack_bf16_ex(const float *src, uint16_t *dst, float *norms, f
             }
             int64_t blocks = (rows + 4 * rows_per - 1) / (4 * rows_per);
             if (blocks > 131072) blocks = 131072;   // measured best at the NQ shape: 16 K - 128 K blocks, one row per wave and trip
-            __bf16 *dp = reinterpret_cast<__bf16 *>(dst);
             if (rows_per == 1)
-                hipLaunchKernelGGL(pack_rows_bound_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, src, dp, rows, dim, bounds);
+                hipLaunchKernelGGL((pack_rows_bound_kernel<E, 1>), dim3((unsigned)blocks), dim3(256), 0, s, src, dp, rows, dim, bounds, overflow);
             else if (rows_per == 2)
-                hipLaunchKernelGGL(pack_rows_bound_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, src, dp, rows, dim, bounds);
+                hipLaunchKernelGGL((pack_rows_bound_kernel<E, 2>), dim3((unsigned)blocks), dim3(256), 0, s, src, dp, rows, dim, bounds, overflow);
             else
-                hipLaunchKernelGGL(pack_rows_bound_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, src, dp, rows, dim, bounds);
+                hipLaunchKernelGGL((pack_rows_bound_kernel<E, 4>), dim3((unsigned)blocks), dim3(256), 0, s, src, dp, rows, dim, bounds, overflow);
             CCR_LAUNCH_CHECK();
             return CCR_OK;
         }
@@ -481,40 +568,126 @@ extern "C" int ccr_pack_bf16_ex(const float *src, uint16_t *dst, float *norms, f
             // one output vector per thread, no loop: many short-lived blocks stream faster than a capped grid-stride loop
             // (measured at the NQ shape: 6.0 TB/s vs 5.5 with 8 vectors per thread and 4.7 with a 4 096-block grid-stride)
             const int64_t blocks = (n8 + 255) / 256;
-            hipLaunchKernelGGL(pack_bf16_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const float4 *>(src),
-                               reinterpret_cast<bf16x8 *>(dst), n8);
+            hipLaunchKernelGGL((pack_kernel<E, 1>), dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const float4 *>(src),
+                               reinterpret_cast<vec8<E> *>(dst), n8, overflow);
             CCR_LAUNCH_CHECK();
         }
         if (n8 * 8 < n) {
-            hipLaunchKernelGGL(pack_bf16_tail_kernel, dim3(1), dim3(64), 0, s, src, reinterpret_cast<__bf16 *>(dst),
-                               n8 * 8, n);
+            hipLaunchKernelGGL(pack_tail_kernel<E>, dim3(1), dim3(64), 0, s, src, dp, n8 * 8, n, overflow);
             CCR_LAUNCH_CHECK();
         }
         return CCR_OK;
     }
-    CCR_REQUIRE(dim % 4 == 0, "ccr_pack_bf16: dim %% 4 != 0 (dim=%d) with normalize/norms", dim);
-    CCR_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 8 == 0), "ccr_pack_bf16: buffers must be 16-byte aligned");
+    CCR_REQUIRE(dim % 4 == 0, "%s: dim %% 4 != 0 (dim=%d) with normalize/norms", who, dim);
+    CCR_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 8 == 0), "%s: buffers must be 16-byte aligned", who);
     int64_t blocks = (rows + 3) / 4;
     if (blocks > 65536) blocks = 65536;   // short-lived waves (a few rows each) stream faster than a 2 048-block grid-stride loop
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, reinterpret_cast<__bf16 *>(dst),
-                       norms, rows, dim, normalize, bounds);
+    hipLaunchKernelGGL(pack_rows_kernel<E>, dim3((unsigned)blocks), dim3(256), 0, s, src, dp, norms, rows, dim, normalize, bounds, overflow);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
 }
 
-extern "C" int ccr_pack_bf16_padded(const float *src, int64_t rows, int src_dim, uint16_t *dst, int dst_dim, float *norms,
-                                    float *row_norm_bounds, int normalize, void *stream) {
-    CCR_REQUIRE(src && dst, "ccr_pack_bf16_padded: null pointer");
+template <class E>
+static int pack_padded(const char *who, const float *src, int64_t rows, int src_dim, uint16_t *dst, int dst_dim, float *norms,
+                       float *row_norm_bounds, int normalize, int32_t *overflow, void *stream) {
+    CCR_REQUIRE(src && dst, "%s: null pointer", who);
     CCR_REQUIRE(rows >= 0 && src_dim > 0 && dst_dim >= src_dim && dst_dim % 8 == 0 && dst_dim - src_dim < 8,
-                "ccr_pack_bf16_padded: bad shape rows=%lld src_dim=%d dst_dim=%d (dst_dim = src_dim rounded up to a multiple of 8)",
-                (long long)rows, src_dim, dst_dim);
+                "%s: bad shape rows=%lld src_dim=%d dst_dim=%d (dst_dim = src_dim rounded up to a multiple of 8)", who, (long long)rows, src_dim,
+                dst_dim);
     if (rows == 0) return CCR_OK;
     int64_t blocks = (rows + 3) / 4;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(pack_rows_padded_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, src_dim,
-                       reinterpret_cast<__bf16 *>(dst), dst_dim, norms, rows, normalize, row_norm_bounds);
+    hipLaunchKernelGGL(pack_rows_padded_kernel<E>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, src_dim,
+                       reinterpret_cast<E *>(dst), dst_dim, norms, rows, normalize, row_norm_bounds, overflow);
     CCR_LAUNCH_CHECK();
     return CCR_OK;
+}
+
+// the mean-pool pack of either form (seq_start == null: the padded form with its mask) on hidden type T and packed type E
+template <class E>
+static int meanpool_pack(const char *who, const void *hidden, int hidden_dtype, const int64_t *mask, const int32_t *seq_start,
+                         const int32_t *seq_len, uint16_t *dst_half, float *dst_f32, const int64_t *dst_rows, float *row_norm_bounds, int B,
+                         int L, int dim, int normalize, int32_t *overflow, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int threads = ((dim / 4 + 63) / 64) * 64;
+    if (threads > 256) threads = 256;
+    E *db = reinterpret_cast<E *>(dst_half);
+    switch (hidden_dtype) {
+        case CCR_DTYPE_F32:
+            hipLaunchKernelGGL((meanpool_pack_kernel<float, E>), dim3(B), dim3(threads), 0, s, (const float *)hidden, mask, db, dst_f32, L, dim,
+                               normalize, dst_rows, row_norm_bounds, seq_start, seq_len, overflow);
+            break;
+        case CCR_DTYPE_F16:
+            hipLaunchKernelGGL((meanpool_pack_kernel<_Float16, E>), dim3(B), dim3(threads), 0, s, (const _Float16 *)hidden, mask, db, dst_f32, L,
+                               dim, normalize, dst_rows, row_norm_bounds, seq_start, seq_len, overflow);
+            break;
+        case CCR_DTYPE_BF16:
+            hipLaunchKernelGGL((meanpool_pack_kernel<__bf16, E>), dim3(B), dim3(threads), 0, s, (const __bf16 *)hidden, mask, db, dst_f32, L, dim,
+                               normalize, dst_rows, row_norm_bounds, seq_start, seq_len, overflow);
+            break;
+        default:
+            set_error("%s: unknown hidden_dtype %d", who, hidden_dtype);
+            return CCR_ERR_INVALID;
+    }
+    CCR_LAUNCH_CHECK();
+    return CCR_OK;
+}
+
+extern "C" int ccr_pack_half_ex(const float *src, uint16_t *dst, float *norms, float *row_norm_bounds, int64_t rows, int dim,
+                                int normalize, int half_dtype, int32_t *overflow, void *stream) {
+    if (const int rc = check_half("ccr_pack_half", half_dtype)) return rc;
+    return dispatch_half(half_dtype, [&](auto dt) {
+        return pack_ex<elem_of<decltype(dt)::value>>("ccr_pack_half", src, dst, norms, row_norm_bounds, rows, dim, normalize, overflow, stream);
+    });
+}
+
+extern "C" int ccr_pack_half_padded(const float *src, int64_t rows, int src_dim, uint16_t *dst, int dst_dim, float *norms,
+                                    float *row_norm_bounds, int normalize, int half_dtype, int32_t *overflow, void *stream) {
+    if (const int rc = check_half("ccr_pack_half_padded", half_dtype)) return rc;
+    return dispatch_half(half_dtype, [&](auto dt) {
+        return pack_padded<elem_of<decltype(dt)::value>>("ccr_pack_half_padded", src, rows, src_dim, dst, dst_dim, norms, row_norm_bounds,
+                                                         normalize, overflow, stream);
+    });
+}
+
+extern "C" int ccr_meanpool_pack_half_ex(const void *hidden, int hidden_dtype, const int64_t *mask, uint16_t *dst_half, float *dst_f32,
+                                         const int64_t *dst_rows, float *row_norm_bounds, int B, int L, int dim, int normalize,
+                                         int half_dtype, int32_t *overflow, void *stream) {
+    if (const int rc = check_half("ccr_meanpool_pack_half", half_dtype)) return rc;
+    CCR_REQUIRE(hidden && mask && (dst_half || dst_f32), "ccr_meanpool_pack_half: null pointer");
+    CCR_REQUIRE(B >= 0 && L > 0 && dim > 0 && dim % 4 == 0 && dim <= 4096,
+                "ccr_meanpool_pack_half: bad shape B=%d L=%d dim=%d (dim %% 4 == 0, dim <= 4096)", B, L, dim);
+    if (B == 0) return CCR_OK;
+    return dispatch_half(half_dtype, [&](auto dt) {
+        return meanpool_pack<elem_of<decltype(dt)::value>>("ccr_meanpool_pack_half", hidden, hidden_dtype, mask, nullptr, nullptr, dst_half, dst_f32,
+                                                           dst_rows, row_norm_bounds, B, L, dim, normalize, overflow, stream);
+    });
+}
+
+extern "C" int ccr_meanpool_pack_half_packed(const void *hidden, int hidden_dtype, const int32_t *seq_start, const int32_t *seq_len,
+                                             uint16_t *dst_half, float *dst_f32, const int64_t *dst_rows, float *row_norm_bounds, int n_seq,
+                                             int dim, int normalize, int half_dtype, int32_t *overflow, void *stream) {
+    if (const int rc = check_half("ccr_meanpool_pack_half_packed", half_dtype)) return rc;
+    CCR_REQUIRE(hidden && seq_start && seq_len && (dst_half || dst_f32), "ccr_meanpool_pack_half_packed: null pointer");
+    CCR_REQUIRE(n_seq >= 0 && dim > 0 && dim % 4 == 0 && dim <= 4096,
+                "ccr_meanpool_pack_half_packed: bad shape n_seq=%d dim=%d (dim %% 4 == 0, dim <= 4096)", n_seq, dim);
+    if (n_seq == 0) return CCR_OK;
+    return dispatch_half(half_dtype, [&](auto dt) {
+        return meanpool_pack<elem_of<decltype(dt)::value>>("ccr_meanpool_pack_half_packed", hidden, hidden_dtype, nullptr, seq_start, seq_len,
+                                                           dst_half, dst_f32, dst_rows, row_norm_bounds, n_seq, 0, dim, normalize, overflow,
+                                                           stream);
+    });
+}
+
+// ---- the bf16 names: the same entry points with half_dtype = CCR_DTYPE_BF16 and no overflow counter
+extern "C" int ccr_pack_bf16_ex(const float *src, uint16_t *dst, float *norms, float *row_norm_bounds, int64_t rows, int dim,
+                                int normalize, void *stream) {
+    return ccr_pack_half_ex(src, dst, norms, row_norm_bounds, rows, dim, normalize, CCR_DTYPE_BF16, nullptr, stream);
+}
+
+extern "C" int ccr_pack_bf16_padded(const float *src, int64_t rows, int src_dim, uint16_t *dst, int dst_dim, float *norms,
+                                    float *row_norm_bounds, int normalize, void *stream) {
+    return ccr_pack_half_padded(src, rows, src_dim, dst, dst_dim, norms, row_norm_bounds, normalize, CCR_DTYPE_BF16, nullptr, stream);
 }
 
 extern "C" int ccr_pack_bf16(const float *src, uint16_t *dst, float *norms, int64_t rows, int dim, int normalize,
@@ -525,66 +698,15 @@ extern "C" int ccr_pack_bf16(const float *src, uint16_t *dst, float *norms, int6
 extern "C" int ccr_meanpool_pack_bf16_ex(const void *hidden, int hidden_dtype, const int64_t *mask, uint16_t *dst_bf16,
                                          float *dst_f32, const int64_t *dst_rows, float *row_norm_bounds, int B, int L, int dim,
                                          int normalize, void *stream) {
-    CCR_REQUIRE(hidden && mask && (dst_bf16 || dst_f32), "ccr_meanpool_pack_bf16: null pointer");
-    CCR_REQUIRE(B >= 0 && L > 0 && dim > 0 && dim % 4 == 0 && dim <= 4096,
-                "ccr_meanpool_pack_bf16: bad shape B=%d L=%d dim=%d (dim %% 4 == 0, dim <= 4096)", B, L, dim);
-    if (B == 0) return CCR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    int threads = ((dim / 4 + 63) / 64) * 64;
-    if (threads > 256) threads = 256;
-    __bf16 *db = reinterpret_cast<__bf16 *>(dst_bf16);
-    float *mb = row_norm_bounds;
-    switch (hidden_dtype) {
-        case CCR_DTYPE_F32:
-            hipLaunchKernelGGL(meanpool_pack_kernel<float>, dim3(B), dim3(threads), 0, s, (const float *)hidden, mask, db,
-                               dst_f32, L, dim, normalize, dst_rows, mb, (const int32_t *)nullptr, (const int32_t *)nullptr);
-            break;
-        case CCR_DTYPE_F16:
-            hipLaunchKernelGGL(meanpool_pack_kernel<_Float16>, dim3(B), dim3(threads), 0, s, (const _Float16 *)hidden,
-                               mask, db, dst_f32, L, dim, normalize, dst_rows, mb, (const int32_t *)nullptr, (const int32_t *)nullptr);
-            break;
-        case CCR_DTYPE_BF16:
-            hipLaunchKernelGGL(meanpool_pack_kernel<__bf16>, dim3(B), dim3(threads), 0, s, (const __bf16 *)hidden, mask,
-                               db, dst_f32, L, dim, normalize, dst_rows, mb, (const int32_t *)nullptr, (const int32_t *)nullptr);
-            break;
-        default:
-            set_error("ccr_meanpool_pack_bf16: unknown hidden_dtype %d", hidden_dtype);
-            return CCR_ERR_INVALID;
-    }
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return ccr_meanpool_pack_half_ex(hidden, hidden_dtype, mask, dst_bf16, dst_f32, dst_rows, row_norm_bounds, B, L, dim, normalize,
+                                     CCR_DTYPE_BF16, nullptr, stream);
 }
 
 extern "C" int ccr_meanpool_pack_bf16_packed(const void *hidden, int hidden_dtype, const int32_t *seq_start, const int32_t *seq_len,
                                              uint16_t *dst_bf16, float *dst_f32, const int64_t *dst_rows, float *row_norm_bounds,
                                              int n_seq, int dim, int normalize, void *stream) {
-    CCR_REQUIRE(hidden && seq_start && seq_len && (dst_bf16 || dst_f32), "ccr_meanpool_pack_bf16_packed: null pointer");
-    CCR_REQUIRE(n_seq >= 0 && dim > 0 && dim % 4 == 0 && dim <= 4096,
-                "ccr_meanpool_pack_bf16_packed: bad shape n_seq=%d dim=%d (dim %% 4 == 0, dim <= 4096)", n_seq, dim);
-    if (n_seq == 0) return CCR_OK;
-    hipStream_t s = (hipStream_t)stream;
-    int threads = ((dim / 4 + 63) / 64) * 64;
-    if (threads > 256) threads = 256;
-    __bf16 *db = reinterpret_cast<__bf16 *>(dst_bf16);
-    switch (hidden_dtype) {
-        case CCR_DTYPE_F32:
-            hipLaunchKernelGGL(meanpool_pack_kernel<float>, dim3(n_seq), dim3(threads), 0, s, (const float *)hidden, nullptr, db,
-                               dst_f32, 0, dim, normalize, dst_rows, row_norm_bounds, seq_start, seq_len);
-            break;
-        case CCR_DTYPE_F16:
-            hipLaunchKernelGGL(meanpool_pack_kernel<_Float16>, dim3(n_seq), dim3(threads), 0, s, (const _Float16 *)hidden, nullptr,
-                               db, dst_f32, 0, dim, normalize, dst_rows, row_norm_bounds, seq_start, seq_len);
-            break;
-        case CCR_DTYPE_BF16:
-            hipLaunchKernelGGL(meanpool_pack_kernel<__bf16>, dim3(n_seq), dim3(threads), 0, s, (const __bf16 *)hidden, nullptr, db,
-                               dst_f32, 0, dim, normalize, dst_rows, row_norm_bounds, seq_start, seq_len);
-            break;
-        default:
-            set_error("ccr_meanpool_pack_bf16_packed: unknown hidden_dtype %d", hidden_dtype);
-            return CCR_ERR_INVALID;
-    }
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return ccr_meanpool_pack_half_packed(hidden, hidden_dtype, seq_start, seq_len, dst_bf16, dst_f32, dst_rows, row_norm_bounds, n_seq, dim,
+                                         normalize, CCR_DTYPE_BF16, nullptr, stream);
 }
 
 extern "C" int ccr_meanpool_pack_bf16(const void *hidden, int hidden_dtype, const int64_t *mask, uint16_t *dst_bf16,

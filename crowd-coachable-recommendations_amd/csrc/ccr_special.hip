@@ -115,6 +115,7 @@ __global__ __launch_bounds__(256) void apply_block_kernel(const float *__restric
 }
 
 // Lp[e] = canonical score of (query of entry e, column idx[e]) for every prior entry inside the shard (0 outside).
+template <int DT>
 __global__ __launch_bounds__(256) void prior_rescore_kernel(const int64_t *__restrict__ ptr, int n_q, const int64_t *__restrict__ idx,
                                                            int64_t nnz, const uint16_t *__restrict__ Q,
                                                            const uint16_t *__restrict__ D, int dim, int64_t id_lo,
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(256) void prior_rescore_kernel(const int64_t *__res
             hi = mid - 1;
     }
     const int64_t j = idx[e] - id_lo;
-    Lp[e] = (j >= 0 && j < n_rows) ? canonical_dot(Q + (int64_t)lo * dim, D + j * dim, dim) : 0.f;
+    Lp[e] = (j >= 0 && j < n_rows) ? canonical_dot<DT>(Q + (int64_t)lo * dim, D + j * dim, dim) : 0.f;
 }
 
 // Merge of (A) a canonical list of the low-rank score with the prior columns removed and (B) the prior columns with
@@ -278,7 +279,8 @@ __global__ __launch_bounds__(256) void apply_prior_kernel(const float *__restric
 
 // out[c] = sum over rows of X[r][c] in fp64.  One workgroup per 64 columns (8 chunks of 16 bytes = one 128-byte line of
 // each row): 32 row lanes x 8 chunk lanes; the row lanes are combined in a fixed order (deterministic).
-__global__ __launch_bounds__(256) void colsum_bf16_kernel(const uint16_t *__restrict__ X, int64_t rows, int dim,
+template <int DT>
+__global__ __launch_bounds__(256) void colsum_kernel(const uint16_t *__restrict__ X, int64_t rows, int dim,
                                                          double *__restrict__ out) {
     __shared__ double s_part[32][8][8];
     const int tid = threadIdx.x;
@@ -291,8 +293,8 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const uint16_t *__rest
             const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                acc[2 * e] += (double)__uint_as_float(w[e] << 16);
-                acc[2 * e + 1] += (double)__uint_as_float(w[e] & 0xffff0000u);
+                acc[2 * e] += (double)elem_lo<DT>(w[e]);
+                acc[2 * e + 1] += (double)elem_hi<DT>(w[e]);
             }
         }
     }
@@ -410,7 +412,7 @@ extern "C" int ccr_search_blocked(ccr_index *ix, const uint16_t *Q_bf16, int n_q
         CCR_HIP_CHECK(hipMemcpyAsync(d_ql, sp.long_list.data(), (size_t)n_long * 4, hipMemcpyHostToDevice, s));
         for (int lo = 0; lo < n_long; lo += FALLBACK_ROWS) {
             const int mq = std::min(FALLBACK_ROWS, n_long - lo);
-            rc = launch_dense_scores(ix->D, ix->n_rows, ix->dim, Q_bf16, d_ql + lo, 0, mq, nullptr, scratch, s);
+            rc = launch_dense_scores(ix->D, ix->dtype, ix->n_rows, ix->dim, Q_bf16, d_ql + lo, 0, mq, nullptr, scratch, s);
             if (rc != CCR_OK) return rc;
             hipLaunchKernelGGL(mask_rows_kernel, dim3(mq), dim3(256), 0, s, scratch, ix->n_rows, d_ql + lo, d_ptr, block_idx, id_lo,
                                -1e6f);
@@ -454,9 +456,13 @@ extern "C" int ccr_search_sparse_prior(ccr_index *ix, const uint16_t *Q_bf16, in
     CCR_HIP_CHECK(hipMemcpyAsync(d_ptr, prior_ptr_host, (size_t)(n_q + 1) * 8, hipMemcpyHostToDevice, s));
     const int64_t id_lo = ix->offset, id_hi = ix->offset + ix->n_rows;
     if (nnz > 0) {
-        hipLaunchKernelGGL(prior_rescore_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, d_ptr, n_q, prior_idx, nnz,
-                           Q_bf16, ix->D, ix->dim, id_lo, ix->n_rows, Lp);
-        CCR_LAUNCH_CHECK();
+        rc = dispatch_half(ix->dtype, [&](auto dt) {
+            hipLaunchKernelGGL(prior_rescore_kernel<decltype(dt)::value>, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, d_ptr, n_q,
+                               prior_idx, nnz, Q_bf16, ix->D, ix->dim, id_lo, ix->n_rows, Lp);
+            CCR_LAUNCH_CHECK();
+            return CCR_OK;
+        });
+        if (rc != CCR_OK) return rc;
     }
     int mp2_max = 1;
     while (mp2_max < sp.max_len) mp2_max <<= 1;
@@ -488,7 +494,7 @@ extern "C" int ccr_search_sparse_prior(ccr_index *ix, const uint16_t *Q_bf16, in
         CCR_HIP_CHECK(hipMemcpyAsync(d_ql, sp.long_list.data(), (size_t)n_long * 4, hipMemcpyHostToDevice, s));
         for (int lo = 0; lo < n_long; lo += FALLBACK_ROWS) {
             const int mq = std::min(FALLBACK_ROWS, n_long - lo);
-            rc = launch_dense_scores(ix->D, ix->n_rows, ix->dim, Q_bf16, d_ql + lo, 0, mq, nullptr, scratch, s);
+            rc = launch_dense_scores(ix->D, ix->dtype, ix->n_rows, ix->dim, Q_bf16, d_ql + lo, 0, mq, nullptr, scratch, s);
             if (rc != CCR_OK) return rc;
             hipLaunchKernelGGL(mask_rows_kernel, dim3(mq), dim3(256), 0, s, scratch, ix->n_rows, d_ql + lo, d_ptr, prior_idx, id_lo,
                                -INFINITY);
@@ -517,11 +523,19 @@ extern "C" int ccr_apply_block(const float *in_scores, const int64_t *in_ids, in
     return CCR_OK;
 }
 
+extern "C" int ccr_colsum_half(const uint16_t *X, int64_t rows, int dim, int half_dtype, double *out, void *stream) {
+    CCR_REQUIRE(X && out, "ccr_colsum_half: null pointer");
+    if (const int rc = check_half("ccr_colsum_half", half_dtype)) return rc;
+    CCR_REQUIRE(rows >= 0 && dim >= 8 && dim % 8 == 0, "ccr_colsum_half: bad shape rows=%lld dim=%d (dim %% 8 == 0)", (long long)rows, dim);
+    CCR_REQUIRE((uintptr_t)X % 16 == 0, "ccr_colsum_half: pointer must be 16-byte aligned");
+    return dispatch_half(half_dtype, [&](auto dt) {
+        hipLaunchKernelGGL(colsum_kernel<decltype(dt)::value>, dim3((unsigned)((dim / 8 + 7) / 8)), dim3(256), 0, (hipStream_t)stream, X, rows,
+                           dim, out);
+        CCR_LAUNCH_CHECK();
+        return CCR_OK;
+    });
+}
+
 extern "C" int ccr_colsum_bf16(const uint16_t *X, int64_t rows, int dim, double *out, void *stream) {
-    CCR_REQUIRE(X && out, "ccr_colsum_bf16: null pointer");
-    CCR_REQUIRE(rows >= 0 && dim >= 8 && dim % 8 == 0, "ccr_colsum_bf16: bad shape rows=%lld dim=%d (dim %% 8 == 0)", (long long)rows, dim);
-    CCR_REQUIRE((uintptr_t)X % 16 == 0, "ccr_colsum_bf16: pointer must be 16-byte aligned");
-    hipLaunchKernelGGL(colsum_bf16_kernel, dim3((unsigned)((dim / 8 + 7) / 8)), dim3(256), 0, (hipStream_t)stream, X, rows, dim, out);
-    CCR_LAUNCH_CHECK();
-    return CCR_OK;
+    return ccr_colsum_half(X, rows, dim, CCR_DTYPE_BF16, out, stream);
 }

@@ -148,7 +148,9 @@ __host__ __device__ __forceinline__ int pow2_ceil(int v) {
 }
 
 // canonical score of one (query, doc) pair: fp64 accumulate in increasing element order.
-// q: bf16 row in LDS (or global), d: bf16 row in global; dim % 8 == 0; both 16-byte aligned.
+// q: row of DT elements in LDS (or global), d: row of DT elements in global; dim % 8 == 0; both 16-byte aligned.  The product of two
+// bf16 or two fp16 values is exact in fp64 (16 or 22 significand bits, exponent >= -266 or -48).
+template <int DT>
 __device__ __forceinline__ float canonical_dot(const uint16_t *__restrict__ q, const uint16_t *__restrict__ d, int dim) {
     double acc = 0.0;
     // the loads of 4 steps are independent of the fp64 chain: unrolled so that they are in flight together
@@ -160,8 +162,8 @@ __device__ __forceinline__ float canonical_dot(const uint16_t *__restrict__ q, c
         const uint32_t qw[4] = {qv.x, qv.y, qv.z, qv.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            acc = fma((double)__uint_as_float(qw[e] << 16), (double)__uint_as_float(dw[e] << 16), acc);
-            acc = fma((double)__uint_as_float(qw[e] & 0xffff0000u), (double)__uint_as_float(dw[e] & 0xffff0000u), acc);
+            acc = fma((double)elem_lo<DT>(qw[e]), (double)elem_lo<DT>(dw[e]), acc);
+            acc = fma((double)elem_hi<DT>(qw[e]), (double)elem_hi<DT>(dw[e]), acc);
         }
     }
     return (float)acc;

@@ -132,6 +132,28 @@ int ccr_meanpool_pack_bf16_packed(const void *hidden, int hidden_dtype, const in
                                   uint16_t *dst_bf16, float *dst_f32, const int64_t *dst_rows, float *row_norm_bounds, int n_seq,
                                   int dim, int normalize, void *stream);
 
+/*
+ * The same packs into either 16-bit element type of a search index: half_dtype = CCR_DTYPE_BF16 or CCR_DTYPE_F16 (fp16 is what the
+ * reference's autocast hands its `Q @ chunk.T`, scripts/ms_marco_eval.py:215: unit roundoff 2^-11 against bf16's 2^-8).  The arguments
+ * are those of the bf16 entry points above -- which call these with CCR_DTYPE_BF16 and overflow = NULL -- plus
+ *   overflow (device int32, may be NULL; the caller zeroes it once and may share it among any number of calls): incremented by the
+ *   number of elements that were finite in fp32 and left fp16's range (|x| >= 65 520 -> +-inf, as torch's .to(float16)); one atomic
+ *   per workgroup that saw any.  Never touched with CCR_DTYPE_BF16.
+ * fp16 output is round-to-nearest-even and bit-identical to torch's conversion, subnormals included.  The normalising form, the norms
+ * and row_norm_bounds are computed as in the bf16 form (a row with an out-of-range element gets an infinite bound).
+ * ccr_version() >= 109.
+ */
+int ccr_pack_half_ex(const float *src, uint16_t *dst, float *norms, float *row_norm_bounds, int64_t rows, int dim, int normalize,
+                     int half_dtype, int32_t *overflow, void *stream);
+int ccr_pack_half_padded(const float *src, int64_t rows, int src_dim, uint16_t *dst, int dst_dim, float *norms, float *row_norm_bounds,
+                         int normalize, int half_dtype, int32_t *overflow, void *stream);
+int ccr_meanpool_pack_half_ex(const void *hidden, int hidden_dtype, const int64_t *mask, uint16_t *dst_half, float *dst_f32,
+                              const int64_t *dst_rows, float *row_norm_bounds, int B, int L, int dim, int normalize, int half_dtype,
+                              int32_t *overflow, void *stream);
+int ccr_meanpool_pack_half_packed(const void *hidden, int hidden_dtype, const int32_t *seq_start, const int32_t *seq_len,
+                                  uint16_t *dst_half, float *dst_f32, const int64_t *dst_rows, float *row_norm_bounds, int n_seq, int dim,
+                                  int normalize, int half_dtype, int32_t *overflow, void *stream);
+
 /* Backward of the pooling for the training forward (the reference's tower is called with gradients on in
  * src/ccrec/models/bbpr.py:130-141,195-197): dhidden[b][l][:] = mask[b][l] ? grad[b][:] / sum(mask[b]) : 0.
  *   grad [B][dim] fp32 (gradient w.r.t. the un-normalised pooled rows), dhidden [B][L][dim] of hidden_dtype. */
@@ -290,9 +312,22 @@ int ccr_index_create(const uint16_t *D_bf16, int64_t n_rows, int dim, int64_t gl
  * bound of each 256-row tile, the select stage each candidate row's own bound). */
 int ccr_index_create_with_norms(const uint16_t *D_bf16, int64_t n_rows, int dim, int64_t global_row_offset,
                                 const float *row_norm_bounds, void *stream, ccr_index **out);
+/*
+ * The same two over a shard of either 16-bit element type: half_dtype = CCR_DTYPE_BF16 (what the two names above pass) or
+ * CCR_DTYPE_F16.  EVERY search-side entry point then takes query matrices of the index's type -- ccr_search, ccr_search_finish,
+ * ccr_scores (both modes), ccr_search_blocked, ccr_search_sparse_prior, ccr_search_shard and the retry, margin and fp64 dense paths
+ * behind them -- with unchanged signatures: the `Q_bf16` arguments read "16-bit rows of ccr_index_dtype(index)".  The canonical
+ * score, the order and the path independence are those of the bf16 index (a product of two fp16 values is exact in fp64 as well);
+ * only the MFMA instruction and the element-to-float conversion differ.  ccr_version() >= 109.
+ */
+int ccr_index_create_half(const uint16_t *D, int64_t n_rows, int dim, int half_dtype, int64_t global_row_offset, void *stream,
+                          ccr_index **out);
+int ccr_index_create_with_norms_half(const uint16_t *D, int64_t n_rows, int dim, int half_dtype, int64_t global_row_offset,
+                                     const float *row_norm_bounds, void *stream, ccr_index **out);
 int ccr_index_destroy(ccr_index *index);
 int64_t ccr_index_rows(const ccr_index *index);
 int ccr_index_dim(const ccr_index *index);
+int ccr_index_dtype(const ccr_index *index);   /* CCR_DTYPE_BF16 or CCR_DTYPE_F16; -1 for NULL.  ccr_version() >= 109 */
 
 /*
  * Exhaustive inner-product top-k of n_q queries against the shard.
@@ -383,6 +418,8 @@ int ccr_search_sparse_prior(ccr_index *index, const uint16_t *Q_bf16, int n_q, i
  * (src/rime_lite/util/score_array.py:460-474 without materialising any batch of S).
  */
 int ccr_colsum_bf16(const uint16_t *X, int64_t rows, int dim, double *out /* [dim] device */, void *stream);
+/* The same for a matrix of half_dtype (CCR_DTYPE_BF16 / CCR_DTYPE_F16) elements.  ccr_version() >= 109. */
+int ccr_colsum_half(const uint16_t *X, int64_t rows, int dim, int half_dtype, double *out /* [dim] device */, void *stream);
 
 /*
  * Merge R per-shard top-k lists (after the RCCL all-gather) into the global top-k.
