@@ -32,6 +32,7 @@ EXPORTS = [
     "ccr_embed_layernorm_train_half", "ccr_embed_layernorm_bwd_half", "ccr_embedding_grad", "ccr_meanpool_bwd_packed",
     "ccr_pack_half_ex", "ccr_pack_half_padded", "ccr_meanpool_pack_half_ex", "ccr_meanpool_pack_half_packed", "ccr_index_create_half",
     "ccr_index_create_with_norms_half", "ccr_index_dtype", "ccr_colsum_half",
+    "ccr_grad_stats_workspace_bytes", "ccr_grad_stats", "ccr_adamw_control_update", "ccr_adamw_step_scaled",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
@@ -43,6 +44,7 @@ THR_PHASES_VERSION = 106   # ... and the threshold kernel's 64-phase form with i
 OPTIM_VERSION = 107   # ... and the multi-tensor AdamW step that keeps the encoder's 16-bit weights current (ccr_adamw_step)
 ENCODER_PACKED_TRAIN_VERSION = 108   # ... and the embedding block's and the packed pooling's backward (ccr_embed_layernorm_bwd_half and its kin)
 HALF_INDEX_VERSION = 109   # ... and the pack, index and search on either 16-bit element type (ccr_index_create_half and its kin)
+AMP_OPTIM_VERSION = 110   # ... and loss scaling, overflow skip and norm clipping inside the AdamW step (ccr_adamw_step_scaled and its kin)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -69,6 +71,15 @@ class AdamwSegment(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
                 ("shadow", ctypes.c_void_p), ("n", ctypes.c_int64), ("decay", ctypes.c_float), ("step_size", ctypes.c_float),
                 ("bc2_sqrt", ctypes.c_float), ("shadow_dtype", ctypes.c_int32)]
+
+
+class AdamwControl(ctypes.Structure):
+    """ccr_adamw_control (include/ccr_retrieval.h): 64 bytes of device memory; CONTROL_WORDS names its 4-byte words."""
+    _fields_ = [("coef", ctypes.c_float), ("skip", ctypes.c_int32), ("norm", ctypes.c_float), ("scale", ctypes.c_float),
+                ("growth_tracker", ctypes.c_int32), ("skipped_total", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 10)]
+
+
+CONTROL_WORDS = {name: i for i, (name, _) in enumerate(AdamwControl._fields_[:6])}
 
 
 class CcrError(RuntimeError):
@@ -180,6 +191,11 @@ def load():
     lib.ccr_add_layernorm_drop_half.argtypes = [vp, vp, f32, vp, vp, vp, f32, vp, vp, i64, i32, i32, vp]
     lib.ccr_add_layernorm_bwd_drop_half.argtypes = [vp, vp, f32, vp, vp, f32, vp, vp, vp, vp, vp, i64, i32, i32, vp, sz, vp]
     lib.ccr_adamw_step.argtypes = [vp, i32, f32, f32, f32, f32, vp]
+    lib.ccr_grad_stats_workspace_bytes.argtypes = [vp, i32]
+    lib.ccr_grad_stats_workspace_bytes.restype = i64
+    lib.ccr_grad_stats.argtypes = [vp, i32, vp, vp]
+    lib.ccr_adamw_control_update.argtypes = [vp, vp, i64, f32, i32, ctypes.c_double, ctypes.c_double, i32, vp, vp, vp]
+    lib.ccr_adamw_step_scaled.argtypes = [vp, i32, f32, f32, f32, f32, vp, vp]
     lib.ccr_embed_layernorm_train_half.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, f32, vp, f32, vp, vp, i64, i32, i32, vp]
     lib.ccr_embed_layernorm_bwd_half.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, f32, vp, f32, vp, vp, vp, vp, i64, i32, vp, sz, vp]
     lib.ccr_embedding_grad.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp]

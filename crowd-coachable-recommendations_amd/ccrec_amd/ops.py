@@ -624,6 +624,23 @@ def _require_optim():
     return lib
 
 
+_OPTIM_AMP_CHECKED = False
+
+
+def _require_optim_amp():
+    """require_gpu() + once: the loaded library has the scaled AdamW step with its statistics and control kernels (ccr_version() >= 110;
+    FusedAdamW(max_grad_norm=...), the GradScaler protocol and optim.LossScaler call them)."""
+    global _OPTIM_AMP_CHECKED
+    lib = require_gpu()
+    if not _OPTIM_AMP_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.AMP_OPTIM_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, loss scaling and clipping in the optimizer step need "
+                                f"{_lib.AMP_OPTIM_VERSION}: rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
+        _OPTIM_AMP_CHECKED = True
+    return lib
+
+
 def dropout_bits_rows(rows, dim, seed, stream_id, p, device="cuda"):
     """Packed keep bits uint32 (stored as int32) [rows, dim / 32] of a row-wise dropout site (ccr_dropout_bits_rows): bit i of word w <->
     column 32 w + i, 1 = keep; a pure function of (seed, stream_id, p, row, column) -- dropout_ref.rows_bits gives the same words."""

@@ -63,3 +63,100 @@ def shadow_bits(p, dtype):
         with np.errstate(all="ignore"):
             return p.astype(np.float16).view(np.uint16)
     raise ValueError(f"shadow_bits: dtype {dtype!r} (bf16 or fp16)")
+
+
+# ------------------------------------------------------------------- loss scaling, overflow skip, norm clipping (library version 110)
+CHUNK, STATS_THREADS, CONTROL_THREADS = 4096, 256, 256
+
+
+def grad_sumsq_partials(g_list):
+    """ccr_grad_stats: one fp32 sum of squares per 4096-element chunk of every non-empty gradient, the chunks counted through the list.
+    The order is the kernel's on either access path: the element at offset j of its chunk belongs to thread (j // 4) % 256, which adds its
+    squares (each rounded to fp32) in increasing j to a sum that starts at +0; a wave's 64 sums fold as x[i] + x[i + h] for
+    h = 32, 16, 8, 4, 2, 1; the four wave sums add as ((w0 + w1) + w2) + w3.  (A chunk's missing elements count as +0, which leaves a sum
+    of squares as it is.)"""
+    out = []
+    with np.errstate(all="ignore"):
+        for g in g_list:
+            g = np.ascontiguousarray(g, dtype=np.float32).reshape(-1)
+            if g.size == 0:
+                continue
+            chunks = (g.size + CHUNK - 1) // CHUNK
+            padded = np.zeros(chunks * CHUNK, np.float32)
+            padded[:g.size] = g
+            sq = (padded * padded).reshape(chunks, CHUNK // (4 * STATS_THREADS), STATS_THREADS, 4)      # [chunk, sweep, thread, element]
+            acc = np.zeros((chunks, STATS_THREADS), np.float32)
+            for k in range(sq.shape[1]):
+                for e in range(4):
+                    acc = acc + sq[:, k, :, e]
+            acc = acc.reshape(chunks, STATS_THREADS // 64, 64)
+            for h in (32, 16, 8, 4, 2, 1):
+                acc = acc[:, :, :h] + acc[:, :, h:2 * h]
+            w = acc[:, :, 0]
+            out.append(((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3])
+            assert out[-1].dtype == np.float32
+    return np.concatenate(out) if out else np.zeros(0, np.float32)
+
+
+def partials_sum(partials):
+    """ccr_adamw_control_update's sum of the partials, a double: index order within 256 equal contiguous slices of ceil(n / 256) partials,
+    then the slice sums in slice order (for n <= 256 that is plain index order)."""
+    partials = np.asarray(partials, dtype=np.float32).reshape(-1)
+    n = partials.size
+    per = (n + CONTROL_THREADS - 1) // CONTROL_THREADS
+    padded = np.zeros(CONTROL_THREADS * per, np.float64)
+    padded[:n] = partials
+    padded = padded.reshape(CONTROL_THREADS, per)
+    s = np.float64(0.0)
+    with np.errstate(all="ignore"):
+        mine = np.zeros(CONTROL_THREADS, np.float64)
+        for i in range(per):
+            mine = mine + padded[:, i]
+        for t in range(CONTROL_THREADS):
+            s = s + mine[t]
+    return s
+
+
+def control_update(partials, scale, tracker, max_norm, growth, backoff, interval, ext_found_inf=None, ext_scale=None):
+    """ccr_adamw_control_update -> dict(coef, skip, norm, scale, tracker).  scale: the block's own loss scale (updated by torch's
+    _amp_update_scale_ rule), or None: no scaling of its own.  ext_scale / ext_found_inf: a stock GradScaler's values; with ext_scale the
+    own scale must be None.  max_norm None, <= 0 or infinite: no clipping (the factor is exactly 1)."""
+    assert ext_scale is None or scale is None
+    s = partials_sum(partials)
+    with np.errstate(all="ignore"):
+        inv = _F(1.0)
+        if ext_scale is not None:
+            inv = _F(1.0 / float(_F(ext_scale)))
+        elif scale is not None:
+            inv = _F(1.0 / float(_F(scale)))
+        skip = bool(not np.isfinite(s)) or (ext_found_inf is not None and float(ext_found_inf) != 0.0)
+        norm = _F(np.sqrt(s)) * inv
+        clip = _F(1.0)
+        max_norm = _F(0.0 if max_norm is None else max_norm)
+        if max_norm > 0 and not np.isinf(max_norm):
+            ratio = max_norm / (norm + _F(1e-6))
+            clip = ratio if ratio < 1 else _F(1.0)
+        coef = inv * clip
+        new_scale, tracker = (None if scale is None else _F(scale)), int(tracker)
+        if scale is not None:
+            if skip:
+                new_scale, tracker = _F(float(new_scale) * float(backoff)), 0      # (in double, rounded once: torch's kernel)
+            else:
+                tracker += 1
+                if tracker == int(interval):
+                    grown = _F(float(new_scale) * float(growth))
+                    if np.isfinite(grown):
+                        new_scale = grown
+                    tracker = 0
+    assert coef.dtype == norm.dtype == np.float32
+    return dict(coef=coef, skip=int(skip), norm=norm, scale=new_scale, tracker=tracker)
+
+
+def adamw_step_scaled(p, g, m, v, t, lr, wd, betas, eps, coef, skip):
+    """ccr_adamw_step_scaled on one tensor: nothing changes on a skip, else adamw_step on g * coef (one fp32 multiply) -> (p', m', v')."""
+    p, g, m, v = (np.asarray(a, dtype=np.float32) for a in (p, g, m, v))
+    if skip:
+        return p.copy(), m.copy(), v.copy()
+    with np.errstate(all="ignore"):
+        scaled = g * _F(coef)
+    return adamw_step(p, scaled, m, v, t, lr, wd, betas, eps)

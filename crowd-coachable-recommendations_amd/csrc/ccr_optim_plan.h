@@ -98,6 +98,23 @@ inline uint32_t next_batch(const ccr_adamw_segment *segments, int n_segments, in
 
 inline int grid_for(uint32_t chunks) { return (int)(chunks < (uint32_t)MAX_GRID ? chunks : (uint32_t)MAX_GRID); }
 
+// ccr_grad_stats writes one fp32 partial per chunk at the chunk's GLOBAL index: the chunks of the list's non-empty segments counted in
+// list order, whatever launch batch carries them.  A batch's first chunk sits at the chunk total of the batches before it, which the
+// caller keeps while it walks the list:   base = 0;  while (chunks = next_batch(...)) { launch(batch, base);  base += chunks; }
+// (the sum over the list of at most 2^31 segments of fewer than 2^31 chunks stays far inside int64)
+inline int64_t list_chunks(const ccr_adamw_segment *segments, int n_segments) {
+    int64_t total = 0;
+    for (int i = 0; i < n_segments; ++i) total += segment_chunks(segments[i].n);
+    return total;
+}
+inline int64_t stats_workspace_bytes(const ccr_adamw_segment *segments, int n_segments) {
+    return list_chunks(segments, n_segments) * (int64_t)sizeof(float);
+}
+
+// ccr_adamw_control_update's slices: CONTROL_THREADS threads each sum ceil(n / CONTROL_THREADS) consecutive partials
+constexpr int CONTROL_THREADS = 256;
+inline int64_t control_slice(int64_t n_partials) { return (n_partials + CONTROL_THREADS - 1) / CONTROL_THREADS; }
+
 // The segment of chunk c in a batch: the largest s with prefix[s] <= c (c < prefix[n_seg]).  Block-uniform in the kernel; the check program
 // runs the same function.
 #if defined(__HIPCC__)

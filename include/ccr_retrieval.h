@@ -688,6 +688,61 @@ int ccr_adamw_step(const ccr_adamw_segment *segments, int n_segments, float one_
                    float eps, void *stream);
 
 /*
+ * Loss scaling, overflow skip and global-norm clipping inside the AdamW step (library version 110; opt-in: ccr_adamw_step is unchanged).
+ * Replaces: the GradScaler that Lightning's Trainer(precision=16) puts around the optimizer (src/ccrec/models/bert_mt.py:314,
+ * src/ccrec/models/bbpr.py:433) -- unscale_'s pass over every gradient, clip_grad_norm_'s two passes and the host read of found_inf.
+ * Three calls on one stream: ccr_grad_stats (read only) -> ccr_adamw_control_update (one workgroup) -> ccr_adamw_step_scaled.
+ *
+ * ccr_adamw_control: 64 bytes of DEVICE memory, written by ccr_adamw_control_update, read by ccr_adamw_step_scaled.
+ *   coef            the multiplier of every gradient: inv * min(1, max_norm / (norm + 1e-6f))
+ *   skip            1: the step writes nothing
+ *   norm            the UNSCALED global L2 norm of the gradients (what clip_grad_norm_ returns)
+ *   scale           the loss scale (read and updated only with own_scale)
+ *   growth_tracker  unskipped steps since the scale last changed (own_scale only)
+ *   skipped_total   skipped steps so far (every mode)
+ *
+ * ccr_grad_stats: partials[c] = the fp32 sum of g * g over chunk c, c counting the 4096-element chunks of the non-empty segments in
+ *   list order (ccr_adamw_step's chunks; only `grad` and `n` of a segment are read, the other pointers decide the access width as
+ *   there).  No atomics, one fixed order whatever the access width: the element at offset j of its chunk belongs to thread (j / 4) % 256,
+ *   which adds its squares in increasing j to a sum that starts at +0 (fp32, the square rounded, not contracted); the 64 sums of a wave
+ *   fold as x[i] + x[i + h] for h = 32, 16, 8, 4, 2, 1; the four wave sums add as ((w0 + w1) + w2) + w3.
+ *   ccr_grad_stats_workspace_bytes: 4 bytes per chunk (0 for an empty list, -1 for an ill-formed one).
+ *
+ * ccr_adamw_control_update: s = the sum of partials[0 .. n_partials) in double, in index order within 256 equal contiguous slices
+ *   (slice t = indices [t * ceil(n / 256), ...)), then the slice sums in slice order; both start at +0.
+ *   inv  = (float)(1 / (double)scale), scale = *ext_grad_scale if that is not NULL, else control->scale if own_scale, else inv = 1
+ *   skip = s is not finite, or ext_found_inf != NULL and *ext_found_inf != 0.  A non-finite s covers a NaN, either infinity AND a finite
+ *          gradient whose square passes fp32's range (|g| > 1.8e19): all three skip the step.  Squares cannot cancel.
+ *   norm = (float)sqrt(s) * inv;  coef = inv * min(1, max_norm / (norm + 1e-6f)) in fp32 (torch's clip_grad_norm_); the clip factor is
+ *          exactly 1 when max_norm is not positive, infinite or a NaN.
+ *   own_scale (torch's _amp_update_scale_): on a skip scale *= backoff, growth_tracker = 0; else growth_tracker += 1 and, when it reaches
+ *          growth_interval, scale *= growth if that product is finite, growth_tracker = 0.  As there, a product is formed in double
+ *          from the double factor and rounded to fp32 once.  skipped_total += 1 on every skip.
+ *   ext_grad_scale / ext_found_inf: NULL or fp32 DEVICE scalars, a stock torch.amp.GradScaler's; the block's own scale is then left
+ *          alone (own_scale together with ext_grad_scale: CCR_ERR_INVALID).
+ *
+ * ccr_adamw_step_scaled: ccr_adamw_step with g replaced by g * control->coef (one fp32 multiply, rounded, not contracted); every
+ *   workgroup reads control->skip first and, if it is set, returns without a store: p, exp_avg, exp_avg_sq and the shadow keep their
+ *   bytes.  With coef == 1.0f and skip == 0 every stored bit is ccr_adamw_step's.
+ */
+typedef struct ccr_adamw_control {
+    float coef;
+    int32_t skip;
+    float norm;
+    float scale;
+    int32_t growth_tracker;
+    int32_t skipped_total;
+    uint32_t reserved[10];   /* zero */
+} ccr_adamw_control;
+int64_t ccr_grad_stats_workspace_bytes(const ccr_adamw_segment *segments, int n_segments);
+int ccr_grad_stats(const ccr_adamw_segment *segments, int n_segments, float *partials, void *stream);
+int ccr_adamw_control_update(ccr_adamw_control *control, const float *partials, int64_t n_partials, float max_norm, int own_scale,
+                             double growth, double backoff, int growth_interval, const float *ext_grad_scale, const float *ext_found_inf,
+                             void *stream);
+int ccr_adamw_step_scaled(const ccr_adamw_segment *segments, int n_segments, float one_minus_beta1, float beta2, float one_minus_beta2,
+                          float eps, const ccr_adamw_control *control, void *stream);
+
+/*
  * The fine-tune step in one packed pass (library version 108): the embedding block with a backward, and mean pooling over a packed token
  * array with a backward.  The reference encodes queries, positives and negatives in three tower calls per step
  * (src/ccrec/models/bbpr.py:195-197) and pools the last hidden state under its mask (src/ccrec/models/item_tower.py:141-146); with these
