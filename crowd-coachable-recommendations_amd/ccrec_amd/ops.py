@@ -1242,7 +1242,31 @@ def colsum_bf16(x):
     return out
 
 
-_INBATCH_LAYOUT = {}   # (B, dim) -> (bytes of the packed blocks padded to 256, workspace bytes, total bytes)
+def _f32_on(t, dev):   # t (or None) as a contiguous fp32 tensor on dev: a value the library reads on the device
+    if t is not None and (t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
+        t = t.detach().to(device=dev, dtype=torch.float32).contiguous()   # stays on the device either way
+    return t
+
+
+def _grad_as(g, dtype):   # an fp32 gradient in its input's dtype
+    return g if dtype == torch.float32 else g.to(dtype)
+
+
+def _workspace_bytes(lib, name, *shape):   # lib.<name>(*shape): host arithmetic only; 0 = the shape was refused, the library says why
+    ws_bytes = int(getattr(lib, name)(*shape))
+    if ws_bytes == 0:
+        raise _lib.CcrError(name + ": " + lib.ccr_last_error().decode("utf-8", "replace"))
+    return ws_bytes
+
+
+def _one_buffer(packed_bytes, ws_bytes, n_lse):
+    """A forward's single uint8 buffer [packed operands | workspace | lse: n_lse floats at the tail]
+    -> (bytes of the packed operands padded to 256 = the workspace's offset, workspace bytes, total bytes)."""
+    head = (packed_bytes + 255) // 256 * 256
+    return head, ws_bytes, head + (ws_bytes + 255) // 256 * 256 + n_lse * 4
+
+
+_INBATCH_LAYOUT = {}   # (B, dim) -> _one_buffer(...): (bytes of the packed blocks padded to 256, workspace bytes, total bytes)
 
 
 class _InBatchCE(torch.autograd.Function):
@@ -1261,9 +1285,7 @@ class _InBatchCE(torch.autograd.Function):
         assert q.is_cuda and p.shape == q.shape == n.shape and p.device == q.device == n.device, "three [B, dim] blocks on one device"
         lay = _INBATCH_LAYOUT.get((B, dim))
         if lay is None:
-            ws_bytes = int(lib.ccr_inbatch_ce_workspace_bytes(B, dim))
-            head = (3 * B * dim * 2 + 255) // 256 * 256
-            lay = _INBATCH_LAYOUT[(B, dim)] = (head, ws_bytes, head + (ws_bytes + 255) // 256 * 256 + B * 4)
+            lay = _INBATCH_LAYOUT[(B, dim)] = _one_buffer(3 * B * dim * 2, int(lib.ccr_inbatch_ce_workspace_bytes(B, dim)), B)
         head, ws_bytes, total = lay
         dev = q.device
         buf = torch.empty(total, dtype=torch.uint8, device=dev)
@@ -1295,17 +1317,14 @@ class _InBatchCE(torch.autograd.Function):
         B, dim, head, ws_bytes, total, inv_t, tq, tp, tn = ctx.lay
         dev = buf.device
         grads = torch.empty(3, B, dim, dtype=torch.float32, device=dev)
-        g = grad_out
-        if g.dtype != torch.float32 or g.device != dev or not g.is_contiguous():
-            g = g.detach().to(device=dev, dtype=torch.float32).contiguous()   # stays on the device either way
+        g = _f32_on(grad_out, dev)
         base, gp, blk = buf.data_ptr(), grads.data_ptr(), B * dim
         with _on(buf):
             _lib.check(lib.ccr_inbatch_ce_bwd_dev(base, base + 2 * blk, base + 4 * blk, base + total - B * 4, B, dim, inv_t, g.data_ptr(),
                                                   gp, gp + 4 * blk, gp + 8 * blk, base + head, ws_bytes, torch.cuda.current_stream(dev).cuda_stream),
                        "ccr_inbatch_ce_bwd")
         dq, dp, dn = grads.unbind(0)
-        f32 = torch.float32
-        return (dq if tq == f32 else dq.to(tq)), (dp if tp == f32 else dp.to(tp)), (dn if tn == f32 else dn.to(tn)), None
+        return _grad_as(dq, tq), _grad_as(dp, tp), _grad_as(dn, tn), None
 
 
 def inbatch_ce(q, p, n, inv_temperature):
@@ -1337,11 +1356,7 @@ def pool_ce_forward(q, c, labels, inv_temperature, weights=None):
         weights = weights.detach().to(device=dev, dtype=torch.float32).contiguous()
         assert weights.shape == (n_q,), "one weight per query"
     pdim = padded_dim(dim)
-    ws_bytes = int(lib.ccr_pool_ce_workspace_bytes(n_q, n_c, pdim))   # (host arithmetic only)
-    if ws_bytes == 0:
-        raise _lib.CcrError("ccr_pool_ce_workspace_bytes: " + lib.ccr_last_error().decode("utf-8", "replace"))
-    head = ((n_q + n_c) * pdim * 2 + 255) // 256 * 256
-    total = head + (ws_bytes + 255) // 256 * 256 + n_q * 4
+    head, ws_bytes, total = _one_buffer((n_q + n_c) * pdim * 2, _workspace_bytes(lib, "ccr_pool_ce_workspace_bytes", n_q, n_c, pdim), n_q)
     buf = torch.empty(total, dtype=torch.uint8, device=dev)
     out3 = torch.empty(3, dtype=torch.float32, device=dev)
     base = buf.data_ptr()
@@ -1373,11 +1388,7 @@ def pool_ce_backward(state, grad_out, W=None):
     buf, labels, weights, (n_q, n_c, dim, pdim, head, ws_bytes, total, inv_t) = state
     dev = buf.device
     grads = torch.empty(n_q + n_c, pdim, dtype=torch.float32, device=dev)
-    g = grad_out
-    if g.dtype != torch.float32 or g.device != dev or not g.is_contiguous():
-        g = g.detach().to(device=dev, dtype=torch.float32).contiguous()   # stays on the device either way
-    if W is not None and (W.dtype != torch.float32 or W.device != dev or not W.is_contiguous()):
-        W = W.detach().to(device=dev, dtype=torch.float32).contiguous()
+    g, W = _f32_on(grad_out, dev), _f32_on(W, dev)
     base, gp = buf.data_ptr(), grads.data_ptr()
     with _on(buf):
         _lib.check(lib.ccr_pool_ce_bwd_dev(base, base + n_q * pdim * 2, labels.data_ptr(), weights.data_ptr() if weights is not None else None,
@@ -1402,8 +1413,7 @@ class _PoolCE(torch.autograd.Function):
     def backward(ctx, grad_out):
         dq, dc = pool_ce_backward(ctx.state, grad_out)
         tq, tc = ctx.dtypes
-        f32 = torch.float32
-        return (dq if tq == f32 else dq.to(tq)), (dc if tc == f32 else dc.to(tc)), None, None, None
+        return _grad_as(dq, tq), _grad_as(dc, tc), None, None, None
 
 
 def pool_ce(q, c, labels, inv_temperature, weights=None):
@@ -1478,21 +1488,12 @@ def bpr_sample_negatives(users, n_negatives, proposal, proposal_cdf, prior=None,
 def _bpr_frozen_args(table, ptr_i, ptr_j, ptr_nj, w):
     assert table.is_cuda and table.dtype == torch.float32 and table.dim() == 2 and table.is_contiguous(), "table: fp32 [n_rows, dim] on the device"
     dev = table.device
-    ptr_i = ptr_i.detach().to(device=dev, dtype=torch.int64).contiguous()
-    ptr_j = ptr_j.detach().to(device=dev, dtype=torch.int64).contiguous()
-    ptr_nj = ptr_nj.detach().to(device=dev, dtype=torch.int64).contiguous()
+    ptr_i, ptr_j, ptr_nj = (p.detach().to(device=dev, dtype=torch.int64).contiguous() for p in (ptr_i, ptr_j, ptr_nj))
     w = w.detach().to(device=dev, dtype=torch.float32).contiguous()
     B = ptr_i.numel()
     assert ptr_i.dim() == 1 and ptr_j.shape == (B,) and w.shape == (B,) and ptr_nj.dim() == 2 and ptr_nj.shape[1] == B, \
         "ptr_i, ptr_j, w [B] and ptr_nj [n_negatives, B]"
     return ptr_i, ptr_j, ptr_nj, w, B, ptr_nj.shape[0]
-
-
-def _bpr_workspace(lib, B, n_neg, dim, dev):
-    ws_bytes = int(lib.ccr_bpr_frozen_workspace_bytes(B, n_neg, dim))   # (host arithmetic only)
-    if ws_bytes == 0:
-        raise _lib.CcrError("ccr_bpr_frozen_workspace_bytes: " + lib.ccr_last_error().decode("utf-8", "replace"))
-    return torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes
 
 
 class _BprFrozen(torch.autograd.Function):
@@ -1511,7 +1512,8 @@ class _BprFrozen(torch.autograd.Function):
         if weight is not None:   # one [2, dim] block: gamma and beta 16-byte aligned whatever views the module holds
             gb = torch.stack([weight.detach().to(device=dev, dtype=torch.float32), bias.detach().to(device=dev, dtype=torch.float32)])
             assert gb.shape == (2, dim), "LayerNorm weight and bias [dim]"
-        ws, ws_bytes = _bpr_workspace(lib, B, n_neg, dim, dev)
+        ws_bytes = _workspace_bytes(lib, "ccr_bpr_frozen_workspace_bytes", B, n_neg, dim)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         out3 = torch.empty(3, dtype=torch.float32, device=dev)
         with _on(table):
             _lib.check(lib.ccr_bpr_frozen_fwd(_ptr(table), n_rows, dim, gb.data_ptr() if gb is not None else None,
@@ -1531,18 +1533,16 @@ class _BprFrozen(torch.autograd.Function):
         n_rows, dim = table.shape
         B, n_neg = ptr_i.numel(), ptr_nj.shape[0]
         dev = table.device
-        g = grad_out
-        if g.dtype != torch.float32 or g.device != dev or not g.is_contiguous():
-            g = g.detach().to(device=dev, dtype=torch.float32).contiguous()   # stays on the device either way
+        g = _f32_on(grad_out, dev)
         grads = torch.empty(2, dim, dtype=torch.float32, device=dev)
-        ws, ws_bytes = _bpr_workspace(lib, B, n_neg, dim, dev)
+        ws_bytes = _workspace_bytes(lib, "ccr_bpr_frozen_workspace_bytes", B, n_neg, dim)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         with _on(table):
             _lib.check(lib.ccr_bpr_frozen_bwd_dev(_ptr(table), n_rows, dim, gb.data_ptr(), gb.data_ptr() + dim * 4, eps, _ptr(ptr_i), _ptr(ptr_j),
                                                   _ptr(ptr_nj), _ptr(w), B, n_neg, out3.data_ptr() + 8, _ptr(g), grads.data_ptr(),
                                                   grads.data_ptr() + dim * 4, _ptr(ws), ws_bytes, _stream(table)), "ccr_bpr_frozen_bwd_dev")
         dw, db = grads.unbind(0)
-        f32 = torch.float32
-        return None, (dw if tw == f32 else dw.to(tw)), (db if tb == f32 else db.to(tb)), None, None, None, None, None
+        return None, _grad_as(dw, tw), _grad_as(db, tb), None, None, None, None, None
 
 
 def bpr_frozen_loss(table, layer_norm_weight, layer_norm_bias, eps, ptr_i, ptr_j, ptr_nj, w):

@@ -25,7 +25,7 @@
 // gradients NaN; every address is formed from clamped indices.
 #include <algorithm>
 
-#include "ccr_common.h"
+#include "ccr_loss_common.h"
 
 namespace ccr {
 namespace bpr {
@@ -33,17 +33,6 @@ namespace bpr {
 constexpr int MAX_ROW_NNZ = 4096;   // entries of one prior row (the limit of ccr_search_sparse_prior)
 constexpr int MAX_DIM = 2048, MAX_B = 1 << 20, MAX_NEG = 4096;
 constexpr int MAX_BWD_BLOCKS = 512;    // partial gradient rows of the backward (4 waves each: 2 048 waves, what the chip holds at width 768)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 // ---- (a) sampler -------------------------------------------------------------------------------------------------------------
 // grid = B, block = one wave, dynamic LDS = 2 * max_row_nnz doubles: S_k (inclusive prefix of the corrections) and F(c_k).
@@ -260,20 +249,10 @@ __global__ __launch_bounds__(256) void bpr_frozen_fwd_kernel(const float *__rest
 // out3 = {loss, numerator sum_b part_b, denominator n_neg sum_b w_b}: fp64, one fixed order
 __global__ __launch_bounds__(256) void bpr_finish_kernel(const float *__restrict__ part, const float *__restrict__ w, int B, int n_neg,
                                                         float *__restrict__ out3) {
-    __shared__ double s_n[256], s_d[256];
-    const int tid = threadIdx.x;
-    double n = 0.0, d = 0.0;
-    for (int i = tid; i < B; i += 256) n += (double)part[i], d += (double)w[i];
-    s_n[tid] = n, s_d[tid] = d;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (tid < s) s_n[tid] += s_n[tid + s], s_d[tid] += s_d[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const double den = s_d[0] * (double)n_neg;
-        out3[0] = (float)(s_n[0] / den), out3[1] = (float)s_n[0], out3[2] = (float)den;
-    }
+    block256_sum2(part, w, B, [&](double num, double wsum) {
+        const double den = wsum * (double)n_neg;
+        out3[0] = (float)(num / den), out3[1] = (float)num, out3[2] = (float)den;
+    });
 }
 
 // grid = nblocks, block = 4 waves; wave (block, y) takes the batch rows 4 block + y, + 4 nblocks, ... and keeps its share of
@@ -382,7 +361,6 @@ static int bwd_blocks(int B) { return std::min((B + 3) / 4, MAX_BWD_BLOCKS); }
 static size_t ws_bytes_for(int B, int dim) {
     return std::max((size_t)B * sizeof(float), (size_t)bwd_blocks(B) * 2 * dim * sizeof(float)) + 256;   // + 256: the caller's pointer need only be 16-byte aligned
 }
-static char *align256(void *p) { return (char *)p + (256 - (uintptr_t)p % 256) % 256; }
 
 #define BPR_DISPATCH_NV(dim, CALL)          \
     switch (((dim) + 255) / 256) {          \
@@ -431,10 +409,7 @@ extern "C" int ccr_bpr_frozen_fwd(const float *table, int64_t n_rows, int dim, c
     if (!shape_ok("ccr_bpr_frozen_fwd", B, n_neg, dim)) return CCR_ERR_INVALID;
     CCR_REQUIRE(table && ptr_i && ptr_j && ptr_nj && w && out3 && n_rows >= 1, "ccr_bpr_frozen_fwd: null pointer or empty table");
     CCR_REQUIRE(((uintptr_t)table | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0, "ccr_bpr_frozen_fwd: table, gamma and beta must be 16-byte aligned");
-    if (!workspace || ws_bytes < ws_bytes_for(B, dim)) {
-        set_error("ccr_bpr_frozen_fwd: workspace %zu bytes required, got %zu", ws_bytes_for(B, dim), ws_bytes);
-        return CCR_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace("ccr_bpr_frozen_fwd", workspace, ws_bytes_for(B, dim), ws_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *part = (float *)align256(workspace);
 #define CALL(NV) \
@@ -456,10 +431,7 @@ extern "C" int ccr_bpr_frozen_bwd_dev(const float *table, int64_t n_rows, int di
                 "ccr_bpr_frozen_bwd_dev: null pointer or empty table");
     CCR_REQUIRE(((uintptr_t)table | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)dgamma | (uintptr_t)dbeta) % 16 == 0,
                 "ccr_bpr_frozen_bwd_dev: table, gamma, beta and the gradients must be 16-byte aligned");
-    if (!workspace || ws_bytes < ws_bytes_for(B, dim)) {
-        set_error("ccr_bpr_frozen_bwd_dev: workspace %zu bytes required, got %zu", ws_bytes_for(B, dim), ws_bytes);
-        return CCR_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace("ccr_bpr_frozen_bwd_dev", workspace, ws_bytes_for(B, dim), ws_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *partial = (float *)align256(workspace);
     const int nblocks = bwd_blocks(B);

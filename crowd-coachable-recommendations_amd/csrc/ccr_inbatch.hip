@@ -22,12 +22,9 @@
 
 #include <algorithm>
 
-#include "ccr_common.h"
+#include "ccr_loss_common.h"
 
 namespace ccr {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ const uint16_t *key_row(const uint16_t *P, const uint16_t *N, int B, int j, int dim) {
     return (j < B) ? P + (int64_t)j * dim : N + (int64_t)(j - B) * dim;
@@ -116,7 +113,7 @@ __global__ __launch_bounds__(64) void inbatch_fwd_kernel(const uint16_t *__restr
         float tm = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int j = t * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int j = mfma32_row(t * 32, e, h);
             const float v = (j < 2 * B) ? acc[e] * inv_t : -INFINITY;
             acc[e] = v;
             tm = fmaxf(tm, v);
@@ -174,8 +171,7 @@ __global__ __launch_bounds__(64) void inbatch_fwd_kernel(const uint16_t *__restr
         lse[i] = v;
         part = (double)(v - dgc);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
+    part = wave_sum(part);
     unsigned int t2 = 0;
     if (lane == 0) {
         __hip_atomic_store(tile_part + blockIdx.x, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -193,16 +189,6 @@ __global__ __launch_bounds__(64) void inbatch_fwd_kernel(const uint16_t *__restr
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void split3(float g, uint16_t &hi, uint16_t &mid, uint16_t &lo) {
-    const __bf16 a = (__bf16)g;
-    const float r1 = g - (float)a;
-    const __bf16 b = (__bf16)r1;
-    const __bf16 c = (__bf16)(r1 - (float)b);
-    hi = __builtin_bit_cast(uint16_t, a);
-    mid = __builtin_bit_cast(uint16_t, b);
-    lo = __builtin_bit_cast(uint16_t, c);
-}
-
 // Stamp the forward leaves in the workspace and the backward checks ON THE DEVICE (a mismatch -- a workspace another forward has
 // used in between, or none -- poisons the gradients with NaN instead of returning plausible garbage; no host round trip).
 struct InbatchStamp {
@@ -220,7 +206,7 @@ constexpr uint32_t INBATCH_MAGIC = 0x43434942u;   // 'CCIB'
 //   Gq [3] x (queries x keys)   parts of G[j][i]^T    (dQ: m = query i, k = key j),    ldq = round_up(2B, 64)
 //   QT (dim x queries) = Q^T    (dK's second operand),   KT (dim x keys) = [P ; N]^T   (dQ's)
 // grid.x = G tiles (64 keys x 64 queries) + Q tiles + K tiles (64 rows x 64 columns each), block = 256.
-constexpr int PREP_T = 64, PREP_P = PREP_T + 8;   // LDS pitch 72 bf16 = 144 B: 16-byte aligned rows, rows 4 banks apart
+constexpr int PREP_T = TILE64;
 __device__ __forceinline__ int64_t frag_major(int r, int k, int nchunks) {   // element offset of (row r, contraction index k), k % 8 == 0
     return ((((int64_t)(r >> 5) * nchunks + (k >> 6)) * 8 + ((k >> 3) & 7)) * 32 + (r & 31)) * 8;
 }
@@ -230,7 +216,7 @@ __global__ __launch_bounds__(256) void inbatch_prep_kernel(const float *__restri
                                                           const float *__restrict__ gscale_dev, const InbatchStamp *__restrict__ stamp,
                                                           uint32_t inv_t_bits, uint16_t *__restrict__ Gk, uint16_t *__restrict__ Gq,
                                                           uint16_t *__restrict__ QT, uint16_t *__restrict__ KT, int ldk, int ldq) {
-    __shared__ __attribute__((aligned(16))) uint16_t s_t[3][PREP_T][PREP_P];
+    __shared__ __attribute__((aligned(16))) uint16_t s_t[3][PREP_T][TILE64_PITCH];
     const int tid = threadIdx.x;
     const int gi = (B + PREP_T - 1) / PREP_T, gj = (2 * B + PREP_T - 1) / PREP_T, gd = (dim + PREP_T - 1) / PREP_T;
     int b = blockIdx.x;
@@ -272,8 +258,7 @@ __global__ __launch_bounds__(256) void inbatch_prep_kernel(const float *__restri
                 *reinterpret_cast<uint4 *>(base + frag_major(j, i0 + c0, ldk / 64)) = make_uint4(w[0], w[1], w[2], w[3]);
                 *reinterpret_cast<uint4 *>(base + frag_major(j, i0 + c0 + 8, ldk / 64)) = make_uint4(w[4], w[5], w[6], w[7]);
             }
-#pragma unroll
-            for (int e = 0; e < 16; ++e) s_t[p][c0 + e][r] = part[p][e];   // transposed: [query][key]
+            tile64_scatter16(s_t[p], r, c0, part[p]);   // transposed: [query][key]
         }
         __syncthreads();
         const int i = i0 + r;
@@ -297,23 +282,8 @@ __global__ __launch_bounds__(256) void inbatch_prep_kernel(const float *__restri
         const int r = tid >> 2, c0 = (tid & 3) * 16;   // row r0 + r, columns d0 + c0 .. + 16
         const int row = r0 + r;
         uint16_t v[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = 0;
-        if (row < rows) {
-            const uint16_t *src = isq ? Q + (int64_t)row * dim : key_row(P, N, B, row, dim);
-#pragma unroll
-            for (int h8 = 0; h8 < 2; ++h8) {
-                const int dc = d0 + c0 + 8 * h8;
-                if (dc < dim) {   // dim % 16 == 0 and dc % 8 == 0: whole 16-byte vectors
-                    const uint4 q = *reinterpret_cast<const uint4 *>(src + dc);
-                    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[8 * h8 + 2 * e] = (uint16_t)(w[e] & 0xffffu), v[8 * h8 + 2 * e + 1] = (uint16_t)(w[e] >> 16);
-                }
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) s_t[0][c0 + e][r] = v[e];
+        tile64_load16(isq ? Q + (int64_t)row * dim : key_row(P, N, B, row, dim), row < rows, d0 + c0, dim, v);   // dim % 16 == 0
+        tile64_scatter16(s_t[0], r, c0, v);
     }
     __syncthreads();
     {
@@ -337,7 +307,6 @@ __global__ __launch_bounds__(256) void inbatch_gemm3_kernel(const uint16_t *__re
                                                            float *__restrict__ dN) {
     __shared__ float s_part[4][32][64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    (void)0;
     const int ntn = (dim + G3_TN - 1) / G3_TN;
     int b = blockIdx.x;
     const bool for_q = b < nq_blocks;
@@ -386,7 +355,7 @@ __global__ __launch_bounds__(256) void inbatch_gemm3_kernel(const uint16_t *__re
         fetch(0, c + 2);
         if (c + 1 < c_hi) mma(1);
     }
-    // C layout of v_mfma_f32_32x32x16: column = lane & 31, register e -> row (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+    // C layout of v_mfma_f32_32x32x16: column = lane & 31, register e -> row mfma32_row(0, e, lane >> 5)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -396,7 +365,7 @@ __global__ __launch_bounds__(256) void inbatch_gemm3_kernel(const uint16_t *__re
         const int r = idx >> 6, ln = idx & 63;
         const float v = ((s_part[0][r][ln] + s_part[1][r][ln]) + s_part[2][r][ln]) + s_part[3][r][ln];
         const int t = r >> 4, e = r & 15;
-        const int mrow = m0 + (e & 3) + 8 * (e >> 2) + 4 * (ln >> 5), ncol = n0 + 32 * t + (ln & 31);
+        const int mrow = mfma32_row(m0, e, ln >> 5), ncol = n0 + 32 * t + (ln & 31);
         if (mrow < M && ncol < dim) {
             float *crow = for_q ? dQ + (int64_t)mrow * dim : (mrow < B ? dP + (int64_t)mrow * dim : dN + (int64_t)(mrow - B) * dim);
             crow[ncol] = v;
@@ -416,16 +385,11 @@ __global__ __launch_bounds__(256) void inbatch_pack3_kernel(const float *__restr
     const float *src = blockIdx.y == 0 ? q : (blockIdx.y == 1 ? p : n);
     uint16_t *dst = out + (int64_t)blockIdx.y * count;
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < count; i += (int64_t)gridDim.x * 256 * 8) {   // count % 8 == 0
-        const float4 v0 = *reinterpret_cast<const float4 *>(src + i), v1 = *reinterpret_cast<const float4 *>(src + i + 4);
-        const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        uint32_t w[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            w[e] = (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f[2 * e]) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f[2 * e + 1]) << 16);
-        *reinterpret_cast<uint4 *>(dst + i) = make_uint4(w[0], w[1], w[2], w[3]);
+        const uint4 w = pack8_bf16(src + i);
+        *reinterpret_cast<uint4 *>(dst + i) = w;
         if (frag) {
             const int row = (int)(i / dim) + (int)blockIdx.y * B, d = (int)(i % dim);
-            *reinterpret_cast<uint4 *>(frag + frag_major(row, d, dim / 64)) = make_uint4(w[0], w[1], w[2], w[3]);
+            *reinterpret_cast<uint4 *>(frag + frag_major(row, d, dim / 64)) = w;
         }
     }
 }
@@ -457,41 +421,33 @@ struct InbatchWs {
     size_t zero_bytes;   // tickets + stamp: zeroed before every forward
     size_t total;
 };
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
 InbatchWs inbatch_ws(void *workspace, int B, int dim) {
     InbatchWs w;
-    const size_t partial = up256((size_t)3 * 64 * B * sizeof(float));
     w.ldS = (B + 3) / 4 * 4;
     w.ldk = (B + 63) / 64 * 64;
     w.ldq = (2 * B + 63) / 64 * 64;
-    const size_t sbytes = up256((size_t)2 * B * w.ldS * sizeof(float));
     const int qtiles = (B + 31) / 32;
-    const size_t tickets = up256((size_t)(qtiles + 1) * 4);
-    w.zero_bytes = tickets + 256;
-    const size_t parts = up256((size_t)qtiles * 8);
-    char *base = (char *)workspace;
-    w.pm = (float *)base;
+    const size_t dimp = (size_t)(dim + 63) / 64 * 64;   // every operand height and width is padded to a multiple of 64
+    Carver c{(char *)workspace};
+    w.pm = c.take<float>((size_t)3 * 64 * B * sizeof(float));
     w.pl = w.pm + (size_t)64 * B;
     w.pd = w.pl + (size_t)64 * B;
-    w.S = (float *)(base + partial);
-    w.tile_ticket = (unsigned int *)(base + partial + sbytes);
+    w.S = c.take<float>((size_t)2 * B * w.ldS * sizeof(float));
+    const size_t zero_from = c.off;
+    w.tile_ticket = c.take<unsigned int>((size_t)(qtiles + 1) * 4);
     w.loss_ticket = w.tile_ticket + qtiles;
-    w.stamp = (uint32_t *)(base + partial + sbytes + tickets);
-    w.tile_part = (double *)(base + partial + sbytes + w.zero_bytes);
-    size_t off = partial + sbytes + w.zero_bytes + parts;
-    const size_t dimp = (size_t)(dim + 63) / 64 * 64;   // every operand height and width is padded to a multiple of 64
-    w.Gk = (uint16_t *)(base + off), off += up256((size_t)3 * w.ldq * w.ldk * 2);
-    w.Gq = (uint16_t *)(base + off), off += up256((size_t)3 * w.ldk * w.ldq * 2);
-    w.QT = (uint16_t *)(base + off), off += up256(dimp * w.ldk * 2);
-    w.KT = (uint16_t *)(base + off), off += up256(dimp * w.ldq * 2);
-    w.Xf = (uint16_t *)(base + off), off += up256((size_t)3 * B * dimp * 2);   // the forward's fragment-major [Q ; P ; N] (fp32 entry point)
-    w.total = off + 256;   // + 256: the caller's pointer need only be 16-byte aligned
+    w.stamp = c.take<uint32_t>(256);
+    w.zero_bytes = c.off - zero_from;
+    w.tile_part = c.take<double>((size_t)qtiles * 8);
+    w.Gk = c.take<uint16_t>((size_t)3 * w.ldq * w.ldk * 2);
+    w.Gq = c.take<uint16_t>((size_t)3 * w.ldk * w.ldq * 2);
+    w.QT = c.take<uint16_t>(dimp * w.ldk * 2);
+    w.KT = c.take<uint16_t>(dimp * w.ldq * 2);
+    w.Xf = c.take<uint16_t>((size_t)3 * B * dimp * 2);   // the forward's fragment-major [Q ; P ; N] (fp32 entry point)
+    w.total = c.off + 256;   // + 256: the caller's pointer need only be 16-byte aligned
     return w;
 }
-char *align256(void *p) { return (char *)p + (256 - (uintptr_t)p % 256) % 256; }
 }  // namespace
-
-extern "C" int ccr_inbatch_pack3_bf16(const float *q, const float *p, const float *n, int B, int dim, uint16_t *out, void *stream);
 
 extern "C" size_t ccr_inbatch_ce_workspace_bytes(int B, int dim) {
     if (B <= 0 || dim <= 0) return 0;
@@ -503,10 +459,7 @@ static int inbatch_fwd_impl(const uint16_t *Qe, const uint16_t *Pe, const uint16
     CCR_REQUIRE(Qe && Pe && Ne && loss && lse, "ccr_inbatch_ce_fwd: null pointer");
     CCR_REQUIRE(B >= 1 && dim >= 16 && dim % 16 == 0, "ccr_inbatch_ce_fwd: B=%d dim=%d (dim %% 16 == 0)", B, dim);
     CCR_REQUIRE(((uintptr_t)Qe | (uintptr_t)Pe | (uintptr_t)Ne) % 16 == 0, "ccr_inbatch_ce_fwd: embedding pointers must be 16-byte aligned");
-    if (!workspace || ws_bytes < ccr_inbatch_ce_workspace_bytes(B, dim)) {
-        set_error("ccr_inbatch_ce_fwd: workspace %zu bytes required, got %zu", ccr_inbatch_ce_workspace_bytes(B, dim), ws_bytes);
-        return CCR_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace("ccr_inbatch_ce_fwd", workspace, ccr_inbatch_ce_workspace_bytes(B, dim), ws_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const InbatchWs w = inbatch_ws(align256(workspace), B, dim);
     const int splits = pick_splits(B);
@@ -549,10 +502,7 @@ extern "C" int ccr_inbatch_ce_fwd_f32(const float *q, const float *p, const floa
                                       uint16_t *packed, float *loss, float *lse, void *workspace, size_t ws_bytes, void *stream) {
     CCR_REQUIRE(packed && workspace, "ccr_inbatch_ce_fwd_f32: null pointer");
     CCR_REQUIRE(B >= 1 && dim >= 16 && dim % 16 == 0, "ccr_inbatch_ce_fwd_f32: B=%d dim=%d (dim %% 16 == 0)", B, dim);
-    if (ws_bytes < ccr_inbatch_ce_workspace_bytes(B, dim)) {
-        set_error("ccr_inbatch_ce_fwd_f32: workspace %zu bytes required, got %zu", ccr_inbatch_ce_workspace_bytes(B, dim), ws_bytes);
-        return CCR_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace("ccr_inbatch_ce_fwd_f32", workspace, ccr_inbatch_ce_workspace_bytes(B, dim), ws_bytes)) return rc;
     const bool frag = B % 32 == 0 && dim % 128 == 0 && getenv("CCR_INBATCH_ROWMAJOR") == nullptr;
     const InbatchWs w = inbatch_ws(align256(workspace), B, dim);
     const int rc = launch_pack3(q, p, n, B, dim, packed, frag ? w.Xf : nullptr, stream, w.tile_ticket, (int)(w.zero_bytes / 4));
@@ -567,10 +517,7 @@ static int inbatch_bwd_impl(const uint16_t *Qe, const uint16_t *Pe, const uint16
     CCR_REQUIRE(Qe && Pe && Ne && lse && dQ && dP && dN, "ccr_inbatch_ce_bwd: null pointer");
     CCR_REQUIRE(B >= 1 && dim >= 16 && dim % 16 == 0, "ccr_inbatch_ce_bwd: B=%d dim=%d (dim %% 16 == 0)", B, dim);
     CCR_REQUIRE(((uintptr_t)Qe | (uintptr_t)Pe | (uintptr_t)Ne) % 16 == 0, "ccr_inbatch_ce_bwd: embedding pointers must be 16-byte aligned");
-    if (!workspace || ws_bytes < ccr_inbatch_ce_workspace_bytes(B, dim)) {
-        set_error("ccr_inbatch_ce_bwd: workspace %zu bytes required, got %zu", ccr_inbatch_ce_workspace_bytes(B, dim), ws_bytes);
-        return CCR_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace("ccr_inbatch_ce_bwd", workspace, ccr_inbatch_ce_workspace_bytes(B, dim), ws_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const InbatchWs w = inbatch_ws(align256(workspace), B, dim);   // the FORWARD's workspace: it holds the scaled logits S and the stamp
     const float gscale = inv_temperature * grad_out / (float)B;

@@ -20,17 +20,15 @@
 // makes every gradient NaN.  Every address is formed from clamped or padded indices, whatever label[] holds.
 #include <algorithm>
 
-#include "ccr_common.h"
+#include "ccr_loss_common.h"
 
 namespace ccr {
 namespace poolce {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // a 16-byte vector of 8 bf16 in flight between global memory and LDS
 
-constexpr int KC = 64;         // contraction depth of one staged chunk
-constexpr int LP = KC + 8;     // LDS row pitch in bf16 elements
+constexpr int KC = TILE64;         // contraction depth of one staged chunk
+constexpr int LP = TILE64_PITCH;   // LDS row pitch in bf16 elements (KC + 8)
 constexpr uint32_t POOL_MAGIC = 0x43435043u;   // 'CCPC'
 constexpr int MAX_NQ = 1 << 16, MAX_NC = 1 << 20, MAX_DIM = 8192;
 constexpr int64_t MAX_LOGITS = (int64_t)1 << 28;   // elements of S: 4 096 x 65 536 = 1 GiB of fp32, the largest shape asked for
@@ -41,31 +39,14 @@ struct PoolHead {
     float num, den;
 };
 
-__device__ __forceinline__ void split3(float g, uint16_t &hi, uint16_t &mid, uint16_t &lo) {
-    const __bf16 a = (__bf16)g;
-    const float r1 = g - (float)a;
-    const __bf16 b = (__bf16)r1;
-    const __bf16 c = (__bf16)(r1 - (float)b);
-    hi = __builtin_bit_cast(uint16_t, a);
-    mid = __builtin_bit_cast(uint16_t, b);
-    lo = __builtin_bit_cast(uint16_t, c);
-}
-
 // fp32 -> bf16 (RNE: torch's .to(bfloat16) bits) of the queries (blockIdx.y = 0) and the candidates (1).  counts % 8 == 0.
 __global__ __launch_bounds__(256) void pool_pack_kernel(const float *__restrict__ q, const float *__restrict__ c, int64_t count_q, int64_t count_c,
                                                        uint16_t *__restrict__ out) {
     const float *src = blockIdx.y == 0 ? q : c;
     const int64_t count = blockIdx.y == 0 ? count_q : count_c;
     uint16_t *dst = out + (blockIdx.y == 0 ? 0 : count_q);
-    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < count; i += (int64_t)gridDim.x * 256 * 8) {
-        const float4 v0 = *reinterpret_cast<const float4 *>(src + i), v1 = *reinterpret_cast<const float4 *>(src + i + 4);
-        const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        uint32_t w[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            w[e] = (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f[2 * e]) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f[2 * e + 1]) << 16);
-        *reinterpret_cast<uint4 *>(dst + i) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
+    for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < count; i += (int64_t)gridDim.x * 256 * 8)
+        *reinterpret_cast<uint4 *>(dst + i) = pack8_bf16(src + i);
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
@@ -124,7 +105,7 @@ __global__ __launch_bounds__(256) void pool_logits_kernel(const uint16_t *__rest
                 for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
         }
     }
-    // C layout of v_mfma_f32_32x32x16: column = lane & 31, register e -> row (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+    // C layout of v_mfma_f32_32x32x16: column = lane & 31, register e -> row mfma32_row(0, e, lane >> 5)
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -132,21 +113,10 @@ __global__ __launch_bounds__(256) void pool_logits_kernel(const uint16_t *__rest
             const int j = j0 + wn * 64 + tn * 32 + l31;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int i = i0 + wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int i = mfma32_row(i0 + wm * 64 + tm * 32, e, h);
                 if (i < n_q && j < n_c) S[(int64_t)i * ldS + j] = acc[tm][tn][e] * inv_t;
             }
         }
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // one workgroup per query: lse_i (NaN for a label outside the pool), cew_i = w_i ce_i, wq_i = w_i
@@ -192,22 +162,12 @@ __global__ __launch_bounds__(256) void pool_lse_kernel(const float *__restrict__
 // out = {loss, numerator, denominator}; the same two sums and the stamp go to the workspace's head
 __global__ __launch_bounds__(256) void pool_finish_kernel(const float *__restrict__ cew, const float *__restrict__ wq, int n_q, int n_c, int dim,
                                                          uint32_t inv_t_bits, float *__restrict__ out, PoolHead *__restrict__ head) {
-    __shared__ double s_n[256], s_d[256];
-    const int tid = threadIdx.x;
-    double n = 0.0, d = 0.0;
-    for (int i = tid; i < n_q; i += 256) n += (double)cew[i], d += (double)wq[i];
-    s_n[tid] = n, s_d[tid] = d;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if (tid < s) s_n[tid] += s_n[tid + s], s_d[tid] += s_d[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        out[0] = (float)(s_n[0] / s_d[0]), out[1] = (float)s_n[0], out[2] = (float)s_d[0];
-        head->num = (float)s_n[0], head->den = (float)s_d[0];
+    block256_sum2(cew, wq, n_q, [&](double num, double den) {
+        out[0] = (float)(num / den), out[1] = (float)num, out[2] = (float)den;
+        head->num = (float)num, head->den = (float)den;
         head->n_q = (uint32_t)n_q, head->n_c = (uint32_t)n_c, head->dim = (uint32_t)dim, head->inv_t_bits = inv_t_bits;
         head->magic = POOL_MAGIC;   // every logit of this forward is in the workspace
-    }
+    });
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------
@@ -225,22 +185,8 @@ __global__ __launch_bounds__(256) void pool_transpose_kernel(const uint16_t *__r
     uint16_t *XT = isq ? QT : CT;
     const int tid = threadIdx.x, r = tid >> 2, c0 = (tid & 3) * 16;
     uint16_t v[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) v[e] = 0;
-    if (r0 + r < rows) {
-#pragma unroll
-        for (int h8 = 0; h8 < 2; ++h8) {
-            const int dc = d0 + c0 + 8 * h8;
-            if (dc < dim) {
-                const uint4 q = *reinterpret_cast<const uint4 *>(X + (int64_t)(r0 + r) * dim + dc);
-                const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[8 * h8 + 2 * e] = (uint16_t)(w[e] & 0xffffu), v[8 * h8 + 2 * e + 1] = (uint16_t)(w[e] >> 16);
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) s_t[c0 + e][r] = v[e];
+    tile64_load16(X + (int64_t)(r0 + r) * dim, r0 + r < rows, d0 + c0, dim, v);
+    tile64_scatter16(s_t, r, c0, v);
     __syncthreads();
     const uint4 *src = reinterpret_cast<const uint4 *>(&s_t[r][c0]);
     uint16_t *dst = XT + (int64_t)(d0 + r) * ld + r0 + c0;
@@ -390,7 +336,7 @@ __global__ __launch_bounds__(256) void pool_grad_kernel(const float *__restrict_
         const int n = n0 + wn * 64 + t * 32 + l31;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int m = m0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int m = mfma32_row(m0 + wm * 32, e, h);
             if (m < M && n < dim) dst[(int64_t)m * dim + n] = acc[t][e];
         }
     }
@@ -427,28 +373,25 @@ struct PoolWs {
     int ks_q, ks_c;
     size_t total;
 };
-static size_t up256(size_t n) { return (n + 255) / 256 * 256; }
 static PoolWs pool_ws(void *workspace, int n_q, int n_c, int dim) {
     PoolWs w;
-    char *base = (char *)workspace;
-    size_t off = 256;
-    w.head = (PoolHead *)base;
     w.ldS = ((int64_t)n_c + 63) / 64 * 64;
     w.ldq = ((int64_t)n_q + 63) / 64 * 64;
     const size_t dimp = (size_t)(dim + 127) / 128 * 128;
-    w.S = (float *)(base + off), off += up256((size_t)w.ldq * w.ldS * sizeof(float));
-    w.cew = (float *)(base + off), off += up256((size_t)n_q * sizeof(float));
-    w.wq = (float *)(base + off), off += up256((size_t)n_q * sizeof(float));
-    w.QT = (uint16_t *)(base + off), off += up256(dimp * w.ldq * 2);
-    w.CT = (uint16_t *)(base + off), off += up256(dimp * w.ldS * 2);
+    Carver c{(char *)workspace};
+    w.head = c.take<PoolHead>(256);
+    w.S = c.take<float>((size_t)w.ldq * w.ldS * sizeof(float));
+    w.cew = c.take<float>((size_t)n_q * sizeof(float));
+    w.wq = c.take<float>((size_t)n_q * sizeof(float));
+    w.QT = c.take<uint16_t>(dimp * w.ldq * 2);
+    w.CT = c.take<uint16_t>(dimp * w.ldS * 2);
     w.ks_q = pick_ksplit(n_q, n_c, dim);
     w.ks_c = pick_ksplit(n_c, n_q, dim);
     const size_t pq = w.ks_q > 1 ? (size_t)w.ks_q * n_q * dim * sizeof(float) : 0, pc = w.ks_c > 1 ? (size_t)w.ks_c * n_c * dim * sizeof(float) : 0;
-    w.partial = (float *)(base + off), off += up256(std::max(pq, pc));
-    w.total = off + 256;   // + 256: the caller's pointer need only be 16-byte aligned
+    w.partial = c.take<float>(std::max(pq, pc));
+    w.total = c.off + 256;   // + 256: the caller's pointer need only be 16-byte aligned
     return w;
 }
-static char *align256(void *p) { return (char *)p + (256 - (uintptr_t)p % 256) % 256; }
 
 static bool shape_ok(const char *who, int n_q, int n_c, int dim) {
     if (n_q < 1 || n_c < 1 || dim < 8 || dim % 8 != 0) {
@@ -480,11 +423,7 @@ extern "C" int ccr_pool_ce_fwd(const uint16_t *Q, const uint16_t *C, const int32
     if (!shape_ok("ccr_pool_ce_fwd", n_q, n_c, dim)) return CCR_ERR_INVALID;
     CCR_REQUIRE(Q && C && label && out3 && lse, "ccr_pool_ce_fwd: null pointer");
     CCR_REQUIRE(((uintptr_t)Q | (uintptr_t)C) % 16 == 0, "ccr_pool_ce_fwd: embedding pointers must be 16-byte aligned");
-    const size_t need = pool_ws(nullptr, n_q, n_c, dim).total;
-    if (!workspace || ws_bytes < need) {
-        set_error("ccr_pool_ce_fwd: workspace %zu bytes required, got %zu", need, ws_bytes);
-        return CCR_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace("ccr_pool_ce_fwd", workspace, pool_ws(nullptr, n_q, n_c, dim).total, ws_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const PoolWs w = pool_ws(align256(workspace), n_q, n_c, dim);
     hipLaunchKernelGGL(pool_logits_kernel, dim3((n_c + 127) / 128, (n_q + 127) / 128), dim3(256), 0, s, Q, C, n_q, n_c, dim, inv_temperature, w.S, w.ldS,
@@ -515,11 +454,7 @@ extern "C" int ccr_pool_ce_bwd_dev(const uint16_t *Q, const uint16_t *C, const i
     if (!shape_ok("ccr_pool_ce_bwd_dev", n_q, n_c, dim)) return CCR_ERR_INVALID;
     CCR_REQUIRE(Q && C && label && lse && grad_out_dev && dQ && dC, "ccr_pool_ce_bwd_dev: null pointer");
     CCR_REQUIRE(((uintptr_t)Q | (uintptr_t)C | (uintptr_t)dQ | (uintptr_t)dC) % 16 == 0, "ccr_pool_ce_bwd_dev: pointers must be 16-byte aligned");
-    const size_t need = pool_ws(nullptr, n_q, n_c, dim).total;
-    if (!workspace || ws_bytes < need) {
-        set_error("ccr_pool_ce_bwd_dev: workspace %zu bytes required, got %zu", need, ws_bytes);
-        return CCR_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace("ccr_pool_ce_bwd_dev", workspace, pool_ws(nullptr, n_q, n_c, dim).total, ws_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const PoolWs w = pool_ws(align256(workspace), n_q, n_c, dim);   // the FORWARD's workspace: the scaled logits and the stamp
     const uint32_t inv_t_bits = __builtin_bit_cast(uint32_t, inv_temperature);
