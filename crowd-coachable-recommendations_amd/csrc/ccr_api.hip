@@ -7,6 +7,8 @@
 
 #include <algorithm>
 #include <mutex>
+#include <set>
+#include <utility>
 #include <vector>
 
 #include "ccr_index.h"
@@ -124,6 +126,20 @@ void block_give(int device, void *p, size_t bytes) {
     if (drop) (void)hipFree(drop);
 }
 }  // namespace
+
+// The dynamic-LDS opt-in (> 64 KiB) is a per-device function attribute: it is set the first time a kernel is launched
+// on a device and remembered per (kernel, device) -- not on every launch.
+int ccr::ensure_dynamic_lds(const void *kernel, size_t lds) {
+    static std::mutex mu;
+    static std::set<std::pair<const void *, int>> done;
+    int dev = 0;
+    CCR_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({kernel, dev})) return CCR_OK;
+    CCR_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    done.insert({kernel, dev});
+    return CCR_OK;
+}
 
 // row_bounds (device, n_rows floats, or null): upper bounds of the packed rows' norms as ccr_pack_bf16_ex wrote them (borrowed for
 // the life of the index: the select stage reads them per candidate); without them the index makes its own pass over the shard.
@@ -307,6 +323,42 @@ static GemmArgs filter_args(const ccr_index *ix, const Plan &p, const SearchWs &
     return g;
 }
 
+// Arguments of the stage launchers for the search in ix->plan and ix->pending, whole batch: what follows from the index, the plan and
+// the workspace, a line per group of the struct.  A call site sets what is particular to it.
+// thresholds of rank k from the sample's group maxima, to w.thr / w.cq
+static ThresholdArgs threshold_args(const ccr_index *ix, const SearchWs &w) {
+    const Plan &p = ix->plan;
+    ThresholdArgs t{};
+    t.gmax = w.gmax, t.n_groups = (int64_t)p.sample_tiles * GROUPS_PER_TILE, t.sample_stride = p.sample_stride;
+    t.n_q = ix->pending.n_q, t.nq_pad = p.nq_pad, t.k = ix->pending.k, t.qnorm = w.qnorm;
+    t.dmax_bits = ix->dmax_bits, t.dim = ix->dim, t.tile_norm = ix->tile_norm;
+    t.thr = w.thr, t.cq = w.cq, t.phases = ix->knobs.thr_phases;
+    return t;
+}
+
+// w.thr re-tightened from candidate lists of the main pass's sub-list count; the call site says which lists (nsub, lay)
+static ThresholdUpdateArgs update_args(const ccr_index *ix, const SearchWs &w) {
+    ThresholdUpdateArgs u{};
+    u.cand = w.cand, u.cnt = w.cnt, u.sp = ix->plan.sublists;
+    u.n_q = ix->pending.n_q, u.nq_pad = ix->plan.nq_pad, u.k = ix->pending.k;
+    u.cq = w.cq, u.tile_norm = ix->tile_norm, u.thr = w.thr;
+    return u;
+}
+
+// the select of the batch's own query rows and bounds, to its outputs; the call site says which lists (ranges, sp, lay) and where the flags go
+static SelectArgs select_args(const ccr_index *ix, const SearchWs &w) {
+    const Plan &p = ix->plan;
+    const auto &pd = ix->pending;
+    SelectArgs a{};
+    a.cand = w.cand, a.cnt = w.cnt, a.n_q = pd.n_q, a.nq_pad = p.nq_pad;
+    a.k = pd.k, a.rescore_cap = p.rescore_cap, a.regular_cap = p.rescore_regular, a.compact = p.select_compact;
+    a.D = ix->D, a.dt = ix->dtype, a.dim = ix->dim, a.n_rows = ix->n_rows;
+    a.tile_norm = ix->tile_norm, a.row_norm = ix->row_norm, a.dmax_bits = ix->dmax_bits, a.id_offset = ix->id_out;
+    a.Q = pd.Q, a.thr = w.thr, a.cq = w.cq;
+    a.out_scores = pd.out_scores, a.out_ids = pd.out_ids;
+    return a;
+}
+
 // EPI_STORE: MFMA score rows of the n_q queries at Q against every corpus row, in `ranges` ranges, to out [n_q][pitch] (0: n_rows)
 static int store_scores(const ccr_index *ix, const uint16_t *Q, int n_q, int ranges, float *out, int64_t pitch, hipStream_t s) {
     GemmArgs g = gemm_args(ix, Q, n_q, (int)round_up(n_q, TILE_Q));
@@ -343,7 +395,7 @@ static int margin_for_rows(const ccr_index *ix, const uint16_t *Qc, const float 
 
 // The main pass: one launch per phase (work items [begin, end) of every XCD set), the thresholds re-tightened from the candidates
 // of the ranges completed so far between two launches.
-static int run_main_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, const uint16_t *Q, int n_q, int k, hipStream_t s) {
+static int run_main_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, const uint16_t *Q, int n_q, hipStream_t s) {
     // (blocks of p.tile_q queries; the sample pass walks blocks of TILE_Q)
     GemmArgs gm = filter_args(ix, p, w, Q, n_q, p.nq_pad, p.main_qblocks, p.main_qgroups, w.thr, w.cq, p.cand);
     gm.qsplit = p.main_qsplit;   // (single launch: items keeps its value, every XCD set holds ranges / 8 * blocks items either way)
@@ -354,20 +406,20 @@ static int run_main_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, 
     }
     const int nrc = NUM_XCD / gm.qgroups, qb_per = gm.qblocks / gm.qgroups, items = p.ranges / nrc * qb_per;
     const int bounds[4] = {0, p.item_a, p.item_b, items};
-    int done = 0, updates = 0, prev_full = 0, prev_part = 0, prev_blocks = 0;
+    ThresholdUpdateArgs u = update_args(ix, w);   // (prev_*: nothing before the first re-tightening)
+    u.lay = p.cand, u.qb_per = qb_per, u.tile_q = p.tile_q, u.top = p.item_b ? w.top : nullptr;
+    int done = 0;
     for (int ph = 1; ph < 4; ++ph) {
         if (bounds[ph] <= done) continue;
         if (done > 0) {
-            const int rl_full = done / qb_per, part = done % qb_per;   // complete range rows; blocks done of the started one
-            const int full = rl_full * nrc * p.sublists, partial = part ? (rl_full + 1) * nrc * p.sublists : 0;
-            const bool more = bounds[ph] < items && ph < 3;   // another re-tightening follows this phase
-            const int rc = launch_threshold_update(w.cand, w.cnt, full, partial, part, prev_full, prev_part, prev_blocks, qb_per, p.sublists, n_q,
-                                                   p.nq_pad, p.cand, k, w.cq, ix->tile_norm, p.item_b ? w.top : nullptr, updates > 0, more, w.thr, s, p.tile_q);
+            const int rl_full = done / qb_per;   // complete range rows
+            u.part_blocks = done % qb_per;       // blocks done of the started one
+            u.nsub = rl_full * nrc * p.sublists;
+            u.nsub_part = u.part_blocks ? (rl_full + 1) * nrc * p.sublists : 0;
+            u.top_out = bounds[ph] < items && ph < 3;   // another re-tightening follows this phase
+            const int rc = launch_threshold_update(u, s);
             if (rc != CCR_OK) return rc;
-            prev_full = full;
-            prev_part = partial;
-            prev_blocks = part;
-            ++updates;
+            u.prev_nsub = u.nsub, u.prev_part = u.nsub_part, u.prev_blocks = u.part_blocks, u.top_in = true;
         }
         gm.item_begin = done;
         gm.item_end = bounds[ph];
@@ -445,12 +497,12 @@ static int fused_stats(ccr_index *ix, uint32_t nflag, unsigned long long ncand) 
 // and FLAG_DENSE).  The sample's group maxima are still in the workspace: the CONSERVATIVE threshold (the k-th largest, a valid
 // bound) is computed now -- only on this path -- and those of the nflag flagged queries join the retry under it.
 static int recover_thresholds(const ccr_index *ix, const SearchWs &w, int nflag) {
-    const auto &pd = ix->pending;
-    const int rc = launch_threshold(w.gmax, (int64_t)ix->plan.sample_tiles * GROUPS_PER_TILE, pd.n_q, ix->plan.nq_pad, pd.k, w.qnorm, ix->dmax_bits,
-                                    ix->dim, ix->tile_norm, ix->plan.sample_stride, w.thr_safe, w.cq_safe, pd.stream, nullptr, 0, nullptr, 0,
-                                    ix->knobs.thr_phases);
+    hipStream_t s = ix->pending.stream;
+    ThresholdArgs t = threshold_args(ix, w);
+    t.thr = w.thr_safe, t.cq = w.cq_safe;
+    const int rc = launch_threshold(t, s);
     if (rc != CCR_OK) return rc;
-    return launch_underfilled_to_retry(w.flag_list, 0, nflag, w.thr_safe, w.thr, pd.stream);
+    return launch_underfilled_to_retry(w.flag_list, 0, nflag, w.thr_safe, w.thr, s);
 }
 
 // appends the n queries of a device list to the dense list (n_dense entries so far)
@@ -479,9 +531,11 @@ static int retry_group(ccr_index *ix, const SearchWs &w, const uint32_t *cur, in
         const GemmArgs g = filter_args(ix, p, w, w.Q2, n_cur, pad2, pad2 / TILE_Q, pick_qgroups(pad2 / TILE_Q, ix->dim, ix->knobs), w.thr2, w.cq2, lay2);
         rc = launch_gemm(g, ix->dtype, p.mfma16 ? MAIN_16X16 : MAIN_32X32, EPI_FILTER, p.grid, s);   // TILE_Q blocks: never the wide kernel
         if (rc != CCR_OK) return rc;
-        rc = launch_select_rescore(w.cand, w.cnt, nsub_all, p.sublists, n_cur, pad2, lay2, pd.k, p.rescore_cap, p.select_compact, ix->n_rows,
-                                   w.thr2, w.cq2, ix->tile_norm, ix->row_norm, ix->dmax_bits, w.Q2, ix->D, ix->dtype, ix->dim, ix->id_out, pd.out_scores, pd.out_ids,
-                                   w.flag2, w.flag2 + 16, nullptr, cur, s, nullptr, 0, 0, 0, nullptr, 0, p.rescore_regular);
+        SelectArgs sel = select_args(ix, w);   // of the gathered queries: row i is query cur[i]
+        sel.ranges = nsub_all, sel.sp = p.sublists, sel.lay = lay2, sel.n_q = n_cur, sel.nq_pad = pad2;
+        sel.Q = w.Q2, sel.thr = w.thr2, sel.cq = w.cq2, sel.out_rows = cur;
+        sel.flag_count = w.flag2, sel.flag_list = w.flag2 + 16;
+        rc = launch_select_rescore(sel, s);
         if (rc != CCR_OK) return rc;
         ix->stats.n_retried += n_cur;
         uint32_t again = 0;
@@ -500,8 +554,9 @@ static int retry_group(ccr_index *ix, const SearchWs &w, const uint32_t *cur, in
         n_cur = (int)hc[0];
         // none left, three rounds done, or no progress (every retried query overflowed again): the dense path takes them
         if (n_cur == 0 || round == 2 || n_cur >= n) break;
-        rc = launch_threshold_update(w.cand, w.cnt, nsub_all, 0, 0, 0, 0, 0, 1, p.sublists, n, pad2, lay2, pd.k, w.cq2, ix->tile_norm, nullptr,
-                                     false, false, w.thr2, s);
+        ThresholdUpdateArgs u = update_args(ix, w);   // of the round's gathered queries, from its lists
+        u.nsub = nsub_all, u.lay = lay2, u.n_q = n, u.nq_pad = pad2, u.cq = w.cq2, u.thr = w.thr2;
+        rc = launch_threshold_update(u, s);
         if (rc != CCR_OK) return rc;
         rc = launch_scatter_thresholds(list, n, w.thr2, w.thr, s);
         if (rc != CCR_OK) return rc;
@@ -517,8 +572,9 @@ static int retry_flagged(ccr_index *ix, const SearchWs &w, int n_retry, int &n_d
     if (nsub_all > 2048) return to_dense(w, w.retry_list, n_retry, n_dense, pd.stream);
     // thresholds re-tightened from everything the first attempt recorded (truncated lists included) -- for every flagged
     // query at once, before the candidate area is reused
-    int rc = launch_threshold_update(w.cand, w.cnt, p.first_nsub, 0, 0, 0, 0, 0, 1, p.first_sp, pd.n_q, p.nq_pad, p.first_lay, pd.k, w.cq,
-                                     ix->tile_norm, nullptr, false, false, w.thr, pd.stream);
+    ThresholdUpdateArgs u = update_args(ix, w);
+    u.nsub = p.first_nsub, u.sp = p.first_sp, u.lay = p.first_lay;
+    int rc = launch_threshold_update(u, pd.stream);
     if (rc != CCR_OK) return rc;
     // The flagged queries are retried in GROUPS that get the whole candidate area to themselves: the fewer queries share
     // it, the larger every sub-list.  A group is as large as still leaves four times the first attempt's capacity (when
@@ -682,6 +738,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     }
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_BEGIN], s));
     if (!p.fused) return search_dense(ix, w, Q_bf16, n_q, k, out_scores, out_ids, flags, s);
+    ix->pending = {false, Q_bf16, n_q, k, out_scores, out_ids, (char *)workspace, s};   // what the stages below and search_complete read
 
     CCR_HIP_CHECK(hipMemsetAsync(w.flag_count, 0, 64, s));
     // every (range, query block) item with at least one tile writes its counters at its end, for the columns below
@@ -703,26 +760,30 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     if (rc != CCR_OK) return rc;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SAMPLE_END], s));
     // (small batches: the streaming pass's sub-list counters are cleared by the threshold launch)
-    rc = launch_threshold(w.gmax, (int64_t)p.sample_tiles * GROUPS_PER_TILE, n_q, p.nq_pad, p.opt_rank ? p.opt_rank : k, w.qnorm, ix->dmax_bits,
-                          ix->dim, ix->tile_norm, p.sample_stride, w.thr, w.cq, s, p.narrow ? w.cnt : nullptr, p.narrow ? NARROW_SUBLISTS : 0,
-                          p.skip_sampled && ix->knobs.skip_list ? w.glist : nullptr, skip_list_cap(p.opt_rank), ix->knobs.thr_phases, &ix->thr_phases_used);
+    const bool skip_list = p.skip_sampled && ix->knobs.skip_list;   // the select joins the sampled tiles from the threshold's short lists
+    ThresholdArgs t = threshold_args(ix, w);
+    if (p.opt_rank) t.k = p.opt_rank;
+    if (p.narrow) t.zero_cnt = w.cnt, t.zero_per_query = NARROW_SUBLISTS;
+    if (skip_list) t.glist = w.glist, t.list_cap = skip_list_cap(p.opt_rank);
+    rc = launch_threshold(t, s, &ix->thr_phases_used);
     if (rc != CCR_OK) return rc;
 
     // main pass -> candidates -> select
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_MAIN_BEGIN], s));
-    rc = p.narrow ? run_narrow_pass(ix, p, w, Q_bf16, n_q, s) : run_main_pass(ix, p, w, Q_bf16, n_q, k, s);
+    rc = p.narrow ? run_narrow_pass(ix, p, w, Q_bf16, n_q, s) : run_main_pass(ix, p, w, Q_bf16, n_q, s);
     if (rc != CCR_OK) return rc;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_MAIN_END], s));
     ix->main_pass_recorded = true;
-    rc = launch_select_rescore(w.cand, w.cnt, p.first_nsub, p.first_sp, n_q, p.nq_pad, p.first_lay, k, p.rescore_cap, p.select_compact, ix->n_rows, w.thr,
-                               w.cq, ix->tile_norm, ix->row_norm, ix->dmax_bits, Q_bf16, ix->D, ix->dtype, ix->dim, ix->id_out, out_scores, out_ids,
-                               w.flag_count, w.flag_list, w.stat_cand, nullptr, s, p.skip_sampled ? w.gmax : nullptr, p.sample_tiles,
-                               (int)p.sample_stride, p.nq_pad, ix->knobs.skip_list ? w.glist : nullptr, skip_list_cap(p.opt_rank),
-                               p.rescore_regular);
+    SelectArgs sel = select_args(ix, w);
+    sel.ranges = p.first_nsub, sel.sp = p.first_sp, sel.lay = p.first_lay;
+    sel.flag_count = w.flag_count, sel.flag_list = w.flag_list, sel.stat_cand = w.stat_cand;
+    if (p.skip_sampled)   // the join of the tiles the main pass left out
+        sel.gmax = w.gmax, sel.sample_tiles = p.sample_tiles, sel.sample_stride = (int)p.sample_stride, sel.gmax_pitch = p.nq_pad;
+    if (skip_list) sel.glist = w.glist, sel.list_cap = t.list_cap;
+    rc = launch_select_rescore(sel, s);
     if (rc != CCR_OK) return rc;
     CCR_HIP_CHECK(hipEventRecord(ix->ev[EV_SELECT_END], s));
 
-    ix->pending = {false, Q_bf16, n_q, k, out_scores, out_ids, (char *)workspace, s};
     if (!async) return search_complete(ix);   // (synchronous form: every flagged query has been re-done, the header's zero stands)
     // The host does not learn the flag count here, and nothing is re-done on the stream: flagged queries (rare: a sub-list
     // overflow, mass ties, an estimated threshold that failed its check) are completed by ccr_search_finish(), which has the

@@ -19,14 +19,10 @@
 
 #include <math.h>
 
-#include "ccr_common.h"
+#include "ccr_index.h"   // launch_dense_select, ensure_dynamic_lds
 #include "ccr_topk_device.h"
 
 namespace ccr {
-int launch_dense_select(const float *scores, int64_t n_rows, int k, const uint32_t *out_rows, int q_begin, int nq_chunk,
-                        const uint32_t *count_dev, int64_t id_offset, float *out_scores, int64_t *out_ids, hipStream_t s,
-                        bool aggregate, const uint32_t *in_rows, bool in_rows_compact);
-int ensure_dynamic_lds(const void *kernel, size_t lds);
 
 struct Bm25Round {       // one (query row of the batch, term) pair of a round
     int64_t begin, end;  // posting range

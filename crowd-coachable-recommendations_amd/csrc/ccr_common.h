@@ -126,7 +126,7 @@ __host__ __device__ __forceinline__ int64_t main_item(int i, int xcd, int qblock
 // epilogues of the fused GEMM kernel; EPI_FILTER's candidate record = one corpus row {MFMA score, row}
 enum { EPI_FILTER = 0, EPI_GMAX = 1, EPI_STORE = 2 };
 
-// arguments of the fused GEMM kernel (ccr_fused.hip)
+// arguments of the fused GEMM kernels (ccr_main_pass.hip)
 struct GemmArgs {
     const uint16_t *D;
     int64_t n_rows;

@@ -1,4 +1,5 @@
-// ccr_gemm_common.h -- definitions shared by the GEMM + top-k kernels (ccr_fused.hip, experimental/gemm4w_proto.hip).
+// ccr_gemm_common.h -- definitions shared by the GEMM + top-k kernels (ccr_main_pass.hip, experimental/gemm4w_proto.hip)
+// and, for its wait macros, the threshold kernels (ccr_threshold.hip).
 #pragma once
 #include "ccr_common.h"
 

@@ -3,7 +3,7 @@
 // scripts/ms_marco_eval.py:205-218 scores every query batch against the whole corpus; with a handful of queries (an interactive
 // ranking() call, the retry of a few flagged queries, SURVEY 8d's Q = 1 / 16 / 64) the arithmetic intensity is n_q flop per corpus
 // byte -- far below the ridge (~315) -- and the pass can at best run at the rate the corpus streams out of HBM.  The 256 x 256 tile
-// kernel (ccr_fused.hip) is the wrong shape there: it computes a full 256-query tile whatever n_q is (256 x the MFMA work at n_q = 1),
+// kernel (ccr_main_pass.hip) is the wrong shape there: it computes a full 256-query tile whatever n_q is (256 x the MFMA work at n_q = 1),
 // moves a 16-KiB query slice through the LDS-DMA path beside every 16 KiB of corpus, and rendezvouses its eight waves twice per 32
 // K-elements; measured 5.0 / 4.8 / 4.0 TB/s of corpus bytes at n_q = 1 / 16 / 64 (profiles/r03_small_batches_pmc.txt).
 //

@@ -1,7 +1,8 @@
 // ccr_topk_device.h -- workgroup-level selection primitives shared by the dense and fused paths.
 //   * block_radix_select : exact k-th largest of M 32-bit orderable keys (4 x 8-bit MSB-first passes,
 //                          256-bin LDS histogram);
-//   * block_bitonic_sort_desc : in-LDS bitonic sort of 64-bit keys, descending.
+//   * block_bitonic_sort_desc : in-LDS bitonic sort of 64-bit keys, descending;
+//   * sweep_sublists : the walk over a query's candidate sub-lists (threshold update and select).
 // 64-bit result keys are (orderable(score) << 32) | ~local_idx : unique per document, so "score
 // descending, index ascending" is plain descending key order.
 #pragma once
@@ -169,5 +170,33 @@ __device__ __forceinline__ float canonical_dot(const uint16_t *__restrict__ q, c
     return (float)acc;
 }
 
+// Visit every record (sub-list j, slot sl) with first <= sl < count[j]: the (sub-list, slot) rectangle is padded to a
+// power of two per sub-list, BATCH independent 8-byte loads are issued before the first record is consumed.
+template <int THREADS, int BATCH, class At, class Want, class Put>
+__device__ __forceinline__ void sweep_sublists(int tid, int n_lists, int first, int longest, const uint32_t *s_cnt, At at,
+                                               Want want, Put put) {
+    if (longest <= first) return;
+    int lw = 0;
+    while ((1 << lw) < longest - first) ++lw;
+    const int sweep = n_lists << lw;
+    for (int i0 = tid; i0 < sweep; i0 += THREADS * BATCH) {
+        uint2 e[BATCH];
+        int jj[BATCH], ss[BATCH];
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            const int i = i0 + u * THREADS;
+            const int j = i >> lw, sl = first + (i & ((1 << lw) - 1));
+            jj[u] = -1;
+            ss[u] = sl;
+            if (i < sweep && (uint32_t)sl < s_cnt[j] && want(j, sl)) {
+                jj[u] = j;
+                e[u] = at(j, sl);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u)
+            if (jj[u] >= 0) put(jj[u], ss[u], e[u]);
+    }
+}
 
 }  // namespace ccr

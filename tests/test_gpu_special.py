@@ -749,3 +749,39 @@ def test_bertbpr_transform_against_the_references_own_methods_golden_g19(golden_
     srt = np.sort(ref, axis=1)
     clear = (srt[:, -1] - srt[:, -2]) > 2 * bound.max()
     assert np.array_equal(top_i.cpu().numpy()[clear, 0], ref.argmax(1)[clear]) and clear.sum() >= 3
+
+
+def test_a_query_that_overflows_again_in_the_retry_takes_a_second_round():
+    """The flooded corpus above, plus 36 whole tiles of ONE range (tiles 5 + 64 j of the plan's 64 ranges) filled with copies of one row
+    that only query 7 scores high: 1 152 equal candidates per sub-list of that range, more than a retry group's sub-lists hold (under
+    512), so query 7 -- and the few queries that happen to score the copies above their threshold -- overflow AGAIN in the retry while
+    the rest of their group finishes.  That is the one path to the re-tightening between two retry rounds (retry_group: thresholds from
+    the round's lists, scattered back): n_retried > n_fallback shows the second round.  What still overflows ends on the dense path.
+    Ids and score bits against the dense path and the oracle."""
+    from ccrec_amd import ops
+    n, d, nq, k, special = 600_000, 128, 1024, 50, 7
+    g = torch.Generator(device="cuda").manual_seed(31)
+    D = torch.randn(n, d, generator=g, device="cuda") / d ** 0.5
+    Q = torch.randn(nq, d, generator=g, device="cuda") / d ** 0.5
+    Q[:, 0] = Q[:, 100] = 0.5
+    copy = Q[special].clone()
+    copy[0] = copy[100] = 0.0                              # (without the part every query shares: the other queries score it at random)
+    copy *= 1.5 / copy.norm()
+    tiles = 5 + 64 * torch.arange(36, device="cuda")
+    D.view(-1)[: (n // 256) * 256 * d].view(-1, 256, d)[tiles] = copy
+    rows = torch.arange(150, device="cuda") * 4_000 + 77
+    D[rows, 0], D[rows, 100] = 65536.0, -65536.0
+    Db, Qb = ops.pack_bf16(D), ops.pack_bf16(Q)
+    index = ops.CorpusIndex(Db)
+    s, i = index.search(Qb, k)
+    st = index.last_stats()
+    print(st)
+    assert st["path"] == 1 and st["ranges"] == 64 and st["n_fallback"] > nq // 2, st
+    assert st["n_retried"] > st["n_fallback"] and 1 <= st["n_dense"] < nq // 4, st
+    pick = torch.cat([torch.tensor([special], device="cuda"), torch.arange(0, nq, 37, device="cuda")])
+    s1, i1 = index.search(Qb[pick], k, 1)
+    assert torch.equal(i[pick], i1) and torch.equal(s[pick].view(torch.int32), s1.view(torch.int32))
+    bits = lambda t: t.view(torch.int16).cpu().numpy().view(np.uint16)   # noqa: E731
+    first = [special, 0, 1, 2]
+    ref_i, ref_s = orc.canonical_search(bits(Qb[first]), bits(Db), k)
+    assert np.array_equal(i[first].cpu().numpy(), ref_i) and np.array_equal(s[first].cpu().numpy().view(np.uint32), ref_s.view(np.uint32))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Same-box A/B of the main pass on 256 x 384 tiles (CCR_WIDE, csrc/ccr_fused.hip gemm_topk16w_kernel) against the 256 x 256 kernel, at the
+"""Same-box A/B of the main pass on 256 x 384 tiles (CCR_WIDE, csrc/ccr_main_pass.hip gemm_topk16w_kernel) against the 256 x 256 kernel, at the
 NQ shape.  Runs ON THE GPU BOX, one process per variant.  Every variant must return the ids and score bits of the first one.
 
   python3 tools/exp_wide.py [outfile] [--rows N --queries Q --k K] [--set NAME]"""
