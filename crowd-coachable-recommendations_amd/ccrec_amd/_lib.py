@@ -63,7 +63,7 @@ class SearchStats(ctypes.Structure):
                 ("ms_main", ctypes.c_float), ("ms_select", ctypes.c_float), ("ms_fallback", ctypes.c_float),
                 ("ms_total", ctypes.c_float), ("n_retried", ctypes.c_int32), ("n_dense", ctypes.c_int32),
                 ("main_launches", ctypes.c_int32), ("opt_rank", ctypes.c_int32), ("main_tile_queries", ctypes.c_int32),
-                ("skipped_tiles", ctypes.c_int32)]
+                ("skipped_tiles", ctypes.c_int32), ("tile_cap", ctypes.c_int32)]
 
 
 class AdamwSegment(ctypes.Structure):

@@ -487,6 +487,7 @@ static int fused_stats(ccr_index *ix, uint32_t nflag, unsigned long long ncand) 
     st.sublists = p.narrow ? p.first_sp : p.sublists;
     st.main_launches = 1 + (p.item_a ? 1 : 0) + (p.item_b ? 1 : 0);
     st.opt_rank = p.opt_rank;
+    st.tile_cap = p.opt_rank ? p.tile_cap : 0;
     st.skipped_tiles = p.skip_sampled ? p.sample_tiles : 0;
     st.main_tile_queries = p.narrow ? 0 : p.tile_q;
     st.n_candidates = (int64_t)ncand;
@@ -762,7 +763,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     // (small batches: the streaming pass's sub-list counters are cleared by the threshold launch)
     const bool skip_list = p.skip_sampled && ix->knobs.skip_list;   // the select joins the sampled tiles from the threshold's short lists
     ThresholdArgs t = threshold_args(ix, w);
-    if (p.opt_rank) t.k = p.opt_rank;
+    if (p.opt_rank) t.k = p.opt_rank, t.tile_cap = p.tile_cap;
     if (p.narrow) t.zero_cnt = w.cnt, t.zero_per_query = NARROW_SUBLISTS;
     if (skip_list) t.glist = w.glist, t.list_cap = skip_list_cap(p.opt_rank);
     rc = launch_threshold(t, s, &ix->thr_phases_used);

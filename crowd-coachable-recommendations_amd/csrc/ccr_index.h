@@ -37,6 +37,7 @@ struct ThresholdArgs {
     int64_t n_groups, sample_stride;
     int n_q, nq_pad, dim;
     int k;                    // the rank of the group maximum that becomes tau_q
+    int tile_cap = GROUPS_PER_TILE;   // ... among the groups that are among the tile_cap largest of their own sampled tile (16 = among all)
     const float *qnorm, *tile_norm;
     const uint32_t *dmax_bits;
     float *thr, *cq;

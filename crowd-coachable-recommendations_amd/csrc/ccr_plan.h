@@ -15,7 +15,7 @@ struct Knobs {
     int sample_div;    // CCR_SAMPLE_DIV   0 = planner's choice, else the pinned sample fraction 1/div
     int ranges;        // CCR_RANGES       0 = planner's choice, else the pinned range count (rounded to a multiple of 8)
     int optimistic;    // CCR_OPTIMISTIC   -1 = planner's choice, 0 = conservative thresholds only, 1 = estimated thresholds wherever the sample allows
-    int opt_rank;      // CCR_OPT_RANK     0 = max(48, 3 k fs), else the pinned rank (tests: a small rank makes the verification fail)
+    int opt_rank;      // CCR_OPT_RANK     0 = planner's choice (optimistic_rank), else the pinned rank (tests: a small rank makes the verification fail)
     int max_lists;     // CCR_MAX_LISTS    0 = planner's limit, else a cap on ranges x sublists (A/B of the select stage's walk)
     int narrow;        // CCR_NARROW       -1 = planner's choice (n_q <= 64 whose rows fit the LDS), 0 = tile kernels only (the A/B knob)
     int narrow_grid;   // CCR_NARROW_GRID  0 = planner's choice, else workgroups of the streaming kernel
@@ -25,6 +25,7 @@ struct Knobs {
     int wide;          // CCR_WIDE         -1 = planner's choice, 0 = 256 x 256 main-pass tiles only (the A/B knob), 1 = 256 x 384 wherever the kernel applies
     int thr_phases;    // CCR_THR_PHASES   0 = launcher's choice by the sample's size, 16 / 64 = the threshold kernel's group phases per query, pinned (tests, the A/B)
     int narrow_groups; // CCR_NARROW_GROUPS 2 = batches of 65 .. 128 queries stream as two query groups (default), 1 = tile kernels above 64 queries (the A/B knob)
+    int tile_cap;      // CCR_TILE_CAP     0 = planner's choice (tile_cap_for), else the pinned number of groups one sampled tile may give an estimated threshold; 16 = no cap (the A/B knob)
 };
 // One row per knob -- its variable, its field, its default: the ONE place a default is written.
 struct KnobDef {
@@ -39,6 +40,7 @@ inline constexpr KnobDef KNOB_DEFS[] = {
     {"CCR_NARROW", &Knobs::narrow, -1},            {"CCR_NARROW_GRID", &Knobs::narrow_grid, 0},   {"CCR_SKIP_SAMPLED", &Knobs::skip_sampled, -1},
     {"CCR_SKIP_LIST", &Knobs::skip_list, 1},       {"CCR_QSPLIT", &Knobs::qsplit, -1},            {"CCR_WIDE", &Knobs::wide, -1},
     {"CCR_THR_PHASES", &Knobs::thr_phases, 0},     {"CCR_NARROW_GROUPS", &Knobs::narrow_groups, NARROW_MAX_GROUPS},
+    {"CCR_TILE_CAP", &Knobs::tile_cap, 0},
 };
 static_assert(sizeof(KNOB_DEFS) / sizeof(KNOB_DEFS[0]) * sizeof(int) == sizeof(Knobs), "a row for every knob");
 inline Knobs default_knobs() {   // what an empty environment gives
@@ -65,6 +67,8 @@ struct Plan {
     int item_a;           // phase A = work items [0, item_a) of every XCD set (0 = single phase); thresholds are re-tightened after it
     int item_b;           // end of the second phase in items (0: two phases)
     int opt_rank;         // > 0: estimated thresholds = the opt_rank-th largest sampled group maximum (single launch; the select verifies)
+    int tile_cap;         // opt_rank > 0: only the tile_cap largest groups of a sampled tile count towards that rank (GROUPS_PER_TILE = no cap)
+    int cap_rank;         // opt_rank > 0: the rank the capacities are sized for (opt_rank, or the floor of 40 above a smaller planner's rank)
     int skip_sampled;     // 1: the main pass does not score the sample_tiles sampled tiles again; the select joins their rows from gmax
     int qgroups;          // query-block groups over the XCDs
     int cap;              // candidate slots per sub-list (the largest segment's: statistics)
@@ -86,6 +90,15 @@ struct Plan {
     size_t total;         // bytes of the search workspace (search_ws lays it out)
     int64_t dense_rows_per_chunk;  // queries per dense chunk
 };
+
+// Estimated thresholds take the opt_rank-th largest among the groups that are among the tile_cap largest of their own sampled tile:
+// tile_cap = ceil(opt_rank / TILE_CAP_TILES), at least TILE_CAP_MIN, so that TILE_CAP_TILES tiles at least set a threshold -- which asks
+// for a rank above TILE_CAP_MIN * (TILE_CAP_TILES - 1) (ccr_plan.hip: optimistic_rank, tile_cap_for).
+constexpr int TILE_CAP_MIN = 4, TILE_CAP_TILES = 5;
+constexpr int OPT_RANK_MIN = TILE_CAP_MIN * (TILE_CAP_TILES - 1) + 1;
+// ... which a plan may take when it leaves out the sampled tiles of a sample of REDUCED_RANK_MIN_TILES tiles or more; every other
+// estimated plan keeps the earlier floor under its rank (optimistic_rank says why).  Capacities stay sized for the floor's rank.
+constexpr int OPT_RANK_FLOOR = 40, REDUCED_RANK_MIN_TILES = 40;
 
 constexpr int FALLBACK_ROWS = 16;   // dense score rows reserved for flagged queries (one on-stream chunk)
 

@@ -43,9 +43,9 @@ static double gamma_upper(double r) { return 1.25 * (r + 4.75 * sqrt(r) + 8.0) /
 static double estimated_pass(int rank, double fs, int k) { return std::max((double)rank / fs, (double)k); }
 // the corpus fraction of the plan's sample, as the capacities see it
 static double sample_fraction(const Plan &p) { return 1.0 / ((double)p.tiles / (double)p.sample_tiles); }
-// ... and its upper quantile for the plan's rank (opt_rank > 0)
+// ... and its upper quantile for the rank the plan's capacities are sized for (opt_rank > 0: cap_rank)
 static double estimated_pass_upper(const Plan &p, int k) {
-    return gamma_upper((double)p.opt_rank) * estimated_pass(p.opt_rank, sample_fraction(p), k);
+    return gamma_upper((double)p.cap_rank) * estimated_pass(p.cap_rank, sample_fraction(p), k);
 }
 // survivors per query under the sample's CONSERVATIVE thresholds alone
 static double conservative_pass(const Plan &p, int k) { return (double)k * ((double)p.tiles / (double)p.sample_tiles) * 1.3 + 64.0; }
@@ -165,22 +165,49 @@ static bool may_skip_sampled(const Plan &p, int64_t sample, const Knobs &kn) {
 // recorded) -- which the select stage checks (L >= tau; a query that fails is retried under a valid bound).  So tau is set to
 // the r-th largest sampled group maximum: about r / fs rows pass over the WHOLE corpus in ONE launch.  Given r, the pass count is
 // (r / fs) x Gamma(r) / r: fewer than k rows pass iff Gamma(r) < k fs.  r is the smallest rank whose 1e-7 lower quantile
-// (Wilson-Hilferty: r (1 - 1/(9r) - 5.2 sqrt(1/(9r)))^3) reaches k fs, and at least 40 -- k = 1001 on a 1/64 sample: r = 41,
-// 2 700 rows pass.  Why the floor: a corpus in topical order can fool the estimate when the sample holds a query's whole
-// cluster tile; with r <= 16 that ONE tile's 16 group maxima set tau (measured with r = 13 at k = 100 on the topically sorted
-// bench corpus: one query in 3 452 fails the check, and its retry costs 5 ms of an 18-ms step), with r >= 40 at least three
-// tiles contribute (k = 1001, same corpus: nobody fails).  With the floor the planner keeps the conservative plan at small k
-// (2 560 rows would pass at k = 100 against 1 296), where the phased plan is cheap anyway.  Exact either way.
+// (Wilson-Hilferty: r (1 - 1/(9r) - 5.2 sqrt(1/(9r)))^3) reaches k fs -- k = 100 on a 1/32 sample: r = 18, k = 1001 on a 1/64
+// sample: r = 41, 2 700 rows pass.
+// The tile cap: a corpus in topical order can fool the estimate when the sample holds a tile that lies inside a query's cluster:
+// all 16 group maxima of that ONE tile are high, and a rank of 16 or less is then settled by it alone (measured with r = 13 at
+// k = 100 on the topically sorted bench corpus: one query in 3 452 fails the check, and its retry costs 5 ms of an 18-ms step).
+// So a sampled tile may speak for only tile_cap = ceil(r / 5), at least 4, of its groups (tile_cap_for): tau is the r-th largest
+// lower bound among the groups that are among the tile_cap largest of their own sampled tile, and with r >= 4 x 4 + 1 = 17 no
+// fewer than five tiles determine it.  Results do not change: any tau is valid if at least k recorded rows pass it
+// with their lower bounds, which the select verifies and a failing query's retry under the conservative bound repairs; and for a
+// given rank the capped tau is never above the uncapped one -- leaving values out can only lower the r-th largest -- so the cap
+// lets more rows through, never fewer, than the statistics above count on.  Exact either way.
+// Where the rank may be that small: the rule before the cap was a floor of OPT_RANK_FLOOR = 40 under the rank (three whole tiles), which
+// cost 2.3 x the candidates on EVERY corpus at k = 100.  The floor goes where the cap can stand in for it, and stays elsewhere:
+//   * the plan that leaves out the sampled tiles (skip, the re-priced plan of choose_launches) on a sample of at least
+//     REDUCED_RANK_MIN_TILES = 40 tiles takes the formula's rank, at least 17: the five tiles that settle tau are then an eighth of
+//     the sample at most.  This is the flagship plan: rank 18 on 328 sampled tiles.
+//   * a smaller sample keeps the floor: with ten sampled tiles five are half of what was seen, and rows that sit in the sampled
+//     tiles only -- tests/test_gpu_skip_sampled.py plants 140 of them -- set a rank of 17 for every query (124 of 300 queries
+//     failed the check there, the query of the hot tile among them; none of that kind under rank 40);
+//   * a plan that scores every tile keeps the floor: the sample size and the kind of plan are chosen on that price, as before
+//     (choose_main_pass), and the planner's invariant check (tests/native/planner_check.cpp) holds such plans to a rank of 40.
+// The cap itself applies to every estimated threshold, whatever set its rank.
 // (skip: the main pass leaves out the sampled tiles, so the k rows must pass among the unsampled fraction 1 - fs: k fs / (1 - fs))
 static int optimistic_rank(int k, int64_t sample, int64_t tiles, const Knobs &kn, bool skip = false) {
     if (kn.opt_rank > 0) return kn.opt_rank;   // tests: a small rank makes most queries fail the check
     const double need = (double)k * (double)sample / (double)(skip ? tiles - sample : tiles);
-    int r = 40;
+    int r = (skip && sample >= REDUCED_RANK_MIN_TILES) ? OPT_RANK_MIN : OPT_RANK_FLOOR;
     for (; r < 1 << 20; ++r) {
         const double a = 1.0 / (9.0 * r), t = 1.0 - a - 5.2 * sqrt(a);
         if (t > 0.0 && (double)r * t * t * t >= need) break;
     }
     return r;
+}
+
+// Groups of one sampled tile that count towards the rank of an estimated threshold (above): ceil(rank / 5) within [4, 16]; 16 = all
+// of them, no cap.  CCR_TILE_CAP pins it (1 .. 16).  Either way the cap is raised to what leaves `rank` groups eligible on `sample`
+// tiles, so that the threshold kernels always find their rank (a pinned rank or cap on a small sample).
+static int tile_cap_for(int rank, int64_t sample, const Knobs &kn) {
+    int cap = (rank + TILE_CAP_TILES - 1) / TILE_CAP_TILES;
+    cap = std::min(GROUPS_PER_TILE, std::max(TILE_CAP_MIN, cap));
+    if (kn.tile_cap >= 1 && kn.tile_cap <= GROUPS_PER_TILE) cap = kn.tile_cap;
+    const int64_t fill = ((int64_t)rank + sample - 1) / std::max<int64_t>(1, sample);
+    return (int)std::min<int64_t>(GROUPS_PER_TILE, std::max<int64_t>(cap, fill));
 }
 
 // The window of range counts a plan is priced over: r_hi = most ranges the select stage walks, target = ~6 items per workgroup.
@@ -234,7 +261,8 @@ static void price_range_count(const Plan &p, int k, const Knobs &kn, int64_t smp
     const double common = sample_cost(p, smp) + select_per_range * (double)R + 1e-3 * std::abs((double)(R - target));
     const double single = rounds(items) * item_cost + hit_w * survivors(0.0, 0.0) + common;
     if (kn.optimistic != 1 && !reprice_skipped) best.offer(single, {smp, R, 0, 0, 0, 0});
-    if (kn.optimistic != 0 && smp * GROUPS_PER_TILE >= 4 * 40) {   // estimated thresholds: one launch, ~rank / fs rows pass
+    // estimated thresholds: one launch, ~rank / fs rows pass (on ten sampled tiles at least: the tile cap asks for five)
+    if (kn.optimistic != 0 && smp * GROUPS_PER_TILE >= 160) {
         // (a main pass that leaves out the sampled tiles walks tiles - smp virtual tiles)
         const bool skip = reprice_skipped && may_skip_sampled(p, smp, kn);
         const int rank = optimistic_rank(k, smp, p.tiles, kn, skip);
@@ -386,6 +414,15 @@ static void choose_tile(const Search &s, Plan &p) {
     p.main_qgroups = pick_qgroups(p.main_qblocks, dim, kn, p.tile_q);
 }
 
+// the tile cap and the capacity rank that follow from the plan's rank and sample
+static void set_rank_dependents(Plan &p, const Knobs &kn) {
+    p.tile_cap = p.opt_rank > 0 ? tile_cap_for(p.opt_rank, p.sample_tiles, kn) : GROUPS_PER_TILE;
+    // Capacities (sub-lists, the select's buffer) stay sized for the floor's rank where the planner's own rank is below it: a corpus
+    // in topical order records several times the estimate (3 054 rows per query on the sorted bench corpus at rank 18, 575 estimated),
+    // and a select buffer sized from rank 18 (2 816 entries) made that corpus 0.07 ms SLOWER than under rank 40.  A pinned rank sizes them.
+    p.cap_rank = (kn.opt_rank > 0 || p.opt_rank == 0) ? p.opt_rank : std::max(p.opt_rank, OPT_RANK_FLOOR);
+}
+
 // sample size, range count, phases and thresholds of the main pass, and with them the sample pass's ranges and the query split
 static void choose_launches(const Search &s, Plan &p, const std::vector<int64_t> &samples) {
     const Knobs &kn = s.kn;
@@ -401,6 +438,7 @@ static void choose_launches(const Search &s, Plan &p, const std::vector<int64_t>
     p.item_a = choice.item_a;
     p.item_b = choice.item_b;
     p.opt_rank = choice.opt_rank;
+    set_rank_dependents(p, kn);
     p.skip_sampled = (p.opt_rank > 0 && !p.narrow) ? choice.skip : 0;
     // unequal query groups: a single launch of a tile kernel only (phase ends are item indices of the equal groups' map, and
     // the re-tightening between two phases takes a query's finished ranges from its block's place in an equal group)
@@ -427,9 +465,14 @@ static void price_skip_sampled(const Search &s, Plan &p) {
     // no other query count has been measured.
     const double saved = 0.5 * (double)p.sample_tiles * p.main_qblocks * tile_cost(p) / (double)p.grid;
     const bool pays = 0.065 * join_rows * query_scale(p) < saved;
-    if (need > 8192.0 || (s.kn.skip_sampled < 0 && !pays))
+    if (need > 8192.0 || (s.kn.skip_sampled < 0 && !pays)) {
         p.skip_sampled = 0;
-    else
+        // every tile is scored after all: the rank is not below what such a plan takes (optimistic_rank: the floor).  As before,
+        // p.ranges stays the range count priced for the walk over tiles - sample, and the estimated plan is not compared again with
+        // the phased and conservative plans; new is only that the rank may rise with the switch (NQ, k = 300: to the floor of 40).
+        p.opt_rank = std::max(p.opt_rank, optimistic_rank(k, p.sample_tiles, p.tiles, s.kn, false));
+        set_rank_dependents(p, s.kn);
+    } else
         p.rescore_cap = std::min(8192, std::max(p.rescore_cap, pow2_ceil((int)need)));
 }
 

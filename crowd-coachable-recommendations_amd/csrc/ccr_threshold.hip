@@ -3,7 +3,8 @@
 //                              at its creation, the query norms at the head of every search.  (They are here, not beside
 //                              index_create_impl: ccr_api.hip holds no kernel, and every reader of these bounds but the select is below.)
 //   threshold_kernel           tau_q = k-th largest group maximum of the sample pass (a lower bound of the k-th largest score: k
-//                              disjoint groups hold a score >= tau_q), minus the MFMA error margins (cq * tile norm)
+//                              disjoint groups hold a score >= tau_q), minus the MFMA error margins (cq * tile norm);
+//                              an ESTIMATED tau_q takes its rank among at most tile_cap groups of each sampled tile (tile_top_mask)
 //   threshold_small_kernel     the same for a small batch, a workgroup per query
 //   threshold_update_kernel    the re-tightening between two phases of the main pass and in front of a retry, from the candidates
 #include <algorithm>
@@ -123,6 +124,29 @@ int launch_tile_norms(const float *row_bounds, int64_t rows, uint32_t *tile_bits
     return CCR_OK;
 }
 
+// The tile cap of estimated thresholds (ccr_plan.hip, optimistic_rank): of the 16 orderable lower bounds o[] of ONE sampled tile and
+// query, bit j of the result says that group j is among the `cap` largest -- fewer than `cap` of the others rank before it, and on
+// equal values the lower group index ranks first, so the answer is a function of the values alone.  From registers: one compare per
+// pair (i < j) and one counter per group -- before[j] starts at the 15 - j pairs with the groups after j, as if j lost them all; a
+// pair that i wins takes one off before[i] and puts one on before[j].
+__device__ __forceinline__ uint32_t tile_top_mask(const uint32_t (&o)[GROUPS_PER_TILE], int cap) {
+    int before[GROUPS_PER_TILE];
+#pragma unroll
+    for (int j = 0; j < GROUPS_PER_TILE; ++j) before[j] = GROUPS_PER_TILE - 1 - j;
+#pragma unroll
+    for (int i = 0; i < GROUPS_PER_TILE; ++i)
+#pragma unroll
+        for (int j = i + 1; j < GROUPS_PER_TILE; ++j) {
+            const int first = o[i] >= o[j] ? 1 : 0;   // i ranks before j
+            before[j] += first;
+            before[i] -= first;
+        }
+    uint32_t in = 0u;
+#pragma unroll
+    for (int j = 0; j < GROUPS_PER_TILE; ++j) in |= (before[j] < cap ? 1u : 0u) << j;
+    return in;
+}
+
 // The wide threshold form: queries per workgroup (x 64 phases) and the smallest sample it is launched for (launch_threshold).
 // 16 queries = 1 024 threads reading 64-byte segments of a gmax row: 113 us at NQ (5 248 groups x 3 584 columns) against 161 us for
 // the 16-phase form.  8 queries x 64 phases (512 threads, twice the workgroups, 32-byte segments) took 187 us: half-used 64-byte
@@ -136,8 +160,11 @@ constexpr int THR_WIDE_MIN_BATCHES = 2;
 // One workgroup = QB queries x PH group phases (thread = ql + QB * ph): a gmax row is read as QB * 4-byte segments (query-contiguous
 // layout), every query has its own 256-bin LDS histogram (no same-address atomics), 4 MSB-first passes.  A pass is a chain of
 // n_groups / (16 PH) dependent batches of 16 loads per thread and nothing bounds the kernel but that chain: the launcher gives a
-// large sample 64 phases (16 waves per workgroup) instead of 16.  The histogram counts do not depend on the order of the adds: every
-// form computes the same thresholds bit for bit and the same short list as a set.
+// large sample 64 phases (16 waves per workgroup) instead of 16.  A batch is the 16 groups of ONE sampled tile (the phases stride
+// over the tiles; n_groups is whole tiles), so that a thread holds a tile's lower bounds together.  The histogram counts do not
+// depend on the order of the adds: every form computes the same thresholds bit for bit and the same short list as a set.
+// tile_cap < 16 (estimated thresholds): only the groups among the tile_cap largest of their tile (tile_top_mask) enter the histograms
+// -- the same decision in every radix pass, it is a function of the tile's values alone.  The short list keeps every group.
 // grid = nq_pad / QB, block = QB * PH.
 // glist (may be null; [nq_pad][list_cap + 1]): the query's SHORT LIST for the select stage's join of the sampled tiles -- entry 0 the
 // count, then the groups whose UPPER bound m + cq * nt reaches tau (written in the last radix pass against tau's upper 24 bits, a value
@@ -148,7 +175,7 @@ constexpr int THR_WIDE_MIN_BATCHES = 2;
 // (hipcc emits a bare s_barrier in loops of this kind).
 template <bool LIST, int PH, int QB>
 __global__ __launch_bounds__(QB * PH) void threshold_kernel(const float *__restrict__ gmax, int64_t n_groups, int n_q, int nq_pad,
-                                                           int k, const float *__restrict__ qnorm,
+                                                           int k, int tile_cap, const float *__restrict__ qnorm,
                                                            const uint32_t *__restrict__ dmax_bits, float gamma,
                                                            const float *__restrict__ tile_norm, int64_t sample_stride,
                                                            float *__restrict__ thr, float *__restrict__ cq,
@@ -172,9 +199,10 @@ __global__ __launch_bounds__(QB * PH) void threshold_kernel(const float *__restr
     // every threshold, so that all queries take the exact dense path
     const float dmax = __uint_as_float(*dmax_bits);
     const float c = (q < n_q) ? ((dmax < INFINITY) ? gamma * (qnorm[q] * 1.001f) * 1.001f : __builtin_nanf("")) : 0.f;
-    // norm bound of the sampled tile of group g (plain vector loads: staging them in LDS, or scalar loads of the wave-uniform
+    // norm bound of the t-th sampled tile (plain vector loads: staging them in LDS, or scalar loads of the wave-uniform
     // index, both made this kernel slower -- 84 vs 70 us at NQ: they share lgkmcnt with the histogram's LDS atomics)
-    auto tile_of = [&](int64_t g) { return tile_norm[(g / GROUPS_PER_TILE) * sample_stride]; };
+    auto tile_of = [&](int64_t t) { return tile_norm[t * sample_stride]; };
+    const int64_t n_tiles = n_groups / GROUPS_PER_TILE;
     auto emit = [&](int64_t g, float v, float tn, uint32_t prefix) {   // last pass only: prefix = tau's upper 24 bits
         if (f32_orderable(fmaf(c, tn, v)) >= prefix) {
             const uint32_t p = atomicAdd(&s_nlist[ql], 1u);
@@ -188,26 +216,23 @@ __global__ __launch_bounds__(QB * PH) void threshold_kernel(const float *__restr
         CCR_WAIT_LGKM0();
         __syncthreads();
         const uint32_t prefix = s_prefix[ql];
-        int64_t i = ph;
-        for (; i + 15 * PH < n_groups; i += 16 * PH) {   // 16 independent loads in flight per thread (the loop is latency-bound)
-            float v[16], tn[16];
+        for (int64_t t = ph; t < n_tiles; t += PH) {   // 16 independent loads in flight per thread (the loop is latency-bound)
+            const int64_t g0 = t * GROUPS_PER_TILE;
+            float v[GROUPS_PER_TILE];
+            uint32_t o[GROUPS_PER_TILE];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                v[j] = gmax[(i + PH * j) * nq_pad + q];
-                tn[j] = tile_of(i + PH * j);
+            for (int j = 0; j < GROUPS_PER_TILE; ++j) v[j] = gmax[(g0 + j) * nq_pad + q];
+            const float tn = tile_of(t);
+            if (listing) {   // (before the lower bounds exist: the last pass holds the maxima no longer than this)
+#pragma unroll
+                for (int j = 0; j < GROUPS_PER_TILE; ++j) emit(g0 + j, v[j], tn, prefix);
             }
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const uint32_t o = f32_orderable(fmaf(-c, tn[j], v[j]));
-                if ((o & mask) == prefix) atomicAdd(&s_hist[ql][(o >> shift) & 255u], 1u);
-                if (listing) emit(i + PH * j, v[j], tn[j], prefix);
-            }
-        }
-        for (; i < n_groups; i += PH) {
-            const float v = gmax[i * nq_pad + q], tn = tile_of(i);
-            const uint32_t o = f32_orderable(fmaf(-c, tn, v));
-            if ((o & mask) == prefix) atomicAdd(&s_hist[ql][(o >> shift) & 255u], 1u);
-            if (listing) emit(i, v, tn, prefix);
+            for (int j = 0; j < GROUPS_PER_TILE; ++j) o[j] = f32_orderable(fmaf(-c, tn, v[j]));
+            const uint32_t in = tile_cap < GROUPS_PER_TILE ? tile_top_mask(o, tile_cap) : 0xffffu;
+#pragma unroll
+            for (int j = 0; j < GROUPS_PER_TILE; ++j)
+                if (((in >> j) & 1u) && (o[j] & mask) == prefix) atomicAdd(&s_hist[ql][(o[j] >> shift) & 255u], 1u);
         }
         CCR_WAIT_LGKM0();
         __syncthreads();
@@ -271,9 +296,10 @@ __global__ __launch_bounds__(QB * PH) void threshold_kernel(const float *__restr
 // The same thresholds for a SMALL batch (the streaming main pass, n_q <= 128): threshold_kernel gives a query 16 threads, which walk its
 // ~4 000 sampled lower bounds four times from global memory -- 70 us for ONE query, a tenth of the whole search.  Here a workgroup
 // per query: the lower bounds are staged in LDS once (every load independent, one round trip), the four radix passes read LDS.
+// tile_cap < 16: the same in-tile rule as threshold_kernel, applied while staging.
 // zero_cnt (may be null): the streaming pass's sub-list counters of this query are cleared here instead of by a memset node.
 // grid = n_q, block = 256, dyn LDS = n_groups * 4 bytes.
-__global__ __launch_bounds__(256) void threshold_small_kernel(const float *__restrict__ gmax, int n_groups, int nq_pad, int k,
+__global__ __launch_bounds__(256) void threshold_small_kernel(const float *__restrict__ gmax, int n_groups, int nq_pad, int k, int tile_cap,
                                                              const float *__restrict__ qnorm, const uint32_t *__restrict__ dmax_bits,
                                                              float gamma, const float *__restrict__ tile_norm, int64_t sample_stride,
                                                              float *__restrict__ thr, float *__restrict__ cq, uint32_t *__restrict__ zero_cnt,
@@ -285,8 +311,22 @@ __global__ __launch_bounds__(256) void threshold_small_kernel(const float *__res
     const int tid = threadIdx.x, q = blockIdx.x;
     const float dmax = __uint_as_float(*dmax_bits);
     const float c = (dmax < INFINITY) ? gamma * (qnorm[q] * 1.001f) * 1.001f : __builtin_nanf("");
-    for (int g = tid; g < n_groups; g += 256)
-        s_low[g] = f32_orderable(fmaf(-c, tile_norm[(int64_t)(g / GROUPS_PER_TILE) * sample_stride], gmax[(int64_t)g * nq_pad + q]));
+    if (tile_cap < GROUPS_PER_TILE) {
+        // the tile cap (threshold_kernel): a thread stages a whole sampled tile, and a group outside its tile's tile_cap largest is
+        // staged as 0, below every real value -- it stays in the count and out of the rank (the planner leaves k groups eligible)
+        for (int t = tid; t < n_groups / GROUPS_PER_TILE; t += 256) {
+            const float tn = tile_norm[(int64_t)t * sample_stride];
+            uint32_t o[GROUPS_PER_TILE];
+#pragma unroll
+            for (int j = 0; j < GROUPS_PER_TILE; ++j) o[j] = f32_orderable(fmaf(-c, tn, gmax[(int64_t)(t * GROUPS_PER_TILE + j) * nq_pad + q]));
+            const uint32_t in = tile_top_mask(o, tile_cap);
+#pragma unroll
+            for (int j = 0; j < GROUPS_PER_TILE; ++j) s_low[t * GROUPS_PER_TILE + j] = ((in >> j) & 1u) ? o[j] : 0u;
+        }
+    } else {
+        for (int g = tid; g < n_groups; g += 256)
+            s_low[g] = f32_orderable(fmaf(-c, tile_norm[(int64_t)(g / GROUPS_PER_TILE) * sample_stride], gmax[(int64_t)g * nq_pad + q]));
+    }
     if (zero_cnt && tid < zero_per_query) zero_cnt[q * zero_per_query + tid] = 0u;
     __syncthreads();
     uint32_t kth = 0;
@@ -319,6 +359,16 @@ __global__ __launch_bounds__(256) void threshold_small_kernel(const float *__res
 
 int launch_threshold(const ThresholdArgs &a, hipStream_t s, int *phases_used) {
     if (phases_used) *phases_used = 0;
+    if (a.n_groups % GROUPS_PER_TILE || a.tile_cap < 1) {   // every form walks whole sampled tiles
+        set_error("threshold: %lld groups are not whole tiles, or tile cap %d", (long long)a.n_groups, a.tile_cap);
+        return CCR_ERR_INVALID;
+    }
+    // a capped selection needs its rank among the capped groups: the small-batch kernel stages a left-out group as 0, which is no
+    // threshold (the planner's tile_cap_for sees to this; other callers of this launcher are held to it here)
+    if (a.tile_cap < GROUPS_PER_TILE && (int64_t)a.tile_cap * (a.n_groups / GROUPS_PER_TILE) < a.k) {
+        set_error("threshold: rank %d above the %d x %lld groups the tile cap leaves", a.k, a.tile_cap, (long long)(a.n_groups / GROUPS_PER_TILE));
+        return CCR_ERR_INVALID;
+    }
     // small batches: a workgroup per query (needs k <= n_groups -- the planner samples >= 2k groups -- and the bounds in 64 KiB of LDS);
     // its kernel clears the caller's counters itself
     if (a.n_q <= 128 && a.n_groups >= a.k && a.n_groups <= 16384 && a.zero_per_query <= 256) {
@@ -327,7 +377,7 @@ int launch_threshold(const ThresholdArgs &a, hipStream_t s, int *phases_used) {
             if (rc != CCR_OK) return rc;
         }
         hipLaunchKernelGGL(threshold_small_kernel, dim3(a.n_q), dim3(256), (size_t)a.n_groups * 4, s, a.gmax, (int)a.n_groups, a.nq_pad, a.k,
-                           a.qnorm, a.dmax_bits, mfma_gamma(a.dim), a.tile_norm, a.sample_stride, a.thr, a.cq, a.zero_cnt, a.zero_per_query,
+                           a.tile_cap, a.qnorm, a.dmax_bits, mfma_gamma(a.dim), a.tile_norm, a.sample_stride, a.thr, a.cq, a.zero_cnt, a.zero_per_query,
                            a.glist, a.list_cap);
         CCR_LAUNCH_CHECK();
         return CCR_OK;
@@ -341,7 +391,7 @@ int launch_threshold(const ThresholdArgs &a, hipStream_t s, int *phases_used) {
     const auto kernel = wide ? (a.glist ? threshold_kernel<true, 64, THR_WIDE_QUERIES> : threshold_kernel<false, 64, THR_WIDE_QUERIES>)
                              : (a.glist ? threshold_kernel<true, 16, 16> : threshold_kernel<false, 16, 16>);
     const int qb = wide ? THR_WIDE_QUERIES : 16, ph = wide ? 64 : 16;   // queries and group phases of a workgroup
-    hipLaunchKernelGGL(kernel, dim3(a.nq_pad / qb), dim3(qb * ph), 0, s, a.gmax, a.n_groups, a.n_q, a.nq_pad, a.k, a.qnorm, a.dmax_bits,
+    hipLaunchKernelGGL(kernel, dim3(a.nq_pad / qb), dim3(qb * ph), 0, s, a.gmax, a.n_groups, a.n_q, a.nq_pad, a.k, a.tile_cap, a.qnorm, a.dmax_bits,
                        mfma_gamma(a.dim), a.tile_norm, a.sample_stride, a.thr, a.cq, a.glist, a.list_cap);
     CCR_LAUNCH_CHECK();
     return CCR_OK;

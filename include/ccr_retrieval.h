@@ -76,6 +76,8 @@ typedef struct ccr_search_stats {
                                   dense path and for the streaming pass of small batches */
     int32_t skipped_tiles;     /* corpus tiles the main pass did not score: the sampled tiles, whose rows the select stage joins from the
                                   sample pass's group maxima (CCR_SKIP_SAMPLED); 0: every tile was scored */
+    int32_t tile_cap;          /* opt_rank > 0: groups of one sampled tile that count towards that rank (CCR_TILE_CAP; 16 = all of them);
+                                  0 without estimated thresholds.  The last field: the struct grew from 80 to 88 bytes with it */
 } ccr_search_stats;
 
 const char *ccr_last_error(void);

@@ -35,6 +35,8 @@ static void plan_fields(const Plan &p, const SearchWs &w, F f) {
     f("item_a", p.item_a);
     f("item_b", p.item_b);
     f("opt_rank", p.opt_rank);
+    f("tile_cap", p.tile_cap);
+    f("cap_rank", p.cap_rank);
     f("skip_sampled", p.skip_sampled);
     f("qgroups", p.qgroups);
     f("cap", p.cap);
