@@ -33,6 +33,7 @@ EXPORTS = [
     "ccr_pack_half_ex", "ccr_pack_half_padded", "ccr_meanpool_pack_half_ex", "ccr_meanpool_pack_half_packed", "ccr_index_create_half",
     "ccr_index_create_with_norms_half", "ccr_index_dtype", "ccr_colsum_half",
     "ccr_grad_stats_workspace_bytes", "ccr_grad_stats", "ccr_adamw_control_update", "ccr_adamw_step_scaled",
+    "ccr_keep_f32", "ccr_rescore_f32_workspace_bytes", "ccr_rescore_f32",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
@@ -45,6 +46,7 @@ OPTIM_VERSION = 107   # ... and the multi-tensor AdamW step that keeps the encod
 ENCODER_PACKED_TRAIN_VERSION = 108   # ... and the embedding block's and the packed pooling's backward (ccr_embed_layernorm_bwd_half and its kin)
 HALF_INDEX_VERSION = 109   # ... and the pack, index and search on either 16-bit element type (ccr_index_create_half and its kin)
 AMP_OPTIM_VERSION = 110   # ... and loss scaling, overflow skip and norm clipping inside the AdamW step (ccr_adamw_step_scaled and its kin)
+RANK_F32_VERSION = 111   # ... and the kept fp32 rows with the verified re-score of a 16-bit search on them (ccr_keep_f32, ccr_rescore_f32)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -209,6 +211,10 @@ def load():
     lib.ccr_index_create_with_norms_half.argtypes = [vp, i64, i32, i32, i64, vp, vp, ctypes.POINTER(vp)]
     lib.ccr_index_dtype.argtypes = [vp]
     lib.ccr_colsum_half.argtypes = [vp, i64, i32, i32, vp, vp]
+    lib.ccr_keep_f32.argtypes = [vp, vp, i32, i32, vp, vp, i64, i32, vp]
+    lib.ccr_rescore_f32_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.ccr_rescore_f32_workspace_bytes.restype = sz
+    lib.ccr_rescore_f32.argtypes = [vp, vp, i64, i32, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.ccr_shard_message_bytes.argtypes = [i32, i32]
     lib.ccr_shard_message_bytes.restype = sz
     lib.ccr_search_shard.argtypes = [vp, vp, i32, i32, vp, vp, sz, i32, vp]

@@ -196,6 +196,7 @@ def score_op(S, op, device=None, reduce_fn=None):
     """score_array.py:460-474 (max / min / sum over the whole matrix) for the lazy scores of this module, without
     materialising any batch: max / min = the best of every row's top-1 (fused search; with a prior: the sparse-prior
     search), sum = colsum(U) . colsum(V) (+ the prior's sum).  Returns a python float."""
+    ops.require_index_rank("bbpr_transform.score_op")
     low = S.low if isinstance(S, LowRankPlusSparse) else S
     assert isinstance(low, LowRankScore), "score_op handles LowRankScore / LowRankPlusSparse"
     prior = S.prior if isinstance(S, LowRankPlusSparse) else None

@@ -414,6 +414,7 @@ def ranking_sharded(corpus, queries, encoder, block_dict=None, rank=0, world=1, 
     global_row_offset, so the result does not depend on the cut."""
     from .ms_marco_eval import KEEP, Retriever
     from .dist import sharded_search
+    ops.require_index_rank("encode.ranking_sharded")
     queries_ids, corpus_ids = list(queries.keys()), list(corpus.keys())
     sim = "cos" if os.environ["CCREC_SIM_TYPE"] == "cos" else "dot"
     keep = KEEP if keep is None else keep

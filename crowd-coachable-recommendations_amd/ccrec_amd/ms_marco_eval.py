@@ -26,12 +26,15 @@ CANONICAL_COS_SIM_MACS = 4e9   # above this many multiply-adds cos_sim() switche
 
 
 def generate_embeddings(data_indices, data_dic, embedding_func, batch_size, embedding_size=768, name=None, pack=None,
-                        device=None, norm_bounds=None, overflow=None):
+                        device=None, norm_bounds=None, overflow=None, kept=None):
     """scripts/ms_marco_eval.py:123-152.  Same batching, progress lines and return value (a [num, dim]
     tensor), but the result stays on the GPU.  pack=None -> fp32; pack="dot"/"cos" -> bf16 shard packed
     batch by batch (cos = L2-normalised first) -- an fp16 shard under CCREC_INDEX_DTYPE=fp16 (ops.index_dtype()), with
-    overflow (an ops.IndexOverflow of that type, optional) counting the elements that left fp16's range."""
+    overflow (an ops.IndexOverflow of that type, optional) counting the elements that left fp16's range.
+    kept (an ops.KeptF32 for these rows, optional; with pack only): the fp32 rows the pack rounded and their residual bounds are kept
+    beside the shard, batch by batch -- what ops.ExactF32Index ranks on under CCREC_RANK_PRECISION=fp32."""
     ops.require_gpu()
+    assert kept is None or pack is not None, "kept: the fp32 rows beside a PACKED shard"
     half = ops.index_dtype() if pack is not None else None   # read once per call
     assert overflow is None or overflow.dtype == half, "overflow: an IndexOverflow of the index's element type"
     num = len(data_indices)
@@ -61,6 +64,8 @@ def generate_embeddings(data_indices, data_dic, embedding_func, batch_size, embe
                 ops.pack_half(emb, half, normalize=(pack == "cos"), out=out[lo:lo + emb.shape[0]],
                               norm_bounds=None if norm_bounds is None else norm_bounds[lo:lo + emb.shape[0]],
                               overflow=None if overflow is None else overflow.counter)
+            if kept is not None:
+                kept.keep(emb, out[lo:lo + emb.shape[0]], lo, pack == "cos")
     torch.cuda.synchronize()
     print(f"Processed total {num} t={time.time() - tic:.1f}s")
     if out is None:
@@ -102,11 +107,19 @@ def block_csr(block_lists, n_rows):
 class Retriever:
     """Build the index once per active-learning step, query many times.
 
-    corpus_ids: list of passage ids in corpus row order; corpus_bf16: packed shard [N, dim], bf16 or fp16 (queries follow it)."""
+    corpus_ids: list of passage ids in corpus row order; corpus_bf16: packed shard [N, dim], bf16 or fp16 (queries follow it).
+    corpus_f32 + res_bounds (ops.keep_f32's outputs for the shard, with norm_bounds): the retriever ranks the fp32 rows through
+    ops.ExactF32Index; its searches then take the queries' fp32 embeddings, and normalize says whether the shard was packed for cos."""
 
-    def __init__(self, corpus_ids, corpus_bf16, global_row_offset=0, norm_bounds=None):
+    def __init__(self, corpus_ids, corpus_bf16, global_row_offset=0, norm_bounds=None, corpus_f32=None, res_bounds=None, normalize=False):
         self.corpus_ids = list(corpus_ids)
-        self.index = ops.CorpusIndex(corpus_bf16, global_row_offset, norm_bounds=norm_bounds)
+        self.exact = None
+        if corpus_f32 is not None:
+            self.exact = ops.ExactF32Index(corpus_bf16, corpus_f32, norm_bounds, res_bounds, global_row_offset)
+            self.normalize = bool(normalize)
+            self.index = self.exact.index
+        else:
+            self.index = ops.CorpusIndex(corpus_bf16, global_row_offset, norm_bounds=norm_bounds)
         self._pos = None
         self._cid_arr = None   # corpus ids as a numpy object array (built on first use)
 
@@ -119,6 +132,9 @@ class Retriever:
         """-> (scores [Q,k], ids [Q,k]) on device.  block_lists: per query list of blocked corpus rows (any length)."""
         n = self.index.n_rows
         k = min(k, n)
+        if self.exact is not None:   # (queries_bf16: the queries' fp32 embeddings here)
+            ptr, idx = (None, None) if block_lists is None else block_csr(block_lists, n)
+            return self.exact.search(queries_bf16, k, ptr, None if idx is None else idx + self.index.offset, normalize=self.normalize)
         if block_lists is None:
             return self.index.search(queries_bf16, k)
         ptr, idx = block_csr(block_lists, n)
@@ -162,6 +178,8 @@ def ranking(corpus, queries, embedding_func, batch_size, block_dict=None, lazy=F
     ops.require_gpu()
     queries_ids, corpus_ids = list(queries.keys()), list(corpus.keys())
     sim = "cos" if os.environ["CCREC_SIM_TYPE"] == "cos" else "dot"
+    if ops.rank_precision() == "fp32":
+        return _ranking_f32(corpus, queries, embedding_func, batch_size, block_dict, lazy, sim)
     # one overflow counter for this index build (fp16 only): queries and passages add to it, it is read once before the search
     overflow = ops.IndexOverflow(ops.index_dtype(), "cuda")
     queries_embeddings = generate_embeddings(queries_ids, queries, embedding_func, batch_size, pack=sim, overflow=overflow)
@@ -172,3 +190,19 @@ def ranking(corpus, queries, embedding_func, batch_size, block_dict=None, lazy=F
     overflow.check()
     retriever = Retriever(corpus_ids, passage_embeddings, norm_bounds=bounds)
     return retriever.ranking_profile(queries_ids, queries_embeddings, block_dict, lazy=lazy)
+
+
+def _ranking_f32(corpus, queries, embedding_func, batch_size, block_dict, lazy, sim):
+    """ranking() under CCREC_RANK_PRECISION=fp32: the same build, plus the fp32 rows and residual bounds kept beside the shard; the
+    queries stay fp32 (ExactF32Index.search packs them itself) and the profile is the ranking of the fp32 embeddings."""
+    queries_ids, corpus_ids = list(queries.keys()), list(corpus.keys())
+    overflow = ops.IndexOverflow(ops.index_dtype(), "cuda")
+    queries_embeddings = generate_embeddings(queries_ids, queries, embedding_func, batch_size)
+    bounds = torch.empty(len(corpus_ids), dtype=torch.float32, device="cuda") if corpus_ids else None
+    kept = ops.KeptF32(len(corpus_ids), "cuda")
+    passage_embeddings = generate_embeddings(corpus_ids, corpus, embedding_func, batch_size, pack=sim, norm_bounds=bounds,
+                                             overflow=overflow, kept=kept)
+    overflow.check()
+    retriever = Retriever(corpus_ids, passage_embeddings, norm_bounds=bounds, corpus_f32=kept.rows, res_bounds=kept.res_bounds,
+                          normalize=(sim == "cos"))
+    return retriever.ranking_profile(queries_ids, queries_embeddings.float(), block_dict, lazy=lazy)

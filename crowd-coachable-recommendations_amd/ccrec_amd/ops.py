@@ -275,6 +275,7 @@ def meanpool(hidden, mask):
     return _MeanPool.apply(hidden, mask)
 
 
+MAX_K = 4096   # the most results per query of a search (csrc/ccr_common.h)
 MAX_QUERIES_PER_SEARCH = 16384   # larger batches are searched in pieces (last_stats() then describes the last piece)
 
 
@@ -1074,6 +1075,7 @@ class CorpusIndex:
     def search_sparse_prior(self, queries_bf16, k, prior_ptr, prior_idx, prior_val, flags=_lib.SEARCH_DEFAULT):
         """Top-k of (low-rank score + sparse prior) (bbpr.py:592-595).  CSR prior over GLOBAL column ids (ascending, unique
         per row, <= 4096 per row), fp64 values.  -> (final scores [n_q, k] fp64, ids [n_q, k]) by (final desc, id asc)."""
+        require_index_rank("CorpusIndex.search_sparse_prior")
         q, ptr, idx = self._special_args(queries_bf16, prior_ptr, prior_idx)
         val = torch.as_tensor(prior_val, dtype=torch.float64).to(q.device).contiguous()
         assert val.numel() == idx.numel()
@@ -1126,6 +1128,253 @@ class CorpusIndex:
         with _on(q):
             _lib.check(self._lib.ccr_scores(self._h, _ptr(q), q.shape[0], m, _ptr(out), _stream(q)), "ccr_scores")
         return out
+
+
+# ---- ranking on the fp32 embeddings (library version 111, csrc/ccr_rank_f32.hip): the 16-bit search fetches somewhat more than k rows,
+# they are re-scored on the kept fp32 rows, and one inequality per query proves that no other row belongs to the fp32 top-k.  The
+# reference's CPU path ranks fp32 scores (scripts/ms_marco_eval.py:204-230); ccrec_amd/rank_f32_ref.py restates all of it in numpy ------
+_RANK_F32_CHECKED = False
+_RANK_PRECISIONS = ("index", "fp32")
+
+
+def _require_rank_f32():
+    """require_gpu() + once: the loaded library keeps and re-scores fp32 rows (ccr_version() >= 111)."""
+    global _RANK_F32_CHECKED
+    lib = _require_half_index()
+    if not _RANK_F32_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.RANK_F32_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, the fp32 ranking needs {_lib.RANK_F32_VERSION}: rebuild it "
+                                f"(python -c 'import __graft_entry__ as g; g.build()')")
+        _RANK_F32_CHECKED = True
+    return lib
+
+
+def rank_precision():
+    """What the ranking paths rank: os.environ["CCREC_RANK_PRECISION"] = "index" (the default when unset: the embeddings as the index
+    holds them, rounded to CCREC_INDEX_DTYPE) or "fp32" (the fp32 embeddings, through ExactF32Index), read at call time."""
+    name = os.environ.get("CCREC_RANK_PRECISION", "index")
+    if name not in _RANK_PRECISIONS:
+        raise ValueError(f"CCREC_RANK_PRECISION={name!r}: expected 'index' or 'fp32'")
+    return name
+
+
+def require_index_rank(what):
+    """Called by the entry points that rank the index's 16-bit rows only: NotImplementedError under CCREC_RANK_PRECISION=fp32."""
+    if rank_precision() == "fp32":
+        raise NotImplementedError(f"{what} ranks the index's 16-bit rows; CCREC_RANK_PRECISION=fp32 is implemented for "
+                                  f"ms_marco_eval.ranking / Retriever / ExactF32Index only: unset CCREC_RANK_PRECISION for this call")
+
+
+def keep_f32(x, packed, normalize=False, out=None, res_bounds=None):
+    """Beside rows that are already packed, keep the fp32 rows the pack rounded (ccr_keep_f32): x fp32 [rows, dim] (cuda), packed
+    [rows, padded_dim(dim)] bf16 or fp16 = pack_half(x, normalize=normalize) -> (kept fp32 [rows, padded_dim(dim)], zero-padded, with
+    normalize the normalised value the pack rounded; res_bounds [rows] fp32 >= ||kept row - packed row||).  out / res_bounds: write
+    into these (slices of shard-sized tensors)."""
+    lib = _require_rank_f32()
+    code = _check_index_dtype(packed.dtype)
+    assert x.is_cuda and x.dim() == 2, "keep_f32 expects a 2-d cuda tensor"
+    x = x.contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    rows, dim = x.shape
+    pdim = padded_dim(dim)
+    assert packed.is_cuda and packed.is_contiguous() and tuple(packed.shape) == (rows, pdim) and packed.device == x.device
+    if out is None:
+        out = torch.empty(rows, pdim, dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (rows, pdim)
+    if res_bounds is None:
+        res_bounds = torch.empty(rows, dtype=torch.float32, device=x.device)
+    _check_bounds(res_bounds, rows)
+    with _on(x):
+        _lib.check(lib.ccr_keep_f32(_ptr(x), _ptr(packed), code, int(bool(normalize)), _ptr(out), _ptr(res_bounds), rows, dim, _stream(x)),
+                   "ccr_keep_f32")
+    return out, res_bounds
+
+
+class KeptF32:
+    """The fp32 side of ONE index build under CCREC_RANK_PRECISION=fp32: `rows` [num, padded_dim(dim)] fp32 (allocated with the first
+    batch, when the width is known) and `res_bounds` [num] fp32; generate_embeddings(kept=...) fills both batch by batch."""
+
+    def __init__(self, num, device="cuda"):
+        self.num, self.device = int(num), torch.device(device)
+        self.rows = None
+        self.res_bounds = torch.empty(self.num, dtype=torch.float32, device=self.device)
+
+    def keep(self, emb, packed, lo, normalize):
+        if self.rows is None:
+            self.rows = torch.empty(self.num, packed.shape[1], dtype=torch.float32, device=self.device)
+        hi = lo + emb.shape[0]
+        keep_f32(emb, packed, normalize, out=self.rows[lo:hi], res_bounds=self.res_bounds[lo:hi])
+
+
+def rescore_f32(queries_f32, corpus_f32, cand_ids, cand_s16, k, q_norm_bounds, q_res_bounds, corpus_max, id_offset=0):
+    """ccr_rescore_f32: kept fp32 queries [n_q, pdim] and corpus [n_rows, pdim], cand_ids / cand_s16 [n_q, n_cand] = the first n_cand
+    results of the 16-bit search (global ids, scores) -> (scores [n_q, k] fp32, ids [n_q, k] int64 by (fp32 score desc, id asc),
+    flags [n_q] int32: 0 = no row outside the list can belong to the fp32 top-k, diag [n_q, 4] fp32 = {tau, cut, E, slack})."""
+    lib = _require_rank_f32()
+    q, d = queries_f32, corpus_f32
+    assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 2 and q.is_contiguous()
+    assert d.is_cuda and d.dtype == torch.float32 and d.dim() == 2 and d.is_contiguous() and d.shape[1] == q.shape[1] and d.device == q.device
+    n_q, pdim = q.shape
+    cand_ids, cand_s16 = cand_ids.contiguous(), cand_s16.contiguous()
+    assert cand_ids.dtype == torch.int64 and cand_s16.dtype == torch.float32 and cand_ids.shape == cand_s16.shape and cand_ids.dim() == 2
+    assert cand_ids.shape[0] == n_q and cand_ids.device == q.device == cand_s16.device
+    n_cand = cand_ids.shape[1]
+    for t in (q_norm_bounds, q_res_bounds):
+        _check_bounds(t, n_q)
+    assert corpus_max.is_cuda and corpus_max.dtype == torch.float32 and corpus_max.numel() == 2 and corpus_max.is_contiguous()
+    need = _workspace_bytes(lib, "ccr_rescore_f32_workspace_bytes", n_q, n_cand, int(k), pdim)
+    diag = torch.empty(need // 4, dtype=torch.float32, device=q.device)
+    scores = torch.empty(n_q, k, dtype=torch.float32, device=q.device)
+    ids = torch.empty(n_q, k, dtype=torch.int64, device=q.device)
+    flags = torch.empty(n_q, dtype=torch.int32, device=q.device)
+    with _on(q):
+        _lib.check(lib.ccr_rescore_f32(_ptr(q), _ptr(d), d.shape[0], pdim, _ptr(cand_ids), _ptr(cand_s16), n_q, n_cand, int(k), int(id_offset),
+                                       _ptr(q_norm_bounds), _ptr(q_res_bounds), _ptr(corpus_max), _ptr(scores), _ptr(ids), _ptr(flags),
+                                       _ptr(diag), need, _stream(q)), "ccr_rescore_f32")
+    return scores, ids, flags, diag[:4 * n_q].view(n_q, 4)
+
+
+DENSE_SCORE_BYTES = 1 << 30   # the dense path of ExactF32Index takes index.scores() in query chunks of at most this many bytes
+
+
+class ExactF32Index:
+    """The fp32 ranking of a shard: a CorpusIndex over the 16-bit rows (`.index`) plus the kept fp32 rows and the bounds that tie the two
+    together.  search() returns exactly the ranking of the fp32 rows by (s32 desc, id asc) -- rank_f32_ref.ranking.
+
+    corpus_half [n_rows, pdim] bf16 or fp16, corpus_f32 [n_rows, pdim] fp32 and res_bounds [n_rows] = keep_f32's outputs for those rows,
+    norm_bounds [n_rows] = the pack's bound of every packed row's norm.  ValueError when a bound is not finite (NaN / inf embeddings,
+    or an element that left fp16's range): such a corpus stays on the 16-bit paths.
+    max_candidates: the most rows the 16-bit search is asked for per query before the dense path takes over (<= MAX_K)."""
+
+    def __init__(self, corpus_half, corpus_f32, norm_bounds, res_bounds, global_row_offset=0, max_candidates=MAX_K):
+        _require_rank_f32()
+        max_candidates = int(max_candidates)
+        assert 1 <= max_candidates <= MAX_K
+        self.index = CorpusIndex(corpus_half, global_row_offset, norm_bounds=norm_bounds)
+        self.n_rows, self.dim, self.dtype, self.offset = self.index.n_rows, self.index.dim, self.index.dtype, self.index.offset
+        assert corpus_f32.is_cuda and corpus_f32.dtype == torch.float32 and tuple(corpus_f32.shape) == (self.n_rows, self.dim)
+        assert corpus_f32.is_contiguous() and corpus_f32.device == self.index.corpus.device
+        _check_bounds(norm_bounds, self.n_rows)
+        _check_bounds(res_bounds, self.n_rows)
+        self.corpus_f32, self.norm_bounds, self.res_bounds = corpus_f32, norm_bounds[:self.n_rows], res_bounds[:self.n_rows]
+        self.max_candidates = max_candidates
+        self.corpus_max = torch.stack([self.res_bounds.max(), self.norm_bounds.max()])   # {Rmax, Nmax}: read on the device
+        if not bool(torch.isfinite(self.corpus_max).all()):
+            raise ValueError("ExactF32Index: a row's norm or residual bound is not finite (NaN / inf embeddings, or fp16 overflow): "
+                             "rank this corpus on the 16-bit paths (CCREC_RANK_PRECISION=index)")
+        self._stats = {"rungs": [], "flagged": [], "dense": 0, "dense_rows": []}
+
+    def last_stats(self):
+        """Of the last search(): {"rungs": candidates per rung that ran, "flagged": queries still unverified after each,
+        "dense": queries the dense path finished, "dense_rows": rows its filter kept per such query}."""
+        return {k: (list(v) if isinstance(v, list) else v) for k, v in self._stats.items()}
+
+    def _search16(self, hq, n, ptr, idx_cpu, rows):
+        """The 16-bit search for n rows of the queries `rows` (None: all) of hq, with their block lists."""
+        q = hq if rows is None else hq[rows]
+        if ptr is None:
+            return self.index.search(q, n)
+        if rows is None:
+            return self.index.search_blocked(q, n, ptr, idx_cpu)
+        parts = [idx_cpu[int(ptr[r]):int(ptr[r + 1])] for r in rows.tolist()]
+        sub = torch.zeros(len(parts) + 1, dtype=torch.int64)
+        sub[1:] = torch.cumsum(torch.tensor([p.numel() for p in parts], dtype=torch.int64), 0)
+        return self.index.search_blocked(q, n, sub, torch.cat(parts) if parts else idx_cpu[:0])
+
+    def search(self, queries_f32, k, block_ptr=None, block_idx=None, normalize=False):
+        """queries_f32 [n_q, dim] fp32 (cuda; the width before padding), normalize = the corpus was packed with normalize (cos) ->
+        (scores [n_q, k] fp32, ids [n_q, k] int64 global).  block_ptr / block_idx: CorpusIndex.search_blocked's CSR of GLOBAL ids
+        (blocked rows score -1e6 and stay in the ranking)."""
+        q = queries_f32
+        assert q.is_cuda and q.dim() == 2 and padded_dim(q.shape[1]) == self.dim, "queries: fp32 [n_q, dim] of the corpus's width"
+        k = int(k)
+        top = min(self.n_rows, self.max_candidates)
+        if not 1 <= k <= top:
+            raise ValueError(f"ExactF32Index.search: k={k} outside [1, min(n_rows, max_candidates) = {top}]")
+        n_q = q.shape[0]
+        dev = q.device
+        scores = torch.empty(n_q, k, dtype=torch.float32, device=dev)
+        ids = torch.empty(n_q, k, dtype=torch.int64, device=dev)
+        stats = self._stats = {"rungs": [], "flagged": [], "dense": 0, "dense_rows": []}
+        if n_q == 0:
+            return scores, ids
+        ptr = idx_cpu = None
+        if block_ptr is not None:
+            ptr = torch.as_tensor(block_ptr, dtype=torch.int64).cpu().contiguous()
+            idx_cpu = torch.as_tensor(block_idx, dtype=torch.int64).cpu().contiguous()
+            assert ptr.numel() == n_q + 1 and idx_cpu.numel() == int(ptr[-1])
+        # 1. the queries as the index takes them, their kept fp32 rows and their two bounds
+        nbq = torch.empty(n_q, dtype=torch.float32, device=dev)
+        hq = pack_half(q, self.dtype, normalize=normalize, norm_bounds=nbq)
+        yq, rq = keep_f32(q, hq, normalize)
+        A = torch.nextafter(nbq + rq, torch.full_like(nbq, float("inf")))   # >= ||kept row||: triangle inequality, one fp32 step up
+        if not bool((torch.isfinite(A) & torch.isfinite(rq)).all()):
+            raise ValueError("ExactF32Index.search: a query's norm or residual bound is not finite (NaN / inf embeddings): rank these "
+                             "queries on the 16-bit paths (CCREC_RANK_PRECISION=index)")
+        # 2./3. the rungs: 2 k + 32 rows first, doubled for the queries still unverified
+        n = min(top, 2 * k + 32)
+        rows = None   # queries still to do (None: all)
+        while True:
+            s16, i16 = self._search16(hq, n, ptr, idx_cpu, rows)
+            sub = slice(None) if rows is None else rows
+            s, i, flags, _ = rescore_f32(yq[sub], self.corpus_f32, i16, s16, k, A[sub], rq[sub], self.corpus_max, self.offset)
+            scores[sub], ids[sub] = s, i
+            bad = flags.nonzero().flatten()          # (the one host read of a rung)
+            rows = bad if rows is None else rows[bad]
+            stats["rungs"].append(n)
+            stats["flagged"].append(int(rows.numel()))
+            if rows.numel() == 0 or n == top:
+                break
+            n = min(top, 2 * n)
+        # 4. still unverified: the dense path
+        if rows.numel():
+            self._dense(hq, yq, A, rq, rows, k, ptr, idx_cpu, scores, ids)
+        return scores, ids
+
+    def _dense(self, hq, yq, A, rq, rows, k, ptr, idx_cpu, scores, ids):
+        """The queries `rows`: every row whose 16-bit score, raised by the row's own bounds, reaches the last rung's tau (a lower bound of
+        the true k-th fp32 score, so the true top-k is among them) is re-scored on the fp32 rows; chunks of MAX_K, merged."""
+        stats = self._stats
+        Rmax, Nmax = (float(v) for v in self.corpus_max.double().tolist())
+        res64, norm64 = self.res_bounds.double(), self.norm_bounds.double()
+        per = max(1, DENSE_SCORE_BYTES // (self.n_rows * 4))
+        row_list = rows.tolist()
+        for lo in range(0, len(row_list), per):
+            part = row_list[lo:lo + per]
+            s16_all = self.index.scores(hq[rows[lo:lo + per]], "canonical")
+            for j, r in enumerate(part):
+                s16 = s16_all[j]
+                if ptr is not None:
+                    blocked = idx_cpu[int(ptr[r]):int(ptr[r + 1])] - self.offset
+                    blocked = blocked[(blocked >= 0) & (blocked < self.n_rows)]
+                    s16[blocked.to(s16.device)] = -1e6
+                tau = scores[r, k - 1].double()
+                a, rr = A[r].double(), rq[r].double()
+                s64 = s16.double()
+                slack = 2.0 ** -21 * (s64.abs() + tau.abs()) + 2.0 ** -40 * (a * (Nmax + Rmax))
+                keep = ((s64 + (a * res64 + rr * norm64)) + slack >= tau).nonzero().flatten()
+                m = int(keep.numel())
+                assert m >= k, "the dense filter keeps the last rung's own top-k"
+                parts_s, parts_i = [], []
+                for c in range(0, m, MAX_K):
+                    rows_c = keep[c:c + MAX_K]
+                    n_c = int(rows_c.numel())
+                    s, i, _, _ = rescore_f32(yq[r:r + 1], self.corpus_f32, (rows_c + self.offset)[None, :], s16[rows_c][None, :], n_c,
+                                             A[r:r + 1], rq[r:r + 1], self.corpus_max, self.offset)
+                    if n_c < k:   # a short last chunk: entries below every real one fill its list
+                        s = torch.cat([s, torch.full((1, k - n_c), float("-inf"), device=s.device)], 1)
+                        i = torch.cat([i, torch.full((1, k - n_c), 1 << 62, dtype=torch.int64, device=i.device)], 1)
+                    parts_s.append(s[:, :k])
+                    parts_i.append(i[:, :k])
+                if len(parts_s) == 1:
+                    scores[r], ids[r] = parts_s[0][0], parts_i[0][0]
+                else:
+                    ms, mi = merge_topk(torch.stack(parts_s), torch.stack(parts_i))
+                    scores[r], ids[r] = ms[0], mi[0]
+                stats["dense"] += 1
+                stats["dense_rows"].append(m)
 
 
 def _rank_strided(t):

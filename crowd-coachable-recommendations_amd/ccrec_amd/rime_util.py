@@ -58,6 +58,7 @@ def _low_rank_plus_sparse(S):
 
 
 def _assign_topk(S, k, tie_breaker=1e-10, device="cpu", batch_size=None):
+    ops.require_index_rank("rime_util._assign_topk")
     if hasattr(S, "topk") and hasattr(S, "shape") and not isinstance(S, torch.Tensor):   # LowRankScore / LowRankPlusSparse
         _, ids = S.topk(k)
         return _csr_of_ones(ids.cpu().numpy(), S.shape)

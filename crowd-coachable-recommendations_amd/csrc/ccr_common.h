@@ -199,6 +199,24 @@ __device__ __forceinline__ float elem_hi(uint32_t w) {
         return __uint_as_float(w & 0xffff0000u);
 }
 
+// The canonical fp64 sum of squares of an fp32 row (dim % 4 == 0, 16-byte aligned), one wave per row: lane l owns the float4 chunks c with
+// c % 64 == l, accumulated in increasing index, then the butterfly p += shfl_xor(p, off) for off = 32..1 (every lane ends with the same
+// sum).  This order is part of the canonical definition (index_ref.row_sumsq); the normalising pack and the kept fp32 rows share it.
+__device__ __forceinline__ double wave_sumsq(const float *__restrict__ x, int dim, int lane) {
+    double p = 0.0;
+    const int nchunk = dim >> 2;
+    for (int c = lane; c < nchunk; c += 64) {
+        float4 v = reinterpret_cast<const float4 *>(x)[c];
+        p = p + (double)v.x * (double)v.x;
+        p = p + (double)v.y * (double)v.y;
+        p = p + (double)v.z * (double)v.z;
+        p = p + (double)v.w * (double)v.w;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) p = p + __shfl_xor(p, off, 64);
+    return p;
+}
+
 // monotone map float -> uint32 (larger float <-> larger uint); NaN maps above +inf (never produced here)
 __device__ __forceinline__ uint32_t f32_orderable(float f) {
     uint32_t u = __float_as_uint(f);

@@ -175,21 +175,7 @@ __global__ __launch_bounds__(256) void pack_rows_bound_kernel(const float *__res
 // One wave per row.  Lane l owns float4 chunks c with c % 64 == l; per-lane fp64 partial sum in
 // increasing index, then the butterfly p += shfl_xor(p, off) for off = 32..1 (every lane ends
 // with the same fp64 sum of squares).  This order is part of the canonical definition.
-__device__ __forceinline__ double wave_sumsq(const float *__restrict__ x, int dim, int lane) {
-    double p = 0.0;
-    const int nchunk = dim >> 2;
-    for (int c = lane; c < nchunk; c += 64) {
-        float4 v = reinterpret_cast<const float4 *>(x)[c];
-        p = p + (double)v.x * (double)v.x;
-        p = p + (double)v.y * (double)v.y;
-        p = p + (double)v.z * (double)v.z;
-        p = p + (double)v.w * (double)v.w;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p = p + __shfl_xor(p, off, 64);
-    return p;
-}
-
+// (wave_sumsq: ccr_common.h -- csrc/ccr_rank_f32.hip keeps the fp32 rows the pack rounded with the same helper)
 template <class E>
 __global__ __launch_bounds__(256) void pack_rows_kernel(const float *__restrict__ src, E *__restrict__ dst,
                                                        float *__restrict__ norms, int64_t rows, int dim,

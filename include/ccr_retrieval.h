@@ -791,6 +791,38 @@ int ccr_embedding_grad(const int64_t *idx, const int64_t *order, const float *d_
 int ccr_meanpool_bwd_packed(const float *grad, const int32_t *seq_start, const int32_t *seq_len, void *d_hidden, int hidden_dtype, int n_seq,
                             int dim, void *stream);
 
+/*
+ * Ranking on the fp32 embeddings (library version 111; opt-in: no other entry point changes).  The reference's CPU path ranks fp32 scores
+ * (scripts/ms_marco_eval.py:204-230); every search here ranks the rows after they were rounded to 16 bits.  These two entry points give
+ * the fp32 ranking on top of the 16-bit search, with a proof per query (DESIGN.md 2.1;
+ * ccrec_amd/rank_f32_ref.py restates both in numpy, bit for bit).
+ * ccr_keep_f32: beside rows that are ALREADY packed (half_rows [rows][pdim], pdim = dim rounded up to a multiple of 8, half_dtype =
+ *   CCR_DTYPE_BF16 / F16) keep the fp32 rows the pack rounded: dst_f32 [rows][pdim] = src [rows][dim] zero-padded, with normalize the
+ *   value (float)((double) x_i / max(sqrt(ss), 1e-12)) of the normalising pack (the same sum of squares in the same order), so that
+ *   rounding dst_f32 gives half_rows bit for bit.  res_bounds [rows] >= ||dst_f32[r] - half_rows[r]||_2: the fp64 norm, inflated by
+ *   1 + 2^-20 and rounded UP to fp32.  One pass over the shard, a wave per row.
+ * ccr_rescore_f32: one workgroup per query.  cand_ids / cand_s16 [n_q][n_cand]: the first n_cand results of the 16-bit search (GLOBAL
+ *   ids = row + id_offset, canonical 16-bit scores, in that search's rank order).  Each candidate is re-scored on the fp32 rows,
+ *   s32 = (float) sum_i ascending fma((double) q_i, (double) d_i, acc); an entry whose cand_s16 is exactly -1e6f (a blocked row) keeps
+ *   -1e6.  out_scores / out_ids [n_q][k]: the k best by (s32 desc, id asc).  flags [n_q]: 0 = verified, no row outside the list can
+ *   belong to -- or tie with -- the fp32 top-k; 1 = not verified (fetch more rows).  With tau = out_scores[q][k - 1],
+ *   cut = cand_s16[q][n_cand - 1], A = q_norm_bounds[q] >= ||query row||, r = q_res_bounds[q] (the query's own ccr_keep_f32 bound),
+ *   corpus_max = {Rmax, Nmax} (DEVICE: the maxima of the corpus's res_bounds and of its packed rows' norm bounds), in fp64:
+ *     E = A * Rmax + r * Nmax,   slack = 2^-21 (|cut| + |tau|) + 2^-40 A (Nmax + Rmax),
+ *     verified <=> n_cand == n_rows  or  cut == -1e6f  or  cut + E + slack < tau.
+ *   A candidate id outside [id_offset, id_offset + n_rows) is not read and leaves its query unverified.
+ *   workspace (DEVICE, 16-byte aligned, ccr_rescore_f32_workspace_bytes; 0 = the shape was refused): on return {tau, cut, E, slack} as
+ *   4 floats per query.  CCR_ERR_INVALID on k > n_cand, n_cand > 4096, n_cand > n_rows, pdim % 8 != 0 or > 4096, or a null pointer: no
+ *   output is touched.
+ */
+int ccr_keep_f32(const float *src, const uint16_t *half_rows, int half_dtype, int normalize, float *dst_f32, float *res_bounds, int64_t rows,
+                 int dim, void *stream);
+size_t ccr_rescore_f32_workspace_bytes(int n_q, int n_cand, int k, int pdim);
+int ccr_rescore_f32(const float *queries_f32, const float *corpus_f32, int64_t n_rows, int pdim, const int64_t *cand_ids,
+                    const float *cand_s16, int n_q, int n_cand, int k, int64_t id_offset, const float *q_norm_bounds,
+                    const float *q_res_bounds, const float *corpus_max, float *out_scores, int64_t *out_ids, int32_t *flags, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
