@@ -1050,3 +1050,106 @@ def bm25_postings_from_lists(lists):
     rows = np.concatenate([np.asarray(d, np.int64) for d, _ in lists]).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
     counts = np.concatenate([np.asarray(f, np.float32) for _, f in lists]).astype(np.float32) if indptr[-1] else np.zeros(0, np.float32)
     return indptr, rows, counts
+
+
+# ------------------------------------------------------------------------------------------------ the exact-score probe of the search
+# A corpus of width 8 whose canonical score row is chosen digit by digit (tests/test_cpu_exact_probe.py checks every claim made here
+# against the oracle; tests/test_gpu_exact_paths.py searches it).  Row j is sign_j 2^e_j (a_j, b_j, c_j, 0, ..), the query is
+# 2^EXACT_PROBE[kind]["query"] on the first three elements: the score is sign 2^(e + q0) (a + b / 256 + c / 65536), a 24-bit number, so
+# the fp64 sum and every fp32 partial sum in any order are exact, and the fp32 pattern's bytes are (sign | exponent >> 1), (exponent's
+# low bit | a's low seven bits), b, c.  fp16 takes another query and a narrower exponent range: 2^-16 is no normal fp16 number.
+EXACT_PROBE = {"bf16": {"query": (0, -8, -16), "e": (-12, 12)}, "fp16": {"query": (8, 0, -8), "e": (-6, 6)}}
+EXACT_PROBE_FP16_WIDE_E = (-12, 6)     # 19 exponents (ten values of exponent >> 1): elements from 2^-12 to 255 x 2^6, all normal in fp16
+
+
+def f32_orderable(x):
+    """uint32 keys whose unsigned order is the order of the fp32 values (ccr_common.h: f32_orderable)."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    return np.where(u >> np.uint32(31), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def exact_probe_pack(values, kind):
+    """fp64 values -> uint16 bit patterns of `kind`; asserts that nothing is lost and, for fp16, that nothing is subnormal."""
+    v64 = np.ascontiguousarray(values, np.float64)
+    v = v64.astype(np.float32)
+    assert np.array_equal(v.astype(np.float64), v64)
+    if kind == "fp16":
+        h = v.astype(np.float16)
+        assert np.array_equal(h.astype(np.float32), v) and np.all((v == 0) | (np.abs(v) >= 2.0 ** -14))
+        return h.view(np.uint16)
+    u = v.view(np.uint32)
+    assert not (u & np.uint32(0xFFFF)).any()
+    return (u >> np.uint32(16)).astype(np.uint16)
+
+
+def exact_probe_draw(n, seed, kind, e_range=None):
+    """n rows with every digit drawn uniformly: (sign, e, a, b, c), int64 arrays."""
+    rs = np.random.RandomState(seed)
+    lo, hi = e_range or EXACT_PROBE[kind]["e"]
+    return (rs.choice([-1, 1], n).astype(np.int64), rs.randint(lo, hi + 1, n).astype(np.int64), rs.randint(128, 256, n).astype(np.int64),
+            rs.randint(0, 256, n).astype(np.int64), rs.randint(0, 256, n).astype(np.int64))
+
+
+def exact_probe_fixed(n, sign, e, a, b, c):
+    """n rows with the same digits."""
+    return tuple(np.full(n, v, np.int64) for v in (sign, e, a, b, c))
+
+
+def exact_probe_cat(*parts):
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(5))
+
+
+def exact_probe_take(digits, rows):
+    return tuple(d[rows] for d in digits)
+
+
+def _exact_probe_check(digits, kind, e_range):
+    sign, e, a, b, c = digits
+    lo, hi = e_range or EXACT_PROBE[kind]["e"]
+    assert np.all(np.abs(sign) == 1) and e.min() >= lo and e.max() <= hi
+    assert a.min() >= 128 and a.max() <= 255 and min(b.min(), c.min()) >= 0 and max(b.max(), c.max()) <= 255
+
+
+def exact_probe_rows(digits, kind, dim=8, e_range=None):
+    """[n, dim] bit patterns of the probe's corpus rows."""
+    _exact_probe_check(digits, kind, e_range)
+    sign, e, a, b, c = digits
+    rows = np.zeros((len(a), dim), np.float64)
+    scale = sign * np.exp2(e.astype(np.float64))
+    for col, digit in enumerate((a, b, c)):
+        rows[:, col] = scale * digit
+    return exact_probe_pack(rows, kind)
+
+
+def exact_probe_queries(scales, kind, dim=8):
+    """[len(scales), dim] bit patterns: the probe's query times each of `scales` (signed powers of two)."""
+    scales = np.asarray(scales, np.float64)
+    assert np.all(np.exp2(np.round(np.log2(np.abs(scales)))) == np.abs(scales))
+    q = np.zeros((len(scales), dim), np.float64)
+    for col, p in enumerate(EXACT_PROBE[kind]["query"]):
+        q[:, col] = scales * 2.0 ** p
+    return exact_probe_pack(q, kind)
+
+
+def exact_probe_scores(digits, kind):
+    """[n] fp32: the score row of the unscaled probe query, from the integers alone (asserted to be exact in fp32)."""
+    sign, e, a, b, c = digits
+    m = (a << 16) + (b << 8) + c
+    assert m.min() >= 1 << 23 and m.max() < 1 << 24
+    s = sign * m * np.exp2((e + EXACT_PROBE[kind]["query"][0] - 16).astype(np.float64))
+    f = s.astype(np.float32)
+    assert np.array_equal(f.astype(np.float64), s)
+    return f
+
+
+def exact_probe_topk(digits, kind, scales, k):
+    """(ids [len(scales), k] int64, scores [len(scales), k] fp32) by (score descending, row ascending), in numpy from the integers: a
+    positive scale keeps the order of the unscaled row, a negative one ranks by ascending score; the scores scale exactly."""
+    base = exact_probe_scores(digits, kind)
+    rows = np.arange(len(base))
+    order = {1: np.lexsort((rows, -base))[:k], -1: np.lexsort((rows, base))[:k]}
+    ids = np.stack([order[1 if s > 0 else -1] for s in scales])
+    sc = np.asarray(scales, np.float64)[:, None] * base[ids].astype(np.float64)
+    out = sc.astype(np.float32)
+    assert np.array_equal(out.astype(np.float64), sc)
+    return ids, out
