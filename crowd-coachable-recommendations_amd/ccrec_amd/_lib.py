@@ -34,6 +34,7 @@ EXPORTS = [
     "ccr_index_create_with_norms_half", "ccr_index_dtype", "ccr_colsum_half",
     "ccr_grad_stats_workspace_bytes", "ccr_grad_stats", "ccr_adamw_control_update", "ccr_adamw_step_scaled",
     "ccr_keep_f32", "ccr_rescore_f32_workspace_bytes", "ccr_rescore_f32",
+    "ccr_attention_bias_half",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
@@ -47,6 +48,7 @@ ENCODER_PACKED_TRAIN_VERSION = 108   # ... and the embedding block's and the pac
 HALF_INDEX_VERSION = 109   # ... and the pack, index and search on either 16-bit element type (ccr_index_create_half and its kin)
 AMP_OPTIM_VERSION = 110   # ... and loss scaling, overflow skip and norm clipping inside the AdamW step (ccr_adamw_step_scaled and its kin)
 RANK_F32_VERSION = 111   # ... and the kept fp32 rows with the verified re-score of a 16-bit search on them (ccr_keep_f32, ccr_rescore_f32)
+ATTENTION_BIAS_VERSION = 112   # ... and the attention forward with a shared relative position bias (ccr_attention_bias_half)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -175,6 +177,7 @@ def load():
     lib.ccr_embed_layernorm.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, i64, i32, vp]
     lib.ccr_gelu_bf16.argtypes = [vp, vp, i64, vp]
     lib.ccr_attention_half.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, vp]
+    lib.ccr_attention_bias_half.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, i32, vp]
     lib.ccr_add_layernorm_half.argtypes = [vp, vp, vp, vp, ctypes.c_float, vp, vp, i64, i32, i32, vp]
     lib.ccr_embed_layernorm_half.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, i64, i32, i32, vp]
     lib.ccr_gelu_half.argtypes = [vp, vp, i64, i32, vp]

@@ -17,9 +17,18 @@ gradients on, on the kernels' backward (ops.attention_train, add_layernorm_train
 packed keep bits that a generator kernel writes from one 64-bit seed per call (ops.dropout_bits_rows / dropout_bits_attention, restated on
 the CPU in dropout_ref); without that opt-in such a model is refused and keeps training as its torch module.
 
-Only what the kernels cover is accepted (unsupported_reason): a BertModel or DistilBertModel encoder (post-LayerNorm layers, absolute
-positions, exact GELU), head width 64, hidden size a multiple of 256, at most 512 tokens, right-padded batches.  Every other encoder keeps
-running as its own torch module -- LengthSortedEncoder picks per model."""
+Only what the kernels cover is accepted (unsupported_reason): post-LayerNorm layers with exact GELU, head width 64, hidden size a
+multiple of 256, at most 512 tokens, right-padded batches, in one of these transformers classes:
+
+  BertModel, DistilBertModel       absolute positions: the position row of a token is its index inside its sequence;
+  RobertaModel, XLMRobertaModel    BERT's layers; the position row is padding_idx + the number of non-pad ids up to and including the
+                                   token, and padding_idx itself for a pad-id token (position_rows); the module's own type table;
+  MPNetModel                       the same position rule, no token types, and one relative position bias shared by every layer, added to
+                                   the scaled attention scores (relative_bias_table, ops.attention(rel_bias=...)).  Inference only: the
+                                   bias table's gradient has no kernel, so MPNet trains as its torch module (train_unsupported_reason).
+
+The reference builds its tower with AutoModel.from_pretrained(MODEL_NAME) (src/ccrec/models/bbpr.py:30, bert_mt.py:74), so any of them
+can arrive.  Every other encoder keeps running as its own torch module -- LengthSortedEncoder picks per model."""
 import collections
 import os
 import threading
@@ -33,40 +42,97 @@ from . import ops
 class _Arch:
     """Where a supported architecture keeps the pieces of its (post-LayerNorm, GELU) encoder layer."""
 
-    def __init__(self, heads, hidden, activation, stack, embeddings, type_table, layer_parts, dropout_parts):
+    def __init__(self, heads, hidden, activation, stack, embeddings, type_table, layer_parts, dropout_parts, padding_idx=None,
+                 bias_source=None):
         self.heads, self.hidden, self.activation = heads, hidden, activation
         self.stack = stack                    # the module whose parameters are the layers' weights
         self.embeddings, self.type_table = embeddings, type_table
         self.layer_parts = layer_parts        # layer module -> (q, k, v, attention out, LayerNorm 1, ffn in, ffn out, LayerNorm 2)
         self.dropout_parts = dropout_parts    # layer module -> the Dropout modules on (probabilities, attention output or None, ffn output)
+        self.padding_idx = padding_idx        # the position rule: None = a token's position row is its in-sequence index; an int = position_rows
+        self.bias_source = bias_source        # None, or the module with relative_attention_bias / relative_position_bucket (relative_bias_table)
+
+
+_BERT_LAYER_PARTS = (lambda m: (m.attention.self.query, m.attention.self.key, m.attention.self.value, m.attention.output.dense,
+                                m.attention.output.LayerNorm, m.intermediate.dense, m.output.dense, m.output.LayerNorm),
+                     lambda m: (m.attention.self.dropout, m.attention.output.dropout, m.output.dropout))
 
 
 def _describe(model):
     """-> _Arch for a transformers BertModel or DistilBertModel (the reference's encoders: facebook/contriever and bert-base-uncased are
     BertModels, src/ccrec/models/bbpr.py:334, scripts/al_0_rank.py:120; distilbert-base-uncased is its default model_name,
-    bbpr.py:50, bert_mt.py:35), or a string saying why the class is not covered."""
+    bbpr.py:50, bert_mt.py:35), a RobertaModel, XLMRobertaModel or MPNetModel (what --MODEL_NAME brings in: bbpr.py:30, bert_mt.py:74), or a
+    string saying why the class is not covered."""
     name, cfg = type(model).__name__, getattr(model, "config", None)
-    if name == "BertModel" and hasattr(model, "embeddings") and hasattr(model, "encoder"):
+    if name in ("BertModel", "RobertaModel", "XLMRobertaModel") and hasattr(model, "embeddings") and hasattr(model, "encoder"):
         if getattr(cfg, "position_embedding_type", None) not in (None, "absolute"):
             return f"position_embedding_type {cfg.position_embedding_type!r}"
         if getattr(cfg, "is_decoder", False) or getattr(cfg, "add_cross_attention", False):
             return "decoder / cross-attention layers"
         e = model.embeddings
         return _Arch(int(cfg.num_attention_heads), int(cfg.hidden_size), getattr(cfg, "hidden_act", "gelu"), model.encoder, e,
-                     e.token_type_embeddings.weight,
-                     lambda m: (m.attention.self.query, m.attention.self.key, m.attention.self.value, m.attention.output.dense,
-                                m.attention.output.LayerNorm, m.intermediate.dense, m.output.dense, m.output.LayerNorm),
-                     lambda m: (m.attention.self.dropout, m.attention.output.dropout, m.output.dropout))
+                     e.token_type_embeddings.weight, *_BERT_LAYER_PARTS,
+                     padding_idx=None if name == "BertModel" else int(e.padding_idx))
+    if name == "MPNetModel" and hasattr(model, "embeddings") and hasattr(model, "encoder"):
+        e = model.embeddings
+        return _Arch(int(cfg.num_attention_heads), int(cfg.hidden_size), getattr(cfg, "hidden_act", "gelu"), model.encoder, e, None,
+                     lambda m: (m.attention.attn.q, m.attention.attn.k, m.attention.attn.v, m.attention.attn.o, m.attention.LayerNorm,
+                                m.intermediate.dense, m.output.dense, m.output.LayerNorm),
+                     lambda m: (m.attention.attn.dropout, m.attention.dropout, m.output.dropout),
+                     padding_idx=int(e.padding_idx), bias_source=model.encoder)
     if name == "DistilBertModel" and hasattr(model, "embeddings") and hasattr(model, "transformer"):
         return _Arch(int(cfg.n_heads), int(cfg.dim), getattr(cfg, "activation", "gelu"), model.transformer, model.embeddings, None,
                      lambda m: (m.attention.q_lin, m.attention.k_lin, m.attention.v_lin, m.attention.out_lin, m.sa_layer_norm,
                                 m.ffn.lin1, m.ffn.lin2, m.output_layer_norm),
                      lambda m: (m.attention.dropout, None, m.ffn.dropout))      # (nothing between out_lin and sa_layer_norm)
-    return f"{name} is not a BertModel or DistilBertModel"
+    return f"{name} is not a BertModel, DistilBertModel, RobertaModel, XLMRobertaModel or MPNetModel"
+
+
+def position_rows(token_ids, positions, padding_idx):
+    """The position-table rows of a flat token array under RoBERTa's rule (transformers' create_position_ids_from_input_ids, restated for
+    arrays whose sequences lie one after another): padding_idx + the number of non-pad ids among the tokens of the same sequence up to and
+    including this one, and padding_idx itself where the id is padding_idx.  token_ids, positions: int64 [T]; positions = each token's
+    0-based index inside its sequence, so row - position is the row of its sequence's first token -- true of a flattened right-padded
+    batch (positions = 0 .. L-1 per row) and of a packed array alike."""
+    live = token_ids.ne(padding_idx).to(torch.int64)
+    upto = torch.cumsum(live, 0)
+    before = upto - live      # non-pad ids in front of each row, over the whole array
+    first = torch.arange(token_ids.numel(), device=token_ids.device) - positions
+    return (upto - before[first]) * live + padding_idx
+
+
+REL_SPAN = 511      # the span the encoder's bias table is built for: every offset of a 512-token sequence, one table for every batch
+
+
+def relative_bias_table(model, R=REL_SPAN):
+    """MPNetEncoder.compute_position_bias as a table: fp32 [heads, 2 R + 1] on the parameters' device, entry [h, R + d] = the bias of head h
+    for key - query = d, from the model's own relative_position_bucket and relative_attention_bias.  The bias of a (query, key) pair depends
+    on nothing else, so table[:, R - (L-1) : R + L][:, (j - i) + L - 1] is compute_position_bias for L tokens, bit for bit."""
+    arch = _describe(model)
+    assert not isinstance(arch, str) and arch.bias_source is not None, "the model has no relative position bias"
+    src = arch.bias_source
+    with torch.no_grad():
+        offsets = torch.arange(-int(R), int(R) + 1, dtype=torch.long)      # (on the CPU, where compute_position_bias takes its buckets)
+        buckets = src.relative_position_bucket(offsets).to(src.relative_attention_bias.weight.device)
+        return src.relative_attention_bias(buckets).t().float().contiguous()
+
+
+def _bias_train_reason(arch):
+    if arch.bias_source is not None:
+        return ("the relative position bias (relative_attention_bias) has no gradient on the layer kernels: "
+                "the attention backward takes no bias, so this encoder trains as its torch module")
+    return None
+
+
+def shadow_unsupported_reason(model):
+    """None when an optimizer may keep a 16-bit weight set of `model` current for the training forward (optim.FusedAdamW(shadow_for=...)):
+    what unsupported_reason asks, and an encoder the kernels can train."""
+    reason = unsupported_reason(model)
+    return reason if reason is not None else _bias_train_reason(_describe(model))
 
 
 def unsupported_reason(model):
-    """None when FusedBertEncoder can run `model` (a transformers BertModel or DistilBertModel); otherwise why not."""
+    """None when FusedBertEncoder can run `model` (one of the transformers classes _describe knows); otherwise why not."""
     arch = _describe(model)
     if isinstance(arch, str):
         return arch
@@ -117,6 +183,8 @@ def train_unsupported_reason(model):
     (train_wanted() and train_dropout_wanted()) active dropout is accepted where every live torch.nn.Dropout module is one of the known
     sites (_dropout_sites: their p is read from the modules at call time); any other live Dropout module is refused by name."""
     reason = unsupported_reason(model)
+    if reason is None:
+        reason = _bias_train_reason(_describe(model))
     if reason is not None:
         return reason
     if getattr(model, "training", False) and train_wanted() and train_dropout_wanted():
@@ -272,6 +340,30 @@ _LAYER_FP32 = ("g1", "b1", "eps1", "g2", "b2", "eps2")
 _DEFERRED = object()      # FusedBertEncoder._signature after a maintained step: taken at the next refresh() (adopted_stepped)
 
 
+class _NoGradRow(torch.autograd.Function):
+    """A table one of whose rows receives no gradient, as torch.nn.Embedding(padding_idx=row) trains it: forward hands out the table
+    itself, backward clears that row of the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, table, row):
+        ctx.row = int(row)
+        return table.view_as(table)
+
+    @staticmethod
+    def backward(ctx, grad):
+        grad = grad.clone()
+        grad[ctx.row] = 0
+        return grad, None
+
+
+def _padding_rows(arch):
+    """(word table's, position table's) padding_idx where the training forward honours it (the architectures with a position rule: a
+    pad-id token can be a live one there, and the module gives its rows no gradient), else (None, None)."""
+    if arch.padding_idx is None:
+        return None, None
+    return arch.embeddings.word_embeddings.padding_idx, arch.embeddings.position_embeddings.padding_idx
+
+
 class _ShadowWeights(torch.autograd.Function):
     """A layer's maintained 16-bit weights in the place of cat(q, k, v).to(half) and the seven other casts: forward hands out the eight
     copies an optimizer keeps current (optim.FusedAdamW), backward returns each incoming 16-bit gradient as fp32 to its masters -- wqkv's
@@ -294,7 +386,8 @@ class _ShadowWeights(torch.autograd.Function):
 
 
 class FusedBertEncoder:
-    """16-bit (bf16 or fp16: the `dtype` of each call) forward of a transformers BertModel / DistilBertModel: forward(input_ids [B, L]
+    """16-bit (bf16 or fp16: the `dtype` of each call) forward of a transformers BertModel / DistilBertModel / RobertaModel /
+    XLMRobertaModel / MPNetModel: forward(input_ids [B, L]
     right-padded, lengths [B]) -> last hidden state fp32 [B, L, hidden]; forward_packed(...) over a packed token array.  Holds 16-bit
     copies of the projection weights, one set per type used (rebuilt when the model's parameters change: fine-tuning between two
     ranking steps, load_state_dict, .to(device))."""
@@ -306,8 +399,11 @@ class FusedBertEncoder:
         self.model = model
         arch = _describe(model)
         self.heads, self.hidden = arch.heads, arch.hidden
-        self.has_token_types = arch.type_table is not None
+        # (a RoBERTa-family type table usually has ONE row: row 0 is added as the module adds it, and a caller that hands over
+        # token_type_ids keeps the module, which alone can say that a nonzero id has no row)
+        self.has_token_types = arch.type_table is not None and (arch.padding_idx is None or arch.type_table.shape[0] > 1)
         self._layers, self._signature, self._no_types = {}, None, None
+        self._rel_bias = None      # relative_bias_table(model, REL_SPAN) of an encoder with a bias source: made and dropped with the weight copies
         self._adopted = self._adopted_stamp = None      # (dtype, layers): a weight set an optimizer keeps current (adopt_weights), and its stamp
         self.last_seed = None      # the seed of the latest training forward that ran with dropout (dropout_ref rebuilds its masks from it)
 
@@ -317,6 +413,7 @@ class FusedBertEncoder:
     def __setstate__(self, state):
         self.__dict__.update(state)
         self._layers, self._signature, self._no_types = {}, None, None
+        self._rel_bias = None
         self._adopted = self._adopted_stamp = None
         self.last_seed = None
 
@@ -331,11 +428,13 @@ class FusedBertEncoder:
             changed = not self.adopted_current()
             self._signature = sig
             if changed:
-                self._layers = {}
+                self._layers, self._rel_bias = {}, None
         else:
             changed = sig != self._signature
             if changed:
-                self._layers, self._signature = {}, sig
+                self._layers, self._signature, self._rel_bias = {}, sig, None
+        if dtype is not None and self._rel_bias is None and _describe(self.model).bias_source is not None:
+            self._rel_bias = relative_bias_table(self.model, REL_SPAN)      # (its parameter is one of the stack's: the signature covers it)
         if dtype is not None and dtype not in self._layers:
             if self._adopted is not None and self._adopted[0] == dtype:
                 self._rebuild_adopted()      # (in place: the optimizer that maintains the set holds its addresses)
@@ -366,6 +465,8 @@ class FusedBertEncoder:
     def adopt_weights(self, dtype):
         """Build the weight set of `dtype` from the masters and keep it as the maintained one -> its layers (exactly _build_layers'
         tensors: the caller writes into wqkv / bqkv / wo / bo / wi / bi / wo2 / bo2)."""
+        reason = shadow_unsupported_reason(self.model)
+        assert reason is None, f"FusedBertEncoder.adopt_weights: {reason}"
         self.refresh()
         layers = self._build_layers(dtype)
         self._layers[dtype] = layers
@@ -462,6 +563,11 @@ class FusedBertEncoder:
         plain = all(t.dtype == torch.float32 and t.is_contiguous() for t in (word, pos, types, ln.weight, ln.bias))
         return word, pos, types, ln, plain
 
+    def _position_rows(self, token_ids, positions):
+        """In-sequence positions (what every forward takes) -> rows of the architecture's position table."""
+        padding_idx = _describe(self.model).padding_idx
+        return positions if padding_idx is None else position_rows(token_ids, positions, padding_idx)
+
     def _embed(self, token_ids, positions, token_types, dtype):
         """The embedding block (BertEmbeddings.forward: (word + type) + position, LayerNorm; DistilBERT's Embeddings: word + position,
         LayerNorm) over flat int64 index vectors [T] -> (fp32 [T, hidden], its copy in `dtype`): one kernel on the module's own fp32
@@ -469,6 +575,7 @@ class FusedBertEncoder:
         in torch when the tables are not plain fp32 (a half-precision checkpoint)."""
         token_ids, positions = token_ids.long(), positions.long()          # (tokenizers may hand over int32 ids)
         token_types = None if token_types is None else token_types.long()
+        positions = self._position_rows(token_ids, positions)
         word, pos, types, ln, plain = self._embedding_tables(token_types)
         if plain:
             return ops.embed_layernorm(word, pos, types, token_ids.contiguous(), positions.contiguous(),
@@ -488,9 +595,15 @@ class FusedBertEncoder:
         (same values: every one of those operations is row-wise) -> [n_seq, hidden]."""
         layers = self._layers[hb.dtype]
         last = len(layers) - 1
+        bias = self._rel_bias
+        assert (bias is not None) == (_describe(self.model).bias_source is not None), "refresh() keeps the bias table with the weight copies"
         for i, l in enumerate(layers):
             qkv = F.linear(hb, l.wqkv, l.bqkv)
-            ctx = ops.attention(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=0.125)
+            if bias is None:
+                ctx = ops.attention(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=0.125)
+            else:      # one table for every layer, as the module shares one position_bias
+                ctx = ops.attention(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=0.125, rel_bias=bias,
+                                    rel_span=REL_SPAN)
             if i == last and cls_rows is not None:
                 ctx, h = ctx[cls_rows].contiguous(), h[cls_rows].contiguous()
             h, hb = ops.add_layernorm(F.linear(ctx, l.wo, l.bo), h, l.g1, l.b1, l.eps1)
@@ -508,20 +621,24 @@ class FusedBertEncoder:
         arch = _describe(self.model)
         e = arch.embeddings
         token_ids, positions = token_ids.long(), positions.long()
+        positions = self._position_rows(token_ids, positions)
+        word_pad, pos_pad = _padding_rows(arch)
         if train_packed_wanted():
             word, pos, types, ln, plain = self._embedding_tables(token_types)
             if plain:
+                word = word if word_pad is None else _NoGradRow.apply(word, word_pad)
+                pos = pos if pos_pad is None else _NoGradRow.apply(pos, pos_pad)
                 bits, inv_keep = (None, 1.0) if drop is None else drop.rows(getattr(e, "dropout", None), EMBEDDINGS_STREAM,
                                                                             token_ids.numel(), self.hidden, word.device)
                 return ops.embed_layernorm_train(word, pos, types, token_ids, positions, None if token_types is None else token_types.long(),
                                                  ln.weight, ln.bias, ln.eps, keep_bits=bits, inv_keep=inv_keep, dtype=dtype)
-        x = F.embedding(token_ids, e.word_embeddings.weight).float()
+        x = F.embedding(token_ids, e.word_embeddings.weight, padding_idx=word_pad).float()
         if arch.type_table is not None:
             types = torch.zeros_like(token_ids) if token_types is None else token_types.long()
             x = x + F.embedding(types, arch.type_table).float()
         else:
             assert token_types is None, "this architecture has no token types"
-        x = x + F.embedding(positions, e.position_embeddings.weight).float()
+        x = x + F.embedding(positions, e.position_embeddings.weight, padding_idx=pos_pad).float()
         ln = e.LayerNorm
         h = F.layer_norm(x, (self.hidden,), ln.weight.float(), ln.bias.float(), ln.eps).contiguous()
         if drop is not None:

@@ -313,20 +313,50 @@ def _check_rows(x, residual, *vectors, keep_bits=None):
     return rows, dim
 
 
-def attention(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, out=None):
+_ATTENTION_BIAS_CHECKED = False
+
+
+def _require_attention_bias():
+    """require_gpu() + once: the loaded library has the attention forward with a relative position bias (ccr_version() >= 112)."""
+    global _ATTENTION_BIAS_CHECKED
+    lib = require_gpu()
+    if not _ATTENTION_BIAS_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.ATTENTION_BIAS_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, attention with a relative bias needs {_lib.ATTENTION_BIAS_VERSION}: "
+                                f"rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
+        _ATTENTION_BIAS_CHECKED = True
+    return lib
+
+
+def attention(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, out=None, rel_bias=None, rel_span=None):
     """Multi-head self-attention of a token array (ccr_attention_half; head width 64): qkv [T, 3 * n_heads * 64] bf16 or fp16 = the
     stacked query | key | value projection of every token, seq_start / seq_len [n_seq] int32 = each sequence's first row and real tokens,
     max_len = the longest seq_len (host int, <= 512), pad_len = L for a right-padded [n_seq, L] batch (its padding rows get
-    zeros) or 0 for a packed array.  -> context rows [T, n_heads * 64] of qkv's dtype."""
-    lib = require_gpu()
+    zeros) or 0 for a packed array.  -> context rows [T, n_heads * 64] of qkv's dtype.
+    rel_bias (ccr_attention_bias_half): fp32 [n_heads, 2 * R + 1] on qkv's device, one additive bias per (head, key - query) shared by
+    every sequence: probability ~ exp(scale * q.k + rel_bias[head, R + key - query]).  rel_span = R (default: what the table's width
+    says), max_len - 1 <= R <= 511.  An all-zero table gives the bits of the call without one."""
+    lib = require_gpu() if rel_bias is None else _require_attention_bias()
     code = _half_code(qkv.dtype)
     T = _check_qkv(qkv, seq_start, seq_len, n_heads)
     if out is None:
         out = torch.empty(T, n_heads * 64, dtype=qkv.dtype, device=qkv.device)
     assert out.is_cuda and out.dtype == qkv.dtype and tuple(out.shape) == (T, n_heads * 64) and out.is_contiguous()
+    if rel_bias is None:
+        assert rel_span is None, "rel_span without rel_bias"
+        with _on(qkv):
+            _lib.check(lib.ccr_attention_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), seq_len.numel(), int(n_heads),
+                                              int(max_len), int(pad_len), float(scale), code, _stream(qkv)), "ccr_attention_half")
+        return out
+    assert rel_bias.is_cuda and rel_bias.device == qkv.device and rel_bias.dtype == torch.float32 and rel_bias.is_contiguous()
+    assert rel_bias.dim() == 2 and rel_bias.shape[0] == n_heads and rel_bias.shape[1] % 2 == 1, tuple(rel_bias.shape)
+    R = rel_bias.shape[1] // 2 if rel_span is None else int(rel_span)
+    assert rel_bias.shape[1] == 2 * R + 1, f"rel_bias has {rel_bias.shape[1]} columns, rel_span={R} needs {2 * R + 1}"
     with _on(qkv):
-        _lib.check(lib.ccr_attention_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), seq_len.numel(), int(n_heads),
-                                          int(max_len), int(pad_len), float(scale), code, _stream(qkv)), "ccr_attention_half")
+        _lib.check(lib.ccr_attention_bias_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), _ptr(rel_bias), R, seq_len.numel(),
+                                               int(n_heads), int(max_len), int(pad_len), float(scale), code, _stream(qkv)),
+                   "ccr_attention_bias_half")
     return out
 
 

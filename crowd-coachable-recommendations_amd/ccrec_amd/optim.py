@@ -118,7 +118,7 @@ class FusedAdamW(torch.optim.Optimizer):
             _refuse("shadow_for", "needs CUDA parameters")
         code, mine = _SHADOW_CODES[dtype], {id(p) for g in self.param_groups for p in g["params"]}
         for m in module.modules():
-            if fused_bert.unsupported_reason(m) is not None:
+            if fused_bert.shadow_unsupported_reason(m) is not None:      # (not covered, or covered for inference only)
                 continue
             enc = fused_bert.for_model(m)
             layers = enc.adopt_weights(dtype)
@@ -143,7 +143,8 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._shadow_tensors += [l.wqkv, l.bqkv, l.wo, l.bo, l.wi, l.bi, l.wo2, l.bo2]
             self._encoders.append((enc, enc.adopted_masters()))
         if not self._encoders:
-            _refuse("shadow_for", "no encoder under the module is one the layer kernels cover (fused_bert.unsupported_reason)")
+            _refuse("shadow_for", "no encoder under the module is one the layer kernels cover (fused_bert.unsupported_reason) and can train "
+                    "(fused_bert.shadow_unsupported_reason)")
         self.shadow_dtype = dtype
 
     # --------------------------------------------------------------------------------------------------------------------- state

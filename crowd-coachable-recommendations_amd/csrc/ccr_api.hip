@@ -76,7 +76,7 @@ void slab_give(int device, uint32_t *p) {
 }  // namespace
 
 extern "C" const char *ccr_last_error(void) { return g_err; }
-extern "C" int ccr_version(void) { return 111; }
+extern "C" int ccr_version(void) { return 112; }
 
 extern "C" int ccr_index_destroy(ccr_index *ix);
 

@@ -34,6 +34,9 @@ constexpr int ATT_KROW = 144;      // bytes per key row in LDS: 128 + 16, so the
 __host__ __device__ inline size_t attention_lds_bytes(int lk_pad) {
     return (size_t)lk_pad * ATT_KROW + (size_t)ATT_HEAD * (2 * (size_t)lk_pad + 8);   // (the row-major image needs 512 bytes less)
 }
+// BIAS = true: behind that image, the window of the head's relative-bias row that this launch can reach, lk_pad + max_len - 1 floats
+// (entry i <-> offset key - query = i - (max_len - 1); the entries past offset max_len - 1 belong to keys >= max_len and hold zeros).
+__host__ __device__ inline size_t attention_bias_lds_bytes(int lk_pad) { return 2 * (size_t)lk_pad * sizeof(float); }
 // S^T = K Q^T on v_mfma_f32_32x32x16_bf16: A = 32 keys (lane & 31) x 8 head columns (8 * (lane >> 5) + j), B = 32 queries
 // likewise -- both operands are 16 contiguous bytes of a row, no transposition.  C layout: lane -> query (lane & 31),
 // register e -> key (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5): a lane owns ONE query and 16 of the tile's 32 keys, so the
@@ -46,6 +49,25 @@ __host__ __device__ inline size_t attention_lds_bytes(int lk_pad) {
 // DROP = true (ccr_attention_fwd_train_drop_half): the probability that is rounded to 16 bits for the P V product becomes
 // p * keep * inv_keep with the keep bit of (query row, head, key) from keep_q [T][H][W]; the online softmax, lsum and lse stay those of
 // the undropped scores.  A lane's 32 keys of a 64-key step are 16 bits each of words 2 kb and 2 kb + 1 of its own query's row.
+// BIAS = true (the inference forward of an encoder with a shared relative position bias, ccr_attention_bias_half): the probability of
+// (query, key) is proportional to exp(scale * q.k + table[head][R + key - query]).  The table entries are staged in LDS divided by scale
+// and are what the score tiles' MFMA accumulators start from in place of zero, so every line after the MFMAs is the plain kernel's code
+// on x = bias / scale + q.k: scale_log2e * x = log2e * (scale * q.k + bias).  An all-zero table starts them from zero: the plain kernel's
+// bits.  BIAS = false takes an empty struct, like LSE and DROP: the other instantiations keep their arguments and their code.
+struct NoBias {};
+struct RelBias {
+    const float *table;   // [n_heads][2 R + 1] fp32
+    int R;                // the table's centre column: offset 0
+    float inv_scale;      // 1 / scale
+};
+template <bool BIAS>
+struct BiasArg {
+    typedef NoBias type;
+};
+template <>
+struct BiasArg<true> {
+    typedef RelBias type;
+};
 struct NoLse {};
 template <bool LSE>
 struct LseArg {
@@ -55,13 +77,14 @@ template <>
 struct LseArg<true> {
     typedef float *type;
 };
-template <int DT, bool TR, bool LSE = false, bool DROP = false>
+template <int DT, bool TR, bool LSE = false, bool DROP = false, bool BIAS = false>
 __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16_t *__restrict__ qkv,
                                                                   const int32_t *__restrict__ seq_start,
                                                                   const int32_t *__restrict__ seq_len,
                                                                   uint16_t *__restrict__ out, int H, int pad_len, int max_len,
                                                                   int lk_pad, float scale_log2e, typename LseArg<LSE>::type lse,
-                                                                  typename KeepArg<DROP>::type keep = {}) {
+                                                                  typename KeepArg<DROP>::type keep = {},
+                                                                  typename BiasArg<BIAS>::type rb = {}) {
     typedef Half16<DT> HT;
     typedef typename HT::vec8 vec8;
     typedef typename HT::elem elem;
@@ -128,10 +151,29 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const vec8 *>(Qg + (int64_t)qr * stride + 16 * s + 8 * g);
     }
+    // BIAS: entries 0 .. lk_pad + max_len - 2 of the window, at most two per thread (the launcher's staging bound: lk_pad <= nthreads);
+    // entry i is the table's column R - (max_len - 1) + i while that offset is at most max_len - 1, and zero beyond
+    float breg[2] = {0.f, 0.f};
+    float *Bs = reinterpret_cast<float *>(smem + attention_lds_bytes(lk_pad));
+    if constexpr (BIAS) {
+        const float *brow = rb.table + (int64_t)h * (2 * rb.R + 1) + (rb.R - (max_len - 1));
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = tid + u * nthreads;
+            if (i <= 2 * (max_len - 1)) breg[u] = brow[i] * rb.inv_scale;
+        }
+    }
 #pragma unroll
     for (int u = 0; u < ATT_KMAX; ++u) {
         const int i = tid + u * nthreads;
         if (i < nk * 8) *reinterpret_cast<uint4 *>(Ks + (i >> 3) * ATT_KROW + (i & 7) * 16) = kreg[u];
+    }
+    if constexpr (BIAS) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int i = tid + u * nthreads;
+            if (i < lk_pad + max_len - 1) Bs[i] = breg[u];
+        }
     }
 #pragma unroll
     for (int u = 0; u < ATT_VMAX; ++u) {
@@ -187,6 +229,10 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
         float m = -INFINITY, lsum = 0.f;
         const uint32_t *keep_row = nullptr;   // DROP: the words of this lane's query row (a lane beyond the sequence repeats its last row)
         if constexpr (DROP) keep_row = keep.bits + ((row0 + (q < len ? q : len - 1)) * H + h) * keep.W;
+        // BIAS: the window entry of (this lane's query, key 4 g); a lane beyond the sequence repeats its last row, so with key < nk <= lk_pad
+        // every index below lies in 0 .. lk_pad + max_len - 2
+        const float *bias_q = nullptr;
+        if constexpr (BIAS) bias_q = Bs + ((max_len - 1) - (q < len ? q : len - 1) + 4 * g);
 
         for (int kb = 0; kb < nkb; ++kb) {
             uint32_t kw0 = 0, kw1 = 0;   // DROP: bit (e & 3) + 8 ((e & 15) >> 2) of kw0 >> 4 g <-> register e < 16, of kw1 >> 4 g <-> register 16 + e
@@ -195,8 +241,17 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attention_kernel(const uint16
                 if (2 * kb + 1 < keep.W) kw1 = keep_row[2 * kb + 1] >> (4 * g);   // (keys of a word beyond W are beyond len: their x is 0)
             }
             ef32x16 s0, s1;
+            if constexpr (BIAS) {   // the score tiles start from bias / scale instead of zero: the MFMAs add q.k onto it, no extra registers
+                const float *bp = bias_q + kb * ATT_KB;   // register e <-> key kb * 64 + (0 | 32) + (e & 3) + 8 (e >> 2) + 4 g, as in the mask below
 #pragma unroll
-            for (int e = 0; e < 16; ++e) s0[e] = s1[e] = 0.f;
+                for (int e = 0; e < 16; ++e) {
+                    s0[e] = bp[(e & 3) + 8 * (e >> 2)];
+                    s1[e] = bp[32 + (e & 3) + 8 * (e >> 2)];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) s0[e] = s1[e] = 0.f;
+            }
             const char *kp = Ks + (kb * ATT_KB + ql) * ATT_KROW + g * 16;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
@@ -432,20 +487,25 @@ __global__ __launch_bounds__(256) void gelu_kernel(const uint4 *__restrict__ x, 
     }
 }
 
-template <int DT, bool LSE = false, bool DROP = false>
+template <int DT, bool LSE = false, bool DROP = false, bool BIAS = false>
 static int attention_any(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, int n_seq, int n_heads,
                          int max_len, int pad_len, float scale, hipStream_t stream, typename LseArg<LSE>::type lse = {},
-                         typename KeepArg<DROP>::type keep = {}) {
+                         typename KeepArg<DROP>::type keep = {}, typename BiasArg<BIAS>::type rb = {}) {
     const int lk_pad = (max_len + ATT_KB - 1) / ATT_KB * ATT_KB;
-    const size_t lds = attention_lds_bytes(lk_pad);
+    const size_t lds = attention_lds_bytes(lk_pad) + (BIAS ? attention_bias_lds_bytes(lk_pad) : 0);
     // the opt-in is cached per (kernel, device) whatever the size: ask for the kernel's maximum once (512 keys), not for this call's
     // image -- length-sorted batches start with the shortest texts
     static const bool tr = [] {
         const char *e = getenv("CCR_ATT_TR");      // A/B knob: 0 = the transposed-image kernel of rounds 3-5
         return !(e && atoi(e) == 0);
     }();
-    const int rc = ensure_dynamic_lds(tr ? reinterpret_cast<const void *>(&attention_kernel<DT, true, LSE, DROP>) : reinterpret_cast<const void *>(&attention_kernel<DT, false, LSE, DROP>),
-                                      attention_lds_bytes(512));
+    if constexpr (BIAS) CCR_REQUIRE(tr, "ccr_attention_bias_half: the transposed-image kernel (CCR_ATT_TR=0) takes no bias");
+    const void *kernel = nullptr;
+    if constexpr (BIAS)
+        kernel = reinterpret_cast<const void *>(&attention_kernel<DT, true, LSE, DROP, true>);
+    else
+        kernel = tr ? reinterpret_cast<const void *>(&attention_kernel<DT, true, LSE, DROP>) : reinterpret_cast<const void *>(&attention_kernel<DT, false, LSE, DROP>);
+    const int rc = ensure_dynamic_lds(kernel, attention_lds_bytes(512) + (BIAS ? attention_bias_lds_bytes(512) : 0));
     if (rc != CCR_OK) return rc;
     int waves = (max_len + ATT_QW - 1) / ATT_QW;   // one wave per 32 query rows, at most 8 (longer sequences: the waves loop)
     if (waves > ATT_MAX_THREADS / 64) waves = ATT_MAX_THREADS / 64;
@@ -455,7 +515,10 @@ static int attention_any(const uint16_t *qkv, const int32_t *seq_start, const in
     // fit either way and 7-8 waves are faster)
     if (lk_pad == 192 && waves > 4) waves = 4;
     CCR_REQUIRE(lk_pad * 8 <= ATT_KMAX * 64 * waves && lk_pad * 4 <= ATT_VMAX * 64 * waves, "ccr_attention: staging bound (internal)");
-    if (tr)
+    if constexpr (BIAS)
+        hipLaunchKernelGGL((attention_kernel<DT, true, LSE, DROP, true>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len,
+                           out, n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f, lse, keep, rb);
+    else if (tr)
         hipLaunchKernelGGL((attention_kernel<DT, true, LSE, DROP>), dim3(n_heads, n_seq), dim3(64 * waves), lds, stream, qkv, seq_start, seq_len, out,
                            n_heads, pad_len, max_len, lk_pad, scale * 1.4426950408889634f, lse, keep);
     else
@@ -549,6 +612,20 @@ extern "C" int ccr_attention_half(const uint16_t *qkv, const int32_t *seq_start,
     if (n_seq == 0) return CCR_OK;
     return dispatch_half(half_dtype, [&](auto dt) {
         return attention_any<decltype(dt)::value>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale, (hipStream_t)stream);
+    });
+}
+
+extern "C" int ccr_attention_bias_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, const float *rel_bias,
+                                       int R, int n_seq, int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *stream) {
+    CCR_REQUIRE(qkv && seq_start && seq_len && out, "ccr_attention_bias_half: null pointer");
+    CCR_REQUIRE(rel_bias, "ccr_attention_bias_half: null bias table");
+    if (const int rc = check_attention_shape("ccr_attention_bias_half", half_dtype, n_seq, n_heads, max_len, pad_len, scale)) return rc;
+    CCR_REQUIRE(R >= max_len - 1 && R <= 511, "ccr_attention_bias_half: R=%d (max_len - 1 = %d <= R <= 511: the table holds every offset of a sequence)", R,
+                max_len - 1);
+    if (n_seq == 0) return CCR_OK;
+    return dispatch_half(half_dtype, [&](auto dt) {
+        return attention_any<decltype(dt)::value, false, false, true>(qkv, seq_start, seq_len, out, n_seq, n_heads, max_len, pad_len, scale,
+                                                                      (hipStream_t)stream, NoLse{}, NoKeep{}, RelBias{rel_bias, R, 1.f / scale});
     });
 }
 

@@ -213,6 +213,14 @@ int ccr_embed_layernorm_half(const float *word_table, int64_t vocab, const float
                              const int64_t *token_types, const float *gamma, const float *beta, float eps, float *out_f32,
                              uint16_t *out_half, int64_t rows, int dim, int half_dtype, void *stream);
 int ccr_gelu_half(const uint16_t *x, uint16_t *y, int64_t n, int half_dtype, void *stream);
+/* ccr_attention_bias_half (library version 112; src/ccrec/models/bbpr.py:30, bert_mt.py:74: AutoModel.from_pretrained(MODEL_NAME) with an
+ * MPNet checkpoint): ccr_attention_half with one additive relative position bias shared by every sequence -- the probability of (query i,
+ * key j) of head h is proportional to exp(scale * q_i.k_j + rel_bias[h][R + j - i]) in fp32, keys beyond the sequence excluded, the
+ * running maximum taken over the biased scores.  rel_bias: fp32 [n_heads][2 * R + 1] on the device, max_len - 1 <= R <= 511 (a table
+ * built once for R = 511 serves every batch).  With an all-zero table `out` has ccr_attention_half's bits.  Inference only: the training
+ * forward and the backward take no bias. */
+int ccr_attention_bias_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, const float *rel_bias,
+                            int R, int n_seq, int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *stream);
 
 /*
  * The layer kernels' training forward and backward (library version 103): fine-tuning through the encoder.  The reference's training
