@@ -49,6 +49,7 @@ HALF_INDEX_VERSION = 109   # ... and the pack, index and search on either 16-bit
 AMP_OPTIM_VERSION = 110   # ... and loss scaling, overflow skip and norm clipping inside the AdamW step (ccr_adamw_step_scaled and its kin)
 RANK_F32_VERSION = 111   # ... and the kept fp32 rows with the verified re-score of a 16-bit search on them (ccr_keep_f32, ccr_rescore_f32)
 ATTENTION_BIAS_VERSION = 112   # ... and the attention forward with a shared relative position bias (ccr_attention_bias_half)
+SIDE_CUS_VERSION = 113   # ... and the main pass that leaves CUs to the caller's side work (CCR_SIDE_CUS; main_grid and side_cus in the search statistics: an older library leaves them 0)
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -67,7 +68,7 @@ class SearchStats(ctypes.Structure):
                 ("ms_main", ctypes.c_float), ("ms_select", ctypes.c_float), ("ms_fallback", ctypes.c_float),
                 ("ms_total", ctypes.c_float), ("n_retried", ctypes.c_int32), ("n_dense", ctypes.c_int32),
                 ("main_launches", ctypes.c_int32), ("opt_rank", ctypes.c_int32), ("main_tile_queries", ctypes.c_int32),
-                ("skipped_tiles", ctypes.c_int32), ("tile_cap", ctypes.c_int32)]
+                ("skipped_tiles", ctypes.c_int32), ("tile_cap", ctypes.c_int32), ("main_grid", ctypes.c_int32), ("side_cus", ctypes.c_int32)]
 
 
 class AdamwSegment(ctypes.Structure):

@@ -1038,8 +1038,11 @@ class CorpusIndex:
         self._deferred = None
 
     def stream_wait_main_pass(self, stream):
-        """ccr_search_stream_wait_main_pass: `stream` (a torch.cuda.Stream) waits for the main pass of this index's last search -- deferred
-        or not --: work on it that does not touch the search's buffers then runs beside the search's select stage."""
+        """ccr_search_stream_wait_main_pass: `stream` (a torch.cuda.Stream) is released when side work can usefully start beside this
+        index's last search -- deferred or not.  That is when its main pass is done (the side work runs beside the select stage), or, when
+        that main pass left CUs free (last_stats()["side_cus"] > 0), as soon as its workgroups are resident: the side work then runs on
+        the free CUs beside it.  The call is also the hint that lets the NEXT fused search on the device leave CUs free.  Either way the
+        side work must not touch any buffer of the search -- inputs included: the select stage reads them all."""
         _lib.check(self._lib.ccr_search_stream_wait_main_pass(self._h, ctypes.c_void_p(stream.cuda_stream)), "ccr_search_stream_wait_main_pass")
 
     def search_shard(self, queries_bf16, k, message, defer=False, flags=_lib.SEARCH_DEFAULT):

@@ -76,7 +76,24 @@ void slab_give(int device, uint32_t *p) {
 }  // namespace
 
 extern "C" const char *ccr_last_error(void) { return g_err; }
-extern "C" int ccr_version(void) { return 112; }
+extern "C" int ccr_version(void) { return 113; }
+
+// The hint behind side CUs, per device: did the caller order a side stream against the main pass of the previous fused search
+// (ccr_search_stream_wait_main_pass)?  Then the next fused search on the device may leave CUs free for that side work; it takes the
+// hint with it, so a search that is not followed by the call switches the carve off again and the first search of a loop never has it.
+namespace {
+bool g_side_hint[MAX_DEVICES];
+bool side_hint_take(int device) {
+    std::lock_guard<std::mutex> lock(g_slab_mutex);
+    const bool hint = g_side_hint[device];
+    g_side_hint[device] = false;
+    return hint;
+}
+void side_hint_set(int device) {
+    std::lock_guard<std::mutex> lock(g_slab_mutex);
+    g_side_hint[device] = true;
+}
+}  // namespace
 
 extern "C" int ccr_index_destroy(ccr_index *ix);
 
@@ -243,18 +260,25 @@ extern "C" int ccr_index_dtype(const ccr_index *ix) { return ix ? ix->dtype : -1
 
 extern "C" size_t ccr_search_workspace_bytes(const ccr_index *ix, int n_q, int k) {
     if (!ix || n_q <= 0 || k <= 0) return 0;
-    // the larger of the three plans, so that flags may be chosen at call time
-    Plan a = make_plan(ix->n_rows, ix->dim, n_q, k, CCR_SEARCH_DEFAULT, ix->num_cu, ix->knobs);
-    Plan b = make_plan(ix->n_rows, ix->dim, n_q, k, CCR_SEARCH_FORCE_DENSE, ix->num_cu, ix->knobs);
-    Plan c = make_plan(ix->n_rows, ix->dim, n_q, k, CCR_SEARCH_FORCE_FUSED, ix->num_cu, ix->knobs);
-    return std::max({a.total, b.total, c.total}) + 256;
+    // the largest of the plans, so that flags may be chosen at call time and the fused plans may or may not leave side CUs
+    size_t total = make_plan(ix->n_rows, ix->dim, n_q, k, CCR_SEARCH_FORCE_DENSE, ix->num_cu, ix->knobs).total;
+    for (int flags : {CCR_SEARCH_DEFAULT, CCR_SEARCH_FORCE_FUSED})
+        for (bool side_hint : {false, true}) total = std::max(total, make_plan(ix->n_rows, ix->dim, n_q, k, flags, ix->num_cu, ix->knobs, side_hint).total);
+    return total + 256;
 }
 
 extern "C" int ccr_search_stream_wait_main_pass(const ccr_index *ix, void *stream) {
     CCR_REQUIRE(ix, "ccr_search_stream_wait_main_pass: null index");
     if (!ix->main_pass_recorded) return CCR_OK;   // dense path / no search yet: nothing to order against
-    CCR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ix->ev[EV_MAIN_END], 0));
-    return CCR_OK;
+    side_hint_set(ix->device);
+    if (ix->plan.side_cus == 0) {
+        CCR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ix->ev[EV_MAIN_END], 0));
+        return CCR_OK;
+    }
+    // the main pass left CUs free: the stream goes on when that pass BEGINS -- behind a gate that lets its workgroups take their
+    // CUs first (a workgroup of the main pass needs a whole empty CU and would starve behind a flood of short side workgroups)
+    CCR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, ix->ev[EV_MAIN_BEGIN], 0));
+    return launch_main_pass_gate(ix->side_arrive, (uint32_t)ix->plan.main_grid, (hipStream_t)stream);
 }
 
 extern "C" int ccr_search_last_stats(const ccr_index *ix, ccr_search_stats *stats) {
@@ -424,7 +448,9 @@ static int run_main_pass(const ccr_index *ix, const Plan &p, const SearchWs &w, 
         gm.item_begin = done;
         gm.item_end = bounds[ph];
         const MainKernel kind = p.tile_q == WIDE_Q ? MAIN_WIDE : p.mfma16 ? MAIN_16X16 : MAIN_32X32;
-        const int rc = launch_gemm(gm, ix->dtype, kind, EPI_FILTER, p.grid, s);
+        // (side CUs: a single launch on main_grid workgroups that count themselves in; every other plan has main_grid = grid)
+        gm.arrive = p.side_cus ? w.arrive : nullptr;
+        const int rc = launch_gemm(gm, ix->dtype, kind, EPI_FILTER, p.main_grid, s);
         if (rc != CCR_OK) return rc;
         done = bounds[ph];
     }
@@ -488,6 +514,8 @@ static int fused_stats(ccr_index *ix, uint32_t nflag, unsigned long long ncand) 
     st.main_launches = 1 + (p.item_a ? 1 : 0) + (p.item_b ? 1 : 0);
     st.opt_rank = p.opt_rank;
     st.tile_cap = p.opt_rank ? p.tile_cap : 0;
+    st.main_grid = p.narrow ? 0 : p.main_grid;
+    st.side_cus = p.side_cus;
     st.skipped_tiles = p.skip_sampled ? p.sample_tiles : 0;
     st.main_tile_queries = p.narrow ? 0 : p.tile_q;
     st.n_candidates = (int64_t)ncand;
@@ -720,11 +748,13 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     ix->id_out = id_out;
     const bool async = (flags & CCR_SEARCH_ASYNC) != 0;
     const int plan_flags = flags & ~CCR_SEARCH_ASYNC;
-    if (!(ix->plan_nq == n_q && ix->plan_k == k && ix->plan_flags == plan_flags)) {
-        ix->plan = make_plan(ix->n_rows, ix->dim, n_q, k, plan_flags, ix->num_cu, ix->knobs);
+    const bool side_hint = side_hint_take(ix->device);   // (a dense search takes it as well: the hint is about the search just before)
+    if (!(ix->plan_nq == n_q && ix->plan_k == k && ix->plan_flags == plan_flags && ix->plan_side_hint == side_hint)) {
+        ix->plan = make_plan(ix->n_rows, ix->dim, n_q, k, plan_flags, ix->num_cu, ix->knobs, side_hint);
         ix->plan_nq = n_q;
         ix->plan_k = k;
         ix->plan_flags = plan_flags;
+        ix->plan_side_hint = side_hint;
     }
     const Plan p = ix->plan;
     if (!workspace || ws_bytes < p.total || (uintptr_t)workspace % 256 != 0) {
@@ -732,6 +762,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
         return CCR_ERR_WORKSPACE;
     }
     const SearchWs w = search_ws(p, ix->n_rows, ix->dim, n_q, k, (char *)workspace);
+    ix->side_arrive = w.arrive;
 
     if (!ix->have_events) {   // phase-boundary events of the statistics, created on first use
         for (int i = 0; i < EV_COUNT; ++i) CCR_HIP_CHECK(hipEventCreate(&ix->ev[i]));
@@ -741,7 +772,7 @@ static int search_impl(ccr_index *ix, const uint16_t *Q_bf16, int n_q, int k, fl
     if (!p.fused) return search_dense(ix, w, Q_bf16, n_q, k, out_scores, out_ids, flags, s);
     ix->pending = {false, Q_bf16, n_q, k, out_scores, out_ids, (char *)workspace, s};   // what the stages below and search_complete read
 
-    CCR_HIP_CHECK(hipMemsetAsync(w.flag_count, 0, 64, s));
+    CCR_HIP_CHECK(hipMemsetAsync(w.flag_count, 0, 64, s));   // (the main pass's arrival counter with it)
     // every (range, query block) item with at least one tile writes its counters at its end, for the columns below
     // main_qblocks * tile_q (the 256 x 384 kernel leaves [main_qblocks * 384, nq_pad) unwritten: no reader goes past n_q);
     // only a plan with more ranges than tiles (forced fused searches of tiny corpora) leaves counters unwritten

@@ -153,6 +153,7 @@ struct GemmArgs {
     uint2 *cand;          // candidate area {score bits, local row}; sub-list addresses and capacities from `lay`
     uint32_t *cnt;        // [ranges][nq_pad][sublists]
     CandLayout lay;
+    uint32_t *arrive;     // null, or the counter every workgroup adds 1 to when it starts (a main pass that leaves CUs to side work)
     // EPI_GMAX
     float *gmax;          // [n_vt * 16][nq_pad]
     // EPI_STORE (debug)

@@ -11,6 +11,8 @@ namespace ccr {
 // 256 x 384 tiles on the 16x16x32 MFMA (MAIN_WIDE: a.qblocks = blocks of 384 queries, EPI_FILTER and dim % 32 == 0 only)
 enum MainKernel { MAIN_32X32, MAIN_16X16, MAIN_WIDE };
 int launch_gemm(const GemmArgs &a, int dt, MainKernel kind, int epi, int grid, hipStream_t s);   // dt: element type of a.D and a.Q (CCR_DTYPE_BF16 / _F16), here and below
+// one wave on `s` that returns when `want` workgroups have counted themselves in at `arrive` (GemmArgs::arrive), or when its bounds run out
+int launch_main_pass_gate(const uint32_t *arrive, uint32_t want, hipStream_t s);
 int launch_shard_header(const ccr_shard_header &h, void *message, hipStream_t s);   // ccr_merge.hip: the 32-byte header, by value
 int ensure_dynamic_lds(const void *kernel, size_t lds);   // ccr_api.hip: per (kernel, device) opt-in to > 64 KiB of dynamic LDS
 // the norm bounds (ccr_threshold.hip).  tile_bits (optional): bit patterns of the largest row norm of every 256-row tile, max-accumulated (zeroed by the caller)
@@ -130,7 +132,8 @@ int launch_margin_select(const float *scores, int64_t pitch, int64_t n_rows, int
                          int q_begin, int nq_chunk, int64_t id_offset, float *out_scores, int64_t *out_ids, uint32_t *flag_count, uint32_t *flag_list,
                          hipStream_t s);
 
-// Events of a search at its phase boundaries.  EV_MAIN_END: what ccr_search_stream_wait_main_pass orders against; EV_DONE: the
+// Events of a search at its phase boundaries.  EV_MAIN_END: what ccr_search_stream_wait_main_pass orders against (EV_MAIN_BEGIN and
+// the gate kernel when the main pass left side CUs); EV_DONE: the
 // flagged queries re-done (or the dense path finished); EV_ASYNC_END: an asynchronous search's flag line copied to the host.
 enum SearchEvent { EV_BEGIN, EV_SAMPLE_BEGIN, EV_SAMPLE_END, EV_MAIN_BEGIN, EV_MAIN_END, EV_SELECT_END, EV_DONE, EV_ASYNC_END, EV_COUNT };
 
@@ -159,6 +162,8 @@ struct ccr_index {
     volatile uint32_t *host_flags;   // pinned host line {flag count, -, candidate count (8 B)} of the per-device slab
     ccr::Plan plan;       // plan of the last search and its key (the planner simulates item assignments: ~25 us)
     int plan_nq, plan_k, plan_flags;
+    bool plan_side_hint;
+    const uint32_t *side_arrive;   // the last fused search's arrival counter in its workspace (the gate of ccr_search_stream_wait_main_pass polls it)
     ccr_search_stats stats;
     // an asynchronous search (CCR_SEARCH_ASYNC) that ccr_search_finish has not completed yet
     struct {

@@ -77,6 +77,13 @@ struct ItemWalk {
     }
 };
 
+// A main pass that leaves CUs to side work counts its workgroups in as they start (a.arrive; null: nobody waits): the gate kernel
+// behind ccr_search_stream_wait_main_pass (ccr_api.hip) holds the side work back until all of them are resident.  Once per
+// workgroup, in front of the item loop.
+__device__ __forceinline__ void announce_arrival(const GemmArgs &a) {
+    if (a.arrive != nullptr && threadIdx.x == 0) atomicAdd(a.arrive, 1u);
+}
+
 // =============================================================================================
 // The two MFMA shapes of the 256 x 256 tile.  Each wave tile is 128 corpus rows x 64 queries of DT x QT square MFMA tiles of
 // edge TILE; a lane holds query column lane % TILE and, per MFMA tile, REGS registers = REGS / 4 groups of four consecutive
@@ -308,6 +315,7 @@ __device__ __forceinline__ void main_pass_256(const GemmArgs &a) {
     const int schunk = (lane & 3) ^ S::src_swizzle(srow);
     const S mfma(lane, wd, wq);
 
+    if constexpr (EPI == EPI_FILTER) announce_arrival(a);
     const ItemWalk walk(a);
     for (int item = walk.first(a); item < walk.end; item += walk.step) {
         int r, qb;
@@ -604,6 +612,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_topk16w_kernel(const Gem
         lane_lds = (uint32_t)((ln & 15) * 64 + (((ln >> 4) ^ (((ln >> 2) & 1) << 1)) << 4));
     }
 
+    announce_arrival(a);
     const ItemWalk walk(a);
     for (int item = walk.first(a); item < walk.end; item += walk.step) {
         int r, qb;
@@ -892,6 +901,26 @@ static int launch_gemm_of(const GemmArgs &a, MainKernel kind, int epi, int grid,
         return CCR_ERR_INVALID;
     }
     return launch_kernel(k, RING * (size_t)SUB_BYTES, a, grid, s);
+}
+
+// The gate of ccr_search_stream_wait_main_pass: one wave that returns when `want` workgroups of the main pass have counted themselves
+// in (announce_arrival) -- or after GATE_MAX_POLLS polls, or GATE_MAX_TICKS of the 100-MHz wall clock (300 us), whichever comes
+// first.  It can delay the side work behind it; it can never hang it.
+constexpr int GATE_MAX_POLLS = 1024;
+constexpr long long GATE_MAX_TICKS = 30000;
+__global__ __launch_bounds__(64) void main_pass_gate_kernel(const uint32_t *arrive, uint32_t want) {
+    const long long t0 = wall_clock64();
+    for (int i = 0; i < GATE_MAX_POLLS; ++i) {
+        if (__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) return;
+        if (wall_clock64() - t0 > GATE_MAX_TICKS) return;
+        __builtin_amdgcn_s_sleep(64);
+    }
+}
+
+int launch_main_pass_gate(const uint32_t *arrive, uint32_t want, hipStream_t s) {
+    hipLaunchKernelGGL(main_pass_gate_kernel, dim3(1), dim3(64), 0, s, arrive, want);
+    CCR_LAUNCH_CHECK();
+    return CCR_OK;
 }
 
 int launch_gemm(const GemmArgs &a, int dt, MainKernel kind, int epi, int grid, hipStream_t s) {

@@ -26,6 +26,7 @@ struct Knobs {
     int thr_phases;    // CCR_THR_PHASES   0 = launcher's choice by the sample's size, 16 / 64 = the threshold kernel's group phases per query, pinned (tests, the A/B)
     int narrow_groups; // CCR_NARROW_GROUPS 2 = batches of 65 .. 128 queries stream as two query groups (default), 1 = tile kernels above 64 queries (the A/B knob)
     int tile_cap;      // CCR_TILE_CAP     0 = planner's choice (tile_cap_for), else the pinned number of groups one sampled tile may give an estimated threshold; 16 = no cap (the A/B knob)
+    int side_cus;      // CCR_SIDE_CUS     -1 = planner's choice (side_cus_for), 0 = the main pass takes every CU (the A/B knob), n = the CUs (rounded to a multiple of 8) a single-launch main pass leaves to side work, pinned; either way only for a search the hint allows (make_plan)
 };
 // One row per knob -- its variable, its field, its default: the ONE place a default is written.
 struct KnobDef {
@@ -40,7 +41,7 @@ inline constexpr KnobDef KNOB_DEFS[] = {
     {"CCR_NARROW", &Knobs::narrow, -1},            {"CCR_NARROW_GRID", &Knobs::narrow_grid, 0},   {"CCR_SKIP_SAMPLED", &Knobs::skip_sampled, -1},
     {"CCR_SKIP_LIST", &Knobs::skip_list, 1},       {"CCR_QSPLIT", &Knobs::qsplit, -1},            {"CCR_WIDE", &Knobs::wide, -1},
     {"CCR_THR_PHASES", &Knobs::thr_phases, 0},     {"CCR_NARROW_GROUPS", &Knobs::narrow_groups, NARROW_MAX_GROUPS},
-    {"CCR_TILE_CAP", &Knobs::tile_cap, 0},
+    {"CCR_TILE_CAP", &Knobs::tile_cap, 0},         {"CCR_SIDE_CUS", &Knobs::side_cus, -1},
 };
 static_assert(sizeof(KNOB_DEFS) / sizeof(KNOB_DEFS[0]) * sizeof(int) == sizeof(Knobs), "a row for every knob");
 inline Knobs default_knobs() {   // what an empty environment gives
@@ -73,7 +74,9 @@ struct Plan {
     int qgroups;          // query-block groups over the XCDs
     int cap;              // candidate slots per sub-list (the largest segment's: statistics)
     CandLayout cand;      // per-phase segments of the candidate area
-    int grid;             // persistent workgroups (multiple of NUM_XCD)
+    int grid;             // persistent workgroups (multiple of NUM_XCD): the sample pass, the retry pass, EPI_STORE, a phased main pass
+    int main_grid;        // ... of the single-launch main pass on a tile kernel: grid - side_cus (multiple of NUM_XCD); every main-pass item is priced and mapped on it
+    int side_cus;         // CUs that main pass leaves free for side work (ccr_search_stream_wait_main_pass releases the side stream when its workgroups are resident); 0: none
     int rescore_cap;      // max rows re-scored per query (power of two)
     int rescore_regular;  // ... of them recorded candidates (skip_sampled: rescore_cap also holds the joined rows of the sampled tiles)
     int select_compact;   // candidates per query the select kernel gathers into LDS
@@ -102,7 +105,14 @@ constexpr int OPT_RANK_FLOOR = 40, REDUCED_RANK_MIN_TILES = 40;
 
 constexpr int FALLBACK_ROWS = 16;   // dense score rows reserved for flagged queries (one on-stream chunk)
 
-Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn);
+// side_hint: the caller ran side work beside the previous search's main pass (ccr_search_stream_wait_main_pass), so this one may
+// leave CUs free for it (CCR_SIDE_CUS says how many; without the hint no plan does)
+Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn, bool side_hint = false);
+// The side CUs of the planner's own choice never take more than this share of the grid from the main pass.
+constexpr int SIDE_CUS_MAX_DIV = 4;
+// the two times that choice compares (ms, the planner's model): a fused tile plan's single-launch main pass, a re-pack of the shard on the whole chip
+double side_main_pass_ms(const Plan &p, int dim);
+double side_pack_ms(int64_t n_rows, int dim);
 
 // pieces of the planner that the retry pass of a search (ccr_api.hip) lays out its own launch with
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
@@ -121,7 +131,8 @@ struct SearchWs {
     float *qnorm, *thr, *cq, *gmax;     // thr, cq (margin coefficients gamma ||q||): [nq_pad] each, cq right after thr
     uint32_t *cnt;                      // sub-list counters
     uint2 *cand;                        // candidate area (cand_bytes): free once the select stage has run
-    uint32_t *flag_count, *flag_list;   // flag area: flag count at +0, candidate count (stat_cand) at +8, flagged queries at +64
+    uint32_t *flag_count, *flag_list;   // flag area: flag count at +0, candidate count (stat_cand) at +8, main-pass arrivals at +16, flagged queries at +64
+    uint32_t *arrive;                   // workgroups of a main pass with side CUs that have started (cleared with the flag count)
     unsigned long long *stat_cand;
     uint32_t *top;                      // the k best lower bounds per query between two re-tightenings (three-phase plans)
     float *thr_safe, *cq_safe, *dense;  // estimated thresholds: the conservative bounds of a failing search; dense scratch (dense_bytes)

@@ -217,10 +217,10 @@ static void range_window(const Plan &p, const Knobs &kn, int64_t &r_hi, int64_t 
     int64_t max_lists = p.rescore_cap > 512 ? 2048 : 1024;
     // one or two query blocks: 128 ranges x 8 sub-lists would leave half of the workgroups without a work item (n_q = 1: main pass
     // 1.34 ms instead of 0.7) -- the select stage's wide form walks 2 048 sub-lists, and its cost does not matter for so few queries
-    if ((max_lists / p.sublists) * p.main_qblocks < p.grid) max_lists = 2048;
+    if ((max_lists / p.sublists) * p.main_qblocks < p.main_grid) max_lists = 2048;
     if (kn.max_lists >= 64 && kn.max_lists < max_lists) max_lists = kn.max_lists;
     r_hi = std::min<int64_t>(max_lists / p.sublists, round_up(std::max<int64_t>(1, p.tiles / 8), NUM_XCD));
-    target = std::min<int64_t>(r_hi, round_up(std::max<int64_t>(NUM_XCD, (int64_t)p.grid * 6 / p.main_qblocks), NUM_XCD));
+    target = std::min<int64_t>(r_hi, round_up(std::max<int64_t>(NUM_XCD, (int64_t)p.main_grid * 6 / p.main_qblocks), NUM_XCD));
 }
 
 // 0.11 ms = 4.9 units of threshold kernel for 328 sample tiles x 3 584 queries
@@ -246,7 +246,7 @@ struct Best {
 // indices, so phase A is exactly one full round (and the middle phase whole rounds) for any R.
 // reprice_skipped: see choose_main_pass.
 static void price_range_count(const Plan &p, int k, const Knobs &kn, int64_t smp, int64_t R, int64_t target, bool reprice_skipped, Best &best) {
-    const int nrc = NUM_XCD / p.main_qgroups, qb_per = p.main_qblocks / p.main_qgroups, per_x = p.grid / NUM_XCD;
+    const int nrc = NUM_XCD / p.main_qgroups, qb_per = p.main_qblocks / p.main_qgroups, per_x = p.main_grid / NUM_XCD;
     const double qscale = query_scale(p);
     const double select_per_range = 0.1 * qscale, hit_w = 0.014 * qscale, phase_w = 3.0;
     const double fs = (double)smp / (double)p.tiles;
@@ -272,8 +272,9 @@ static void price_range_count(const Plan &p, int k, const Knobs &kn, int64_t smp
             best.offer(opt, {smp, R, 0, 0, rank, skip ? 1 : 0});
         }
     }
-    // phased plans: not for the re-pricing, CCR_PROGRESSIVE=0 (single launch) or the streaming kernel of small batches (it has no phases)
-    if (reprice_skipped || kn.progressive == 0 || p.narrow || !(items > per_x && (double)p.tiles / (double)R >= 8.0)) return;
+    // phased plans: not for the re-pricing, CCR_PROGRESSIVE=0 (single launch), the streaming kernel of small batches (it has no phases)
+    // or a main pass that leaves CUs to side work (one launch: make_plan tried it because the plan on every CU is one)
+    if (reprice_skipped || kn.progressive == 0 || p.narrow || p.side_cus || !(items > per_x && (double)p.tiles / (double)R >= 8.0)) return;
     // the thresholds after phase A come from the ranges it completed (+ the started one for part of the queries)
     const double fa = (double)per_x / (double)items;
     best.offer((1.0 + rounds(items - per_x)) * item_cost + phase_w + hit_w * survivors(fa, 0.0) + common, {smp, R, per_x, 0, 0, 0});
@@ -313,6 +314,7 @@ struct Search {
     int64_t n_rows;
     int dim, n_q, k, flags, num_cu;
     const Knobs &kn;
+    int side_cus;   // CUs a single-launch main pass on a tile kernel leaves free (multiple of NUM_XCD; 0: none)
 };
 
 // the sample pass scores group maxima of 16 rows: 1/div of the tiles, and comfortably more groups than k
@@ -336,6 +338,8 @@ static Plan plan_geometry(const Search &s, int mfma16) {
     p.tiles = (s.n_rows + TILE_DOCS - 1) / TILE_DOCS;
     p.full_tiles = s.n_rows / TILE_DOCS;
     p.grid = std::max(NUM_XCD, s.num_cu / NUM_XCD * NUM_XCD);
+    p.side_cus = std::min(s.side_cus, p.grid - NUM_XCD);
+    p.main_grid = p.grid - p.side_cus;
     p.mfma16 = mfma16;   // main pass on v_mfma_f32_16x16x32_bf16 (8 sub-lists per (range, query)) or 32x32x16 (4)
     p.sublists = p.mfma16 ? 8 : 4;
     p.rescore_cap = p.rescore_regular = std::min(8192, std::max(256, 2 * pow2_ceil(s.k)));
@@ -463,7 +467,7 @@ static void price_skip_sampled(const Search &s, Plan &p) {
     // The three constants (0.065, the 3 584-query scale of the planner's other per-query terms, the half) are fitted to
     // those TWO measured points: at NQ the rule switches the skip off above k of about 240; nothing between the points and
     // no other query count has been measured.
-    const double saved = 0.5 * (double)p.sample_tiles * p.main_qblocks * tile_cost(p) / (double)p.grid;
+    const double saved = 0.5 * (double)p.sample_tiles * p.main_qblocks * tile_cost(p) / (double)p.main_grid;
     const bool pays = 0.065 * join_rows * query_scale(p) < saved;
     if (need > 8192.0 || (s.kn.skip_sampled < 0 && !pays)) {
         p.skip_sampled = 0;
@@ -582,7 +586,7 @@ static int64_t dense_chunk_rows(const Search &s) {
     return rows;
 }
 
-static Plan make_plan_for(const Search &s, int mfma16) {
+static Plan plan_once(const Search &s, int mfma16) {
     Plan p = plan_geometry(s, mfma16);
     const int64_t sample = decide_fused(s, p);
     if (p.fused) {
@@ -602,6 +606,15 @@ static Plan make_plan_for(const Search &s, int mfma16) {
     return p;
 }
 
+// Side CUs are left by ONE launch of a tile kernel alone: a phased plan (its launches would each wait for their stragglers on fewer
+// CUs), the streaming kernel and the dense path are planned again on every CU.
+static Plan make_plan_for(const Search &s, int mfma16) {
+    Plan p = plan_once(s, mfma16);
+    if (s.side_cus == 0 || (p.fused && !p.narrow && p.item_a == 0 && p.item_b == 0)) return p;
+    const Search whole = {s.n_rows, s.dim, s.n_q, s.k, s.flags, s.num_cu, s.kn, 0};
+    return plan_once(whole, mfma16);
+}
+
 SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char *base) {
     SearchWs w;
     memset(&w, 0, sizeof(w));
@@ -610,7 +623,8 @@ SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char 
     auto take = [&](size_t bytes) { return at(b.take(bytes)); };
     if (!p.fused) {
         w.flag_count = (uint32_t *)take(64 + (size_t)n_q * 4);   // queries the margin select hands to the fp64 path
-        w.flag_list = w.flag_count + 16;
+        w.arrive = w.flag_count + 4;
+    w.flag_list = w.flag_count + 16;
         w.dense_bytes = (size_t)p.dense_rows_per_chunk * (n_rows + 3) * 4;
         w.dense = (float *)take(w.dense_bytes);
         w.total = b.off;
@@ -625,6 +639,7 @@ SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char 
     w.cand = (uint2 *)take((size_t)p.cand_recs * 8);
     w.flag_count = (uint32_t *)take(64 + (size_t)n_q * 4);
     w.stat_cand = (unsigned long long *)(w.flag_count + 2);
+    w.arrive = w.flag_count + 4;
     w.flag_list = w.flag_count + 16;
     w.cand_bytes = (char *)w.flag_count - (char *)w.cand;
     w.top = (uint32_t *)take(p.item_b ? (nq_pad + (size_t)n_q * k) * 4 : 0);
@@ -653,13 +668,75 @@ SearchWs search_ws(const Plan &p, int64_t n_rows, int dim, int n_q, int k, char 
 // whenever its eight sub-lists per (range, query) do not force FEWER ranges than the 32x32x16 plan wants: up to k = 512 always
 // (measured), above that when the four-sub-list plan's range count times 8 stays within the select stage's 2 048
 // sub-lists (config-4 shard, k = 1000, 62 ranges: main pass 111 vs 120 ms, select 8.9 vs 9.4 ms).
-Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn) {
-    const Search s = {n_rows, dim, n_q, k, flags, num_cu, kn};
+static Plan plan_on_best_kernel(const Search &s) {
+    const Knobs &kn = s.kn;
     if (kn.mfma16 >= 0) return make_plan_for(s, kn.mfma16 ? 1 : 0);
-    if (k <= 512) return make_plan_for(s, 1);
+    if (s.k <= 512) return make_plan_for(s, 1);
     const Plan p32 = make_plan_for(s, 0);
     if (p32.fused && p32.ranges * 8 <= 2048) return make_plan_for(s, 1);
     return p32;
+}
+
+// ------------------------------------------------------------------ side CUs
+// A caller that re-packs the shard for its next search beside this one (ccr_search_stream_wait_main_pass) gets CUs to do it on: the
+// single-launch main pass holds every register of each CU it runs on and nearly idles the HBM, the pack is HBM-bound and needs no
+// matrix core.  The model, in milliseconds (profiles/side_cus.md has the points):
+//   main pass      its items' rounds x tiles per item (the planner's tile units) x SIDE_TILE_MS per unit of a 768-wide tile: 9.82 ms
+//                  on 256 workgroups (112 ranges, four rounds), 11.4 on 224 (72 ranges, three rounds) by the kernel trace
+//   pack           n_rows x dim x 6 bytes (fp32 read, 16-bit write) at SIDE_PACK_CU_GBPS per free CU beside the main pass (measured:
+//                  50 on 8 CUs, 34 or more on 32, where the 12.4-GB pack ends with the main pass), at SIDE_PACK_ALL_GBPS on the whole
+//                  chip behind it (2.34 ms)
+//   select         no longer covered by the pack.  The cover was worth the whole select at k = 100 (0.33 ms) and next to nothing at
+//                  k = 1001, where the 1.8-ms select is HBM-bound like the pack and the step was their sum: at most SIDE_SELECT_COVER_MS
+// The planner's own choice is the multiple of 8 CUs on which the pack ends about when the main pass does, at most a quarter of
+// the grid; it is 0 where the main pass is shorter than the pack at full speed (the pack cannot hide behind it) and where the
+// re-planned main pass grows by more than the pack's hidden part saves.  Every constant is fitted to ONE shape, the NQ step
+// (2 681 468 x 768, 3 452 queries) at k = 100, on gaussian, clustered and sorted rows; at k = 1001 the same 32 CUs were measured
+// (-0.5 ms); the MS-MARCO-scale step has a phased plan and keeps every CU.  No other width or query count has been measured.
+constexpr double SIDE_TILE_MS = 0.0198, SIDE_PACK_CU_GBPS = 40.0, SIDE_PACK_ALL_GBPS = 5300.0, SIDE_SELECT_COVER_MS = 0.35;
+
+// length of a single-launch main pass on a tile kernel, in tile units of one workgroup (price_range_count's first term)
+static double main_pass_units(const Plan &p) {
+    const int nrc = NUM_XCD / p.main_qgroups, qb_per = p.main_qblocks / p.main_qgroups, per_x = p.main_grid / NUM_XCD;
+    const int64_t items = p.ranges / nrc * qb_per, walked = p.tiles - (p.skip_sampled ? p.sample_tiles : 0);
+    return (double)((items + per_x - 1) / per_x) * ((double)((walked + p.ranges - 1) / p.ranges) + 0.15) * tile_cost(p);
+}
+static double side_ms_per_unit(const Search &s) { return SIDE_TILE_MS * (double)s.dim / 768.0; }
+static double side_pack_bytes(const Search &s) { return (double)s.n_rows * s.dim * 6.0; }
+double side_main_pass_ms(const Plan &p, int dim) { return main_pass_units(p) * SIDE_TILE_MS * (double)dim / 768.0; }
+double side_pack_ms(int64_t n_rows, int dim) { return (double)n_rows * dim * 6.0 / (SIDE_PACK_ALL_GBPS * 1e6); }
+
+// CUs to plan the carve with: the pinned count, or the model's (0: none)
+static int side_cus_for(const Search &s, const Plan &whole) {
+    const Knobs &kn = s.kn;
+    if (kn.side_cus == 0 || !whole.fused || whole.narrow || whole.item_a || whole.item_b) return 0;
+    if (kn.side_cus > 0) return (int)std::min<int64_t>(round_up(kn.side_cus, NUM_XCD), whole.grid - NUM_XCD);
+    const double main_ms = main_pass_units(whole) * side_ms_per_unit(s), bytes = side_pack_bytes(s);
+    if (main_ms < side_pack_ms(s.n_rows, s.dim)) return 0;   // the pack outlasts the main pass even on the whole chip
+    const int want = (int)(bytes / (main_ms * SIDE_PACK_CU_GBPS * 1e6) / NUM_XCD + 0.5) * NUM_XCD;
+    return std::min(want, whole.grid / SIDE_CUS_MAX_DIV / NUM_XCD * NUM_XCD);
+}
+
+// does the plan `carved` beat `whole` for a caller that packs beside the main pass?
+static bool side_cus_pay(const Search &s, const Plan &whole, const Plan &carved) {
+    const double unit = side_ms_per_unit(s), main_ms = main_pass_units(carved) * unit;
+    const double cost = main_ms - main_pass_units(whole) * unit;
+    const double pack_ms = side_pack_bytes(s) / (SIDE_PACK_ALL_GBPS * 1e6);
+    const double hidden = std::min(pack_ms, main_ms * carved.side_cus * SIDE_PACK_CU_GBPS / SIDE_PACK_ALL_GBPS);
+    const double pass = carved.opt_rank ? estimated_pass(carved.opt_rank, sample_fraction(carved), s.k) : conservative_pass(carved, s.k);
+    const double select_ms = (0.1 * carved.ranges + 0.014 * pass) * query_scale(carved) * unit;   // it ran beside the pack
+    return cost + std::min(select_ms, SIDE_SELECT_COVER_MS) < hidden;
+}
+
+// The plan of one search: on every CU, or -- side_hint -- with side CUs where they apply and, by the planner's own choice, pay.
+Plan make_plan(int64_t n_rows, int dim, int n_q, int k, int flags, int num_cu, const Knobs &kn, bool side_hint) {
+    Search s = {n_rows, dim, n_q, k, flags, num_cu, kn, 0};
+    const Plan whole = plan_on_best_kernel(s);
+    s.side_cus = side_hint ? side_cus_for(s, whole) : 0;
+    if (s.side_cus == 0) return whole;
+    const Plan carved = plan_on_best_kernel(s);
+    if (carved.side_cus == 0 || (kn.side_cus < 0 && !side_cus_pay(s, whole, carved))) return whole;
+    return carved;
 }
 
 }  // namespace ccr

@@ -77,7 +77,11 @@ typedef struct ccr_search_stats {
     int32_t skipped_tiles;     /* corpus tiles the main pass did not score: the sampled tiles, whose rows the select stage joins from the
                                   sample pass's group maxima (CCR_SKIP_SAMPLED); 0: every tile was scored */
     int32_t tile_cap;          /* opt_rank > 0: groups of one sampled tile that count towards that rank (CCR_TILE_CAP; 16 = all of them);
-                                  0 without estimated thresholds.  The last field: the struct grew from 80 to 88 bytes with it */
+                                  0 without estimated thresholds.  The struct grew from 80 to 88 bytes with it */
+    int32_t main_grid;         /* workgroups of the main pass's tile kernel (0: the streaming pass of a small batch, the dense path) */
+    int32_t side_cus;          /* CUs that main pass left free for the caller's side work (ccr_search_stream_wait_main_pass, CCR_SIDE_CUS);
+                                  0: it ran on every CU.  The last field: the struct grew from 88 to 96 bytes with these two
+                                  (ccr_version() >= 113) */
 } ccr_search_stats;
 
 const char *ccr_last_error(void);
@@ -363,11 +367,20 @@ int ccr_search(ccr_index *index, const uint16_t *Q_bf16, int n_q, int k, float *
 int ccr_search_finish(ccr_index *index);
 int ccr_search_last_stats(const ccr_index *index, ccr_search_stats *stats /* host */);
 /*
- * Makes `stream` wait until the MAIN PASS (the dominant kernel) of the index's last search -- possibly still pending
- * (CCR_SEARCH_ASYNC) -- has completed on the search's stream.  Work that does not depend on that search's results and does not
- * touch its buffers (packing the NEXT corpus shard into another buffer, the reference's next `embedding_func` batch of
- * scripts/ms_marco_eval.py:141-149) can then run beside the search's select stage instead of behind it.  No-op when the
- * last search took the dense path (nothing recorded).  No host synchronisation.
+ * Releases `stream` when SIDE WORK can usefully start beside the index's last search -- possibly still pending (CCR_SEARCH_ASYNC).
+ * Side work is work that does not depend on that search's results and touches none of its buffers, inputs included (the select
+ * stage reads them all): packing the NEXT corpus shard into another buffer, the reference's next `embedding_func` batch of
+ * scripts/ms_marco_eval.py:141-149.
+ *   - A main pass (the dominant kernel) that ran on every CU: `stream` waits until it has completed; the side work runs beside the
+ *     select stage instead of behind it.
+ *   - A main pass that left CUs free (ccr_search_stats.side_cus > 0): `stream` waits until that pass BEGINS, then for a one-wave gate
+ *     kernel that returns when the pass's workgroups are resident (bounded: at most a few hundred microseconds); the side work runs
+ *     on the free CUs beside the main pass.  An HBM-bound pack hides behind the matrix-core-bound pass that way.
+ * The call is also the HINT that lets a search leave CUs free: a fused search does so only if this function was called for the
+ * previous fused search on the same device (and CCR_SIDE_CUS is not 0: -1 = the planner's choice of their number, where it
+ * prices them as paying; n = that many, rounded to a multiple of 8).  A search that is not followed by the call switches it off
+ * again; the first search of a loop never leaves CUs free.  Results do not depend on any of this.
+ * No-op when the last search took the dense path (nothing recorded).  No host synchronisation.  ccr_version() >= 113 for the second form.
  */
 int ccr_search_stream_wait_main_pass(const ccr_index *index, void *stream);
 /*

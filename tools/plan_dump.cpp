@@ -1,8 +1,10 @@
 // plan_dump -- what the search planner (ccr::make_plan in libccr_hip.so) decides, host-only: no GPU call.
 //   hipcc -O1 -std=c++17 -I include -I crowd-coachable-recommendations_amd/csrc tools/plan_dump.cpp -o plan_dump -L crowd-coachable-recommendations_amd/lib -lccr_hip -Wl,-rpath,$PWD/crowd-coachable-recommendations_amd/lib
 //
-//   plan_dump n_rows dim n_q k [flags] [num_cu]   every field of that search's plan and the workspace offsets (knobs from the CCR_*
-//                                                 environment, flags as in ccr_retrieval.h, 256 CUs): what one wants beside a profile
+//   plan_dump n_rows dim n_q k [flags] [num_cu] [side_hint]
+//                                                 every field of that search's plan and the workspace offsets (knobs from the CCR_*
+//                                                 environment, flags as in ccr_retrieval.h, 256 CUs; side_hint 1: the plan of a search
+//                                                 that may leave CUs to side work): what one wants beside a profile
 //   plan_dump --grid                              a fixed grid of shapes under a dozen knob variants: per variant the plan count, the
 //                                                 fused count and a 64-bit FNV-1a hash over every field of every plan.  A change of
 //                                                 the planner that is meant to keep every plan prints the same lines before and after
@@ -51,6 +53,8 @@ static void plan_fields(const Plan &p, const SearchWs &w, F f) {
     f("cand.base[1]", p.cand.base[1]);
     f("cand.base[2]", p.cand.base[2]);
     f("grid", p.grid);
+    f("main_grid", p.main_grid);
+    f("side_cus", p.side_cus);
     f("rescore_cap", p.rescore_cap);
     f("rescore_regular", p.rescore_regular);
     f("select_compact", p.select_compact);
@@ -91,9 +95,9 @@ static void plan_fields(const Plan &p, const SearchWs &w, F f) {
     f("ws.total", (long long)w.total);
 }
 
-static int dump_one(long long n, int dim, int nq, int k, int flags, int num_cu) {
-    const Plan p = make_plan(n, dim, nq, k, flags, num_cu, read_knobs());
-    printf("n_rows %lld dim %d n_q %d k %d flags %d num_cu %d\n", n, dim, nq, k, flags, num_cu);
+static int dump_one(long long n, int dim, int nq, int k, int flags, int num_cu, bool side_hint) {
+    const Plan p = make_plan(n, dim, nq, k, flags, num_cu, read_knobs(), side_hint);
+    printf("n_rows %lld dim %d n_q %d k %d flags %d num_cu %d side_hint %d\n", n, dim, nq, k, flags, num_cu, (int)side_hint);
     plan_fields(p, search_ws(p, n, dim, nq, k, nullptr), [](const char *name, long long v) { printf("  %-22s %lld\n", name, v); });
     return 0;
 }
@@ -122,7 +126,7 @@ static int dump_grid() {
                     variant("phases=2 optimistic=0", 256, 17), variant("mfma16=0", 256, 17), variant("mfma16=1 max_lists=512", 256, 17),
                     variant("sample_div=16", 256, 17),   variant("ranges=64 qgroups=2", 256, 17), variant("opt_rank=13", 256, 17),
                     variant("wide=0 qsplit=1", 256, 17), variant("wide=1 qgroups=8 qsplit=1", 256, 17), variant("skip_sampled=1", 256, 17),
-                    variant("narrow_groups=1 skip_sampled=0", 256, 17)};
+                    variant("narrow_groups=1 skip_sampled=0", 256, 17), variant("side hint", 256, 17), variant("side hint side_cus=24", 256, 17)};
     int v = 2;
     vs[v].kn.narrow = vs[v].kn.skip_sampled = vs[v].kn.skip_list = vs[v].kn.qsplit = vs[v].kn.narrow_groups = 0, ++v;
     vs[v++].kn.optimistic = 0;
@@ -138,6 +142,8 @@ static int dump_grid() {
     vs[v].kn.wide = 1, vs[v].kn.qgroups = 8, vs[v].kn.qsplit = 1, ++v;
     vs[v++].kn.skip_sampled = 1;
     vs[v].kn.narrow_groups = 1, vs[v].kn.skip_sampled = 0, ++v;
+    const int first_hinted = v++;   // the last two variants plan with the side hint
+    vs[v++].kn.side_cus = 24;
 
     long long all_plans = 0;
     unsigned long long all_hash = 0xcbf29ce484222325ull;
@@ -154,7 +160,7 @@ static int dump_grid() {
                     for (int k : ks)
                         for (int flags : flag_set) {
                             if (point++ % var.stride != vi % var.stride || k > n) continue;
-                            const Plan p = make_plan(n, d, nq, k, flags, var.num_cu, var.kn);
+                            const Plan p = make_plan(n, d, nq, k, flags, var.num_cu, var.kn, vi >= first_hinted);
                             plan_fields(p, search_ws(p, n, d, nq, k, nullptr), mix);
                             ++plans;
                             fused += p.fused;
@@ -170,10 +176,10 @@ static int dump_grid() {
 
 int main(int argc, char **argv) {
     if (argc == 2 && !strcmp(argv[1], "--grid")) return dump_grid();
-    if (argc < 5 || argc > 7) {
-        fprintf(stderr, "usage: %s n_rows dim n_q k [flags] [num_cu]   |   %s --grid\n", argv[0], argv[0]);
+    if (argc < 5 || argc > 8) {
+        fprintf(stderr, "usage: %s n_rows dim n_q k [flags] [num_cu] [side_hint]   |   %s --grid\n", argv[0], argv[0]);
         return 2;
     }
     return dump_one(atoll(argv[1]), atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), argc > 5 ? atoi(argv[5]) : CCR_SEARCH_DEFAULT,
-                    argc > 6 ? atoi(argv[6]) : 256);
+                    argc > 6 ? atoi(argv[6]) : 256, argc > 7 && atoi(argv[7]) != 0);
 }
