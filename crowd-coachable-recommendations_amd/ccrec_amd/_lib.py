@@ -35,6 +35,7 @@ EXPORTS = [
     "ccr_grad_stats_workspace_bytes", "ccr_grad_stats", "ccr_adamw_control_update", "ccr_adamw_step_scaled",
     "ccr_keep_f32", "ccr_rescore_f32_workspace_bytes", "ccr_rescore_f32",
     "ccr_attention_bias_half",
+    "ccr_attention_head_half",
 ]
 
 MIN_VERSION = 101   # ccr_version() of the oldest library load() accepts (101: the ccr_pool_ce_* entry points)
@@ -50,6 +51,7 @@ AMP_OPTIM_VERSION = 110   # ... and loss scaling, overflow skip and norm clippin
 RANK_F32_VERSION = 111   # ... and the kept fp32 rows with the verified re-score of a 16-bit search on them (ccr_keep_f32, ccr_rescore_f32)
 ATTENTION_BIAS_VERSION = 112   # ... and the attention forward with a shared relative position bias (ccr_attention_bias_half)
 SIDE_CUS_VERSION = 113   # ... and the main pass that leaves CUs to the caller's side work (CCR_SIDE_CUS; main_grid and side_cus in the search statistics: an older library leaves them 0)
+HEAD32_VERSION = 114   # ... and the attention forward with the head width as an argument, 32 or 64 (ccr_attention_head_half), with the inference LayerNorm rows at every multiple of 128
 
 SHARD_HEADER_BYTES = 32
 SHARD_MAGIC = 0x4D524343
@@ -179,6 +181,7 @@ def load():
     lib.ccr_gelu_bf16.argtypes = [vp, vp, i64, vp]
     lib.ccr_attention_half.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, ctypes.c_float, i32, vp]
     lib.ccr_attention_bias_half.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, i32, vp]
+    lib.ccr_attention_head_half.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.c_float, i32, vp]
     lib.ccr_add_layernorm_half.argtypes = [vp, vp, vp, vp, ctypes.c_float, vp, vp, i64, i32, i32, vp]
     lib.ccr_embed_layernorm_half.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, i64, i32, i32, vp]
     lib.ccr_gelu_half.argtypes = [vp, vp, i64, i32, vp]

@@ -17,8 +17,9 @@ gradients on, on the kernels' backward (ops.attention_train, add_layernorm_train
 packed keep bits that a generator kernel writes from one 64-bit seed per call (ops.dropout_bits_rows / dropout_bits_attention, restated on
 the CPU in dropout_ref); without that opt-in such a model is refused and keeps training as its torch module.
 
-Only what the kernels cover is accepted (unsupported_reason): post-LayerNorm layers with exact GELU, head width 64, hidden size a
-multiple of 256, at most 512 tokens, right-padded batches, in one of these transformers classes:
+Only what the kernels cover is accepted (unsupported_reason): post-LayerNorm layers with exact GELU, head width 64 (32 as well with
+CCREC_FUSED_ENCODER_HEAD32=1, head32_wanted: the MiniLM-class encoders, inference only), hidden size a multiple of 128 from 256 on (the training
+kernels: of 256), at most 512 tokens, right-padded batches, in one of these transformers classes:
 
   BertModel, DistilBertModel       absolute positions: the position row of a token is its index inside its sequence;
   RobertaModel, XLMRobertaModel    BERT's layers; the position row is padding_idx + the number of non-pad ids up to and including the
@@ -124,11 +125,36 @@ def _bias_train_reason(arch):
     return None
 
 
+def _train_shape_reason(arch):
+    """Why the TRAINING kernels (forward with a backward, keep bits) cannot take an architecture the inference kernels can: they are built
+    for head width 64 and for rows of 256 C elements only."""
+    heads, hidden = arch.heads, arch.hidden
+    if hidden % heads or hidden // heads != 64:
+        return f"head width {hidden / heads:g} (the training attention kernels are built for 64: this encoder trains as its torch module)"
+    if hidden % 256 or hidden > 2048:
+        return f"hidden size {hidden} (the training kernels take multiples of 256 up to 2048: this encoder trains as its torch module)"
+    return None
+
+
+def _train_reason(model):
+    """unsupported_reason, then what only the training kernels refuse."""
+    reason = unsupported_reason(model)
+    if reason is not None:
+        return reason
+    arch = _describe(model)
+    return _train_shape_reason(arch) or _bias_train_reason(arch)
+
+
 def shadow_unsupported_reason(model):
     """None when an optimizer may keep a 16-bit weight set of `model` current for the training forward (optim.FusedAdamW(shadow_for=...)):
     what unsupported_reason asks, and an encoder the kernels can train."""
-    reason = unsupported_reason(model)
-    return reason if reason is not None else _bias_train_reason(_describe(model))
+    return _train_reason(model)
+
+
+def head32_wanted():
+    """The opt-in of the head-width-32 attention kernel: CCREC_FUSED_ENCODER_HEAD32=1, read at call time (default off: a model with
+    32-wide heads -- the MiniLM-class encoders, hidden 384 with 12 heads -- keeps running as its torch module)."""
+    return os.environ.get("CCREC_FUSED_ENCODER_HEAD32", "").strip() == "1"
 
 
 def unsupported_reason(model):
@@ -137,10 +163,14 @@ def unsupported_reason(model):
     if isinstance(arch, str):
         return arch
     heads, hidden = arch.heads, arch.hidden
-    if hidden % heads or hidden // heads != 64:
+    width = hidden // heads if hidden % heads == 0 else None
+    if width == 32 and head32_wanted():
+        if arch.bias_source is not None:
+            return "head width 32 with a relative position bias (the bias form of the attention kernel is built for head width 64 only)"
+    elif width != 64:
         return f"head width {hidden / heads:g} (the attention kernel is built for 64)"
-    if hidden % 256 or hidden > 2048:
-        return f"hidden size {hidden} (the LayerNorm kernel takes multiples of 256 up to 2048)"
+    if hidden % 128 or hidden < 256 or hidden > 2048:
+        return f"hidden size {hidden} (the LayerNorm kernel takes multiples of 128 from 256 to 2048)"
     if arch.activation != "gelu":
         return f"activation {arch.activation!r} (exact GELU only)"
     return None
@@ -182,9 +212,7 @@ def train_unsupported_reason(model):
     training mode with any dropout probability above 0 is refused; eval mode or all-zero dropout is fine.  With the second opt-in
     (train_wanted() and train_dropout_wanted()) active dropout is accepted where every live torch.nn.Dropout module is one of the known
     sites (_dropout_sites: their p is read from the modules at call time); any other live Dropout module is refused by name."""
-    reason = unsupported_reason(model)
-    if reason is None:
-        reason = _bias_train_reason(_describe(model))
+    reason = _train_reason(model)
     if reason is not None:
         return reason
     if getattr(model, "training", False) and train_wanted() and train_dropout_wanted():
@@ -311,7 +339,17 @@ def for_model(model):
         if enc is False or (enc is not None and enc.model is not model):
             enc = FusedBertEncoder(model) if unsupported_reason(model) is None else None
             model.__dict__[_SLOT] = enc
+        elif _head_width_32(model):      # the one answer that a switch read at call time can change (head32_wanted): asked again per call
+            if unsupported_reason(model) is not None:
+                return None      # (an encoder built while the switch was on stays in its slot, unused)
+            if enc is None:
+                enc = model.__dict__[_SLOT] = FusedBertEncoder(model)
         return enc
+
+
+def _head_width_32(model):
+    arch = _describe(model)
+    return not isinstance(arch, str) and arch.heads > 0 and arch.hidden == 32 * arch.heads
 
 
 def prefix_lengths(attention_mask):
@@ -597,13 +635,15 @@ class FusedBertEncoder:
         last = len(layers) - 1
         bias = self._rel_bias
         assert (bias is not None) == (_describe(self.model).bias_source is not None), "refresh() keeps the bias table with the weight copies"
+        width = self.hidden // self.heads      # 64, or 32 (unsupported_reason let it in: head32_wanted)
+        scale = width ** -0.5
         for i, l in enumerate(layers):
             qkv = F.linear(hb, l.wqkv, l.bqkv)
             if bias is None:
-                ctx = ops.attention(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=0.125)
+                ctx = ops.attention(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=scale, head_width=width)
             else:      # one table for every layer, as the module shares one position_bias
-                ctx = ops.attention(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=0.125, rel_bias=bias,
-                                    rel_span=REL_SPAN)
+                ctx = ops.attention(qkv, seq_start, lengths, self.heads, max_len=max_len, pad_len=pad_len, scale=scale, rel_bias=bias,
+                                    rel_span=REL_SPAN, head_width=width)
             if i == last and cls_rows is not None:
                 ctx, h = ctx[cls_rows].contiguous(), h[cls_rows].contiguous()
             h, hb = ops.add_layernorm(F.linear(ctx, l.wo, l.bo), h, l.g1, l.b1, l.eps1)

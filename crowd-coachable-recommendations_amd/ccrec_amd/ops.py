@@ -288,12 +288,12 @@ def _half_code(dtype):
     return _HALF_DTYPES[dtype]
 
 
-def _check_qkv(qkv, seq_start, seq_len, n_heads):
-    """The token array and sequence table every attention op takes: qkv [T, 3 * n_heads * 64] contiguous on the GPU, seq_start / seq_len
-    [n_seq] contiguous int32 on the GPU.  -> T"""
+def _check_qkv(qkv, seq_start, seq_len, n_heads, head_width=64):
+    """The token array and sequence table every attention op takes: qkv [T, 3 * n_heads * head_width] contiguous on the GPU, seq_start /
+    seq_len [n_seq] contiguous int32 on the GPU.  -> T"""
     assert qkv.is_cuda and qkv.dim() == 2 and qkv.is_contiguous()
     T, width = qkv.shape
-    assert width == 3 * n_heads * 64, f"qkv rows are {width} wide, expected 3 x {n_heads} heads x 64"
+    assert width == 3 * n_heads * head_width, f"qkv rows are {width} wide, expected 3 x {n_heads} heads x {head_width}"
     assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
     assert seq_start.is_contiguous() and seq_len.is_contiguous() and seq_start.numel() == seq_len.numel()
     return T
@@ -329,25 +329,54 @@ def _require_attention_bias():
     return lib
 
 
-def attention(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, out=None, rel_bias=None, rel_span=None):
+_HEAD32_CHECKED = False
+
+
+def _require_head32():
+    """require_gpu() + once: the loaded library has the attention forward for head width 32 (ccr_version() >= 114)."""
+    global _HEAD32_CHECKED
+    lib = require_gpu()
+    if not _HEAD32_CHECKED:
+        have = int(lib.ccr_version())
+        if have < _lib.HEAD32_VERSION:
+            raise _lib.CcrError(f"{_lib.LIB_PATH} is version {have}, attention at head width 32 needs {_lib.HEAD32_VERSION}: "
+                                f"rebuild it (python -c 'import __graft_entry__ as g; g.build()')")
+        _HEAD32_CHECKED = True
+    return lib
+
+
+def attention(qkv, seq_start, seq_len, n_heads, max_len, pad_len=0, scale=0.125, out=None, rel_bias=None, rel_span=None, head_width=64):
     """Multi-head self-attention of a token array (ccr_attention_half; head width 64): qkv [T, 3 * n_heads * 64] bf16 or fp16 = the
     stacked query | key | value projection of every token, seq_start / seq_len [n_seq] int32 = each sequence's first row and real tokens,
     max_len = the longest seq_len (host int, <= 512), pad_len = L for a right-padded [n_seq, L] batch (its padding rows get
     zeros) or 0 for a packed array.  -> context rows [T, n_heads * 64] of qkv's dtype.
     rel_bias (ccr_attention_bias_half): fp32 [n_heads, 2 * R + 1] on qkv's device, one additive bias per (head, key - query) shared by
     every sequence: probability ~ exp(scale * q.k + rel_bias[head, R + key - query]).  rel_span = R (default: what the table's width
-    says), max_len - 1 <= R <= 511.  An all-zero table gives the bits of the call without one."""
-    lib = require_gpu() if rel_bias is None else _require_attention_bias()
+    says), max_len - 1 <= R <= 511.  An all-zero table gives the bits of the call without one.
+    head_width = 32 (ccr_attention_head_half; the MiniLM-class encoders): qkv [T, 3 * n_heads * 32] -> [T, n_heads * 32], the caller's
+    scale (32 ** -0.5 for BERT's layers), no rel_bias.  head_width = 64 is the call above, whichever entry point carries it."""
+    if head_width not in (32, 64):
+        raise ValueError(f"head_width={head_width}: the attention kernels are built for 32 and 64")
+    if head_width == 32 and rel_bias is not None:
+        raise ValueError("head_width=32 with rel_bias: the relative-bias attention kernel is built for head width 64 only")
+    if head_width == 32:
+        lib = _require_head32()
+    else:
+        lib = require_gpu() if rel_bias is None else _require_attention_bias()
     code = _half_code(qkv.dtype)
-    T = _check_qkv(qkv, seq_start, seq_len, n_heads)
+    T = _check_qkv(qkv, seq_start, seq_len, n_heads, head_width)
     if out is None:
-        out = torch.empty(T, n_heads * 64, dtype=qkv.dtype, device=qkv.device)
-    assert out.is_cuda and out.dtype == qkv.dtype and tuple(out.shape) == (T, n_heads * 64) and out.is_contiguous()
+        out = torch.empty(T, n_heads * head_width, dtype=qkv.dtype, device=qkv.device)
+    assert out.is_cuda and out.dtype == qkv.dtype and tuple(out.shape) == (T, n_heads * head_width) and out.is_contiguous()
     if rel_bias is None:
         assert rel_span is None, "rel_span without rel_bias"
         with _on(qkv):
-            _lib.check(lib.ccr_attention_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), seq_len.numel(), int(n_heads),
-                                              int(max_len), int(pad_len), float(scale), code, _stream(qkv)), "ccr_attention_half")
+            if head_width == 32:
+                _lib.check(lib.ccr_attention_head_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), seq_len.numel(), int(n_heads), 32,
+                                                       int(max_len), int(pad_len), float(scale), code, _stream(qkv)), "ccr_attention_head_half")
+            else:
+                _lib.check(lib.ccr_attention_half(_ptr(qkv), _ptr(seq_start), _ptr(seq_len), _ptr(out), seq_len.numel(), int(n_heads),
+                                                  int(max_len), int(pad_len), float(scale), code, _stream(qkv)), "ccr_attention_half")
         return out
     assert rel_bias.is_cuda and rel_bias.device == qkv.device and rel_bias.dtype == torch.float32 and rel_bias.is_contiguous()
     assert rel_bias.dim() == 2 and rel_bias.shape[0] == n_heads and rel_bias.shape[1] % 2 == 1, tuple(rel_bias.shape)
@@ -408,7 +437,7 @@ def gelu_(x):
 
 def add_layernorm(x, residual, gamma, beta, eps, want_f32=True, want_bf16=True, keep_bits=None, inv_keep=1.0):
     """LayerNorm(x + residual) * gamma + beta per row (ccr_add_layernorm_half): x [rows, dim] bf16 or fp16, residual [rows, dim] fp32 or
-    None, gamma / beta [dim] fp32, dim a multiple of 256 (<= 2048).  -> (fp32 rows or None, their copy in x's dtype or None:
+    None, gamma / beta [dim] fp32, dim a multiple of 128 (256 .. 2048; with keep_bits: of 256).  -> (fp32 rows or None, their copy in x's dtype or None:
     want_bf16 asks for that 16-bit copy whichever of the two types x has).
     keep_bits int32 [rows, dim / 32] (dropout_bits_rows): LayerNorm(x * keep * inv_keep + residual) (ccr_add_layernorm_drop_half)."""
     lib = require_gpu() if keep_bits is None else _require_encoder_dropout()

@@ -117,8 +117,12 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._host_state_only:
             _refuse("shadow_for", "needs CUDA parameters")
         code, mine = _SHADOW_CODES[dtype], {id(p) for g in self.param_groups for p in g["params"]}
+        refused = []      # why the encoders under the module that fused_bert knows by class were turned down
         for m in module.modules():
-            if fused_bert.shadow_unsupported_reason(m) is not None:      # (not covered, or covered for inference only)
+            reason = fused_bert.shadow_unsupported_reason(m)
+            if reason is not None:      # (not covered, or covered for inference only)
+                if not isinstance(fused_bert._describe(m), str):
+                    refused.append(f"{type(m).__name__}: {reason}")
                 continue
             enc = fused_bert.for_model(m)
             layers = enc.adopt_weights(dtype)
@@ -144,7 +148,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._encoders.append((enc, enc.adopted_masters()))
         if not self._encoders:
             _refuse("shadow_for", "no encoder under the module is one the layer kernels cover (fused_bert.unsupported_reason) and can train "
-                    "(fused_bert.shadow_unsupported_reason)")
+                    "(fused_bert.shadow_unsupported_reason)" + "".join(f"; {r}" for r in refused))
         self.shadow_dtype = dtype
 
     # --------------------------------------------------------------------------------------------------------------------- state

@@ -76,7 +76,7 @@ void slab_give(int device, uint32_t *p) {
 }  // namespace
 
 extern "C" const char *ccr_last_error(void) { return g_err; }
-extern "C" int ccr_version(void) { return 113; }
+extern "C" int ccr_version(void) { return 114; }
 
 // The hint behind side CUs, per device: did the caller order a side stream against the main pass of the previous fused search
 // (ccr_search_stream_wait_main_pass)?  Then the next fused search on the device may leave CUs free for that side work; it takes the

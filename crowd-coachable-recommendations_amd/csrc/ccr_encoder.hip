@@ -566,10 +566,11 @@ static int add_layernorm(const char *who, const uint16_t *x, const uint32_t *bit
                          const float *beta, float eps, float *out_f32, uint16_t *out_half, int64_t rows, int dim, int half_dtype,
                          hipStream_t s) {
     if (const int rc = check_half(who, half_dtype)) return rc;
-    if (const int rc = check_rows_dim(who, rows, dim)) return rc;
+    if (const int rc = bits ? check_rows_dim(who, rows, dim) : check_rows_dim_infer(who, rows, dim)) return rc;
     if (bits)
         if (const int rc = check_inv_keep(who, inv_keep)) return rc;
     if (rows == 0) return CCR_OK;
+    if (dim % 256) return add_layernorm_odd128(x, res, gamma, beta, eps, out_f32, out_half, rows, dim, half_dtype, s);   // (no bits: checked above)
     return dispatch_width(dim, [&](auto c) {
         return dispatch_half(half_dtype, [&](auto dt) {
             return dispatch_drop(bits != nullptr, [&](auto drop) {
@@ -584,15 +585,19 @@ static int add_layernorm(const char *who, const uint16_t *x, const uint32_t *bit
 static int embed_layernorm(const char *who, const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,
                            const float *type_table, int64_t n_types, const int64_t *token_ids, const int64_t *positions,
                            const int64_t *token_types, const float *gamma, const float *beta, float eps, const uint32_t *bits, float inv_keep,
-                           float *out_f32, uint16_t *out_half, int64_t rows, int dim, int half_dtype, hipStream_t s) {
+                           float *out_f32, uint16_t *out_half, int64_t rows, int dim, int half_dtype, hipStream_t s, bool odd_widths = false) {
     CCR_REQUIRE(word_table && position_table && type_table && token_ids && positions && gamma && beta && (out_f32 || out_half),
                 "%s: null pointer", who);
     if (const int rc = check_half(who, half_dtype)) return rc;
     CCR_REQUIRE(vocab > 0 && n_positions > 0 && n_types > 0, "%s: empty table", who);
-    if (const int rc = check_rows_dim(who, rows, dim)) return rc;
+    // odd_widths: the inference entry points (no bits) also take the odd multiples of 128; the training block keeps 256 C with or without bits
+    if (const int rc = odd_widths && !bits ? check_rows_dim_infer(who, rows, dim) : check_rows_dim(who, rows, dim)) return rc;
     if (bits)
         if (const int rc = check_inv_keep(who, inv_keep)) return rc;
     if (rows == 0) return CCR_OK;
+    if (dim % 256)   // (an inference entry point without bits: checked above)
+        return embed_layernorm_odd128(word_table, vocab, position_table, n_positions, type_table, n_types, token_ids, positions, token_types, gamma,
+                                      beta, eps, out_f32, out_half, rows, dim, half_dtype, s);
     return dispatch_width(dim, [&](auto c) {
         return dispatch_half(half_dtype, [&](auto dt) {
             return dispatch_drop(bits != nullptr, [&](auto drop) {   // no bits: the inference kernel, no extra loads
@@ -674,7 +679,7 @@ extern "C" int ccr_embed_layernorm_half(const float *word_table, int64_t vocab, 
                                         const int64_t *token_types, const float *gamma, const float *beta, float eps, float *out_f32,
                                         uint16_t *out_half, int64_t rows, int dim, int half_dtype, void *stream) {
     return embed_layernorm("ccr_embed_layernorm_half", word_table, vocab, position_table, n_positions, type_table, n_types, token_ids, positions,
-                           token_types, gamma, beta, eps, nullptr, 1.f, out_f32, out_half, rows, dim, half_dtype, (hipStream_t)stream);
+                           token_types, gamma, beta, eps, nullptr, 1.f, out_f32, out_half, rows, dim, half_dtype, (hipStream_t)stream, true);
 }
 
 extern "C" int ccr_embed_layernorm_train_half(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions,

@@ -263,9 +263,26 @@ inline int check_inv_keep(const char *who, float inv_keep) {
     return CCR_OK;
 }
 inline int check_rows_dim(const char *who, int64_t rows, int dim) {   // the row kernels: one wave per row of 256 C elements
-    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048, "%s: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048)", who, (long long)rows, dim);
+    CCR_REQUIRE(rows >= 0 && dim > 0 && dim % 256 == 0 && dim <= 2048,
+                "%s: rows=%lld dim=%d (dim %% 256 == 0, dim <= 2048: the rule of the keep-bit, training and backward row kernels)", who,
+                (long long)rows, dim);
     return CCR_OK;
 }
+// the inference row kernels (no keep bits): also the odd multiples of 128 from 384 on, one wave per row of 128 P elements
+// (ccr_encoder_h32.hip); a row of 128 stays refused, as it always was (tests/test_gpu_row_kernels.py pins that)
+inline int check_rows_dim_infer(const char *who, int64_t rows, int dim) {
+    CCR_REQUIRE(rows >= 0 && dim >= 256 && dim % 128 == 0 && dim <= 2048,
+                "%s: rows=%lld dim=%d (dim %% 128 == 0, 256 <= dim <= 2048: the rule of the inference row kernels, no keep bits)", who,
+                (long long)rows, dim);
+    return CCR_OK;
+}
+// The inference row kernels at dim = 128 P, P = 3, 5 .. 15 (ccr_encoder_h32.hip); the callers (ccr_encoder.hip) have checked every argument.
+int add_layernorm_odd128(const uint16_t *x, const float *res, const float *gamma, const float *beta, float eps, float *out_f32,
+                         uint16_t *out_half, int64_t rows, int dim, int half_dtype, hipStream_t s);
+int embed_layernorm_odd128(const float *word_table, int64_t vocab, const float *position_table, int64_t n_positions, const float *type_table,
+                           int64_t n_types, const int64_t *token_ids, const int64_t *positions, const int64_t *token_types,
+                           const float *gamma, const float *beta, float eps, float *out_f32, uint16_t *out_half, int64_t rows, int dim,
+                           int half_dtype, hipStream_t s);
 inline int check_attention_shape(const char *who, int half_dtype, int n_seq, int n_heads, int max_len, int pad_len, float scale) {
     if (const int rc = check_half(who, half_dtype)) return rc;
     CCR_REQUIRE(n_seq >= 0 && n_seq <= 65535 && n_heads > 0 && n_heads <= 1024, "%s: bad shape n_seq=%d n_heads=%d", who, n_seq, n_heads);

@@ -225,6 +225,14 @@ int ccr_gelu_half(const uint16_t *x, uint16_t *y, int64_t n, int half_dtype, voi
  * forward and the backward take no bias. */
 int ccr_attention_bias_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, const float *rel_bias,
                             int R, int n_seq, int n_heads, int max_len, int pad_len, float scale, int half_dtype, void *stream);
+/* ccr_attention_head_half (library version 114; the MiniLM-class encoders: hidden 384, 12 heads of width 32): ccr_attention_half with the
+ * head width as an argument.  head_width = 64 runs exactly what ccr_attention_half runs; head_width = 32 runs the narrow-head kernel on
+ * qkv [T][3 * n_heads * 32] -> out [T][n_heads * 32] (scale: 1 / sqrt(32) for BERT), with the same rules for padding rows, empty and
+ * over-long entries; any other head_width: CCR_ERR_INVALID.  Inference only, no bias form at width 32.
+ * With the same library version ccr_add_layernorm(_half) and ccr_embed_layernorm(_half) also take the odd multiples of 128
+ * (dim % 128 == 0, 256 <= dim <= 2048); the entry points that read keep bits, the training forward and the backward keep dim % 256 == 0. */
+int ccr_attention_head_half(const uint16_t *qkv, const int32_t *seq_start, const int32_t *seq_len, uint16_t *out, int n_seq, int n_heads,
+                            int head_width, int max_len, int pad_len, float scale, int half_dtype, void *stream);
 
 /*
  * The layer kernels' training forward and backward (library version 103): fine-tuning through the encoder.  The reference's training

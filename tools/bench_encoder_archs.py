@@ -9,6 +9,11 @@ every figure is the median of the timed calls with their min-max band.
   --part plain       the plain ops.attention alone, one JSON line: run it in fresh processes on two checkouts (--pkg names the other
                      checkout's package directory) to compare their builds of the same kernel
 
+  --part head32      the MiniLM-class shapes behind CCREC_FUSED_ENCODER_HEAD32=1 (profiles/encoder_head32.md): a random-init BertModel of
+                     6 and of 12 layers x 384, 12 heads of 32, FFN 1536 over the same passages under fp16 autocast.  Per shape, alternating
+                     in one process: FusedBertEncoder.forward (packed), the torch module, and the attention call alone at head width 32
+                     against the 64-wide call on the same tokens and head count
+
 A GPU is required; nothing here falls back."""
 import argparse
 import json
@@ -116,9 +121,53 @@ def part_models(ops, args):
                           **{k: band(v, 1.0, 2) for k, v in times.items()}}), flush=True)
 
 
+def part_head32(ops, args):
+    import transformers
+    from ccrec_amd import fused_bert
+    os.environ["CCREC_FUSED_ENCODER_HEAD32"] = "1"      # (read at call time)
+    lens = corpus_lengths()
+    g = torch.Generator().manual_seed(1)
+    ids = torch.zeros(B, L_HI, dtype=torch.int64)
+    mask = torch.zeros(B, L_HI, dtype=torch.int64)
+    for r, n in enumerate(lens.tolist()):
+        ids[r, :n] = torch.randint(2, 30000, (n,), generator=g)
+        mask[r, :n] = 1
+    ids, mask, lens_dev = ids.cuda(), mask.cuda(), lens.cuda()
+    start = (torch.cumsum(lens, 0, dtype=torch.int32) - lens).cuda()
+    T = int(lens.sum())
+    torch.manual_seed(0)
+    qkv32 = torch.randn(T, 3 * HEADS * 32, device="cuda").to(torch.float16)
+    qkv64 = torch.randn(T, 3 * HEADS * 64, device="cuda").to(torch.float16)
+    out32 = torch.empty(T, HEADS * 32, dtype=torch.float16, device="cuda")
+    out64 = torch.empty(T, HEADS * 64, dtype=torch.float16, device="cuda")
+    for name, layers in (("MiniLM-L6", 6), ("MiniLM-L12", 12)):
+        torch.manual_seed(0)
+        model = transformers.BertModel(transformers.BertConfig(vocab_size=30522, hidden_size=384, num_hidden_layers=layers, num_attention_heads=HEADS,
+                                                               intermediate_size=1536, max_position_embeddings=512)).cuda().eval()
+        enc = fused_bert.for_model(model)
+        assert enc is not None, fused_bert.unsupported_reason(model)
+        enc.refresh(torch.float16)
+
+        def kernels():
+            return enc.forward(ids, lens_dev, packed=True, lengths_host=lens, dtype=torch.float16)
+
+        def module():
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+                return model(input_ids=ids, attention_mask=mask).last_hidden_state
+
+        variants = {"kernels": kernels, "module": module,
+                    "attention32": lambda: ops.attention(qkv32, start, lens_dev, HEADS, max_len=L_HI, scale=32 ** -0.5, out=out32, head_width=32),
+                    "attention64": lambda: ops.attention(qkv64, start, lens_dev, HEADS, max_len=L_HI, out=out64)}
+        times = timed_alternating(variants, args.warmup, args.reps)
+        live = mask.bool()
+        diff = (kernels()[live] - module().float()[live]).abs().max().item()
+        print(json.dumps({"part": "head32", "model": name, "passages": B, "tokens": T, "max_abs_diff": round(diff, 5), "unit": "ms",
+                          **{k: band(v, 1.0, 3) for k, v in times.items()}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=["attention", "models", "plain"], required=True)
+    ap.add_argument("--part", choices=["attention", "models", "plain", "head32"], required=True)
     ap.add_argument("--pkg", default=None, help="package directory of another checkout (the directory that holds ccrec_amd/)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--reps", type=int, default=50)
@@ -128,7 +177,7 @@ def main():
     from ccrec_amd import ops
     assert os.path.dirname(os.path.dirname(os.path.abspath(ops.__file__))) == pkg, ops.__file__
     assert torch.cuda.is_available(), "a GPU is required"
-    {"attention": part_attention, "models": part_models, "plain": part_plain}[args.part](ops, args)
+    {"attention": part_attention, "models": part_models, "plain": part_plain, "head32": part_head32}[args.part](ops, args)
 
 
 if __name__ == "__main__":
